@@ -10,12 +10,15 @@ shard of a tau = 42 monomial SRS (BASELINE.json configs[1]; with N GPUs the job 
 of N*2^20 terms with the bases split across ranks, partial sums exchanged over RCCL — "weak").
 `value` = total scalar·muls per second over all ranks, inputs resident in HBM.  Up to three commitments are in flight
 (the library's FIFO).  The headline region is exactly what the contract says: W untimed warm-up steps, then K timed steps
-between barrier + synchronize brackets, nothing else before it (`--settle-steps` defaults to 0).  Because a step is
-~1.3 ms, W = 5 is only ~7 ms of load and the GPU reaches its sustained rate after ~70 ms of it; the line therefore also
-carries `sustained` = the same K-step region timed once more after 50 further commitments (value_sustained), so both
-protocols can be read from one run.
+between barrier + synchronize brackets, nothing else before it (`--settle-steps` defaults to 0).
 
-The one JSON line also carries
+A plain run does only that: set up, warm up, time the K steps, write the outputs (`--dump-outputs DIR`: the commitment
+of the last timed step) and print the line with the headline fields and `config`.  Everything below runs only with
+`--full`.  Because a step is ~1.3 ms, W = 5 is only ~7 ms of load and the GPU reaches its sustained rate after ~70 ms of
+it; a --full line therefore also carries `sustained` = the same K-step region timed once more after 50 further
+commitments (value_sustained), so both protocols can be read from one run.
+
+A --full line also carries
   roofline      dominant kernel msm_accumulate.  `kernel_ms` is its HIP-event duration with ONE commitment in flight
                 (--pipeline-depth 1 region, timed right after the headline region); `kernel_ms_pipelined` is what the
                 same kernel takes inside the headline region, where it shares the GPU with the bucket reduction of the
@@ -73,6 +76,7 @@ MAD_RATE_TLANE_S = 576.11e9 * 64 / 1e12
 MADS_PER_MIXED_ADD = 1467
 VALU_PEAK_GMADD = MAD_RATE_TLANE_S * 1e3 / MADS_PER_MIXED_ADD
 LOOP_ISOLATED_GMADD = 16.3
+SCALAR_SEED = 0x706c6f6e6b6974   # rank r commits rand_scalars(2^log_n, SCALAR_SEED + r): the same inputs in every run with the same arguments
 
 
 FAILED_LEGS = []                 # (leg, repr(exception), is_correctness) of every secondary leg that raised: the line keeps going, the exit status does not lie
@@ -520,16 +524,17 @@ def compact_line(full):
                    "pipeline_depth": cfg.get("pipeline_depth"), "settle_steps": cfg.get("settle_steps")}
     if "comm_ranks" in cfg:
         L["config"]["comm_ranks"] = cfg["comm_ranks"]
-    r = full.get("roofline", {})
-    L["roofline"] = pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms", "kernel_ms_pipelined",
-                             "ms_per_step_one_in_flight", "algorithmic_bytes", "valu_frac"))
-    if isinstance(r.get("valu"), dict):
-        L["roofline"]["valu"] = pick(r["valu"], ("achieved_gmadd_s", "peak_gmadd_s", "frac_of_isolated_loop"))
-    src = r.get("traffic_source") or ""
-    L["roofline"]["traffic_source"] = ("this run (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child runs of --msm-only)" if src.startswith("measured in this run")
-                                       else "profiles/ (rocprofv3 --pmc of the same command; not this run)")
-    if "traffic_over_algorithmic" in r:
-        L["roofline"]["traffic_over_algorithmic"] = r["traffic_over_algorithmic"]
+    if "roofline" in full:                                           # (--full only)
+        r = full["roofline"]
+        L["roofline"] = pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms", "kernel_ms_pipelined",
+                                 "ms_per_step_one_in_flight", "algorithmic_bytes", "valu_frac"))
+        if isinstance(r.get("valu"), dict):
+            L["roofline"]["valu"] = pick(r["valu"], ("achieved_gmadd_s", "peak_gmadd_s", "frac_of_isolated_loop"))
+        src = r.get("traffic_source") or ""
+        L["roofline"]["traffic_source"] = ("this run (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child runs of --msm-only)" if src.startswith("measured in this run")
+                                           else "profiles/ (rocprofv3 --pmc of the same command; not this run)")
+        if "traffic_over_algorithmic" in r:
+            L["roofline"]["traffic_over_algorithmic"] = r["traffic_over_algorithmic"]
     if "value_sustained" in full:
         L["value_sustained"] = full["value_sustained"]
     cb = full.get("cpu_baseline")
@@ -575,11 +580,12 @@ def compact_line(full):
         if key in full:
             L[key] = strip_prose(full[key])
     L["failed_legs"] = full.get("failed_legs", [])
-    L["notes"] = NOTES
+    if "roofline" in full:
+        L["notes"] = NOTES
     return L
 
 
-WRITE_FULL_RECORD = [True]           # False in --msm-only runs (profiling / counter children): they must not overwrite the record of the run that started them
+WRITE_FULL_RECORD = [True]           # True only in --full runs without --msm-only: profiling / counter children and plain runs must not overwrite the record
 
 
 def emit(line):
@@ -860,6 +866,16 @@ def time_commitments(ctx, msm, scalars, n, steps, stream, depth):
     return time.perf_counter() - t0, kernel_ms, out
 
 
+def dump_outputs(d, point):
+    """--dump-outputs: what the timed path handed its caller in the last timed step — the commitment, one affine G1 point — as
+    d/commitment.npy, float32 [2, 32]: the big-endian bytes of x and y (plk_g1_to_bytes' encoding), every value exact.  The inputs
+    are fixed by the arguments (seeded scalars, tau = 42 SRS), so two builds can be compared file for file."""
+    import plonkit_amd as pa
+    os.makedirs(d, exist_ok=True)
+    b = np.frombuffer(pa.g1_to_bytes(point), dtype=np.uint8).reshape(2, 32)
+    np.save(os.path.join(d, "commitment.npy"), b.astype(np.float32))
+
+
 def spawn_ranks(n_gpus):
     """re-run this command line as N ranks: python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>; returns the launcher's exit status"""
@@ -895,13 +911,19 @@ def main():
                     help="extra untimed commitments BEFORE the W warm-up steps of the headline region (default 0: the headline is "
                          "W warm-up + K timed steps and nothing else; round 2 defaulted to 50)")
     ap.add_argument("--sustained-settle-steps", type=int, default=50,
-                    help="untimed commitments between the headline region and the `sustained` region (the same K steps timed again "
-                         "once the GPU has been under load for >= 70 ms: DESIGN.md §5); 0 = no sustained region")
+                    help="--full: untimed commitments between the headline region and the `sustained` region (the same K steps timed "
+                         "again once the GPU has been under load for >= 70 ms: DESIGN.md §5); 0 = no sustained region")
     ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 --pmc child runs that measure roofline.traffic (the constant from profiles/ is reported instead)")
-    ap.add_argument("--msm-only", action="store_true", help="only the timed commitments (no cpu_baseline / prove / kernels legs): "
-                                                            "the command the rocprofv3 summary under profiles/ is taken from")
+    ap.add_argument("--msm-only", action="store_true", help="with --full: no cpu_baseline / prove / kernels legs, only the commitment regions "
+                                                            "(headline, sustained, one in flight); the command the rocprofv3 summary under profiles/ is taken from")
+    ap.add_argument("--full", action="store_true", help="after the headline region, also the sustained and one-in-flight regions (roofline), the CPU "
+                                                        "baselines, live PMC traffic, the prove / CLI / kernel legs and, at N > 1, the strong-scaling and "
+                                                        "sharded-prove legs; writes bench_line_full.json.  Off: the headline region and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the commitment of the last timed step to DIR/commitment.npy (see dump_outputs)")
     args = ap.parse_args()
-    WRITE_FULL_RECORD[0] = not args.msm_only
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    WRITE_FULL_RECORD[0] = args.full and not args.msm_only
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: spawn the N ranks ourselves, exactly as the driver's documented command does
@@ -939,7 +961,7 @@ def main():
     ctx = pa.Context(local_rank)
     n = 1 << args.log_n
     ctx.srs_generate(n, start=rank * n, tau=42)          # this rank's shard of the N*2^20 monomial SRS
-    scalars = rand_scalars(n, 0x706c6f6e6b6974 + rank, device)
+    scalars = rand_scalars(n, SCALAR_SEED + rank, device)
     torch.cuda.synchronize()                             # the scalars are consumed on another stream
     stream = torch.cuda.Stream(device=device)
     multi = world > 1 or force_dist
@@ -1013,9 +1035,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_device(device))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # the same K steps once more after sustained load (`sustained`: what round 2's default --settle-steps 50 measured)
+    if args.dump_outputs and rank == 0:                   # (every rank holds the same combined commitment)
+        dump_outputs(args.dump_outputs, out)
+    # --full: the same K steps once more after sustained load (`sustained`: what round 2's default --settle-steps 50 measured)
     sustained = None
-    if args.sustained_settle_steps:
+    if args.full and args.sustained_settle_steps:
         time_commitments(ctx, msm, scalars, n, args.sustained_settle_steps, stream, args.pipeline_depth)
         torch.cuda.synchronize()
         if dist:
@@ -1031,20 +1055,16 @@ def main():
             t = torch.tensor([sustained], dtype=torch.float64, device=red_device(device))
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             sustained = float(t.item())
-    # the dominant kernel alone: one commitment in flight, so nothing shares the GPU with msm_accumulate
-    solo_elapsed, solo_kernel_ms, _ = time_commitments(ctx, msm, scalars, n, max(5, args.steps // 2), stream, 1)
-    if dist:
-        dist.barrier()
+    # --full: the dominant kernel alone: one commitment in flight, so nothing shares the GPU with msm_accumulate
+    if args.full:
+        solo_elapsed, solo_kernel_ms, _ = time_commitments(ctx, msm, scalars, n, max(5, args.steps // 2), stream, 1)
+        if dist:
+            dist.barrier()
 
     line = None
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
         value = world * n / (elapsed / args.steps) / 1e6
-        k_pipe = float(np.mean(kernel_ms))
-        k_solo = float(np.mean(solo_kernel_ms))
-        k_ms = k_solo if args.pipeline_depth >= 2 else k_pipe
-        achieved = ALGO_BYTES_PER_TERM * n / (k_ms * 1e-3) / 1e9
-        gmadd = n * MSM_WINDOWS / (k_ms * 1e-3) / 1e9
         line = {
             "metric": "G1 MSM throughput at 2^%d terms per GPU (KZG commitment of the PLONK prover)" % args.log_n,
             "value": round(value, 3), "unit": "Mscalar·mul/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1060,45 +1080,51 @@ def main():
                        # travel another way (fallback / the shared-device test tier) — DESIGN.md section 6 says what a SCALE line must show
                        "comm_ranks": (ctx.comm_nccl_count() if multi else 1),
                        "result_x_be": pa.g1_to_bytes(out).hex()[:64]},
+        }
+        if args.full:
+            k_pipe = float(np.mean(kernel_ms))
+            k_solo = float(np.mean(solo_kernel_ms))
+            k_ms = k_solo if args.pipeline_depth >= 2 else k_pipe
+            achieved = ALGO_BYTES_PER_TERM * n / (k_ms * 1e-3) / 1e9
+            gmadd = n * MSM_WINDOWS / (k_ms * 1e-3) / 1e9
             # `bound`: what limits the kernel is VALU issue (v_mad_u64_u32), not HBM and not MFMA (integer modular arithmetic) — said so here;
             # achieved / peak / frac stay the HBM figures north_star and the bench contract ask for (hbm_frac repeats frac under its own name),
             # the VALU figures are in `valu`
-            "roofline": {"bound": "valu", "kernel": "msm_accumulate", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "hbm_frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "valu_frac": round(gmadd / VALU_PEAK_GMADD, 3),
-                         "traffic": PMC_TRAFFIC_BYTES_2POW20 if (args.log_n == 20) else None,
-                         "traffic_source": PMC_TRAFFIC_SOURCE if (args.log_n == 20) else None,
-                         "kernel_ms": round(k_ms, 4), "kernel_ms_pipelined": round(k_pipe, 4),
-                         "ms_per_step_one_in_flight": round(solo_elapsed * 1e3 / len(solo_kernel_ms), 4),
-                         "algorithmic_bytes": ALGO_BYTES_PER_TERM * n,
-                         "valu": {"achieved_gmadd_s": round(gmadd, 2), "peak_gmadd_s": round(VALU_PEAK_GMADD, 2),
-                                  "frac": round(gmadd / VALU_PEAK_GMADD, 3),
-                                  "loop_isolated_gmadd_s": LOOP_ISOLATED_GMADD,
-                                  "frac_of_isolated_loop": round(gmadd / LOOP_ISOLATED_GMADD, 3),
-                                  "derivation": "peak = measured v_mad_u64_u32 issue rate (576.1 G wave-instr/s x 64 lanes, "
-                                                "profiles/r01_ubench_int.txt) / 1467 mads per XYZZ mixed addition; "
-                                                "loop_isolated = the same loop with its 625 non-mad instructions, alone on the chip (profiles/r03_ubench_mulw_forms.txt)"},
-                         "note": "kernel_ms = HIP-event duration of msm_accumulate with one commitment in flight (the region timed right "
-                                 "after the headline one; rocprofv3 of `bench.py --msm-only --pipeline-depth 1` agrees, profiles/); "
-                                 "kernel_ms_pipelined = the same kernel inside the headline region, where up to three commitments are in "
-                                 "flight and it shares the GPU with the bucket reduction of the previous one and the partition of the next "
-                                 "(its duration there can exceed the step time: kernels of consecutive commitments overlap).  The kernel is bound by v_mad_u64_u32 issue, "
-                                 "not HBM (SURVEY.md §8d); `traffic` is 11x the algorithmic bytes because Pippenger gathers one "
-                                 "64-byte point per (term, window): 15 windows, each from its own shifted copy of the SRS "
-                                 "(0.94 GiB fixed-base table in HBM)"},
-        }
+            line["roofline"] = {"bound": "valu", "kernel": "msm_accumulate", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "hbm_frac": round(achieved / HBM_PEAK_GBS, 5),
+                                "valu_frac": round(gmadd / VALU_PEAK_GMADD, 3),
+                                "traffic": PMC_TRAFFIC_BYTES_2POW20 if (args.log_n == 20) else None,
+                                "traffic_source": PMC_TRAFFIC_SOURCE if (args.log_n == 20) else None,
+                                "kernel_ms": round(k_ms, 4), "kernel_ms_pipelined": round(k_pipe, 4),
+                                "ms_per_step_one_in_flight": round(solo_elapsed * 1e3 / len(solo_kernel_ms), 4),
+                                "algorithmic_bytes": ALGO_BYTES_PER_TERM * n,
+                                "valu": {"achieved_gmadd_s": round(gmadd, 2), "peak_gmadd_s": round(VALU_PEAK_GMADD, 2),
+                                         "frac": round(gmadd / VALU_PEAK_GMADD, 3),
+                                         "loop_isolated_gmadd_s": LOOP_ISOLATED_GMADD,
+                                         "frac_of_isolated_loop": round(gmadd / LOOP_ISOLATED_GMADD, 3),
+                                         "derivation": "peak = measured v_mad_u64_u32 issue rate (576.1 G wave-instr/s x 64 lanes, "
+                                                       "profiles/r01_ubench_int.txt) / 1467 mads per XYZZ mixed addition; "
+                                                       "loop_isolated = the same loop with its 625 non-mad instructions, alone on the chip (profiles/r03_ubench_mulw_forms.txt)"},
+                                "note": "kernel_ms = HIP-event duration of msm_accumulate with one commitment in flight (the region timed right "
+                                        "after the headline one; rocprofv3 of `bench.py --full --msm-only --pipeline-depth 1` agrees, profiles/); "
+                                        "kernel_ms_pipelined = the same kernel inside the headline region, where up to three commitments are in "
+                                        "flight and it shares the GPU with the bucket reduction of the previous one and the partition of the next "
+                                        "(its duration there can exceed the step time: kernels of consecutive commitments overlap).  The kernel is bound by v_mad_u64_u32 issue, "
+                                        "not HBM (SURVEY.md §8d); `traffic` is 11x the algorithmic bytes because Pippenger gathers one "
+                                        "64-byte point per (term, window): 15 windows, each from its own shifted copy of the SRS "
+                                        "(0.94 GiB fixed-base table in HBM)"}
         if sustained is not None:
             # (top-level copy of sustained.value: round 2's `value` was measured after 50 settle commitments, i.e. it corresponds to THIS figure)
             line["value_sustained"] = round(world * n / (sustained / args.steps) / 1e6, 3)
             line["sustained"] = {"value": round(world * n / (sustained / args.steps) / 1e6, 3), "ms_per_step": round(sustained * 1e3 / args.steps, 4),
                                  "steps": args.steps, "untimed_steps_before": args.settle_steps + args.warmup + args.steps + args.sustained_settle_steps,
                                  "what": "the headline region repeated after %d further untimed commitments (GPU under load for >= 70 ms)" % args.sustained_settle_steps}
-        if world > 1 and not args.no_cpu_baseline and not args.msm_only:
+        if world > 1 and args.full and not args.no_cpu_baseline and not args.msm_only:
             # the N > 1 line is self-contained: the same dense_multiexp port on this box's host cores (rank 0's GPU shard supplies the bases)
             cb, ref, s_host = cpu_msm_baseline(ctx, min(args.cpu_log_n, args.log_n), 1234)
             cb["note"] = "MSM leg only at N > 1; the N = 1 line carries the NTT / prove / G1-iNTT rows"
             line["cpu_baseline"] = cb
-        if world == 1 and not args.no_cpu_baseline and not args.msm_only:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.msm_only:
             cb, ref, s_host = cpu_msm_baseline(ctx, min(args.cpu_log_n, args.log_n), 1234)
             got = ctx.msm(s_host)                         # same sample through the HIP path
             cb["matches_gpu"] = bool(np.array_equal(got, ref))
@@ -1114,14 +1140,14 @@ def main():
             if rb:
                 cb["reference_binary"] = rb
             line["cpu_baseline"] = cb
-        if world == 1 and not force_dist and not args.msm_only and not args.no_live_traffic:
+        if world == 1 and not force_dist and args.full and not args.msm_only and not args.no_live_traffic:
             try:
                 tb, src = measure_traffic_live(args.log_n)
                 line["roofline"]["traffic"], line["roofline"]["traffic_source"] = tb, src
                 line["roofline"]["traffic_over_algorithmic"] = round(tb / (ALGO_BYTES_PER_TERM * n), 2)
             except Exception as exc:                               # noqa: BLE001 — the constant stays, and says why
                 FAILED_LEGS.append(("roofline.traffic", repr(exc), False))
-        if world == 1 and not force_dist and not args.msm_only:
+        if world == 1 and not force_dist and args.full and not args.msm_only:
             from plonkit_amd import prover_bench
             line["prove"] = leg("prove", lambda: prover_bench.run(ctx, args.log_n))      # a failing leg must not cost the headline line
             # the same circuit shape with a live d column (11 of 11 commitments), prove THROUGHPUT (two / three proofs in flight on this GPU),
@@ -1145,7 +1171,7 @@ def main():
                 FAILED_LEGS.append(("prove.dense", "the host verifier rejects the dense proof", True))
             line["kernels"] = leg("kernels", lambda: prover_bench.kernel_table(ctx, device))
     watchdog = None
-    if world > 1 or force_dist:
+    if args.full and (world > 1 or force_dist):
         watchdog = start_leg_watchdog(rank, [line])
         # (a) strong scaling of ONE 2^24-term commitment (configs[2]); (b) multi-GPU prove at the 2^log_n domain: the SRS
         # sliced across the ranks, commitments combined over RCCL, NTTs replicated.  Every rank takes part;

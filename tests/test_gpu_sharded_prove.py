@@ -318,7 +318,7 @@ def test_bench_n2_control_flow_on_one_gpu():
     env = dict(os.environ, PLK_BENCH_SHARE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--log-n", "16", "--strong-log-n", "18"]
+           "--log-n", "16", "--strong-log-n", "18", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -346,7 +346,7 @@ def test_bench_leg_watchdog_prints_the_line_and_exits():
     env = dict(os.environ, PLK_BENCH_SHARE_DEVICE="1", PLK_BENCH_LEG_TIMEOUT_S="25", PLK_BENCH_TEST_STALL_LEG="prove(sharded)")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--log-n", "14", "--strong-log-n", "16", "--no-cpu-baseline"]
+           "--log-n", "14", "--strong-log-n", "16", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -367,7 +367,7 @@ def test_bench_falls_back_to_torch_distributed_without_the_library_communicator(
     env = dict(os.environ, PLK_BENCH_SHARE_DEVICE="1", PLK_BENCH_TEST_NO_COMM="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--log-n", "14", "--strong-log-n", "16", "--no-cpu-baseline"]
+           "--log-n", "14", "--strong-log-n", "16", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -398,8 +398,8 @@ def _run_plain_bench(n_gpus, extra, timeout=900):
 
 
 def test_plain_bench_gpus_2_spawns_its_ranks():
-    """the driver's N = 1 form with N = 2: `python3 bench.py --gpus 2 --steps K --warmup W` and nothing else"""
-    line = _run_plain_bench(2, ["--steps", "3", "--warmup", "1", "--log-n", "14", "--strong-log-n", "16", "--no-cpu-baseline"])
+    """the driver's N = 1 form with N = 2: `python3 bench.py --gpus 2 --steps K --warmup W` (plus --full: the legs checked below)"""
+    line = _run_plain_bench(2, ["--steps", "3", "--warmup", "1", "--log-n", "14", "--strong-log-n", "16", "--no-cpu-baseline", "--full"])
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0
     assert "error" not in line["strong"] and "error" not in line["prove"] and line["strong_scaling_vs_1gpu"] > 0
 
@@ -411,7 +411,7 @@ def test_eight_rank_rehearsal_on_one_gpu():
     with the key split in eight, sharded prove — and every rank derived the same proof (sharded_prove asserts equality with
     its warm-up proof on each rank; the combiner gives every rank the same bytes).  Timings mean nothing here; what this
     guards is that the day an 8-GPU node runs `bench.py --gpus 8`, nothing in the control flow is new."""
-    line = _run_plain_bench(8, ["--steps", "3", "--warmup", "1", "--log-n", "14", "--strong-log-n", "17"], timeout=1200)
+    line = _run_plain_bench(8, ["--steps", "3", "--warmup", "1", "--log-n", "14", "--strong-log-n", "17", "--full"], timeout=1200)
     assert line["n_gpus"] == 8 and line["scaling"] == "weak" and line["value"] > 0
     assert line["config"]["terms_per_gpu"] == 1 << 14
     st = line["strong"]

@@ -5,7 +5,7 @@
 # stages:
 #   tests[:<pytest args>]   pytest -m gpu (default: the whole suite; e.g. tests:"tests/test_gpu_prove.py -k zero")
 #   smoke                   __graft_entry__.smoke()
-#   bench[:<args>]          python bench.py <args> (default: the driver's --gpus 1 --steps 20 --warmup 5)
+#   bench[:<args>]          python bench.py <args> (default: the driver's --gpus 1 --steps 20 --warmup 5, plus --full)
 #   prof-solo | prof-pipe   rocprofv3 --kernel-trace --stats of `bench.py --msm-only` with one / three commitments in flight
 #   prof-prove[:<log_n>]    rocprofv3 --kernel-trace --stats of tools/prove_probe.py <log_n> 6
 #   prof-py:<name>=<script and args>   rocprofv3 --kernel-trace --stats of `python <script and args>`; summary <name>_kernel_stats.csv
@@ -20,8 +20,9 @@ export TMPDIR=/tmp
 show='import json,sys
 ls=[l for l in sys.stdin.read().splitlines() if l.startswith("{")]
 if not ls: sys.exit("no JSON line")
-d=json.loads(ls[-1]); r=d["roofline"]
-print("value %.1f M/s  ms_per_step %.4f  kernel_ms %.4f  pipelined %.4f  one_in_flight %.4f  sustained %s" % (d["value"], d["ms_per_step"], r["kernel_ms"], r["kernel_ms_pipelined"], r["ms_per_step_one_in_flight"], d.get("sustained", {}).get("value")))
+d=json.loads(ls[-1]); r=d.get("roofline")
+print("value %.1f M/s  ms_per_step %.4f" % (d["value"], d["ms_per_step"]))
+if r: print("kernel_ms %.4f  pipelined %.4f  one_in_flight %.4f  sustained %s" % (r["kernel_ms"], r["kernel_ms_pipelined"], r["ms_per_step_one_in_flight"], d.get("sustained", {}).get("value")))
 p=d.get("prove")
 if p and "rounds_ms" in p: print("prove wall %.4f s rounds %s" % (p["wall_s"], p["rounds_ms"]))
 if "kernels" in d: print({k: v["ms"] for k, v in d["kernels"].items()})'
@@ -36,7 +37,7 @@ for st in "$@"; do
   case $kind in
     tests) ( time eval "timeout 1500 python -m pytest ${arg:-tests} -m gpu -x -q --durations=8" ) > "$O/pytest.log" 2>&1; tail -16 "$O/pytest.log" ;;
     smoke) python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;
-    bench) ( time timeout 900 python bench.py ${arg:---gpus 1 --steps 20 --warmup 5} ) > "$O/bench.log" 2> "$O/bench.err"; python -c "$show" < "$O/bench.log"; tail -3 "$O/bench.err" ;;
+    bench) ( time timeout 900 python bench.py ${arg:---gpus 1 --steps 20 --warmup 5 --full} ) > "$O/bench.log" 2> "$O/bench.err"; python -c "$show" < "$O/bench.log"; tail -3 "$O/bench.err" ;;
     prof-solo) prof solo python bench.py --msm-only --pipeline-depth 1 --steps 20 --warmup 5 ;;
     prof-pipe) prof pipe python bench.py --msm-only --steps 20 --warmup 5 ;;
     prof-prove) prof prove python tools/prove_probe.py ${arg:-20} 6 ;;
