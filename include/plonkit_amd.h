@@ -324,6 +324,45 @@ int32_t plk_prove_timings(const plk_ctx *ctx, double *out_ms, uint32_t cap, uint
  * reports the length.                                                                                                    */
 int32_t plk_prove_trace(plk_ctx *ctx, uint32_t which, plk_fr *out_host, uint64_t cap, uint64_t *n);
 
+/* ---- assembled input: SetupPolynomials and the wire columns of bellman's own synthesis (src/plonk.rs:50-55,104,152-159) */
+/* plonkit's SetupForProver holds bellman's SetupPolynomials (src/plonk.rs:50-55, built by setup() at :104) and prove_by_steps takes
+ * that setup plus the circuit bellman has already synthesised (:152-159).  These entry points take the same data one level below
+ * plk_circuit_load: no transpiler of this library is involved, so a circuit proved this way gets the proof bellman's own assembly
+ * defines.
+ *   Layout.      Every vector is an array of plk_fr, Montgomery form, byte-identical to ff_ce's Fr.  The order is the one vk.bin stores the
+ *                commitments in: selectors q_a q_b q_c q_d q_m q_const, then the next-step selector q_d_next, then sigma_1..sigma_4.
+ *   Domain.      N = n + 1 must be a power of two with log2 N + 2 <= 28; otherwise PLK_ERR_SIZE "setup power of two is not in the
+ *                correct range" (plk_setup_prepare's code and words).
+ *   Length.      Coefficient form (flags = 0): 1 <= len <= N monomial coefficients per vector, zero-extended to N.  Value form
+ *                (PLK_POLY_VALUES): len == N evaluations on <omega_N> in row order.  Otherwise PLK_ERR_ARG.  num_inputs <= n.
+ *   Rows.        num_inputs <= rows <= N (else PLK_ERR_ARG); columns are zero-extended to N.  Public input i is column a at row i,
+ *                the row whose gate is q_a = -1 in plk_setup_prepare's setup and where plk_prove takes it from: there is no separate
+ *                inputs argument that could disagree with the columns.
+ *   Checks.      Any selector, sigma or column element that is not a canonical residue (limbs >= r): PLK_ERR_ARG.  A row that fails
+ *                the width-4 gate equation q_a a + q_b b + q_c c + q_d d + q_m a b + q_const + q_d_next d_next + PI = 0:
+ *                PLK_ERR_UNSAT, "must satisfy: ... at row <lowest failing row> ..." (src/plonk.rs:137).  A permutation argument
+ *                that does not close (prod of numerators != prod of denominators at the transcript's beta, gamma — the columns
+ *                break the copy constraints of sigma): PLK_ERR_UNSAT, "copy constraints: ...".  No proof bytes in either case.
+ *                Key too small: PLK_ERR_SRS, as plk_prove.
+ *   Both kinds of setup.  plk_prove on a setup from plk_setup_from_polynomials is PLK_ERR_ARG (it has no gate structure);
+ *                plk_prove_assembled* work on a plk_setup_prepare setup too.  plk_setup_write_vk, plk_setup_upload (a no-op: the
+ *                setup is resident when the call returns), plk_setup_domain_size and plk_setup_free work on both, and
+ *                plk_prove_timings / plk_prove_trace describe an assembled proof as any other ([0] is the column upload there).
+ *   Host columns are never page-locked: they are copied as pageable memory.  The _dev variant reads columns_dev[j][0, rows) on the
+ *   device, ordered after the work already enqueued on `stream` (NULL: the context's stream, see the conventions above); it blocks
+ *   like plk_prove and keeps no reference to the columns once it returns.                                                         */
+#define PLK_POLY_VALUES 1u    /* vectors are evaluations on <omega_N> in row order, not monomial coefficients */
+/* SetupPolynomials<Bn256, PlonkCsWidth4WithNextStepParams> -> a resident setup (src/plonk.rs:50-55,104): 11 uploads, 11 NTT(N) */
+int32_t plk_setup_from_polynomials(plk_ctx *ctx, uint64_t n, uint64_t num_inputs,
+                                   const plk_fr *const selectors[6],      /* q_a q_b q_c q_d q_m q_const */
+                                   const plk_fr *next_step_selector,      /* q_d_next                    */
+                                   const plk_fr *const sigmas[4], uint64_t len, uint32_t flags, plk_setup **out);
+/* prove_by_steps from the assembled columns a, b, c, d (src/plonk.rs:152-159) -> proof.bin bytes (Proof::write) */
+int32_t plk_prove_assembled(plk_ctx *ctx, const plk_setup *s, const plk_fr *const columns[4], uint64_t rows,
+                            uint8_t *proof_out, uint64_t cap, uint64_t *len);
+int32_t plk_prove_assembled_dev(plk_ctx *ctx, const plk_setup *s, const void *const columns_dev[4], uint64_t rows,
+                                uint8_t *proof_out, uint64_t cap, uint64_t *len, void *stream);
+
 /* ---- the polynomial helpers of rounds 2, 4 and 5 on their own (bellman_ce::plonk::polynomials / better_cs::prover, reached
  *      from prove_by_steps src/plonk.rs:152-159): Polynomial::evaluate_at, the division by (x - z) behind the two opening
  *      proofs ((p(x) - p(z)) / (x - z), n coefficients, the top one zero), and the permutation grand product

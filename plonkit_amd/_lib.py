@@ -68,6 +68,23 @@ def _np(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _fr_vectors(arrays, who, allow_empty=False):
+    """numpy (len, 4) uint64 Montgomery vectors of one common length, C-contiguous; anything else raises ValueError"""
+    out = []
+    for i, a in enumerate(arrays):
+        if a is None:
+            raise ValueError("%s: vector %d is None" % (who, i))
+        v = np.asarray(a)
+        if v.dtype != np.uint64 or v.ndim != 2 or v.shape[1] != 4:
+            raise ValueError("%s: vector %d must be a (len, 4) uint64 array of Montgomery Fr, got %s %s" % (who, i, v.dtype, v.shape))
+        if v.shape[0] != np.asarray(arrays[0]).shape[0]:
+            raise ValueError("%s: vectors of different lengths (%d and %d)" % (who, np.asarray(arrays[0]).shape[0], v.shape[0]))
+        if v.shape[0] == 0 and not allow_empty:
+            raise ValueError("%s: vector %d is empty" % (who, i))
+        out.append(np.ascontiguousarray(v))
+    return out
+
+
 def _devptr(x):
     """torch tensor / int -> void*"""
     if hasattr(x, "data_ptr"):
@@ -479,6 +496,61 @@ class SetupForProver:
             rc = lib().plk_prove(h, self._h, circuit._h, out, ctypes.c_uint64(cap), ctypes.byref(n))
         _check(rc)
         return out.raw[:n.value]
+
+    # ---- assembled input (plk_setup_from_polynomials / plk_prove_assembled*): bellman's SetupPolynomials and the prover assembly's
+    #      wire columns (src/plonk.rs:50-55,104,152-159) instead of circuit bytes
+    @classmethod
+    def from_polynomials(cls, ctx, n, num_inputs, selectors, next_step, sigmas, values=False):
+        """a resident setup from the 6 selectors (q_a q_b q_c q_d q_m q_const), the next-step selector q_d_next and the 4 sigmas,
+        each a numpy (len, 4) uint64 array of Montgomery Fr (oracle_lib.fr_vec's format); values=False: monomial coefficients
+        (1 <= len <= n + 1, zero-extended), values=True: the n + 1 evaluations on <omega_N> in row order"""
+        if len(selectors) != 6 or len(sigmas) != 4:
+            raise ValueError("from_polynomials: 6 selectors and 4 sigmas expected, got %d and %d" % (len(selectors), len(sigmas)))
+        vecs = _fr_vectors(list(selectors) + [next_step] + list(sigmas), "from_polynomials")
+        length = vecs[0].shape[0]
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        sel = (ctypes.c_void_p * 6)(*[_np(v) for v in vecs[:6]])
+        sig = (ctypes.c_void_p * 4)(*[_np(v) for v in vecs[7:]])
+        _check(lib().plk_setup_from_polynomials(ctx._h if ctx is not None else None, ctypes.c_uint64(n), ctypes.c_uint64(num_inputs), sel,
+                                                _np(vecs[6]), sig, ctypes.c_uint64(length), ctypes.c_uint32(1 if values else 0),
+                                                ctypes.byref(self._h)))
+        return self
+
+    def _prove_into(self, call):
+        cap = 1 << 16
+        out = ctypes.create_string_buffer(cap)
+        n = ctypes.c_uint64(0)
+        rc = call(out, cap, n)
+        if rc == 1 and n.value > cap:                                 # many public inputs: retry with the reported size
+            cap = n.value
+            out = ctypes.create_string_buffer(cap)
+            rc = call(out, cap, n)
+        _check(rc)
+        return out.raw[:n.value]
+
+    def prove_assembled(self, columns, ctx=None):
+        """proof.bin bytes from the assembled wire columns a, b, c, d: four numpy (rows, 4) uint64 Montgomery arrays (zero-extended to
+        the domain; public input i is a[i])"""
+        if len(columns) != 4:
+            raise ValueError("prove_assembled: 4 columns expected, got %d" % len(columns))
+        cols = _fr_vectors(columns, "prove_assembled", allow_empty=True)
+        rows = cols[0].shape[0]
+        arr = (ctypes.c_void_p * 4)(*[_np(c) for c in cols])
+        h = (ctx or self.ctx)._h
+        return self._prove_into(lambda out, cap, n: lib().plk_prove_assembled(h, self._h, arr, ctypes.c_uint64(rows), out,
+                                                                              ctypes.c_uint64(cap), ctypes.byref(n)))
+
+    def prove_assembled_dev(self, ptrs, rows, stream=None, ctx=None):
+        """the same from columns already on the device (4 torch tensors / ints, rows x 32 bytes each), ordered after `stream`"""
+        if len(ptrs) != 4:
+            raise ValueError("prove_assembled_dev: 4 column pointers expected, got %d" % len(ptrs))
+        arr = (ctypes.c_void_p * 4)(*[_devptr(p) for p in ptrs])
+        h = (ctx or self.ctx)._h
+        st = _stream(stream)
+        return self._prove_into(lambda out, cap, n: lib().plk_prove_assembled_dev(h, self._h, arr, ctypes.c_uint64(rows), out,
+                                                                                  ctypes.c_uint64(cap), ctypes.byref(n), st))
 
     def timings_ms(self, ctx=None):
         arr = (ctypes.c_double * 16)()

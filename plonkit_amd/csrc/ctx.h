@@ -59,6 +59,7 @@ struct plk_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t flag_ready = nullptr;         // the satisfiability verdict of plk_prove has reached `pinned`
+    hipEvent_t in_ready = nullptr;           // plk_prove_assembled_dev: the caller's columns are complete on the caller's stream
     int num_cus = 0;
     // NTT tables (device): omega_{2^28} powers forward / inverse, coset generator 7 and 7^-1
     plk::DevBuf tables;

@@ -88,6 +88,19 @@ int32_t scan_pair_mult(plk_ctx *ctx, Fr *out0, const Fr *in0, bool reverse0, boo
                        uint32_t n, hipStream_t s, const Fr **pre0 = nullptr, const Fr **pre1 = nullptr);
 int32_t mul3_blocks(Fr *out, const Fr *a, const Fr *b, const Fr *pre_a, const Fr *pre_b, const Fr &sc, uint32_t n, hipStream_t s);
 int32_t quotient(const QuotientArgs &a, hipStream_t s);
+// assembled.hip: the inputs of plk_setup_from_polynomials / plk_prove_assembled*.
+// check_canonical: bit k of *flag <- some element of v[k][0, len) is >= r (count <= CANON_MAX)
+constexpr uint32_t CANON_MAX = 16;
+int32_t check_canonical(const Fr *const *v, uint32_t count, uint64_t len, uint32_t *flag, hipStream_t s);
+// the four caller columns src[j][0, rows) -> vals[j] and coef[j] (n elements, zero-padded), canonical check (flag[0], bit j = column j)
+// and the gate equation of check_gates on the values (flag[1] = n - lowest failing row, 0 when every gate holds)
+struct IngestArgs {
+    const Fr *src[4], *q[7];
+    Fr *vals[4], *coef[4];
+    uint32_t n, rows, num_inputs;
+    uint32_t *flag;
+};
+int32_t ingest_columns(const IngestArgs &a, hipStream_t s);
 // data = the four per-coset coefficient vectors u_k of icoset4cm_dev (u_k at data + k*n) -> the 4n coefficients, natural order, in place;
 // constants in the W domain: i^-1 (i = omega_4) and s_c = 7^(-N c) / 4
 int32_t icoset_combine(Fr *data, uint32_t n, const Fr &iinv_w, const Fr s_w[4], hipStream_t s);

@@ -248,6 +248,7 @@ struct plk_setup {
     std::vector<plk::WitnessTerm> op_terms;
     plk::big_vector<plk::HFr> h_cols;      // host phase only: 7 selector columns x N, until plk_setup_upload
     plk::big_vector<uint32_t> h_vars;      // host phase only: 4 variable-index columns x N
+    bool from_polys = false;               // plk_setup_from_polynomials: selectors and sigmas given, no gate structure (gate_vars, ops)
 };
 
 using namespace plk;
@@ -474,122 +475,85 @@ int32_t plk_prove_timings(const plk_ctx *ctx, double *out_ms, uint32_t cap, uint
     return PLK_OK;
 }
 
-static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
-    if (!ctx || !S || !c || !proof_out || !len) { set_error("plk_prove: bad argument"); return PLK_ERR_ARG; }
-    *len = 0;
-    if (!c->has_witness) { set_error("plk_prove: circuit has no witness"); return PLK_ERR_ARG; }
-    PLK_HIP(hipSetDevice(ctx->device));
-    if (!ctx->srs || (!ctx->combine && ctx->srs_n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
-    if (!S->store.p) { set_error("plk_prove: the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
-    PLK_TRY(fifo_must_be_empty(ctx, "plk_prove"));
-    FifoGuard fifo_guard(ctx);
-    ctx->timings.clear();
-    ctx->trace.valid = false;
-    double t_prev = now_ms();
-    auto lap = [&]() { double t = now_ms(); ctx->timings.push_back(t - t_prev); t_prev = t; };
-    hipStream_t st = ctx->stream;
-
-    // ---- witness synthesis (host): circom wires, then the transpiler's temporaries from their recorded
-    //      linear forms (the gate structure itself lives in plk_setup; the reference re-synthesises here)
-    if (c->r1cs.num_variables != S->num_circuit_vars || c->witness.size() < S->num_circuit_vars) {
-        set_error("plk_prove: circuit does not match the prepared setup"); return PLK_ERR_ARG; }
-    // circom wires are uploaded straight from the (page-locked) witness buffer; only the temporaries are
-    // computed here, into a pinned staging area.  id 0 (dummy) is zeroed on the device.
-    const uint64_t ncv = S->num_circuit_vars, n_tmp = S->num_vars - ncv;
-    // page-locking the witness (hipHostRegister) makes its upload 2 ms faster at 2^20 but costs ~50 ms once, plus the
-    // un-pinning when the process ends: worth it from the second proof of the same circuit object on, not for the
-    // one-proof-per-process pattern of the CLI (profiles/r02_cli_scale.txt: 0.36 -> 0.29 s whole `plonkit prove`)
-    static const int reg_mode = [] { const char *e = getenv("PLK_HOST_REGISTER"); return !e ? 1 : (!strcmp(e, "always") ? 0 : (!strcmp(e, "never") ? 1 << 30 : 1)); }();
-    // Only a witness that owns its pages is page-locked: >= 4 MB sits in a 2 MiB-aligned block of its own (circuit.h, HugeAlloc).
-    // A small one lives on the malloc heap and shares its 4 KiB pages with unrelated objects — numpy buffers, other circuits'
-    // witnesses — that the runtime locks and unlocks on its own for pageable copies; pinning and unpinning such pages behind its
-    // back ended, once in two or three runs of the whole GPU test suite, in "Memory access fault by GPU ... on address <heap page>"
-    // during a LATER, unrelated host-to-device copy (round 4; profiles/r04_host_register_fault.txt).  A small upload gains nothing anyway.
-    {
-        std::lock_guard<std::mutex> reg_lock(c->reg_mu);
-        const size_t wit_bytes = c->witness.size() * sizeof(HFr);
-        if (!c->witness_registered && wit_bytes >= ((size_t)4 << 20) && (int)(c->proofs_started++) >= reg_mode) {
-            if (hipHostRegister((void *)c->witness.data(), wit_bytes, hipHostRegisterDefault) == hipSuccess) c->witness_registered = true;
-            else (void)hipGetLastError();                                    // not fatal: the copy is just slower
-        }
-    }
-    static const bool tmp_host_env = [] { const char *e = getenv("PLK_WITNESS_TMP_HOST"); return e && e[0] == '1'; }();      // tests: the host loop
-    const bool tmp_on_device = !tmp_host_env && (S->ops_independent || S->ops_chained) && (S->ops_dev.p || S->ops.empty());
-    PLK_TRY(ensure_pinned2(ctx, (tmp_on_device ? 1 : n_tmp + 1) * sizeof(HFr)));
-    HFr *tmp_vals = reinterpret_cast<HFr *>(ctx->pinned2);
-    const HFr *wit = c->witness.data();
-    if (!tmp_on_device) {
-        const size_t n_ops = S->ops.size();
-        auto value_of = [&](uint32_t v) -> HFr { return v == 0 ? HFr::zero() : (v < ncv ? wit[v] : tmp_vals[v - ncv]); };
-        auto eval_range = [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; i++) {
-                const WitnessOp &op = S->ops[i];
-                HFr acc = op.constant;
-                for (uint32_t k = 0; k < op.count; k++) { const WitnessTerm &t = S->op_terms[op.first + k]; acc = acc + t.coeff * value_of(t.var); }
-                tmp_vals[i] = acc;
-            }
-        };
-        if (S->ops_independent && n_ops > 4096) {
-            unsigned nt = std::thread::hardware_concurrency();
-            if (nt > 16) nt = 16;
-            if (nt < 1) nt = 1;
-            std::vector<std::thread> th;
-            size_t per = (n_ops + nt - 1) / nt;
-            for (unsigned t = 0; t < nt; t++) { size_t lo = t * per, hi = std::min(n_ops, lo + per); if (lo < hi) th.emplace_back(eval_range, lo, hi); }
-            for (auto &x : th) x.join();
-        } else eval_range(0, n_ops);
-    }
-    struct { uint64_t num_vars; } T;
-    T.num_vars = S->num_vars;
-    lap();                                                                    // [0] witness synthesis
-
+// ---- the prover's workspace and its two front ends
+// Everything of a proof lives in ctx->prove_ws; d_values (the witness by variable index) only on the circuit path.
+struct ProveWs {
+    Fr *d_values = nullptr, *w_vals[4] = {}, *w_coef[4] = {};
+    Fr *z_coef = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr, *r_poly = nullptr, *agg = nullptr, *pi_coef = nullptr, *l0_coef = nullptr;
+    Fr *ext[18] = {}, *t_ext = nullptr, *tab[4] = {}, *d_results = nullptr;
+    uint32_t *d_flag = nullptr;
+    bool direct_pi = false;
+};
+static int32_t prove_workspace(plk_ctx *ctx, const plk_setup *S, uint64_t num_vars, ProveWs *W) {
     const uint64_t N = S->N, M = 4 * N;
-    const uint32_t log_n = S->log_n, log_m = log_n + 2;
     const size_t NB = (N * sizeof(Fr) + 255) & ~(size_t)255, MB = (M * sizeof(Fr) + 255) & ~(size_t)255;
     const size_t TB = ((size_t)2 * POW_TAB * sizeof(Fr) + 255) & ~(size_t)255;
-    const size_t VB = (T.num_vars * sizeof(Fr) + 255) & ~(size_t)255;
+    const size_t VB = (num_vars * sizeof(Fr) + 255) & ~(size_t)255;
     const bool direct_pi = S->num_inputs <= QUOTIENT_MAX_DIRECT_PI;       // few inputs: PI comes from the cached L0 vector inside the quotient kernel
+    W->direct_pi = direct_pi;
     PLK_TRY(ctx->prove_ws.reserve(VB + 16 * NB + (direct_pi ? 6 : 7) * MB + 4 * TB + 8192));   // 5 extensions (+ PI) + the quotient
     Arena A{&ctx->prove_ws};
-    Fr *d_values = A.take<Fr>(T.num_vars);
-    Fr *w_vals[4], *w_coef[4];
-    for (int j = 0; j < 4; j++) { w_vals[j] = A.take<Fr>(N); w_coef[j] = A.take<Fr>(N); }
-    Fr *z_coef = A.take<Fr>(N), *t1 = A.take<Fr>(N), *t2 = A.take<Fr>(N), *t3 = A.take<Fr>(N);
-    Fr *r_poly = A.take<Fr>(N), *agg = A.take<Fr>(N), *pi_coef = A.take<Fr>(N), *l0_coef = A.take<Fr>(N);
-    Fr *ext[18] = {nullptr};
-    for (int k = 0; k < 5; k++) ext[k] = A.take<Fr>(M);          // w0..w3, z
-    if (!direct_pi) ext[16] = A.take<Fr>(M);                      // PI
-    Fr *t_ext = A.take<Fr>(M);
-    Fr *tab[4];
-    for (int k = 0; k < 4; k++) tab[k] = A.take<Fr>(2 * POW_TAB);
-    Fr *d_results = A.take<Fr>(16);
+    W->d_values = A.take<Fr>(num_vars);
+    for (int j = 0; j < 4; j++) { W->w_vals[j] = A.take<Fr>(N); W->w_coef[j] = A.take<Fr>(N); }
+    W->z_coef = A.take<Fr>(N); W->t1 = A.take<Fr>(N); W->t2 = A.take<Fr>(N); W->t3 = A.take<Fr>(N);
+    W->r_poly = A.take<Fr>(N); W->agg = A.take<Fr>(N); W->pi_coef = A.take<Fr>(N); W->l0_coef = A.take<Fr>(N);
+    for (int k = 0; k < 18; k++) W->ext[k] = nullptr;
+    for (int k = 0; k < 5; k++) W->ext[k] = A.take<Fr>(M);       // w0..w3, z
+    if (!direct_pi) W->ext[16] = A.take<Fr>(M);                    // PI
+    W->t_ext = A.take<Fr>(M);
+    for (int k = 0; k < 4; k++) W->tab[k] = A.take<Fr>(2 * POW_TAB);
+    W->d_results = A.take<Fr>(16);
+    W->d_flag = A.take<uint32_t>(64);
+    return PLK_OK;
+}
 
-    uint32_t *d_flag = A.take<uint32_t>(64);
-    {   // (under the circuit's lock: another context proving the SAME circuit object may be about to page-lock this buffer —
-        //  not while a pageable copy of it is being staged)
-        std::lock_guard<std::mutex> upload_lock(c->reg_mu);
-        PLK_HIP(hipMemcpyAsync(d_values, wit, ncv * sizeof(Fr), hipMemcpyHostToDevice, st));
+// What a front end hands to the rounds: w_vals / w_coef of the workspace hold the wire values (w_coef still to be interpolated in place),
+// the satisfiability verdict is on its way to ctx->pinned behind ctx->flag_ready, and the public inputs are known — or, for columns
+// that live on the device, on their way to inputs_pinned behind the same event.
+struct ProveFront {
+    std::vector<HFr> inputs;
+    const HFr *inputs_pinned = nullptr;
+    bool assembled = false;                  // verdict layout: circuit = one flag word; assembled = ingest_columns' two words
+    bool close_perm = false;                 // sigma came from the caller: check that the permutation argument closes (round 2)
+    double t_prev = 0;                       // plk_prove_timings: start of the phase in progress
+};
+
+// the verdict of the front end's checks, read after round 1 has been enqueued (before any commitment is used)
+static int32_t front_verdict(plk_ctx *ctx, const plk_setup *S, ProveFront &F) {
+    const volatile uint32_t *flag = reinterpret_cast<volatile uint32_t *>(ctx->pinned);
+    if (!F.assembled) {
+        if (flag[0]) { set_error("must satisfy: witness does not satisfy the circuit"); return PLK_ERR_UNSAT; }
+        return PLK_OK;
     }
-    PLK_HIP(hipMemsetAsync(d_values, 0, sizeof(Fr), st));
-    if (n_tmp && tmp_on_device && S->ops_chained)
-        PLK_TRY(eval_witness_runs(d_values, S->ops_dev.p, S->terms_dev.p, S->runs_dev.p, (uint32_t)S->run_start.size(), (uint32_t)S->ops.size(), (uint32_t)ncv, st));
-    else if (n_tmp && tmp_on_device) PLK_TRY(eval_witness_ops(d_values, S->ops_dev.p, S->terms_dev.p, (uint32_t)S->ops.size(), (uint32_t)ncv, st));
-    else if (n_tmp) PLK_HIP(hipMemcpyAsync(d_values + ncv, tmp_vals, n_tmp * sizeof(Fr), hipMemcpyHostToDevice, st));
-    std::vector<HFr> inputs(wit + 1, wit + 1 + S->num_inputs);
-    {   // is_satisfied_using_one_shot_check (src/plonk.rs:137) on the device
-        CheckArgs ca;
-        ca.values = d_values; ca.n = (uint32_t)N; ca.num_inputs = (uint32_t)S->num_inputs; ca.flag = d_flag;
-        for (int k = 0; k < 7; k++) ca.q[k] = S->sel_vals[k];
-        for (int j = 0; j < 4; j++) ca.vars[j] = S->gate_vars[j];
-        PLK_HIP(hipMemsetAsync(d_flag, 0, 4, st));
-        PLK_TRY(check_gates(ca, st));
-        // the verdict is read back into the pinned result buffer and looked at after round 1 has been enqueued (before any
-        // commitment is used): the host does not stall the GPU for it.  An unsatisfied witness still ends the call with
-        // PLK_ERR_UNSAT and no proof bytes — the commitments under way are drained by the FIFO guard.
-        PLK_HIP(hipMemcpyAsync(ctx->pinned, d_flag, 4, hipMemcpyDeviceToHost, st));
-        if (!ctx->flag_ready) PLK_HIP(hipEventCreateWithFlags(&ctx->flag_ready, hipEventDisableTiming));
-        PLK_HIP(hipEventRecord(ctx->flag_ready, st));
+    if (const uint32_t bad = flag[0]) {
+        std::string which;
+        for (int j = 0; j < 4; j++) if (bad >> j & 1) { which += which.empty() ? "" : ", "; which += "abcd"[j]; }
+        set_error("plk_prove_assembled: column " + which + " holds an element that is not a canonical residue (limbs >= r)");
+        return PLK_ERR_ARG;
     }
+    if (const uint32_t f = flag[1]) {
+        set_error("must satisfy: the assembled columns fail the gate equation at row " + std::to_string(S->N - f) + " (the lowest failing row)");
+        return PLK_ERR_UNSAT;
+    }
+    if (F.inputs_pinned) F.inputs.assign(F.inputs_pinned, F.inputs_pinned + S->num_inputs);
+    return PLK_OK;
+}
+
+// Rounds 1-5 and Proof::write, shared by plk_prove and plk_prove_assembled*: from the wire values a front end left in the workspace.
+static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, ProveFront &F, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    auto lap = [&]() { double t = now_ms(); ctx->timings.push_back(t - F.t_prev); F.t_prev = t; };
+    hipStream_t st = ctx->stream;
+    const uint64_t N = S->N, M = 4 * N;
+    const uint32_t log_n = S->log_n, log_m = log_n + 2;
+    const size_t MB = (M * sizeof(Fr) + 255) & ~(size_t)255;
+    const bool direct_pi = W.direct_pi;
+    Fr *const *w_vals = W.w_vals, *const *w_coef = W.w_coef;
+    Fr *const z_coef = W.z_coef, *const t1 = W.t1, *const t2 = W.t2, *const t3 = W.t3, *const r_poly = W.r_poly, *const agg = W.agg;
+    Fr *const pi_coef = W.pi_coef, *const l0_coef = W.l0_coef, *const t_ext = W.t_ext, *const d_results = W.d_results;
+    Fr *const *tab = W.tab;
+    Fr *ext[18];
+    for (int k = 0; k < 18; k++) ext[k] = W.ext[k];
+    std::vector<HFr> &inputs = F.inputs;
 
     // The extensions that no challenge waits for (wires, z, public inputs: round-3 inputs) run on a low-priority stream of
     // their own with their own NTT scratch: they fill the SIMDs that the latency-bound ends of a commitment leave idle
@@ -628,8 +592,8 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
         return PLK_OK;
     };
 
+
     // ---- round 1: wire polynomials, 4 x iNTT(N) in one launch per pass, 4 x MSM(N)
-    PLK_TRY(gather4_dual(w_vals, w_coef, d_values, S->gate_vars, (uint32_t)N, st));
     if (log_n <= 22) PLK_TRY(ntt_batch_dev(ctx, w_coef, 4, log_n, true, nullptr, st, 0));
     else for (int j = 0; j < 4; j++) PLK_TRY(ntt_dev(ctx, w_coef[j], log_n, true, nullptr, st));
     // with a Lagrange-form key of the domain's size resident (`prove -l`, src/plonk.rs:138-146) the witness and
@@ -641,7 +605,7 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
     PLK_TRY(bg_after_main(bg_gate_w != 0));
     PLK_TRY(lde4cm_batch_dev(ctx, w_coef, 4, log_n, ext, bg, bg_lane));                       // round-3 work that needs no challenge
     PLK_HIP(hipEventSynchronize(ctx->flag_ready));
-    if (*reinterpret_cast<volatile uint32_t *>(ctx->pinned)) { set_error("must satisfy: witness does not satisfy the circuit"); return PLK_ERR_UNSAT; }
+    PLK_TRY(front_verdict(ctx, S, F));
     PLK_TRY(commit_end(ctx, 4, wire_c));
     RollingKeccak tr;
     for (const HFr &x : inputs) tr.absorb_fr(x);
@@ -666,10 +630,23 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
         static const bool fuse_scan_tail = [] { const char *e = getenv("PLK_PROVE_FUSE_SCAN_TAIL"); return !(e && e[0] == '0'); }();   // A/B knob, read once
         PLK_TRY(scan_pair_mult(ctx, t1, t1, false, true, t2, t2, true, false, (uint32_t)N, st, fuse_scan_tail ? &pre_a : nullptr, fuse_scan_tail ? &pre_c : nullptr));
         const uint32_t scan_blocks = pre_c ? (uint32_t)((N + POLY_SCAN_BLOCK - 1) / POLY_SCAN_BLOCK) : 0;
-        HFr total;
+        HFr total, num_total;
         PLK_HIP(hipMemcpyAsync(total.l, pre_c ? pre_c + scan_blocks : t2, sizeof(Fr), hipMemcpyDeviceToHost, st));
+        // copy constraints of a caller's sigma (assembled front): the argument closes iff prod num == prod den.  The numerators' grand total
+        // sits in the scan's block-total slot (poly.hip: behind the nb prefixes; with one block the block total itself, lazily reduced) and
+        // comes back with the same synchronisation as the denominators' one
+        const uint32_t nb_all = (uint32_t)((N + POLY_SCAN_BLOCK - 1) / POLY_SCAN_BLOCK);
+        if (F.close_perm) PLK_HIP(hipMemcpyAsync(num_total.l, ctx->poly_tmp.as<Fr>() + (nb_all > 1 ? nb_all : 0), sizeof(Fr), hipMemcpyDeviceToHost, st));
         PLK_HIP(hipStreamSynchronize(st));
         if (total.is_zero()) { set_error("grand product denominator vanished (probability ~2^-230)"); return PLK_ERR_UNSAT; }
+        if (F.close_perm) {
+            if (HFr::geq_p(num_total.l)) HFr::sub_p(num_total.l);
+            if (num_total != total) {
+                set_error("copy constraints: the permutation argument does not close (prod of numerators != prod of denominators at beta, gamma): "
+                          "the columns break the copy constraints of the setup's sigma");
+                return PLK_ERR_UNSAT;
+            }
+        }
         // the scans live in the W domain: what was read is 32 * C_0, so E(1 / C_0) = 32 * E(1 / (32 C_0))
         const Fr inv_c0 = to_dev(total.inv() * HFr::from_u64(32));
         if (pre_c) PLK_TRY(mul3_blocks(z_coef, t1, t2, pre_a, pre_c, inv_c0, (uint32_t)N, st));
@@ -905,6 +882,243 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
     return PLK_OK;
 }
 
+static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    if (!ctx || !S || !c || !proof_out || !len) { set_error("plk_prove: bad argument"); return PLK_ERR_ARG; }
+    *len = 0;
+    if (S->from_polys) {
+        set_error("plk_prove: this setup was built from polynomials (plk_setup_from_polynomials) and has no gate structure: "
+                  "prove it from assembled columns with plk_prove_assembled / plk_prove_assembled_dev");
+        return PLK_ERR_ARG;
+    }
+    if (!c->has_witness) { set_error("plk_prove: circuit has no witness"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    if (!ctx->srs || (!ctx->combine && ctx->srs_n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
+    if (!S->store.p) { set_error("plk_prove: the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
+    PLK_TRY(fifo_must_be_empty(ctx, "plk_prove"));
+    FifoGuard fifo_guard(ctx);
+    ctx->timings.clear();
+    ctx->trace.valid = false;
+    double t_prev = now_ms();
+    auto lap = [&]() { double t = now_ms(); ctx->timings.push_back(t - t_prev); t_prev = t; };
+    hipStream_t st = ctx->stream;
+
+    // ---- witness synthesis (host): circom wires, then the transpiler's temporaries from their recorded
+    //      linear forms (the gate structure itself lives in plk_setup; the reference re-synthesises here)
+    if (c->r1cs.num_variables != S->num_circuit_vars || c->witness.size() < S->num_circuit_vars) {
+        set_error("plk_prove: circuit does not match the prepared setup"); return PLK_ERR_ARG; }
+    // circom wires are uploaded straight from the (page-locked) witness buffer; only the temporaries are
+    // computed here, into a pinned staging area.  id 0 (dummy) is zeroed on the device.
+    const uint64_t ncv = S->num_circuit_vars, n_tmp = S->num_vars - ncv;
+    // page-locking the witness (hipHostRegister) makes its upload 2 ms faster at 2^20 but costs ~50 ms once, plus the
+    // un-pinning when the process ends: worth it from the second proof of the same circuit object on, not for the
+    // one-proof-per-process pattern of the CLI (profiles/r02_cli_scale.txt: 0.36 -> 0.29 s whole `plonkit prove`)
+    static const int reg_mode = [] { const char *e = getenv("PLK_HOST_REGISTER"); return !e ? 1 : (!strcmp(e, "always") ? 0 : (!strcmp(e, "never") ? 1 << 30 : 1)); }();
+    // Only a witness that owns its pages is page-locked: >= 4 MB sits in a 2 MiB-aligned block of its own (circuit.h, HugeAlloc).
+    // A small one lives on the malloc heap and shares its 4 KiB pages with unrelated objects — numpy buffers, other circuits'
+    // witnesses — that the runtime locks and unlocks on its own for pageable copies; pinning and unpinning such pages behind its
+    // back ended, once in two or three runs of the whole GPU test suite, in "Memory access fault by GPU ... on address <heap page>"
+    // during a LATER, unrelated host-to-device copy (round 4; profiles/r04_host_register_fault.txt).  A small upload gains nothing anyway.
+    {
+        std::lock_guard<std::mutex> reg_lock(c->reg_mu);
+        const size_t wit_bytes = c->witness.size() * sizeof(HFr);
+        if (!c->witness_registered && wit_bytes >= ((size_t)4 << 20) && (int)(c->proofs_started++) >= reg_mode) {
+            if (hipHostRegister((void *)c->witness.data(), wit_bytes, hipHostRegisterDefault) == hipSuccess) c->witness_registered = true;
+            else (void)hipGetLastError();                                    // not fatal: the copy is just slower
+        }
+    }
+    static const bool tmp_host_env = [] { const char *e = getenv("PLK_WITNESS_TMP_HOST"); return e && e[0] == '1'; }();      // tests: the host loop
+    const bool tmp_on_device = !tmp_host_env && (S->ops_independent || S->ops_chained) && (S->ops_dev.p || S->ops.empty());
+    PLK_TRY(ensure_pinned2(ctx, (tmp_on_device ? 1 : n_tmp + 1) * sizeof(HFr)));
+    HFr *tmp_vals = reinterpret_cast<HFr *>(ctx->pinned2);
+    const HFr *wit = c->witness.data();
+    if (!tmp_on_device) {
+        const size_t n_ops = S->ops.size();
+        auto value_of = [&](uint32_t v) -> HFr { return v == 0 ? HFr::zero() : (v < ncv ? wit[v] : tmp_vals[v - ncv]); };
+        auto eval_range = [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; i++) {
+                const WitnessOp &op = S->ops[i];
+                HFr acc = op.constant;
+                for (uint32_t k = 0; k < op.count; k++) { const WitnessTerm &t = S->op_terms[op.first + k]; acc = acc + t.coeff * value_of(t.var); }
+                tmp_vals[i] = acc;
+            }
+        };
+        if (S->ops_independent && n_ops > 4096) {
+            unsigned nt = std::thread::hardware_concurrency();
+            if (nt > 16) nt = 16;
+            if (nt < 1) nt = 1;
+            std::vector<std::thread> th;
+            size_t per = (n_ops + nt - 1) / nt;
+            for (unsigned t = 0; t < nt; t++) { size_t lo = t * per, hi = std::min(n_ops, lo + per); if (lo < hi) th.emplace_back(eval_range, lo, hi); }
+            for (auto &x : th) x.join();
+        } else eval_range(0, n_ops);
+    }
+    struct { uint64_t num_vars; } T;
+    T.num_vars = S->num_vars;
+    lap();                                                                    // [0] witness synthesis
+
+    const uint64_t N = S->N;
+    ProveWs W;
+    PLK_TRY(prove_workspace(ctx, S, T.num_vars, &W));
+    Fr *const d_values = W.d_values;
+    uint32_t *const d_flag = W.d_flag;
+    {   // (under the circuit's lock: another context proving the SAME circuit object may be about to page-lock this buffer —
+        //  not while a pageable copy of it is being staged)
+        std::lock_guard<std::mutex> upload_lock(c->reg_mu);
+        PLK_HIP(hipMemcpyAsync(d_values, wit, ncv * sizeof(Fr), hipMemcpyHostToDevice, st));
+    }
+    PLK_HIP(hipMemsetAsync(d_values, 0, sizeof(Fr), st));
+    if (n_tmp && tmp_on_device && S->ops_chained)
+        PLK_TRY(eval_witness_runs(d_values, S->ops_dev.p, S->terms_dev.p, S->runs_dev.p, (uint32_t)S->run_start.size(), (uint32_t)S->ops.size(), (uint32_t)ncv, st));
+    else if (n_tmp && tmp_on_device) PLK_TRY(eval_witness_ops(d_values, S->ops_dev.p, S->terms_dev.p, (uint32_t)S->ops.size(), (uint32_t)ncv, st));
+    else if (n_tmp) PLK_HIP(hipMemcpyAsync(d_values + ncv, tmp_vals, n_tmp * sizeof(Fr), hipMemcpyHostToDevice, st));
+    std::vector<HFr> inputs(wit + 1, wit + 1 + S->num_inputs);
+    {   // is_satisfied_using_one_shot_check (src/plonk.rs:137) on the device
+        CheckArgs ca;
+        ca.values = d_values; ca.n = (uint32_t)N; ca.num_inputs = (uint32_t)S->num_inputs; ca.flag = d_flag;
+        for (int k = 0; k < 7; k++) ca.q[k] = S->sel_vals[k];
+        for (int j = 0; j < 4; j++) ca.vars[j] = S->gate_vars[j];
+        PLK_HIP(hipMemsetAsync(d_flag, 0, 4, st));
+        PLK_TRY(check_gates(ca, st));
+        // the verdict is read back into the pinned result buffer and looked at after round 1 has been enqueued (before any
+        // commitment is used): the host does not stall the GPU for it.  An unsatisfied witness still ends the call with
+        // PLK_ERR_UNSAT and no proof bytes — the commitments under way are drained by the FIFO guard.
+        PLK_HIP(hipMemcpyAsync(ctx->pinned, d_flag, 4, hipMemcpyDeviceToHost, st));
+        if (!ctx->flag_ready) PLK_HIP(hipEventCreateWithFlags(&ctx->flag_ready, hipEventDisableTiming));
+        PLK_HIP(hipEventRecord(ctx->flag_ready, st));
+    }
+    PLK_TRY(gather4_dual(W.w_vals, W.w_coef, d_values, S->gate_vars, (uint32_t)N, st));
+    ProveFront F;
+    F.inputs.swap(inputs);
+    F.t_prev = t_prev;
+    return prove_rounds(ctx, S, W, F, proof_out, cap, len);
+}
+
+
+// ---- the assembled-input path: SetupPolynomials (src/plonk.rs:50-55,104) and prove_by_steps on a circuit bellman has synthesised
+//      (src/plonk.rs:152-159) — the setup polynomials and the four wire columns come from the caller, not from this library's transpiler
+static int32_t setup_polys_impl(plk_ctx *ctx, uint64_t n, uint64_t num_inputs, const plk_fr *const selectors[6], const plk_fr *next_step,
+                                const plk_fr *const sigmas[4], uint64_t len, uint32_t flags, plk_setup **out) {
+    if (!ctx || !selectors || !next_step || !sigmas || !out) { set_error("plk_setup_from_polynomials: bad argument"); return PLK_ERR_ARG; }
+    *out = nullptr;
+    const plk_fr *src[11];
+    for (int k = 0; k < 6; k++) src[k] = selectors[k];
+    src[6] = next_step;
+    for (int j = 0; j < 4; j++) src[7 + j] = sigmas[j];
+    for (int i = 0; i < 11; i++) if (!src[i]) { set_error("plk_setup_from_polynomials: a selector or sigma vector is NULL"); return PLK_ERR_ARG; }
+    if (flags & ~PLK_POLY_VALUES) { set_error("plk_setup_from_polynomials: unknown flag bits"); return PLK_ERR_ARG; }
+    const uint64_t N = n + 1;
+    if (N < 2 || (N & (N - 1))) { set_error("setup power of two is not in the correct range (n + 1 must be a power of two)"); return PLK_ERR_SIZE; }
+    uint32_t log_n = 0;
+    while ((1ull << log_n) < N) log_n++;
+    if (log_n + 2 > MAX_LOG_N) { set_error("setup power of two is not in the correct range"); return PLK_ERR_SIZE; }   // src/plonk.rs:109-112
+    const bool values = (flags & PLK_POLY_VALUES) != 0;
+    if (values ? len != N : (len == 0 || len > N)) {
+        set_error(values ? "plk_setup_from_polynomials: value form needs len == N = n + 1 evaluations per vector"
+                         : "plk_setup_from_polynomials: coefficient form needs 1 <= len <= N = n + 1");
+        return PLK_ERR_ARG;
+    }
+    if (num_inputs > n) { set_error("plk_setup_from_polynomials: num_inputs exceeds n"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<plk_setup, void (*)(plk_setup *)> S(new plk_setup(), plk_setup_free);
+    S->n = n; S->N = N; S->log_n = log_n; S->num_inputs = num_inputs; S->n_real = n;
+    S->from_polys = true;
+    hipStream_t st = ctx->stream;
+    // no variable-index columns, no permutation sort, no witness records: 22 vectors of N (the circuit path adds 4 x N x 4 B of indices)
+    PLK_TRY(S->store.reserve(22 * ((N * sizeof(Fr) + 255) & ~(size_t)255) + 256));
+    Arena A{&S->store};
+    for (int k = 0; k < 7; k++) S->sel_coef[k] = A.take<Fr>(N);
+    for (int k = 0; k < 7; k++) S->sel_vals[k] = A.take<Fr>(N);
+    for (int j = 0; j < 4; j++) S->sig_coef[j] = A.take<Fr>(N);
+    for (int j = 0; j < 4; j++) S->sig_vals[j] = A.take<Fr>(N);
+    uint32_t *flag = A.take<uint32_t>(64);
+    // given form -> the other one: coefficients get one forward NTT each (the values the gate check and round 2 read), values one iNTT each
+    Fr *given[11], *derived[11];
+    for (int k = 0; k < 7; k++) { given[k] = values ? S->sel_vals[k] : S->sel_coef[k]; derived[k] = values ? S->sel_coef[k] : S->sel_vals[k]; }
+    for (int j = 0; j < 4; j++) { given[7 + j] = values ? S->sig_vals[j] : S->sig_coef[j]; derived[7 + j] = values ? S->sig_coef[j] : S->sig_vals[j]; }
+    PLK_HIP(hipMemsetAsync(flag, 0, 4, st));
+    for (int i = 0; i < 11; i++) {                               // pageable copies: the caller's buffers are not page-locked
+        PLK_HIP(hipMemcpyAsync(given[i], src[i], len * sizeof(Fr), hipMemcpyHostToDevice, st));
+        if (len < N) PLK_HIP(hipMemsetAsync(given[i] + len, 0, (N - len) * sizeof(Fr), st));
+    }
+    PLK_TRY(check_canonical(given, 11, len, flag, st));
+    for (int i = 0; i < 11; i++) PLK_HIP(hipMemcpyAsync(derived[i], given[i], N * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+    // (four transforms per launch where the batch scratch is small, one at a time above, as the circuit path's setup does)
+    if (log_n <= 22) for (int i = 0; i < 11; i += 4) PLK_TRY(ntt_batch_dev(ctx, derived + i, 11 - i < 4 ? 11 - i : 4, log_n, values, nullptr, st, 0));
+    else for (int i = 0; i < 11; i++) PLK_TRY(ntt_dev(ctx, derived[i], log_n, values, nullptr, st));
+    uint32_t bad = 0;
+    PLK_HIP(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st));
+    PLK_HIP(hipStreamSynchronize(st));
+    if (bad) {
+        static const char *const names[11] = {"q_a", "q_b", "q_c", "q_d", "q_m", "q_const", "q_d_next", "sigma_1", "sigma_2", "sigma_3", "sigma_4"};
+        std::string which;
+        for (int i = 0; i < 11; i++) if (bad >> i & 1) { which += which.empty() ? "" : ", "; which += names[i]; }
+        set_error("plk_setup_from_polynomials: " + which + " holds an element that is not a canonical residue (limbs >= r)");
+        return PLK_ERR_ARG;
+    }
+    *out = S.release();
+    return PLK_OK;
+}
+
+// the assembled front end: columns a, b, c, d (rows values each, zero beyond) -> w_vals / w_coef, gate check, public inputs = a[0, num_inputs)
+static int32_t prove_assembled_impl(plk_ctx *ctx, const plk_setup *S, const void *const cols[4], bool on_device, uint64_t rows,
+                                    uint8_t *proof_out, uint64_t cap, uint64_t *len, hipStream_t caller) {
+    const std::string who = on_device ? "plk_prove_assembled_dev" : "plk_prove_assembled";
+    if (!ctx || !S || !cols || !proof_out || !len) { set_error(who + ": bad argument"); return PLK_ERR_ARG; }
+    *len = 0;
+    for (int j = 0; j < 4; j++) if (!cols[j]) { set_error(who + ": a column pointer is NULL"); return PLK_ERR_ARG; }
+    if (rows < S->num_inputs || rows > S->N) { set_error(who + ": rows must satisfy num_inputs <= rows <= N"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    if (!ctx->srs || (!ctx->combine && ctx->srs_n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
+    if (!S->store.p) { set_error(who + ": the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
+    PLK_TRY(fifo_must_be_empty(ctx, who.c_str()));
+    FifoGuard fifo_guard(ctx);
+    ctx->timings.clear();
+    ctx->trace.valid = false;
+    ProveFront F;
+    F.assembled = true;
+    F.close_perm = true;
+    F.t_prev = now_ms();
+    hipStream_t st = ctx->stream;
+    const uint64_t N = S->N;
+    ProveWs W;
+    PLK_TRY(prove_workspace(ctx, S, 0, &W));
+    IngestArgs ia;
+    if (on_device) {
+        if (caller && caller != st) {                             // ordered after what the caller has enqueued on its stream
+            if (!ctx->in_ready) PLK_HIP(hipEventCreateWithFlags(&ctx->in_ready, hipEventDisableTiming));
+            PLK_HIP(hipEventRecord(ctx->in_ready, caller));
+            PLK_HIP(hipStreamWaitEvent(st, ctx->in_ready, 0));
+        }
+        for (int j = 0; j < 4; j++) ia.src[j] = static_cast<const Fr *>(cols[j]);
+    } else {
+        // pageable copies into the quotient's 4N scratch (free until round 3): the caller's buffers are never page-locked (see the
+        // witness note in prove_impl — pinning heap pages behind the runtime's back once ended in a GPU memory fault)
+        for (int j = 0; j < 4; j++) {
+            if (rows) PLK_HIP(hipMemcpyAsync(W.t_ext + j * N, cols[j], rows * sizeof(Fr), hipMemcpyHostToDevice, st));
+            ia.src[j] = W.t_ext + j * N;
+        }
+        const HFr *a = static_cast<const HFr *>(cols[0]);
+        F.inputs.assign(a, a + S->num_inputs);
+    }
+    { double t = now_ms(); ctx->timings.push_back(t - F.t_prev); F.t_prev = t; }     // [0] column upload
+    for (int k = 0; k < 7; k++) ia.q[k] = S->sel_vals[k];
+    for (int j = 0; j < 4; j++) { ia.vals[j] = W.w_vals[j]; ia.coef[j] = W.w_coef[j]; }
+    ia.n = (uint32_t)N; ia.rows = (uint32_t)rows; ia.num_inputs = (uint32_t)S->num_inputs; ia.flag = W.d_flag;
+    PLK_HIP(hipMemsetAsync(W.d_flag, 0, 8, st));
+    PLK_TRY(ingest_columns(ia, st));
+    // the verdict (and the public inputs of device columns) travel behind the same event as the circuit path's verdict: read after round 1
+    // has been enqueued, no extra stall
+    PLK_HIP(hipMemcpyAsync(ctx->pinned, W.d_flag, 8, hipMemcpyDeviceToHost, st));
+    if (on_device && S->num_inputs) {
+        PLK_TRY(ensure_pinned2(ctx, S->num_inputs * sizeof(HFr)));
+        PLK_HIP(hipMemcpyAsync(ctx->pinned2, W.w_vals[0], S->num_inputs * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        F.inputs_pinned = reinterpret_cast<const HFr *>(ctx->pinned2);
+    }
+    if (!ctx->flag_ready) PLK_HIP(hipEventCreateWithFlags(&ctx->flag_ready, hipEventDisableTiming));
+    PLK_HIP(hipEventRecord(ctx->flag_ready, st));
+    return prove_rounds(ctx, S, W, F, proof_out, cap, len);
+}
+
 // ---- tracing / test hooks: the vectors between the rounds, and the polynomial helpers of rounds 2, 4 and 5 on their own
 int32_t plk_prove_trace(plk_ctx *ctx, uint32_t which, plk_fr *out_host, uint64_t cap, uint64_t *n) {
     if (!ctx || !n || which >= 9) { set_error("plk_prove_trace: bad argument"); return PLK_ERR_ARG; }
@@ -1008,6 +1222,21 @@ int32_t plk_setup_write_vk(plk_ctx *ctx, const plk_setup *s, const uint8_t g2_by
 int32_t plk_prove(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
     PLK_TRY(not_a_worker(ctx, "plk_prove"));
     return guarded("plk_prove", PLK_ERR_HIP, [&] { return prove_impl(ctx, S, c, proof_out, cap, len); });
+}
+int32_t plk_setup_from_polynomials(plk_ctx *ctx, uint64_t n, uint64_t num_inputs, const plk_fr *const selectors[6], const plk_fr *next_step_selector,
+                                   const plk_fr *const sigmas[4], uint64_t len, uint32_t flags, plk_setup **out) {
+    return guarded("plk_setup_from_polynomials", PLK_ERR_HIP, [&] { return setup_polys_impl(ctx, n, num_inputs, selectors, next_step_selector, sigmas, len, flags, out); });
+}
+int32_t plk_prove_assembled(plk_ctx *ctx, const plk_setup *s, const plk_fr *const columns[4], uint64_t rows, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    PLK_TRY(not_a_worker(ctx, "plk_prove_assembled"));
+    return guarded("plk_prove_assembled", PLK_ERR_HIP, [&] {
+        return prove_assembled_impl(ctx, s, reinterpret_cast<const void *const *>(columns), false, rows, proof_out, cap, len, nullptr); });
+}
+int32_t plk_prove_assembled_dev(plk_ctx *ctx, const plk_setup *s, const void *const columns_dev[4], uint64_t rows, uint8_t *proof_out, uint64_t cap,
+                                uint64_t *len, void *stream) {
+    PLK_TRY(not_a_worker(ctx, "plk_prove_assembled_dev"));
+    return guarded("plk_prove_assembled_dev", PLK_ERR_HIP, [&] {
+        return prove_assembled_impl(ctx, s, columns_dev, true, rows, proof_out, cap, len, (hipStream_t)stream); });
 }
 int32_t plk_comm_serve(plk_ctx *ctx, uint64_t *batches) {
     if (batches) *batches = 0;

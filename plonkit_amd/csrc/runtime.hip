@@ -206,6 +206,7 @@ void plk_destroy(plk_ctx *ctx) {
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned2) (void)hipHostFree(ctx->pinned2);
     if (ctx->flag_ready) (void)hipEventDestroy(ctx->flag_ready);
+    if (ctx->in_ready) (void)hipEventDestroy(ctx->in_ready);
     if (ctx->bg_go) (void)hipEventDestroy(ctx->bg_go);
     if (ctx->bg_done) (void)hipEventDestroy(ctx->bg_done);
     if (ctx->bg_stream) (void)hipStreamDestroy(ctx->bg_stream);
