@@ -100,7 +100,8 @@ PLK_HD Fp<PR> pack(const W9<WP> &a) {
     return r;
 }
 
-// carry propagation: limbs (any u32, total value < 2^261) -> limbs < 2^29
+// carry propagation: limbs (<= 2^32 - 8: a carry is at most 7 and limb + carry must fit 32 bits; total value < 2^261) -> limbs < 2^29.
+// (The lazy butterflies of ntt.hip feed in x + PAD2 - y + c, limbs < 3.74e9.)  Pinned at 2^32 - 8 by tests/test_arith_kat_host.py.
 template <class WP>
 PLK_HD W9<WP> normw(const W9<WP> &a) {
     W9<WP> r;

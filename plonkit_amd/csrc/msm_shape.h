@@ -43,8 +43,8 @@ struct MsmParams {
 
 struct ScalarSet { const Fr *v[MSM_MAX_BATCH]; };
 
-// ---- scalar recoding shared by msm.hip (fused pre-phase) and msm_small.hip
-__device__ __forceinline__ uint32_t extract_bits(const uint32_t *k, uint32_t pos, uint32_t c) {
+// ---- scalar recoding shared by msm.hip (fused pre-phase) and msm_small.hip (host-callable too: tests/host/arith_kat.hip runs them on the CPU and on the GPU)
+PLK_HD uint32_t extract_bits(const uint32_t *k, uint32_t pos, uint32_t c) {
     uint32_t limb = pos >> 5, off = pos & 31;
     if (limb >= 8) return 0;
     uint64_t v = k[limb];
@@ -53,7 +53,7 @@ __device__ __forceinline__ uint32_t extract_bits(const uint32_t *k, uint32_t pos
 }
 constexpr int RC_WINDOWS = 15;                      // 17-bit windows over the 254-bit scalars
 // the signed digits of msm_digits for c = 17, 15 windows, in registers: d[w] in [-2^16, 2^16], top window unsigned
-__device__ __forceinline__ void recode17(const Fr &k, int32_t (&d)[RC_WINDOWS]) {
+PLK_HD void recode17(const Fr &k, int32_t (&d)[RC_WINDOWS]) {
     uint32_t carry = 0;
 #pragma unroll
     for (uint32_t w = 0; w < RC_WINDOWS; w++) {

@@ -1,7 +1,9 @@
 """The lazy 9 x 29-bit field layer and the XYZZ group law built on it (plonkit_amd/csrc/field29_dev.h, ec29_dev.h) compiled
 for the HOST and compared with the 8 x 32-bit layer on random inputs: products, squarings, fused sums, lazy add/sub
 chains, zero tests, the quotient-estimate reduction, and a random walk of mixed additions / doublings / full additions
-including P + P and P - P.  No GPU involved (hipcc only compiles); the GPU suite pins both layers to the oracle."""
+including P + P and P - P.  No GPU involved (hipcc only compiles); the GPU suite pins both layers to the oracle end to end.
+This test compares the two layers with EACH OTHER on the host.  What pins each primitive to an independent reference (Python integers), on directed
+operands, and the DEVICE build of the same functions to the host build limb for limb, is tests/test_arith_kat_host.py and tests/test_gpu_arith_kat.py."""
 import os
 import shutil
 import subprocess

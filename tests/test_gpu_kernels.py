@@ -424,6 +424,60 @@ def test_batches_in_flight(ctx, srs16):
     assert all(np.array_equal(g, s) for g, s in zip(got, single + single[:1]))
 
 
+def _overflow_batch(n):
+    """four scalar vectors of n terms for one batch: uniform | the constant column of test_msm_short_path_list_overflow (its bucket lists overflow) |
+    half constant, half uniform (overflows too) | uniform with a sparse half.  Returns (lists of ints, trapdoor answers)."""
+    rep = sum(3 << (17 * w) for w in range(5)) + sum((7 << 8) << (17 * w) for w in range(6, 11))
+    rng = random.Random(7000 + n)
+    kss = [[rng.randrange(R_MOD) for _ in range(n)],
+           [rep] * n,
+           [rep if i % 2 else rng.randrange(R_MOD) for i in range(n)],
+           [0 if i < n // 2 else rng.randrange(R_MOD) for i in range(n)]]
+    return kss, [_trapdoor(ks) for ks in kss]
+
+
+@pytest.mark.parametrize("n", [300, 3000, 4096, 10000, 1 << 15])
+def test_msm_short_path_list_overflow_inside_a_batch(ctx, srs16, n):
+    """the overflow fallback of msm_finish_batch re-runs the ordinary pipeline (or, below 4096 terms, the per-term double-and-add) with the arguments it
+    captured at enqueue time: here the overflowing vectors sit in a batch BETWEEN vectors that do not overflow, so the fallback must pick the right scalar
+    vector of the batch and leave its neighbours' results alone.  Every result against the tau = 42 trapdoor answer."""
+    import torch
+    ctx.srs_upload(srs16)
+    kss, want = _overflow_batch(n)
+    ts = [torch.from_numpy(ol.fr_vec(ks).view(np.int64)).to("cuda:0") for ks in kss]
+    torch.cuda.synchronize()
+    got = ctx.msm_batch_dev(ts, n)
+    for k in range(len(kss)):
+        assert np.array_equal(np.asarray(got[k]), want[k]), (n, k)
+    got = ctx.msm_batch_dev(ts[1:3], n)                              # every vector of the batch overflows
+    assert np.array_equal(np.asarray(got[0]), want[1]) and np.array_equal(np.asarray(got[1]), want[2]), n
+
+
+@pytest.mark.parametrize("n", [3000, 10000])
+def test_msm_short_path_list_overflow_with_another_batch_in_flight(ctx, srs16, n):
+    """the same batch enqueued while another batch is in flight, and the other way round, finished in order: the fallback of the first finish runs the
+    ordinary pipeline while the second batch's kernels are queued or running, and must neither disturb it nor read its scratch."""
+    import torch
+    import plonkit_amd as pa
+    ctx.srs_upload(srs16)
+    kss, want = _overflow_batch(n)
+    rng = random.Random(8000 + n)
+    other = [[rng.randrange(R_MOD) for _ in range(n)] for _ in range(2)]
+    other_want = [_trapdoor(ks) for ks in other]
+    ts = [torch.from_numpy(ol.fr_vec(ks).view(np.int64)).to("cuda:0") for ks in kss]
+    to = [torch.from_numpy(ol.fr_vec(ks).view(np.int64)).to("cuda:0") for ks in other]
+    torch.cuda.synchronize()
+    for first, first_want, second, second_want in ((to, other_want, ts, want), (ts, want, to, other_want), (ts, want, ts, want)):
+        ctx.msm_enqueue_batch_dev(first, n)
+        ctx.msm_enqueue_batch_dev(second, n)
+        a = ctx.msm_finish_batch(len(first))
+        b = ctx.msm_finish_batch(len(second))
+        for k in range(len(first)):
+            assert np.array_equal(pa.g1_sum_jacobian(a[k]), first_want[k]), (n, "first", k)
+        for k in range(len(second)):
+            assert np.array_equal(pa.g1_sum_jacobian(b[k]), second_want[k]), (n, "second", k)
+
+
 def test_ntt_twiddle_table_cap_evicts_idle_tables_and_composes_when_full():
     """ntt.hip keeps the inter-pass twiddles of a (direction, digit plan) as a table, under a cap (PLK_NTT_DIRECT_CAP_MB).  With a
     64 MB cap: 2^20 transforms (32 MB per table, forward + inverse fill the cap) stay bit-exact against the oracle when a 2^21
