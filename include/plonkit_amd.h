@@ -135,6 +135,32 @@ int32_t plk_msm_g1_finish_batch_sharded(plk_ctx *ctx, plk_g1_affine *out, uint32
 /* tracing hook: HIP events around the bucket-accumulation kernel of the last MSM (bench roofline) */
 int32_t plk_set_kernel_timing(plk_ctx *ctx, int32_t on);
 int32_t plk_msm_last_kernel_ms(plk_ctx *ctx, float *accumulate_ms);
+/* DIAGNOSTIC, not part of the computing interface: which dispatch shape the commitment (or batch) finished last on this context
+ * took — what tests/test_gpu_msm_shapes.py asserts before it looks at the result, so that a moved threshold fails loudly instead
+ * of silently shifting what a test covers.  Plain integers stored in the commitment's slot where the decisions are made (at
+ * enqueue; the fallback of a short commitment at its finish): no launch, no synchronisation, no device memory.  The values
+ * name internals that may change with any release.  PLK_ERR_ARG before the first finished commitment.                      */
+enum { PLK_MSM_PATH_EMPTY = 0,           /* zero terms: nothing was launched                                                   */
+       PLK_MSM_PATH_NAIVE = 1,           /* one double-and-add per term (fewer than 4096 terms and the short path not wanted)  */
+       PLK_MSM_PATH_SHORT = 2,           /* the short-commitment kernels (all 15 table copies)                                 */
+       PLK_MSM_PATH_SHORT_FALLBACK = 3,  /* short, a bucket list overflowed, run again by the kernels the other fields describe */
+       PLK_MSM_PATH_ORDINARY = 4 };      /* the bucket pipeline                                                                */
+typedef struct plk_msm_shape {
+    uint32_t path;                       /* PLK_MSM_PATH_*                                                                     */
+    uint32_t batch;                      /* commitments sharing the launches                                                   */
+    uint32_t table_copies;               /* shifted copies of the key a commitment addresses: 15, 5, 3 or 1                    */
+    /* the bucket pipeline only (0 on the naive and short paths, and for a fallback of fewer than 4096 terms):                 */
+    uint32_t window_bits, windows;       /* c and floor(254 / c) + 1                                                           */
+    uint32_t bucket_sets;                /* per commitment: windows / table_copies                                             */
+    uint32_t fine_bits, coarse_bins;     /* buckets per task = 2^fine_bits; bins per bucket set                                */
+    uint32_t accumulate_variant;         /* 0 equal pieces per lane, 1 the one-wave measurement build, 2 lanes own buckets     */
+    uint32_t prephase;                   /* 1 recoding fused with the partition (digits stay in registers), 2 through the digit array */
+    uint32_t reduce_lanes;               /* per task of the bucket reduction: 4 = quads of lanes (one wave per task), 16 or 32 lanes */
+    /* the last call of plk_msm_g1 / _dev / _partial_dev, if no other commitment finished since (otherwise 1 and the length):  */
+    uint32_t pieces;                     /* passes the call was cut into; the other fields describe the last of them           */
+    uint64_t piece_terms;                /* terms per pass (the last one may be shorter)                                       */
+} plk_msm_shape;
+int32_t plk_msm_last_shape(plk_ctx *ctx, plk_msm_shape *out);
 
 /* ---- Crs::<Lagrange>::from_powers (src/plonk.rs:179-185): inverse NTT over G1 (dump-lagrange)  */
 int32_t plk_g1_intt(plk_ctx *ctx, const plk_g1_affine *in_host, uint32_t log_n, plk_g1_affine *out_host);

@@ -100,6 +100,15 @@ def _stream(s):
     return ctypes.c_void_p(int(s))
 
 
+MSM_PATHS = ("empty", "naive", "short", "short_fallback", "ordinary")      # PLK_MSM_PATH_*
+
+
+class MsmShape(ctypes.Structure):
+    """plk_msm_shape (include/plonkit_amd.h)"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("path", "batch", "table_copies", "window_bits", "windows", "bucket_sets", "fine_bits", "coarse_bins",
+                                               "accumulate_variant", "prephase", "reduce_lanes", "pieces")] + [("piece_terms", ctypes.c_uint64)]
+
+
 class Context:
     """plk_ctx: one GPU.  Mirrors where the reference builds `Worker::new()` (src/plonk.rs:41,47,183)."""
 
@@ -254,6 +263,15 @@ class Context:
         v = ctypes.c_float(0)
         _check(lib().plk_msm_last_kernel_ms(self._h, ctypes.byref(v)))
         return v.value
+
+    def msm_last_shape(self):
+        """diagnostic (plk_msm_last_shape): the dispatch shape of the commitment finished last, as a dict of the struct's fields;
+        `path` is one of MSM_PATHS"""
+        v = MsmShape()
+        _check(lib().plk_msm_last_shape(self._h, ctypes.byref(v)))
+        d = {name: int(getattr(v, name)) for name, _ in MsmShape._fields_}
+        d["path"] = MSM_PATHS[d["path"]]
+        return d
 
     # ---- NTT
     def ntt(self, data, log_n, inverse=False, coset=None):

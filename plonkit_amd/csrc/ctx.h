@@ -111,10 +111,13 @@ struct plk_ctx {
         const void *fb_bases = nullptr, *fb_scalars[8] = {nullptr};
         uint64_t fb_srs_n = 0, fb_n = 0;
         uint32_t fb_copies = 0, fb_cbits = 0, fb_nbits = 0;
+        plk_msm_shape shape = {};            // which kernels this commitment was given (plk_msm_last_shape: diagnostic, host integers only)
     } slot[MSM_SLOTS];
     uint64_t msm_enq = 0, msm_fin = 0;       // FIFO counters; commitment number k lives in slot[fifo[k % MSM_SLOTS]]
     uint8_t fifo[MSM_SLOTS] = {};
-    uint32_t last_slot = 0;                  // slot of the commitment finished last (plk_msm_last_kernel_ms)
+    uint32_t last_slot = 0;                  // slot of the commitment finished last (plk_msm_last_kernel_ms, plk_msm_last_shape)
+    uint32_t call_pieces = 0;                // plk_msm_g1_partial_dev: passes of its last call, their length, and msm_fin when it returned
+    uint64_t call_piece_terms = 0, call_fin = 0;
     MsmSlot &front_slot() { return slot[fifo[msm_fin % MSM_SLOTS]]; }
     plk::DevBuf prove_ws;                    // workspace of the prover rounds (grows only)
     plk::DevBuf poly_tmp, poly_tmp2;         // scan block totals / evaluation partials

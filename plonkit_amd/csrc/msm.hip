@@ -908,7 +908,9 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
     }
     // PLK_MSM_FUSED_RECODE=0 (A/B knob): the three-launch pre-phase through the digit array, as for several bucket sets
     static const bool fused_ok = [] { const char *e = getenv("PLK_MSM_FUSED_RECODE"); return !(e && e[0] == '0'); }();
-    if (fused_ok && p.groups == 1 && p.c == 17 && p.windows == RC_WINDOWS && p.nbins <= 1024) {
+    uint32_t shape_variant = 0, shape_lanes = 0;              // (what S.shape reports, noted where it is decided)
+    const uint32_t shape_prephase = (fused_ok && p.groups == 1 && p.c == 17 && p.windows == RC_WINDOWS && p.nbins <= 1024) ? 1u : 2u;
+    if (shape_prephase == 1) {
         // one bucket set per commitment (the 2^20 shape): digits never leave the registers (msm_recode_count / _scatter)
         const uint32_t cblocks = (uint32_t)((n + (uint64_t)RC_THREADS * RC_COUNT_PER - 1) / ((uint64_t)RC_THREADS * RC_COUNT_PER));
         const uint32_t sblocks = (uint32_t)((n + RC_SCALARS - 1) / RC_SCALARS);
@@ -943,6 +945,7 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
         // commitments of <= 2^16 terms: the build whose lanes own the buckets of an evenly filled task (msm_accumulate.hip; PLK_MSM_OWNED_MAX overrides, 0 = never)
         static const long long owned_max = [] { const char *e = getenv("PLK_MSM_OWNED_MAX"); return e ? (long long)strtoull(e, nullptr, 10) : (1ll << 16); }();
         const int variant = one_wave ? 1 : (FB == 6 && (long long)n <= owned_max ? 2 : 0);
+        shape_variant = (uint32_t)variant;
         msm_accumulate_launch(FB, variant, max_tasks, stream, bases, (const uint32_t *)entries, (const uint32_t *)bin_start, (const uint32_t *)task_start, partials, task_meta, p);
         if (ctx->ev_on) (void)hipEventRecord(S.ev[1], stream);
         (void)hipEventRecord(S.acc_done, stream);
@@ -954,14 +957,17 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
         //  commitments — whose reductions share the GPU with the next accumulation — pays for: three in flight at 2^16 terms 0.243 -> 0.255 ms, measured)
         // and ONE bucket set (above 2^20 terms a commitment has 3 or 5: 5120 tasks are five waves of quads per SIMD — 0.71 ms at 2^22 terms against ~0.45 lane-wise)
         if (tr_quad && probe_rl == 0 && total_sets == 1 && ctx->msm_enq == ctx->msm_fin) {
+            shape_lanes = 4;
             hipLaunchKernelGGL((msm_fold_hot<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
             hipLaunchKernelGGL((msm_task_reduce_quad<FB>), dim3((max_tasks + MSM_THREADS / 64 - 1) / (MSM_THREADS / 64)), dim3(MSM_THREADS), 0, stream,
                                (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins, early_exit);
         } else if (rl_log == 4) {
+            shape_lanes = 16;
             hipLaunchKernelGGL((msm_fold_hot<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
             hipLaunchKernelGGL((msm_task_reduce<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
                                (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins, early_exit);
         } else {
+            shape_lanes = 32;
             hipLaunchKernelGGL((msm_fold_hot<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
             hipLaunchKernelGGL((msm_task_reduce<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
                                (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins, early_exit);
@@ -984,6 +990,10 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
     S.windows = p.groups;
     S.c_bits = p.c;
     S.fine_bits = p.fine_bits;
+    plk_msm_shape &sh = S.shape;                              // diagnostic record (plk_msm_last_shape): the decisions taken above
+    sh.table_copies = copies; sh.window_bits = p.c; sh.windows = p.windows; sh.bucket_sets = p.groups;
+    sh.fine_bits = p.fine_bits; sh.coarse_bins = p.nbins;
+    sh.accumulate_variant = shape_variant; sh.prephase = shape_prephase; sh.reduce_lanes = shape_lanes;
     return PLK_OK;
 }
 
@@ -1046,11 +1056,14 @@ int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t b
     S.windows = 0;
     S.batch = batch;
     S.small = false;
+    S.shape = plk_msm_shape{};
+    S.shape.batch = batch; S.shape.pieces = 1; S.shape.piece_terms = n;
     if (n == 0) { (void)hipEventRecord(S.acc_done, stream); in_flight(); return PLK_OK; }
     BigArgs A{bases, ctx->srs_n, copies, c_bits, nbits, ScalarSet{}, batch, n};
     for (uint32_t m = 0; m < batch; m++) A.set.v[m] = scalars_dev[m];
     if (n < 4096 && !small) {
         PLK_TRY(msm_naive_launch(S, stream, A));
+        S.shape.path = PLK_MSM_PATH_NAIVE; S.shape.table_copies = 1;
         in_flight();
         return PLK_OK;
     }
@@ -1059,12 +1072,14 @@ int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t b
         PLK_TRY(slot_pinned(S, (size_t)MSM_MAX_BATCH * SM_PLANES_HOST * sizeof(G1Xyzz) + 16));
         PLK_TRY(msm_small_launch(S, stream, bases, (uint32_t)ctx->srs_n, A.set, batch, (uint32_t)n, ctx->ev_on, S.pinned));
         S.small = true;
+        S.shape.path = PLK_MSM_PATH_SHORT; S.shape.table_copies = copies;
         S.fb_bases = bases; S.fb_srs_n = ctx->srs_n; S.fb_n = n; S.fb_copies = copies; S.fb_cbits = c_bits; S.fb_nbits = nbits;
         for (uint32_t m = 0; m < batch; m++) S.fb_scalars[m] = scalars_dev[m];
         in_flight();
         return PLK_OK;
     }
     PLK_TRY(msm_big_launch(ctx, S, stream, A));
+    S.shape.path = PLK_MSM_PATH_ORDINARY;
     in_flight();
     return PLK_OK;
 }
@@ -1101,6 +1116,7 @@ int32_t msm_finish_batch(plk_ctx *ctx, hipStream_t, host::HJac *out) {
             BigArgs A{static_cast<const G1Affine *>(S.fb_bases), S.fb_srs_n, S.fb_copies, S.fb_cbits, S.fb_nbits, ScalarSet{}, S.batch, S.fb_n};
             for (uint32_t m = 0; m < S.batch; m++) A.set.v[m] = static_cast<const Fr *>(S.fb_scalars[m]);
             S.small = false;
+            S.shape.path = PLK_MSM_PATH_SHORT_FALLBACK;
             if (S.fb_n < 4096) PLK_TRY(msm_naive_launch(S, S.stream, A)); else PLK_TRY(msm_big_launch(ctx, S, S.stream, A));
             PLK_HIP(hipStreamSynchronize(S.stream));
         }
@@ -1229,7 +1245,7 @@ int32_t plk_msm_g1_partial_dev(plk_ctx *ctx, const void *scalars_dev, uint64_t n
     const bool pipelined = pipe_piece != 0 && ctx->msm_enq == ctx->msm_fin;
     if (n <= PIECE && !pipelined) {
         PLK_TRY(plk_msm_g1_enqueue_dev(ctx, scalars_dev, n, base_offset, stream));
-        return plk_msm_g1_finish(ctx, out);
+        return plk_msm_g1_finish(ctx, out);                   // (one pass: the slot's own record says so)
     }
     if (!ctx || !scalars_dev || !out) { set_error("plk_msm_g1: bad argument"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
@@ -1253,6 +1269,7 @@ int32_t plk_msm_g1_partial_dev(plk_ctx *ctx, const void *scalars_dev, uint64_t n
         if (rc == PLK_OK) acc = host::jac_add(acc, j);
     }
     if (rc != PLK_OK) return rc;
+    ctx->call_pieces = (uint32_t)((n + piece - 1) / piece); ctx->call_piece_terms = piece; ctx->call_fin = ctx->msm_fin;
     memcpy(out->x, acc.x.l, 32); memcpy(out->y, acc.y.l, 32); memcpy(out->z, acc.z.l, 32);
     return PLK_OK;
 }
@@ -1337,6 +1354,15 @@ int32_t plk_msm_last_kernel_ms(plk_ctx *ctx, float *accumulate_ms) {
     if (!S.ev[0]) { set_error("the last commitment was enqueued with kernel timing off"); return PLK_ERR_ARG; }
     PLK_HIP(hipEventSynchronize(S.ev[1]));
     PLK_HIP(hipEventElapsedTime(accumulate_ms, S.ev[0], S.ev[1]));
+    return PLK_OK;
+}
+
+// diagnostic: the record the last finished commitment's slot was given at enqueue (host integers only)
+int32_t plk_msm_last_shape(plk_ctx *ctx, plk_msm_shape *out) {
+    if (!ctx || !out) { set_error("plk_msm_last_shape: bad argument"); return PLK_ERR_ARG; }
+    if (ctx->msm_fin == 0) { set_error("plk_msm_last_shape: no commitment finished yet"); return PLK_ERR_ARG; }
+    *out = ctx->slot[ctx->last_slot].shape;
+    if (ctx->call_pieces && ctx->call_fin == ctx->msm_fin) { out->pieces = ctx->call_pieces; out->piece_terms = ctx->call_piece_terms; }
     return PLK_OK;
 }
 

@@ -29,19 +29,20 @@ def _rand_fr(n, seed):
     return a
 
 
-@pytest.mark.parametrize("log_n", [1, 2, 3, 5, 8, 10, 11, 12, 13, 14, 16, 18])
+@pytest.mark.parametrize("log_n", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 18, 19])
 def test_ntt_matches_oracle(ctx, log_n):
     a = _rand_fr(1 << log_n, 100 + log_n)
     assert np.array_equal(ctx.ntt(a, log_n), ol.ntt(a, log_n))
     assert np.array_equal(ctx.ntt(a, log_n, inverse=True), ol.ntt(a, log_n, inverse=True))
 
 
-@pytest.mark.parametrize("log_n", [11, 13, 14, 15, 16, 18, 20])
+@pytest.mark.parametrize("log_n", [11, 13, 14, 15, 16, 17, 18, 19, 20, 21])
 def test_ntt_extreme_residues(ctx, log_n):
     """the lazy bounds of the butterflies at their worst inputs (random vectors of `_rand_fr` stay below 2^252): every element r - 1, r - 1
     alternating with 0 at stride 1 and at the stride of the first pass, residues within 2^16 of r, and all zeros — plain, inverse and
-    coset transforms against the oracle.  The sizes cover every pass shape: the old kernels (2^11, 6-bit passes of 2^13) and the wave-owned
-    ones at 7 + 7, 8 + 7, 8 + 8, 9 + 9 and 10 + 10 bits."""
+    coset transforms against the oracle.  The sizes cover every pass shape of the one- and two-pass plans: the old kernels (2^11, 6-bit passes of 2^13) and the
+    wave-owned ones at 7 + 7, 8 + 7, 8 + 8, 9 + 8 (2^17), 9 + 9, 10 + 9 (2^19), 10 + 10 and, on the 4096-element tile with sixteen waves, 11 + 10 bits (2^21).
+    The three-pass plans (2^22, 2^23, 2^25) see the same inputs against closed forms in tests/test_gpu_large.py."""
     n = 1 << log_n
     top = np.array(ol.int_to_limbs(R_MOD - 1), dtype=np.uint64)
     cases = [np.tile(top, (n, 1))]
@@ -60,7 +61,7 @@ def test_ntt_extreme_residues(ctx, log_n):
         assert np.array_equal(ctx.ntt(a, log_n, coset=ol.fr_mont(7)), ol.ntt(a, log_n, coset=7))
 
 
-@pytest.mark.parametrize("log_n", [3, 9, 12, 15, 17])
+@pytest.mark.parametrize("log_n", [3, 9, 12, 15, 17, 19, 21])
 def test_coset_ntt_and_roundtrip(ctx, log_n):
     a = _rand_fr(1 << log_n, 7 + log_n)
     g = ol.fr_mont(7)
@@ -71,14 +72,14 @@ def test_coset_ntt_and_roundtrip(ctx, log_n):
     assert np.array_equal(ctx.ntt(a, log_n, inverse=True, coset=ol.fr_mont(other)), ol.ntt(a, log_n, inverse=True, coset=other))
 
 
-@pytest.mark.parametrize("log_n", [20, 22])
+@pytest.mark.parametrize("log_n", [20, 21, 22, 23, 25])
 def test_ntt_large_properties(ctx, log_n):
-    """full BASELINE size: oracle parity at 2^20, plus size-independent properties (round trip,
-    linearity, evaluation at a point)."""
+    """full BASELINE size and every plan above it that nothing else runs (2^21 = 11 + 10 on the 4096-element tile, 2^23 = 9 + 7 + 7,
+    2^25 = 9 + 8 + 8): oracle parity up to 2^21, plus size-independent properties (round trip, linearity, evaluation at a point)."""
     n = 1 << log_n
     a, b = _rand_fr(n, 1), _rand_fr(n, 2)
     fa = ctx.ntt(a, log_n)
-    if log_n <= 20:
+    if log_n <= 21:
         assert np.array_equal(fa, ol.ntt(a, log_n))
     assert np.array_equal(ctx.ntt(fa, log_n, inverse=True), a)
     fb = ctx.ntt(b, log_n)

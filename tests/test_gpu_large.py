@@ -122,6 +122,95 @@ def test_ntt_up_to_the_two_adicity_of_fr(log_n):
     torch.cuda.empty_cache()
 
 
+@pytest.mark.parametrize("log_n", [22, 23, 25])
+def test_ntt_worst_case_residues_above_the_oracle_sizes(log_n):
+    """the inputs the lazy bounds of the butterflies were written for, at the three-pass plans the oracle cannot re-run in test time: 2^22 = 8 + 7 + 7 and
+    2^23 = 9 + 7 + 7 (ntt_pass_cols in the middle) and 2^25 = 9 + 8 + 8.  EVERY output element is compared, on the device, against a closed form
+    (raw residues: a vector of limbs a_j transforms to sum_j a_j x_k^j mod r whatever domain the limbs are read in):
+      constant r - 1        forward: n (r - 1) at index 0, zero elsewhere; inverse: r - 1 at index 0; coset 7: (r - 1)(7^n - 1) / (7 w^k - 1) at every k
+                            (one batch inversion in the oracle's C arithmetic); inverse coset: r - 1 at index 0
+      r - 1 at even j       forward: (r - 1) n / 2 at 0 and n / 2; inverse: (r - 1) / 2 at 0 and n / 2; coset 7: (r - 1)(7^n - 1) / (49 w^2k - 1);
+                            inverse coset: (r - 1) / 2 at 0 and (r - 1) / 2 * 7^(-n/2) at n / 2
+      all zero              zero
+    and every transform followed by its inverse returns the input.  Residues within 2^16 of r (a 4096-element pattern, tiled): evaluation at eight
+    indices against the oracle's Horner, plain and on the coset, and the round trips."""
+    import torch
+    import plonkit_amd as pa
+    ctx = pa.Context(0)
+    n = 1 << log_n
+    w = ol.omega(log_n)
+    top = R_MOD - 1
+    inv2, rinv = pow(2, -1, R_MOD), pow(ol.MONT_R, -1, R_MOD)
+    g = ol.fr_mont(7)
+
+    def dev(a):
+        t = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to("cuda:0")
+        torch.cuda.synchronize()                                   # the library runs on its own stream
+        return t
+
+    def spikes(items):
+        t = torch.zeros((n, 4), dtype=torch.int64, device="cuda:0")
+        for idx, val in items:
+            t[idx] = torch.from_numpy(ol.int_to_limbs(val % R_MOD).view(np.int64).copy()).to("cuda:0")
+        torch.cuda.synchronize()
+        return t
+
+    def coset_dense(base, first):
+        """(r - 1)(7^n - 1) / (first * base^k - 1) for every k, as raw residues"""
+        den = ol.vadd_scalar(ol.vpowers(base, n, first), R_MOD - 1)
+        return dev(ol.vscale(ol.vbatch_inv(den), top * (pow(7, n, R_MOD) - 1) % R_MOD * rinv % R_MOD))
+
+    def check(src, inverse, coset, want, what):
+        x = src.clone()
+        torch.cuda.synchronize()
+        ctx.ntt_dev(x, log_n, inverse=inverse, coset=coset)
+        ctx.synchronize()
+        assert torch.equal(x, want), what
+        ctx.ntt_dev(x, log_n, inverse=not inverse, coset=coset)
+        ctx.synchronize()
+        assert torch.equal(x, src), what + ", and back"
+        del x
+
+    const = dev(np.tile(ol.int_to_limbs(top), (n, 1)))
+    check(const, False, None, spikes([(0, n * top)]), "constant r - 1")
+    check(const, True, None, spikes([(0, top)]), "constant r - 1, inverse")
+    check(const, True, g, spikes([(0, top)]), "constant r - 1, inverse coset")
+    check(const, False, g, coset_dense(w, 7), "constant r - 1, coset 7")
+    del const
+    alt = np.zeros((n, 4), dtype=np.uint64)
+    alt[::2] = ol.int_to_limbs(top)
+    even = dev(alt)
+    del alt
+    check(even, False, None, spikes([(0, top * (n // 2)), (n // 2, top * (n // 2))]), "r - 1 at even indices")
+    check(even, True, None, spikes([(0, top * inv2), (n // 2, top * inv2)]), "r - 1 at even indices, inverse")
+    check(even, True, g, spikes([(0, top * inv2), (n // 2, top * inv2 % R_MOD * pow(7, -(n // 2), R_MOD))]), "r - 1 at even indices, inverse coset")
+    check(even, False, g, coset_dense(w * w % R_MOD, 49), "r - 1 at even indices, coset 7")
+    del even
+    zero = torch.zeros((n, 4), dtype=torch.int64, device="cuda:0")
+    for inverse in (False, True):
+        for coset in (None, g):
+            check(zero, inverse, coset, zero, "all zero")
+    del zero
+    rng = np.random.default_rng(log_n)
+    near = ol.ints_to_array([R_MOD - 1 - int(x) for x in rng.integers(0, 1 << 16, size=1 << 12)])
+    a = np.ascontiguousarray(np.tile(near, (n >> 12, 1)))
+    src = dev(a)
+    for coset in (None, 7):
+        x = src.clone()
+        torch.cuda.synchronize()
+        ctx.ntt_dev(x, log_n, coset=ol.fr_mont(coset) if coset else None)
+        ctx.synchronize()
+        for k in (0, 1, 2, 977, n // 3, n // 2, n - 2, n - 1):
+            assert ol.fr_ints(x[k:k + 1].cpu().numpy().view(np.uint64))[0] == ol.poly_eval(a, (coset or 1) * pow(w, k, R_MOD) % R_MOD), (k, coset)
+        ctx.ntt_dev(x, log_n, inverse=True, coset=ol.fr_mont(coset) if coset else None)
+        ctx.synchronize()
+        assert torch.equal(x, src), coset
+        del x
+    del src
+    ctx.close()
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize("log_n", [24, 26])
 def test_ntt_recursive_prover_shapes(log_n):
     """NTT 2^24 (N) and 2^26 (4N) of the recursive circuit: round trip, linearity, evaluation at four points"""
