@@ -270,6 +270,35 @@ int32_t plk_key_parse(const uint8_t *data, uint64_t len, plk_g1_affine *points, 
 int32_t plk_key_serialize(const plk_g1_affine *points, uint64_t n, const uint8_t g2[256], uint8_t *out, uint64_t cap, uint64_t *len);
 void plk_crs42_g2_bytes(uint8_t out[256]);        /* G2 section of Crs::crs_42: {G2, 42*G2} */
 
+/* ---- SRS key files on the GPU: Crs::read straight into HBM and Crs::write straight out of it (src/reader.rs:67-89;
+ *      src/bin/main.rs:341,379).  The 64-byte points are decoded, range- and curve-checked (and encoded) by kernels; the
+ *      host only moves file bytes.  A point is refused exactly when plk_key_parse refuses it (pairing_ce's into_affine:
+ *      flag bits, x, y < q, y^2 = x^3 + 3; BN254's G1 has cofactor 1, no subgroup check). */
+#define PLK_KEY_LAGRANGE 1u   /* the Lagrange-form slot (plk_srs_lagrange_*) instead of the monomial one */
+/* Crs::read.  `data`/`len` = the whole key file in host memory (pageable is fine).  Container checks, codes and words exactly as
+ * plk_key_parse.  EVERY point of the file is checked, whatever slice is kept.  Kept resident: points [first, first + count)
+ * (count = 0: all from `first`) — a rank's slice.  *n_out = points in the file.  A refused point: PLK_ERR_FORMAT with
+ * plk_key_parse's words ("read key err: point not on curve"), *bad_out = the LOWEST refused index (UINT64_MAX if none), and the
+ * context's resident key(s) and MSM table(s) are exactly what they were before the call.  first > n, first + count > n, an empty
+ * slice, unknown flag bits, null ctx / data / n_out: PLK_ERR_ARG.  A context whose key is lent (plk_ctx_share_srs): PLK_ERR_ARG,
+ * as plk_srs_upload.  Device memory beyond the kept points: the file goes up in chunks of plk_key_chunk_points() = 2^20 points
+ * through two 64 MiB buffers (copy k + 1 beside kernel k) that stay in the context's staging arena — at most 144 MiB with the
+ * arena's slack, whatever the size of the key — and the previous key lives until the new one is complete.                     */
+int32_t plk_srs_load_key(plk_ctx *ctx, const uint8_t *data, uint64_t len, uint64_t first, uint64_t count, uint32_t flags,
+                         uint64_t *n_out, uint8_t g2_out[256], uint64_t *bad_out /* may be NULL */);
+/* Crs::write: the resident key (or the Lagrange-form one) as key-file bytes, through the same two buffers; out == NULL only
+ * reports len.  No key of that form resident: PLK_ERR_SRS.                                                                      */
+int32_t plk_srs_store_key(plk_ctx *ctx, uint32_t flags, const uint8_t g2[256], uint8_t *out, uint64_t cap, uint64_t *len);
+/* the two kernels on device pointers (16-byte aligned, else PLK_ERR_ARG), ordered on `stream` like every _dev call.  decode
+ * returns its verdict, so it waits for `stream`: PLK_ERR_FORMAT and *bad_out = lowest refused index (points_dev then holds
+ * infinity at every refused index), else *bad_out = UINT64_MAX.  One decode at a time per context.                             */
+int32_t plk_g1_decode_dev(plk_ctx *ctx, const void *bytes_dev, uint64_t n, void *points_dev, uint64_t *bad_out /* may be NULL */, void *stream);
+int32_t plk_g1_encode_dev(plk_ctx *ctx, const void *points_dev, uint64_t n, void *bytes_dev, void *stream);
+uint64_t plk_key_chunk_points(void);              /* points per staging chunk of plk_srs_load_key / plk_srs_store_key */
+/* Crs::<Lagrange>::from_powers (src/plonk.rs:179-185) without leaving the device: the G1 iNTT of the first 2^log_n resident
+ * points becomes the context's Lagrange-form key (`dump-lagrange` = this + plk_srs_store_key(PLK_KEY_LAGRANGE)).               */
+int32_t plk_srs_lagrange_from_powers(plk_ctx *ctx, uint32_t log_n);
+
 /* ---- RollingKeccakTranscript (src/plonk.rs:10,140,152; spec contrib/template.sol:267-307) ---- */
 typedef struct { uint8_t state0[32], state1[32]; uint32_t counter; } plk_transcript;
 void plk_transcript_init(plk_transcript *t);

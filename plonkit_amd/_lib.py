@@ -45,6 +45,8 @@ def lib():
         L.plk_last_error.restype = ctypes.c_char_p
         L.plk_version.restype = ctypes.c_char_p
         L.plk_srs_size.restype = ctypes.c_uint64
+        if hasattr(L, "plk_key_chunk_points"):
+            L.plk_key_chunk_points.restype = ctypes.c_uint64
         if hasattr(L, "plk_setup_domain_size"):
             L.plk_setup_domain_size.restype = ctypes.c_uint64
         _lib = L
@@ -255,6 +257,47 @@ class Context:
         out = np.zeros((n, 8), dtype=np.uint64)
         _check(lib().plk_srs_download(self._h, ctypes.c_uint64(offset), ctypes.c_uint64(n), _np(out)))
         return out
+
+    # ---- key files on the GPU (Crs::read / Crs::write): the points are decoded, checked and encoded by kernels
+    def srs_load_key(self, data, first=0, count=0, lagrange=False):
+        """key-file bytes -> resident key (points [first, first + count) of it; count = 0: all from `first`); every point of the
+        file is checked.  Returns (points in the file, the 256 G2 bytes).  A refused point raises PlkError with `.bad_index` = the
+        lowest refused index, and the resident key stays what it was."""
+        buf = np.frombuffer(data, dtype=np.uint8)                     # bytes, bytearray, memoryview, uint8 array: no copy
+        n, bad, g2 = ctypes.c_uint64(0), ctypes.c_uint64(0), np.zeros(256, dtype=np.uint8)
+        rc = lib().plk_srs_load_key(self._h, _np(buf), ctypes.c_uint64(buf.size), ctypes.c_uint64(first), ctypes.c_uint64(count),
+                                    ctypes.c_uint32(1 if lagrange else 0), ctypes.byref(n), _np(g2), ctypes.byref(bad))
+        if rc != 0:
+            e = PlkError(rc, last_error())
+            e.bad_index = bad.value if bad.value != 2**64 - 1 else None
+            raise e
+        return n.value, g2.tobytes()
+
+    def srs_store_key(self, g2_bytes, lagrange=False):
+        """the resident key (or the Lagrange-form one) as key-file bytes"""
+        g2 = np.frombuffer(bytes(g2_bytes), dtype=np.uint8)
+        assert g2.shape == (256,)
+        flags, n = ctypes.c_uint32(1 if lagrange else 0), ctypes.c_uint64(0)
+        _check(lib().plk_srs_store_key(self._h, flags, _np(g2), None, ctypes.c_uint64(0), ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        _check(lib().plk_srs_store_key(self._h, flags, _np(g2), _np(out), ctypes.c_uint64(n.value), ctypes.byref(n)))
+        return out.tobytes()
+
+    def g1_decode_dev(self, bytes_ptr, n, points_ptr, stream=None):
+        """n x 64 file bytes -> n x G1 affine on the device; raises PlkError (`.bad_index`) if a point is refused"""
+        bad = ctypes.c_uint64(0)
+        rc = lib().plk_g1_decode_dev(self._h, _devptr(bytes_ptr), ctypes.c_uint64(n), _devptr(points_ptr), ctypes.byref(bad), _stream(stream))
+        if rc != 0:
+            e = PlkError(rc, last_error())
+            e.bad_index = bad.value if bad.value != 2**64 - 1 else None
+            raise e
+
+    def g1_encode_dev(self, points_ptr, n, bytes_ptr, stream=None):
+        _check(lib().plk_g1_encode_dev(self._h, _devptr(points_ptr), ctypes.c_uint64(n), _devptr(bytes_ptr), _stream(stream)))
+
+    def srs_lagrange_from_powers(self, log_n):
+        """Crs::<Lagrange>::from_powers on the device: G1 iNTT of the first 2^log_n resident points -> the Lagrange-form key"""
+        _check(lib().plk_srs_lagrange_from_powers(self._h, ctypes.c_uint32(log_n)))
 
     def set_kernel_timing(self, on=True):
         _check(lib().plk_set_kernel_timing(self._h, ctypes.c_int32(1 if on else 0)))

@@ -250,28 +250,27 @@ static int serve_owner(plk_ctx *ctx) {
     fprintf(stderr, "served %llu batches of commitments\n", (unsigned long long)batches);
     return 0;
 }
-// a key file read and checked on the host (Crs::read: every point on the curve): no GPU needed, so the single-process commands do it on a
-// thread of its own WHILE the HIP runtime initialises (0.06 s of the 0.24 s the GPU side of `prove` used to take at the 2^20 domain)
-struct ParsedKey { std::vector<plk_g1_affine> pts; uint64_t n = 0; uint8_t g2[256]; };
+// a key file read and its container checked on the host: no GPU needed, so the single-process commands do it on a thread of its own
+// WHILE the HIP runtime initialises.  The points themselves (Crs::read: every one range- and curve-checked) are decoded by
+// plk_srs_load_key's kernels once the context exists: the host only moves the file's bytes.
+struct ParsedKey { std::vector<uint8_t> raw; uint64_t n = 0; uint8_t g2[256]; };
 static void parse_key(const std::string &path, bool lagrange, ParsedKey *k) {
     const char *what = lagrange ? "read key_lagrange_form err" : "read key_monomial_form err";
-    std::vector<uint8_t> raw = slurp(path, what);
-    CK(what, plk_key_parse(raw.data(), raw.size(), nullptr, 0, &k->n, k->g2));
-    k->pts.resize(k->n);
-    CK(what, plk_key_parse(raw.data(), raw.size(), k->pts.data(), k->n, &k->n, k->g2));
+    k->raw = slurp(path, what);
+    CK(what, plk_key_parse(k->raw.data(), k->raw.size(), nullptr, 0, &k->n, k->g2));
 }
-// uploads the key; with several ranks only this rank's slice [rank * N/world, (rank + 1) * N/world) of its first N points
+// decodes, checks and keeps the key; with several ranks only this rank's slice [rank * N/world, (rank + 1) * N/world) of its first N
+// points is kept (every point of the file is checked all the same)
 static void upload_key(plk_ctx *ctx, const ParsedKey &k, bool lagrange, const Ranks &rk = Ranks(), uint64_t N = 0) {
     const char *what = lagrange ? "read key_lagrange_form err" : "read key_monomial_form err";
-    const plk_g1_affine *first = k.pts.data();
-    uint64_t n = k.n;
+    uint64_t first = 0, count = 0, n = 0;
     if (rk.world > 1) {
-        if (n < N) fatal(101, std::string(what) + ": key has " + std::to_string(n) + " points, the domain needs " + std::to_string(N));
-        first += (uint64_t)rk.rank * (N / rk.world);
-        n = N / rk.world;
+        if (k.n < N) fatal(101, std::string(what) + ": key has " + std::to_string(k.n) + " points, the domain needs " + std::to_string(N));
+        first = (uint64_t)rk.rank * (N / rk.world);
+        count = N / rk.world;
     }
-    if (lagrange) CK("srs upload", plk_srs_lagrange_upload(ctx, first, n));
-    else CK("srs upload", plk_srs_upload(ctx, first, n));
+    uint8_t g2[256];
+    CK(what, plk_srs_load_key(ctx, k.raw.data(), k.raw.size(), first, count, lagrange ? PLK_KEY_LAGRANGE : 0, &n, g2, nullptr));
 }
 static void load_key(plk_ctx *ctx, const std::string &path, uint8_t g2[256], bool lagrange = false, const Ranks &rk = Ranks(), uint64_t N = 0) {
     ParsedKey k;
@@ -301,15 +300,13 @@ static int run(int argc, char **argv) {
         phase("plk_create (HIP init)");
         uint64_t n = 1ull << power;
         CK("crs_42", plk_srs_generate(ctx, n, 0, 42));
-        std::vector<plk_g1_affine> pts(n);
-        CK("srs download", plk_srs_download(ctx, 0, n, pts.data()));
-        phase("crs_42 + download");
+        phase("crs_42");
         uint8_t g2[256]; plk_crs42_g2_bytes(g2);
         uint64_t len = 0;
-        CK("serialize", plk_key_serialize(pts.data(), n, g2, nullptr, 0, &len));
+        CK("serialize", plk_srs_store_key(ctx, 0, g2, nullptr, 0, &len));
         std::vector<uint8_t> bytes(len);
-        CK("serialize", plk_key_serialize(pts.data(), n, g2, bytes.data(), len, &len));
-        phase("serialize");
+        CK("serialize", plk_srs_store_key(ctx, 0, g2, bytes.data(), len, &len));
+        phase("encode (GPU) + download");
         refuse_duplicate(a, out, "srs_monomial_form");
         spit(out, bytes.data(), len);
         phase("file written");
@@ -317,7 +314,7 @@ static int run(int argc, char **argv) {
     } else if (cmd == "dump-lagrange") {                             // src/bin/main.rs:360-381
         Args a = parse(argc, argv, {{"m", "srs_monomial_form"}, {"l", "srs_lagrange_form"}, {"c", "circuit"}});
         phase("start");
-        // as in `prove`: HIP initialisation and the key (read + parse + upload) on a second thread while this one parses the circuit; of the setup
+        // as in `prove`: HIP initialisation and the key (read, then decode + check on the GPU) on a second thread while this one parses the circuit; of the setup
         // only the domain size is needed (plk_circuit_domain_size: transpile, no columns, no device work) — round 6, 0.55 -> 0.43 s at the 2^20 domain
         const std::string key_path = a.get("srs_monomial_form");
         uint8_t g2[256];
@@ -348,15 +345,13 @@ static int run(int argc, char **argv) {
         phase("HIP init + key (other thread)");
         uint32_t log_n = 0; while ((1ull << log_n) < N) log_n++;
         if (plk_srs_size(ctx) < N) { fprintf(stderr, "SRS too small for the circuit domain\n"); return 101; }
-        std::vector<plk_g1_affine> mono(N), lag(N);
-        CK("srs download", plk_srs_download(ctx, 0, N, mono.data()));
-        CK("from_powers", plk_g1_intt(ctx, mono.data(), log_n, lag.data()));
-        phase("download + G1 iNTT");
+        CK("from_powers", plk_srs_lagrange_from_powers(ctx, log_n));     // resident monomial key -> resident Lagrange-form key
+        phase("G1 iNTT (resident)");
         uint64_t len = 0;
-        CK("serialize", plk_key_serialize(lag.data(), N, g2, nullptr, 0, &len));
+        CK("serialize", plk_srs_store_key(ctx, PLK_KEY_LAGRANGE, g2, nullptr, 0, &len));
         std::vector<uint8_t> bytes(len);
-        CK("serialize", plk_key_serialize(lag.data(), N, g2, bytes.data(), len, &len));
-        phase("serialize");
+        CK("serialize", plk_srs_store_key(ctx, PLK_KEY_LAGRANGE, g2, bytes.data(), len, &len));
+        phase("encode (GPU) + download");
         std::string out = a.get("srs_lagrange_form");
         refuse_duplicate(a, out, "srs_lagrange_form");
         spit(out, bytes.data(), len);
@@ -375,7 +370,7 @@ static int run(int argc, char **argv) {
             plk_ctx *gpu_ctx = nullptr;
             std::thread gpu([&gpu_err, &gpu_ctx, &g2, rk, key_path] {
                 worker_guard(&gpu_err, [&] {
-                    ParsedKey key;                                      // read + checked beside the HIP initialisation
+                    ParsedKey key;                                      // read beside the HIP initialisation
                     Fatal key_err{0, ""};
                     std::thread reader([&] { worker_guard(&key_err, [&] { parse_key(key_path, false, &key); }); });
                     JoinOnExit reader_guard{reader};
@@ -429,7 +424,7 @@ static int run(int argc, char **argv) {
         // proof bytes (src/plonk.rs:138-146); an empty or missing option means "monomial only" as in the reference
         const std::string lag = a.get("srs_lagrange_form", "");
         if (single) {
-            // the GPU side of the start-up (HIP initialisation, key parse + upload, fixed-base table of the MSM) runs on a
+            // the GPU side of the start-up (HIP initialisation, key read + GPU decode/check, fixed-base table of the MSM) runs on a
             // second thread while this one parses the circuit and the witness: neither needs the other until the setup
             const std::string key_path = a.get("srs_monomial_form");   // (a missing option exits here, on the main thread)
             Fatal gpu_err{0, ""};
@@ -439,7 +434,7 @@ static int run(int argc, char **argv) {
                     const bool tm = getenv("PLK_CLI_TIMING") != nullptr;
                     double t0 = now_s(), t1;
                     auto lap = [&](const char *what) { if (tm) { t1 = now_s(); fprintf(stderr, "[timing]   gpu thread: %-24s +%.3f s\n", what, t1 - t0); t0 = t1; } };
-                    ParsedKey key, lkey;                                // read + checked beside the HIP initialisation
+                    ParsedKey key, lkey;                                // read beside the HIP initialisation
                     Fatal key_err{0, ""};
                     std::thread reader([&] { worker_guard(&key_err, [&] { parse_key(key_path, false, &key); if (!lag.empty()) parse_key(lag, true, &lkey); }); });
                     JoinOnExit reader_guard{reader};
@@ -450,7 +445,7 @@ static int run(int argc, char **argv) {
                     memcpy(g2, key.g2, 256);
                     upload_key(gpu_ctx, key, false);
                     if (!lag.empty()) upload_key(gpu_ctx, lkey, true);
-                    lap("key upload (read + parse ran beside HIP init)");
+                    lap("key: copy + decode/check (GPU)");
                     CK("srs precompute", plk_srs_precompute(gpu_ctx));
                     lap("MSM table");
                 });
@@ -480,7 +475,7 @@ static int run(int argc, char **argv) {
             const uint64_t N = plk_setup_domain_size(s);
             load_key(ctx, a.get("srs_monomial_form"), g2, false, rk, N);
             if (!lag.empty()) { uint8_t g2l[256]; load_key(ctx, lag, g2l, true, rk, N); }
-            phase("load key (parse + upload)");
+            phase("load key (read + GPU decode/check)");
             if (worker) return serve_owner(ctx);
         }
         if (!s) {

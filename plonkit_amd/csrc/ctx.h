@@ -122,6 +122,7 @@ struct plk_ctx {
     plk::DevBuf prove_ws;                    // workspace of the prover rounds (grows only)
     plk::DevBuf poly_tmp, poly_tmp2;         // scan block totals / evaluation partials
     plk::DevBuf stage;                       // host<->device staging for the host-pointer API
+    plk::DevBuf key_bad;                     // keyio.hip: the verdict word of plk_g1_decode_dev (lowest refused index)
     void *pinned = nullptr;                  // small pinned host buffer for results
     size_t pinned_cap = 0;
     void *pinned2 = nullptr;                 // pinned staging of the prover's temporaries
