@@ -8,6 +8,7 @@ Python owns the operands and the expected answers.  Every expected value comes f
     subk(a, b)        = A + k*p - B        neg2(a) = 2p - A        normw / pack / unpack keep the integer
     csub_p, reduce_full, reduce_small, s_from_w: the canonical residue
     curve operations: a plain affine BN254 group law; XYZZ results are brought to affine with integers (x = X/ZZ, y = Y/ZZZ, ZZ^3 == ZZZ^2)
+    g1_mul_scalar*(b, k) = k * b with that group law: every base is m * (1, 2) for a known m, so the expected point is (k m mod r) * (1, 2)
 
 where A is the integer value of a limb vector (sum l[i] * 2^(29 i) on the lazy layer, 2^(32 i) on the packed one).  generate() builds the groups
 from a fixed seed, write_cases() / read_results() speak the program's file format, check_group() compares one group and raises an AssertionError
@@ -32,7 +33,11 @@ MULTW3_X_LIMB_MAX = 3600000000
 LAMBDA = 0x30644e72e131a029048b6e193fd84104cc37a73fec2bc5e9b8ca0b2d36636f23     # glv_dev.h
 CHAIN_STEPS = 32
 RANDOM_CASES = 4096
-KAT_PARTS = 9                           # translation units of arith_kat.hip (KAT_PART)
+KAT_PARTS = 12                          # translation units of arith_kat.hip (KAT_PART)
+MAX_LOG_N = 28                          # the 2-adicity of r - 1: the largest transform
+# glv_dev.h: the reduced lattice basis (A1, -B1N), (A2, B2) of {(a, b): a + b lambda = 0 mod r}
+GLV_A1, GLV_B1N = 0x6f4d8248eeb859fc8211bbeb7d4f1128, 0x89d3256894d213e3
+GLV_A2, GLV_B2 = 0x89d3256894d213e3, 0x6f4d8248eeb859fd0be4e1541221250b
 
 # name: (id, in_words, out_words, fields, device_only)       (the same table as KAT_OPS in arith_kat.hip; the program refuses a group that disagrees)
 OPS = {
@@ -52,14 +57,17 @@ OPS = {
     "E_XYZZ_ADD_MIXED": (60, 49, 32, (1,), False), "E_XYZZ_ADD": (61, 64, 32, (1,), False), "E_XYZZ_DOUBLE": (62, 32, 32, (1,), False),
     "E_XYZZW_ADD_MIXED": (63, 55, 36, (1,), False), "E_XYZZW_ADD": (64, 72, 36, (1,), False), "E_XYZZW_DOUBLE": (65, 36, 36, (1,), False),
     "E_XYZZW_DOUBLE_AFFINE": (66, 18, 36, (1,), False), "E_XYZZW_ADD_MIXED_SPECIAL": (67, 73, 36, (1,), False),
-    "E_XYZZW_CHAIN": (68, 140, 36 * CHAIN_STEPS, (1,), False),
+    "E_XYZZW_CHAIN": (68, 140, 36 * CHAIN_STEPS, (1,), False), "E_XYZZW_ADD_MIXED_OS": (76, 55, 36, (1,), False),
     "E_XYZZW_EXPORT": (69, 36, 32, (1,), True), "E_XYZZW_STORE_LOAD": (70, 36, 72, (1,), True),
     "Q_ADD_DIST": (71, 72, 36, (1,), True),
     "Q_DISTRIBUTE_GATHER0": (72, 144, 144, (1,), True), "Q_DISTRIBUTE_GATHER1": (73, 144, 144, (1,), True),
     "Q_DISTRIBUTE_GATHER2": (74, 144, 144, (1,), True), "Q_DISTRIBUTE_GATHER3": (75, 144, 144, (1,), True),
     "G_GLV_SPLIT": (80, 8, 12, (0,), False), "G_GLV_DIGITS": (81, 5, 6, (0,), False), "G_GLV_DIGITS4": (82, 5, 6, (0,), False),
     "G_RECODE17": (83, 8, 15, (0,), False), "G_EXTRACT_BITS": (84, 10, 1, (0,), False),
+    # g1_mul_dev.h: an XyzzW base (Fq) and a canonical Fr scalar; filed under Fq like the other point operations
+    "G_MUL_SCALAR": (85, 44, 36, (1,), True), "G_MUL_SCALAR_ISO": (86, 44, 36, (1,), True), "G_MUL_SCALAR_ISO8": (87, 44, 36, (1,), True),
 }
+MUL_OPS = ("G_MUL_SCALAR", "G_MUL_SCALAR_ISO", "G_MUL_SCALAR_ISO8")
 
 
 # ------------------------------------------------------------------------------------ limbs <-> integers
@@ -177,6 +185,41 @@ def multiple(k):
     while len(_MULTIPLES) <= k:
         _MULTIPLES.append(ec_add(_MULTIPLES[-1], (1, 2)))
     return _MULTIPLES[k]
+
+
+_FIXED_BASE = []                        # [i][j] = j * 256^i * (1, 2), j = 0 .. 255
+
+
+def g_mul(k):
+    """(k mod r) * (1, 2) by the affine group law above: one table look-up and one ec_add per byte of k"""
+    k %= R_MOD
+    if not _FIXED_BASE:
+        b = (1, 2)
+        for _ in range(32):
+            row = [None, b]
+            for _ in range(254):
+                row.append(ec_add(row[-1], b))
+            _FIXED_BASE.append(row)
+            b = ec_add(row[255], b)
+    acc = None
+    for i in range(32):
+        acc = ec_add(acc, _FIXED_BASE[i][(k >> (8 * i)) & 255])
+    return acc
+
+
+def glv_split_model(k):
+    """what glv_dev.h states glv_split computes, in integers: (|k1|, |k2|, k1 < 0, k2 < 0).  Only used to CHOOSE scalars with a given split; the
+    expected result of a multiplication never depends on it"""
+    g1, g2 = (GLV_B2 << 256) // R_MOD, (GLV_B1N << 256) // R_MOD
+    c1, c2 = (k * g1) >> 256, (k * g2) >> 256
+    k1, k2 = k - c1 * GLV_A1 - c2 * GLV_A2, c1 * GLV_B1N - c2 * GLV_B2
+    assert (k1 + k2 * LAMBDA - k) % R_MOD == 0
+    return abs(k1), abs(k2), k1 < 0, k2 < 0
+
+
+def omega(log_n):
+    """the generator of the size-2^log_n domain (Fr's multiplicative generator is 7)"""
+    return pow(7, (R_MOD - 1) >> log_n, R_MOD)
 
 
 def xyzz_words(pt, l, radix, i=0, j=0, zz_up=False, zzz_up=False, lazy=True):
@@ -418,7 +461,7 @@ CHECKERS = {
     "W_S_FROM_W": _exact_w(lambda p, i: _w(i, 0) * R256 % p * pow(R261, -1, p) % p, all_limbs=True),
     "E_XYZZ_ADD_MIXED": _chk_point_s, "E_XYZZ_ADD": _chk_point_s, "E_XYZZ_DOUBLE": _chk_point_s,
     "E_XYZZW_ADD_MIXED": _chk_point_w, "E_XYZZW_ADD": _chk_point_w, "E_XYZZW_DOUBLE": _chk_point_w, "E_XYZZW_DOUBLE_AFFINE": _chk_point_w,
-    "E_XYZZW_ADD_MIXED_SPECIAL": _chk_point_w, "E_XYZZW_CHAIN": _chk_chain, "E_XYZZW_EXPORT": _chk_export, "E_XYZZW_STORE_LOAD": _chk_store_load,
+    "E_XYZZW_ADD_MIXED_SPECIAL": _chk_point_w, "E_XYZZW_ADD_MIXED_OS": _chk_point_w, "E_XYZZW_CHAIN": _chk_chain, "E_XYZZW_EXPORT": _chk_export, "E_XYZZW_STORE_LOAD": _chk_store_load,
     "Q_ADD_DIST": _chk_point_w,
     "Q_DISTRIBUTE_GATHER0": _chk_gather, "Q_DISTRIBUTE_GATHER1": _chk_gather, "Q_DISTRIBUTE_GATHER2": _chk_gather, "Q_DISTRIBUTE_GATHER3": _chk_gather,
     "G_GLV_SPLIT": _chk_glv_split,
@@ -426,11 +469,15 @@ CHECKERS = {
     "G_GLV_DIGITS4": _digits_checker(32, 4, 6, -7, 8),
     "G_RECODE17": _chk_recode17,
     "G_EXTRACT_BITS": _chk_extract_bits,
+    # k * b; the result goes straight into the stage's xyzzw_add, so it must meet that function's operand contract: the same checks
+    "G_MUL_SCALAR": _chk_point_w, "G_MUL_SCALAR_ISO": _chk_point_w, "G_MUL_SCALAR_ISO8": _chk_point_w,
 }
 assert sorted(CHECKERS) == sorted(OPS)
 
 
 def describe_inputs(g, words):
+    if g.name in MUL_OPS:
+        return " | ".join(hexw(words[k:k + 9]) for k in range(0, 36, 9)) + " | scalar %x" % f_int(words[36:])
     if g.name[0] in "FG" or g.name.startswith("E_XYZZ_"):
         return hexw(words)
     return " | ".join(hexw(words[k:k + 9]) for k in range(0, len(words), 9))
@@ -931,11 +978,157 @@ def _scalar_groups(rng):
     return groups
 
 
+def _mixed_os_group(rng):
+    """xyzzw_add_mixed_os (g1_mul_dev.h): the mixed addition of the G1 iNTT's multiplications.  Unlike xyzzw_add_mixed it has no test for an
+    infinite q: its callers only pass table entries, so no such case is asked"""
+    q = Q_MOD
+    pt = multiple
+    g = Group("E_XYZZW_ADD_MIXED_OS", 1)
+
+    def xw(k, var):
+        l, i, j, u1, u2 = var
+        return xyzz_words(pt(k), l, R261, i, j, u1, u2)
+
+    def aff_top(k):
+        """the affine operand at the top of its range (below 1.1 q): canonical + q in the coordinates where that stays below"""
+        x, y = pt(k)[0] * R261 % q, pt(k)[1] * R261 % q
+        return int_w(x + q if 10 * x < q else x) + int_w(y + q if 10 * y < q else y)
+    liftable = [k for k in range(1, 600) if 10 * (pt(k)[0] * R261 % q) < q or 10 * (pt(k)[1] * R261 % q) < q]
+    assert len(liftable) >= 16
+    ks = [1, 2, 3, 4, 5, 7, 8, 11, 16, 17, 29, 31, 32, 33, 64, 100, 127, 128, 255, 256, 300, 500]
+    pair_list = [(1, 2), (2, 1), (3, 5), (7, 11), (16, 17), (127, 128), (255, 300), (500, 1), (5, 5), (1, 1), (33, 33), (256, 256)]
+    inf_garbage = int_w(rng.randrange(q)) + int_w(rng.randrange(q)) + int_w(0) + int_w(rng.randrange(q))
+    # acc and q distinct, equal (the doubling exit) and opposite (the cancellation exit): every representation of the accumulator contract
+    # (x, y up to 5 q above canonical, zz / zzz canonical + q, ZZ != 1), both values of neg_q, and q given as the point or as its opposite
+    for ka, kb in pair_list:
+        for var in _point_variants(rng):
+            for neg in (0, 1):
+                g.add(xw(ka, var) + aff_words(pt(kb), R261) + [neg], ec_add(pt(ka), pt(-kb) if neg else pt(kb)))
+        for var in _point_variants(rng, full=False):
+            for neg in (0, 1):
+                g.add(xw(ka, var) + aff_words(pt(-kb), R261) + [neg], ec_add(pt(ka), pt(kb) if neg else pt(-kb)))
+    # both operands at the upper ends of their ranges at once
+    for kb in liftable[:16]:
+        for ka in (kb, -kb, kb + 1):
+            for var in _point_variants(rng, full=False):
+                for neg in (0, 1):
+                    g.add(xw(ka, var) + aff_top(kb) + [neg], ec_add(pt(ka), pt(-kb) if neg else pt(kb)))
+    for kb in ks:                                                # acc at infinity: all zero, or ZZ == 0 beside arbitrary coordinates
+        for neg in (0, 1):
+            want = pt(-kb) if neg else pt(kb)
+            g.add([0] * 36 + aff_words(pt(kb), R261) + [neg], want)
+            g.add(inf_garbage + aff_words(pt(kb), R261) + [neg], want)
+    for _ in range(RANDOM_CASES):
+        ka, kb, neg = rng.randrange(1, 512), rng.randrange(1, 512), rng.randrange(2)
+        var = (rng.randrange(1, q), rng.randrange(6), rng.randrange(6), False, False)
+        g.add(xw(ka, var) + aff_words(pt(kb), R261) + [neg], ec_add(pt(ka), pt(-kb) if neg else pt(kb)))
+    return g
+
+
+def _window_extremes(bits, windows):
+    """magnitudes whose signed recoding (glv_digits4 / glv_digits) is the extreme digit in each of the low `windows` windows: +2^(bits-1) throughout
+    (every window holds 2^(bits-1), no carry), or -(2^(bits-1) - 1) throughout (the lowest window holds 2^(bits-1) + 1, each later one 2^(bits-1) plus the
+    carry of the one below; the last carry is a digit +1 in the window above)"""
+    half = 1 << (bits - 1)
+    plus = sum(half << (bits * w) for w in range(windows))
+    return plus, plus + 1
+
+
+def mul_scalars(rng):
+    """the directed scalars of the G1 multiplications, as [(k, why)].  glv_split is applied INSIDE the functions under test, so a split can only be
+    asked for through a scalar that has it; glv_split_model picks those scalars.  What that leaves out of reach, by the definition in glv_dev.h:
+    k1 = k - c1 A1 - c2 A2 with c1 <= k B2 / r, c2 <= k B1N / r and A1 B2 + A2 B1N = r, so k1 >= 0 always (neg1 is never set), and k1 = 0 only
+    for k = 0; k2 = c1 B1N - c2 B2 lies in (-B1N, B2), so a negative k2 is below 2^64 in magnitude"""
+    r = R_MOD
+    out = [(k, "small") for k in range(18)]
+    out += [(r - 1, "r-1"), (r - 2, "r-2"), ((r - 1) // 2, "(r-1)/2"), (LAMBDA, "lambda"), (LAMBDA + 1, "lambda+1"), (LAMBDA - 1, "lambda-1"),
+            (r - LAMBDA, "r-lambda"), (1 << 127, "2^127"), ((1 << 128) + 1, "2^128+1"), ((1 << 128) - 1, "2^128-1")]
+    # the halves of the split and the sign of the second one
+    assert glv_split_model(0)[:2] == (0, 0)                      # k1 == 0
+    k2_zero = [k for k in (1, 17, 1 << 64, (1 << 100) + 12345, GLV_A1 - 1, rng.randrange(1 << 120)) if glv_split_model(k)[1] == 0]
+    assert len(k2_zero) >= 5
+    out += [(k, "k2 == 0") for k in k2_zero]
+    neg2, tries = [], 0
+    while len(neg2) < 12:                                        # k2 = -j and k1 between j A1 / B1N and (r - j A2) / B2: inside the domain of the split
+        tries += 1
+        assert tries < 1000
+        j = rng.randrange(1, GLV_B1N) >> rng.choice((0, 0, 20, 60))
+        k1 = rng.randrange(j * GLV_A1 // GLV_B1N + 1, (r - j * GLV_A2) // GLV_B2)
+        k = (k1 - j * LAMBDA) % r
+        if glv_split_model(k) == (k1, j, False, True):
+            neg2.append(k)
+    out += [(k, "k2 < 0") for k in neg2]
+    assert glv_split_model(LAMBDA)[2:] == (False, False)         # k2 > 0 (with k1 > 0: the split of lambda is not (0, 1))
+    # every window at its extreme digit, each sign, in both halves at once: as many low windows as keep (k1, k2) inside the domain of the split
+    for bits, total, least in ((4, 32, 30), (3, 43, 41)):
+        for windows in range(total, 0, -1):
+            ext = _window_extremes(bits, windows)
+            ks = [(a + b * LAMBDA) % r for a in ext for b in ext]
+            if all(glv_split_model(k) == (a, b, False, False) for k, (a, b) in zip(ks, [(a, b) for a in ext for b in ext])):
+                break
+        assert windows >= least, (bits, windows)
+        out += [(k, "extreme digits, %d-bit windows" % bits) for k in ks]
+    # what the transform multiplies by: twiddles omega^-j, 1 / n, and their products (the last stage), for every domain size
+    for log_n in range(1, MAX_LOG_N + 1):
+        n = 1 << log_n
+        w_inv, n_inv = pow(omega(log_n), -1, r), pow(n, -1, r)
+        out += [(n_inv, "1/n, log_n %d" % log_n), (w_inv, "1/omega, log_n %d" % log_n), (w_inv * n_inv % r, "1/(omega n), log_n %d" % log_n)]
+        for j in sorted(set([n // 2 - 1] + [rng.randrange(n // 2) for _ in range(3)]) - {0}):
+            out += [(pow(w_inv, j, r) * n_inv % r, "omega^-%d / n, log_n %d" % (j, log_n)), (pow(w_inv, j, r), "omega^-%d, log_n %d" % (j, log_n))]
+    assert all(0 <= k < r for k, _ in out)
+    return out
+
+
+def _mul_groups(rng):
+    """g1_mul_scalar, g1_mul_scalar_iso, g1_mul_scalar_iso8 (g1_mul_dev.h): the same cases for the three.  A base is m * (1, 2) in some
+    representation, so the expected point is (k m mod r) * (1, 2)"""
+    q, r = Q_MOD, R_MOD
+    cases = []
+
+    def add(m, var, k):
+        l, i, j, u1, u2 = var
+        cases.append((xyzz_words(g_mul(m), l, R261, i, j, u1, u2) + int_f(k), g_mul(k * m)))
+
+    def top_variant():
+        """x, y at 5 q above canonical (the contract says below 6 q) and ZZ, ZZZ at canonical + q (below 1.3 q): the top of what a preceding
+        xyzzw_add or xyzzw_double may hand to a later stage"""
+        while True:
+            l = rng.randrange(2, q)
+            if 10 * (l * l % q * R261 % q) < 3 * q and 10 * (l * l * l % q * R261 % q) < 3 * q:
+                return (l, 5, 5, True, True)
+    AFFINE = (1, 0, 0, False, False)                             # as g1ntt_load leaves a point: canonical x, y, ZZ = ZZZ = 1
+    bases = [(1, AFFINE), (2, AFFINE), (rng.randrange(1, r), AFFINE), (rng.randrange(1, r), AFFINE), (r - 1, AFFINE),
+             (rng.randrange(1, r), top_variant()), (rng.randrange(1, r), top_variant()), (3, top_variant()),
+             (rng.randrange(1, r), (rng.randrange(2, q), 0, 0, False, False)), (rng.randrange(1, r), (rng.randrange(2, q), 5, 0, False, False)),
+             (rng.randrange(1, r), (rng.randrange(2, q), 0, 5, False, False))]
+    directed = mul_scalars(rng)
+    for k, _ in directed:
+        for m, var in bases:
+            add(m, var, k)
+    inf_garbage = int_w(rng.randrange(q)) + int_w(rng.randrange(q)) + int_w(0) + int_w(rng.randrange(q))
+    for k, _ in directed[:40] + [(rng.randrange(r), "") for _ in range(24)]:     # the base at infinity
+        cases.append(([0] * 36 + int_f(k), None))
+        cases.append((inf_garbage + int_f(k), None))
+    for n in range(RANDOM_CASES):
+        var = AFFINE if n % 2 == 0 else top_variant() if n % 16 == 1 else (rng.randrange(1, q), rng.randrange(6), rng.randrange(6), False, False)
+        add(rng.randrange(1, r), var, rng.randrange(r))
+    groups = []
+    for name in MUL_OPS:
+        g = Group(name, 1)
+        for words, want in cases:
+            g.add(words, want)
+        groups.append(g)
+    return groups
+
+
 def generate(device, seed=20260131):
     """all groups of a run: the host-callable primitives, plus the __device__-only ones when `device` (appended: the others are the same either way)"""
     rng = random.Random(seed)
     groups = _field_groups(0, rng) + _field_groups(1, rng) + _scalar_groups(rng)
     groups += _curve_groups(random.Random(seed + 1), device)
+    groups.append(_mixed_os_group(random.Random(seed + 2)))
+    if device:
+        groups += _mul_groups(random.Random(seed + 3))
     return groups
 
 

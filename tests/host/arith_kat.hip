@@ -1,5 +1,5 @@
 // Known-answer driver for the header-level primitives (plonkit_amd/csrc/field_dev.h, field29_dev.h, ec_dev.h, ec29_dev.h, ec29_quad_dev.h,
-// glv_dev.h, msm_shape.h).  It reads a file of cases, applies the named primitive to each case and writes the raw result limbs to an output
+// glv_dev.h, g1_mul_dev.h, msm_shape.h).  It reads a file of cases, applies the named primitive to each case and writes the raw result limbs to an output
 // file.  It checks nothing: tests/gen/arith_cases.py owns the cases and the integer model, tests/test_arith_kat_host.py and
 // tests/test_gpu_arith_kat.py build this program with hipcc, run it and compare.
 //
@@ -8,6 +8,7 @@
 // With --host the cases are looped over on the CPU (the PLK_HD functions compile for the host too); without it they are copied to the GPU and run
 // by one kernel instantiation per primitive (one case per lane, or per quad for the four-lane addition; 256-thread blocks, every lane of the last
 // block busy: the case buffers are padded with copies of the last case).  Same dispatch function, same cases, same output format either way.
+// The scalar multiplications of g1_mul_dev.h get the dynamic LDS their production kernel (g1ntt_stage) launches with: their window tables live there.
 //
 // File format, little-endian 32-bit words.  Cases: a sequence of groups { op, field, count, in_words, out_words, count * in_words words }.
 // Results: the same groups with count * out_words words each.  field: 0 = Fr / FrW, 1 = Fq / FqW.  Operands are stored limb by limb in the order of
@@ -15,6 +16,7 @@
 // G1Xyzz = 32, G1Affine = 16, a bool or a 32-bit integer = 1 word, a 64-bit integer = 2.
 #include "ec29_quad_dev.h"
 #include "glv_dev.h"
+#include "g1_mul_dev.h"
 #include "msm_shape.h"
 #include <cstdio>
 #include <cstdlib>
@@ -79,11 +81,15 @@ constexpr int CHAIN_STEPS = 32;
     X(Q_DISTRIBUTE_GATHER1, 73, 144, 144, 2, 1, 4, 8) \
     X(Q_DISTRIBUTE_GATHER2, 74, 144, 144, 2, 1, 4, 8) \
     X(Q_DISTRIBUTE_GATHER3, 75, 144, 144, 2, 1, 4, 8) \
+    X(E_XYZZW_ADD_MIXED_OS, 76, 55,  36, 2, 0, 1, 3) \
     X(G_GLV_SPLIT,          80, 8,   12, 1, 0, 1, 8) \
     X(G_GLV_DIGITS,         81, 5,   6,  1, 0, 1, 8) \
     X(G_GLV_DIGITS4,        82, 5,   6,  1, 0, 1, 8) \
     X(G_RECODE17,           83, 8,   15, 1, 0, 1, 8) \
-    X(G_EXTRACT_BITS,       84, 10,  1,  1, 0, 1, 8)
+    X(G_EXTRACT_BITS,       84, 10,  1,  1, 0, 1, 8) \
+    X(G_MUL_SCALAR,         85, 44,  36, 2, 1, 1, 9) \
+    X(G_MUL_SCALAR_ISO,     86, 44,  36, 2, 1, 1, 10) \
+    X(G_MUL_SCALAR_ISO8,    87, 44,  36, 2, 1, 1, 11)
 
 enum OpId : uint32_t {
 #define X(name, id, in_w, out_w, fields, dev_only, lanes, part) name = id,
@@ -106,10 +112,10 @@ PLK_HD G1Affine get_a(const uint32_t *p) { G1Affine r; r.x = get_f<FqParams>(p);
 
 // ---- THE dispatch function: one primitive applied to one case.  OP is a template parameter, so every kernel holds one primitive.
 // `in` / `out`: this case's words (for a four-lane primitive: the quad's case, shared by its lanes); `mem`: 72 words of global memory of this
-// lane's own, 16-byte aligned; role: lane & 3 (four-lane primitives only).
+// lane's own, 16-byte aligned; role: lane & 3 (four-lane primitives only); lds: the block's dynamic shared memory (lds_bytes<OP>() of it).
 template <uint32_t OP, class PR, class WP>
-PLK_HD void apply(const uint32_t *in, uint32_t *out, uint32_t *mem, uint32_t role) {
-    (void)mem; (void)role;
+PLK_HD void apply(const uint32_t *in, uint32_t *out, uint32_t *mem, uint32_t role, uint32_t *lds) {
+    (void)mem; (void)role; (void)lds;
     // ---- field_dev.h
     if constexpr (OP == F_ADD) put_f(out, add(get_f<PR>(in), get_f<PR>(in + 8)));
     else if constexpr (OP == F_SUB) put_f(out, sub(get_f<PR>(in), get_f<PR>(in + 8)));
@@ -162,6 +168,8 @@ PLK_HD void apply(const uint32_t *in, uint32_t *out, uint32_t *mem, uint32_t rol
         xyzzw_add_mixed_special(acc, get_aw(in + 36), in[54] != 0, get_w<FqW>(in + 55), get_w<FqW>(in + 64));
         put_xw(out, acc);
     }
+    // ---- g1_mul_dev.h
+    else if constexpr (OP == E_XYZZW_ADD_MIXED_OS) { XyzzW acc = get_xw(in); xyzzw_add_mixed_os(acc, get_aw(in + 36), in[54] != 0); put_xw(out, acc); }
     else if constexpr (OP == E_XYZZW_CHAIN) {                      // acc | affine 0 | affine 1 | xyzz | 32 schedule words; every intermediate result is written
         XyzzW acc = get_xw(in);
         const AffW a0 = get_aw(in + 36), a1 = get_aw(in + 54);
@@ -192,6 +200,10 @@ PLK_HD void apply(const uint32_t *in, uint32_t *out, uint32_t *mem, uint32_t rol
         const XyzzW mine = get_xw(in + 36 * role);
         put_xw(out + 36 * role, quad_gather(quad_distribute<(int)(OP - Q_DISTRIBUTE_GATHER0)>(mine, role)));
     }
+    // ---- g1_mul_dev.h: the base | a canonical scalar below r; the window table of the lane is in the block's LDS, as in g1ntt_stage
+    else if constexpr (OP == G_MUL_SCALAR) put_xw(out, g1_mul_scalar(get_xw(in), get_f<FrParams>(in + 36), lds));
+    else if constexpr (OP == G_MUL_SCALAR_ISO) put_xw(out, g1_mul_scalar_iso(get_xw(in), get_f<FrParams>(in + 36), lds));
+    else if constexpr (OP == G_MUL_SCALAR_ISO8) put_xw(out, g1_mul_scalar_iso8(get_xw(in), get_f<FrParams>(in + 36), lds));
 #endif
     // ---- glv_dev.h, msm_shape.h
     else if constexpr (OP == G_GLV_SPLIT) {
@@ -219,11 +231,18 @@ PLK_HD void apply(const uint32_t *in, uint32_t *out, uint32_t *mem, uint32_t rol
     }
 }
 
+// dynamic LDS of a block: what g1_intt_dev launches g1ntt_stage with for the same multiplication (256 lanes wide: G1NTT_THREADS)
+template <uint32_t OP> constexpr size_t lds_bytes() {
+    return OP == G_MUL_SCALAR ? G1NTT_LDS : OP == G_MUL_SCALAR_ISO ? G1NTT_LDS_ISO : OP == G_MUL_SCALAR_ISO8 ? G1NTT_LDS_ISO8 : 0;
+}
+static_assert(G1NTT_THREADS == 256, "the kernels below are launched with 256-thread blocks");
+
 // n_padded cases (a multiple of 256 / LANES), all of them real work: no lane idles and none leaves early
 template <uint32_t OP, class PR, class WP, uint32_t IN_W, uint32_t OUT_W, uint32_t LANES>
 __global__ void __launch_bounds__(256) kat_kernel(const uint32_t *in, uint32_t *out, uint32_t *mem) {
+    extern __shared__ uint32_t kat_lds[];
     const uint32_t tid = blockIdx.x * 256u + threadIdx.x, c = tid / LANES;
-    apply<OP, PR, WP>(in + (size_t)c * IN_W, out + (size_t)c * OUT_W, mem + (size_t)tid * 72u, tid % LANES);
+    apply<OP, PR, WP>(in + (size_t)c * IN_W, out + (size_t)c * OUT_W, mem + (size_t)tid * 72u, tid % LANES, kat_lds);
 }
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fprintf(stderr, "arith_kat: %s failed: %s\n", #call, hipGetErrorString(e_)); exit(3); } } while (0)
@@ -242,7 +261,10 @@ static void run_device(const uint32_t *in, uint32_t *out, uint32_t n) {
     CK(hipMemcpy(d_in, h_in.data(), h_in.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemset(d_out, 0xee, h_out.size() * 4));
     CK(hipMemset(d_mem, 0xee, (size_t)blocks * 256 * 72 * 4));
-    hipLaunchKernelGGL((kat_kernel<OP, PR, WP, IN_W, OUT_W, LANES>), dim3(blocks), dim3(256), 0, 0, d_in, d_out, d_mem);
+    constexpr size_t lds = lds_bytes<OP>();
+    if constexpr (lds > 64 * 1024)                               // above the default limit of a launch: raised as g1_intt_dev does
+        CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kat_kernel<OP, PR, WP, IN_W, OUT_W, LANES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((kat_kernel<OP, PR, WP, IN_W, OUT_W, LANES>), dim3(blocks), dim3(256), lds, 0, d_in, d_out, d_mem);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(h_out.data(), d_out, h_out.size() * 4, hipMemcpyDeviceToHost));
@@ -252,7 +274,7 @@ static void run_device(const uint32_t *in, uint32_t *out, uint32_t n) {
 
 template <uint32_t OP, class PR, class WP, uint32_t IN_W, uint32_t OUT_W>
 static void run_host(const uint32_t *in, uint32_t *out, uint32_t n) {
-    for (uint32_t i = 0; i < n; i++) apply<OP, PR, WP>(in + (size_t)i * IN_W, out + (size_t)i * OUT_W, nullptr, 0);
+    for (uint32_t i = 0; i < n; i++) apply<OP, PR, WP>(in + (size_t)i * IN_W, out + (size_t)i * OUT_W, nullptr, 0, nullptr);
 }
 
 struct Entry {
@@ -271,7 +293,7 @@ static Entry entry(const char *name, uint32_t field) {
 // The primitives are spread over KAT_PARTS translation units so that the tests can compile them side by side: hipcc -DKAT_PART=<k> -c builds the
 // kernels and host loops of part k alone, -DKAT_MAIN -c builds main(), and the objects link into one program.  With neither macro the whole program
 // is one translation unit.
-constexpr int KAT_PARTS = 9;
+constexpr int KAT_PARTS = 12;
 template <int PART>
 static void add_part(std::vector<Entry> &t) {
 #define X(name, id, in_w, out_w, fields, dev_only, lanes, part) \
@@ -289,9 +311,11 @@ void KAT_CAT(kat_add_part_, KAT_PART)(std::vector<Entry> &t) { add_part<KAT_PART
 void kat_add_part_0(std::vector<Entry> &t); void kat_add_part_1(std::vector<Entry> &t); void kat_add_part_2(std::vector<Entry> &t);
 void kat_add_part_3(std::vector<Entry> &t); void kat_add_part_4(std::vector<Entry> &t); void kat_add_part_5(std::vector<Entry> &t);
 void kat_add_part_6(std::vector<Entry> &t); void kat_add_part_7(std::vector<Entry> &t); void kat_add_part_8(std::vector<Entry> &t);
+void kat_add_part_9(std::vector<Entry> &t); void kat_add_part_10(std::vector<Entry> &t); void kat_add_part_11(std::vector<Entry> &t);
 static std::vector<Entry> table() {
     std::vector<Entry> t;
     kat_add_part_0(t); kat_add_part_1(t); kat_add_part_2(t); kat_add_part_3(t); kat_add_part_4(t); kat_add_part_5(t); kat_add_part_6(t); kat_add_part_7(t); kat_add_part_8(t);
+    kat_add_part_9(t); kat_add_part_10(t); kat_add_part_11(t);
     return t;
 }
 #else

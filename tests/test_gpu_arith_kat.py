@@ -1,7 +1,9 @@
 """-m gpu: known answers for the header-level primitives, DEVICE run.  The same program and the same cases as tests/test_arith_kat_host.py, run by
 one kernel instantiation per primitive (one case per lane, or per quad for the four-lane addition), plus the primitives that exist on the device
 only: xyzzw_export, a store_xyzzw / load_xyzzw round trip through global memory (and the memory image it leaves), xyzzw_add_dist on the cases of the
-lane-wise addition, quad_distribute + quad_gather from each lane of the quad.  Every device result is compared with the integer model of
+lane-wise addition, quad_distribute + quad_gather from each lane of the quad, and the three scalar multiplications of the G1 inverse NTT
+(g1_mul_dev.h: g1_mul_scalar, g1_mul_scalar_iso, g1_mul_scalar_iso8, with the dynamic LDS their production kernel launches with) on bases as the
+transform's load and its earlier stages leave them and on directed scalars (tests/gen/arith_cases.py: mul_scalars).  Every device result is compared with the integer model of
 tests/gen/arith_cases.py, and with the host build's result LIMB FOR LIMB: the lazy results are not unique as residues, but they are deterministic
 functions of their inputs, so the two builds of one function must agree exactly (PLK_CHAIN, the out-of-line product of ec_dev.h and the AMDGPU
 backend's multiply-add and carry sequences are device-only code).  All comparisons are exact."""
@@ -49,3 +51,18 @@ def test_device_results_equal_the_integer_model_and_the_host_build(runs, name, f
     assert len(h) == len(o)
     for idx, (a, b) in enumerate(zip(o, h)):
         assert a == b, "%s<%s> case %d: device %s != host %s\n  operands: %s" % (name, ac.FIELD_NAME[field], idx, ac.hexw(a), ac.hexw(b), ac.describe_inputs(g, g.cases[idx]))
+
+
+def test_the_three_scalar_multiplications_agree_as_points(runs):
+    """same cases, three window tables (XYZZ; four and eight effectively affine entries on the isomorphic curve): the same point from each"""
+    groups, dev, _, _ = runs
+    by_name = dict((g.name, (g, o)) for g, o in zip(groups, dev))
+    ref_g, ref_o = by_name[ac.MUL_OPS[0]]
+    ref_pts = [ac.decode_xyzz(o, ac.R261) for o in ref_o]
+    for name in ac.MUL_OPS[1:]:
+        g, outs = by_name[name]
+        assert g.cases == ref_g.cases
+        for idx, o in enumerate(outs):
+            got = ac.decode_xyzz(o, ac.R261)
+            assert got[1] is None and got == ref_pts[idx], "%s case %d: %s, %s gives %s\n  operands: %s" % (
+                name, idx, got, ac.MUL_OPS[0], ref_pts[idx], ac.describe_inputs(g, g.cases[idx]))

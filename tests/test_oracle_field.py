@@ -137,3 +137,22 @@ def test_g1_intt_is_lagrange_basis(golden_crs):
         wi = pow(w, i, R_MOD)
         li = wi * zh % R_MOD * pow(n * (tau - wi) % R_MOD, -1, R_MOD) % R_MOD
         assert np.array_equal(out[i], ol.g1_mul(G, li))
+
+
+def test_g1_intt_on_sparse_spectra_gives_the_chosen_scalars():
+    """the reference of tests/test_gpu_g1_intt.py, validated on its own: for inputs c_j Q with c the forward transform of chosen scalars e, the
+    oracle's transform over the group returns e_i Q (infinity where e_i = 0) — inputs with equal, opposite and infinite operands at every stage"""
+    from tests.gen import g1_intt_check as gc
+    for log_n in range(7):
+        n = 1 << log_n
+        w = ol.omega(log_n)
+        for pattern in gc.SPARSE_PATTERNS:
+            pts, want, e = gc.sparse_case(log_n, pattern)
+            if log_n <= 4:                                             # the forward transform of the case builder against the definition
+                assert gc.forward_transform(e, log_n) == [sum(x * pow(w, i * j, R_MOD) for i, x in enumerate(e)) % R_MOD for j in range(n)]
+            assert [ol.g1_is_inf(p) for p in want] == [x == 0 for x in e]
+            for i in (0, n // 2, n - 1):
+                assert np.array_equal(want[i], ol.g1_mul(ol.g1_mul(ol.g1_generator(), gc.Q_SCALAR), e[i]))
+            for threads in (1, 3):
+                assert np.array_equal(ol.g1_intt(pts, log_n, threads=threads), want), (log_n, pattern)
+    assert np.array_equal(gc.sparse_case(3, "first_only")[0], np.stack([gc.sparse_case(3, "first_only")[0][0]] * 8))      # all inputs equal
