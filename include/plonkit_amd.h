@@ -299,6 +299,51 @@ uint64_t plk_key_chunk_points(void);              /* points per staging chunk of
  * points becomes the context's Lagrange-form key (`dump-lagrange` = this + plk_srs_store_key(PLK_KEY_LAGRANGE)).               */
 int32_t plk_srs_lagrange_from_powers(plk_ctx *ctx, uint32_t log_n);
 
+/* ---- structure checks of the resident key(s).  NO COUNTERPART IN THE REFERENCE: bellman's Crs::read (src/reader.rs:67-89) checks that every
+ *      point is on the curve and nothing else, and so does plk_srs_load_key.  A file of curve points that are not P_0, tau P_0, tau^2 P_0, ...
+ *      for the tau of its G2 section (truncated and padded, spliced from two ceremonies, paired with the wrong G2 section), or a Lagrange-form
+ *      key that belongs to another monomial key, loads without complaint and every proof made from it is silently invalid.  These two calls say so.
+ *
+ *      plk_srs_check.  P_0 .. P_{n-1} = the resident monomial points (the whole key or a rank's contiguous slice), g2 = {Q_0, Q_1} = the
+ *      2 x 128 bytes of the key file's G2 section.  *valid = 1 exactly when
+ *        - P_0 is not the point at infinity;
+ *        - Q_0 and Q_1 are on the twist, not infinity, and in the subgroup of order r ([r]Q = O, computed on the host inside this call: the
+ *          decoding of plk_pairing_check does not check the subgroup and BN254's G2 has a cofactor);
+ *        - every link i < n - 1 holds: e(P_{i+1}, Q_0) = e(P_i, Q_1).
+ *      The links are established by ONE random linear combination, in the ONE-COMMITMENT FORM: rho = keccak256("plk_srs_check" || seed) mod r
+ *      (hashed again while it is zero), the vector rho^i, i < n, is filled on the device, T = sum_i rho^i P_i is one pass of the commitment
+ *      pipeline (plk_msm_g1_dev), and on the host A = T - P_0, B = rho (T - rho^(n-1) P_{n-1}); accepted iff e(A, Q_0) e(-B, Q_1) = 1
+ *      (sum_{i<n-1} rho^i P_{i+1} = (T - P_0) / rho: one commitment gives both sums).  A broken link makes the error a nonzero polynomial of
+ *      degree < n in rho, so a bad key is accepted with probability <= n / r < 2^-225 (n <= 2^28).  n = 1: only the conditions on P_0 and g2.
+ *      ON A SLICE THE LINK INTO IT FROM THE PREVIOUS RANK'S LAST POINT IS NOT COVERED (and nothing ties P_0 of a slice to its global index).
+ *      seed == NULL: 32 bytes from the OS (getrandom).  The same seed gives the same rho and the same verdict; a caller who fixes the seed
+ *      BEFORE the key is chosen keeps the bound, one who publishes it first does not.
+ *      *bad_out: UINT64_MAX for a valid key; 0 when P_0 is infinity; with PLK_KEY_LOCATE on a key whose links fail, the lowest i with
+ *      P_{i+1} != tau P_i, found by bisection with the same check on sub-ranges (base_offset = lo, the same vector from index 0: at most n further
+ *      commitment terms and ~log2 n pairing checks); without the flag, or when g2 itself is refused, UINT64_MAX.
+ *      PLK_OK with *valid = 0 / 1 for every well-formed input — a wrong key is a verdict, not an error.  PLK_ERR_ARG: null ctx / g2 / valid,
+ *      unknown flag bits, a commitment still in flight on the context, a G2 encoding that is out of range or not on the twist ("G2 point not
+ *      on the twist", as plk_pairing_check).  PLK_ERR_SRS: no key resident.  PLK_ERR_SIZE: more than 2^28 points.  PLK_ERR_IO: getrandom failed.
+ *      The call only reads the key: allowed on a borrowed key (plk_ctx_share_srs) and on a plk_srs_set_dev key; the resident key(s), the
+ *      Lagrange slot and any loan are what they were.  Side effects: the MSM fixed-base table is built as by a first commitment; the vector
+ *      lives in the prover's workspace (see "Workspace" below), so plk_prove_trace has nothing to hand out until the next proof.
+ *
+ *      plk_srs_lagrange_check.  L_0 .. L_{N-1} = the Lagrange-form slot, N a power of two.  *valid = 1 iff sum_i rho^i L_i = sum_j c_j P_j with
+ *      c = iNTT_N(rho^0 .. rho^(N-1)) and rho = keccak256("plk_srs_lagrange_check" || seed) mod r: the same vector, one inverse transform
+ *      (plk_ntt_dev's), one commitment against each key, two affine points compared on the host.  No pairing: G1 has cofactor 1.  Same bound.
+ *      PLK_ERR_SRS: either key missing, or the monomial key shorter than N.  PLK_ERR_ARG: null ctx / valid, a commitment in flight, or the
+ *      context holds a slice: its first index as set by plk_set_commit_shard / plk_comm_init / plk_comm_set_shard is nonzero (tying the two
+ *      forms needs the whole prefix).  ONLY THAT INDEX IS LOOKED AT: the context does not remember that plk_srs_load_key(first != 0) or
+ *      plk_srs_generate(n, start != 0, ..) gave it a slice; such a pair of keys is simply refused (PLK_OK, *valid = 0).
+ *      PLK_ERR_SIZE: N not a power of two.
+ *      Workspace: the vector (32 B per point) and its 1 MiB table live in the prover's grows-only workspace for the duration of a call.  A call
+ *      that had to GROW that workspace frees it again before it returns (the next proof allocates what it needs), so a one-off check of a 2^26-point
+ *      key does not leave 2 GiB attached to a long-lived context; a workspace that was already large enough is reused and kept. */
+#define PLK_KEY_LOCATE 2u   /* on a refused monomial key, find the lowest broken link */
+int32_t plk_srs_check(plk_ctx *ctx, const uint8_t g2[256], const uint8_t seed[32] /* NULL: OS randomness */,
+                      uint32_t flags, int32_t *valid, uint64_t *bad_out /* may be NULL */);
+int32_t plk_srs_lagrange_check(plk_ctx *ctx, const uint8_t seed[32] /* NULL: OS randomness */, int32_t *valid);
+
 /* ---- RollingKeccakTranscript (src/plonk.rs:10,140,152; spec contrib/template.sol:267-307) ---- */
 typedef struct { uint8_t state0[32], state1[32]; uint32_t counter; } plk_transcript;
 void plk_transcript_init(plk_transcript *t);

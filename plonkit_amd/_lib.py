@@ -299,6 +299,34 @@ class Context:
         """Crs::<Lagrange>::from_powers on the device: G1 iNTT of the first 2^log_n resident points -> the Lagrange-form key"""
         _check(lib().plk_srs_lagrange_from_powers(self._h, ctypes.c_uint32(log_n)))
 
+    # ---- structure checks of the resident key(s) (keycheck.hip; the reference has no counterpart: Crs::read checks the curve equation only)
+    @staticmethod
+    def _seed(seed):
+        if seed is None:
+            return None
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("seed must be 32 bytes, got %d" % len(seed))
+        return seed
+
+    def srs_check(self, g2_bytes, seed=None, locate=False):
+        """are the resident monomial points P_0, tau P_0, tau^2 P_0, ... for the tau of the key file's G2 section `g2_bytes` (256 bytes)?
+        One random linear combination (rho from `seed`, 32 bytes; None: OS randomness), one commitment, one pairing product.  Returns
+        (valid, bad_index): bad_index is None for a valid key, 0 when P_0 is infinity, and with locate=True the lowest i with
+        P_{i+1} != tau P_i; otherwise None."""
+        g2 = bytes(g2_bytes)
+        if len(g2) != 256:
+            raise ValueError("g2_bytes must be the 256 bytes of a key file's G2 section, got %d" % len(g2))
+        valid, bad = ctypes.c_int32(0), ctypes.c_uint64(0)
+        _check(lib().plk_srs_check(self._h, g2, self._seed(seed), ctypes.c_uint32(2 if locate else 0), ctypes.byref(valid), ctypes.byref(bad)))
+        return bool(valid.value), (bad.value if bad.value != 2**64 - 1 else None)
+
+    def srs_lagrange_check(self, seed=None):
+        """does the resident Lagrange-form key belong to the resident monomial key (same tau, same domain, same order)?"""
+        valid = ctypes.c_int32(0)
+        _check(lib().plk_srs_lagrange_check(self._h, self._seed(seed), ctypes.byref(valid)))
+        return bool(valid.value)
+
     def set_kernel_timing(self, on=True):
         _check(lib().plk_set_kernel_timing(self._h, ctypes.c_int32(1 if on else 0)))
 

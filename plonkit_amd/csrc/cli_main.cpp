@@ -1,5 +1,6 @@
 // `plonkit` command line over the C ABI — the five prover commands of the reference's CLI
-// (src/bin/main.rs:27-53): setup, dump-lagrange, prove, export-verification-key, analyse, verify.
+// (src/bin/main.rs:27-53): setup, dump-lagrange, prove, export-verification-key, analyse, verify — and one the reference does not
+// have, check-key (the structure checks of include/plonkit_amd.h on a key file).
 // Same option names, short flags and defaults (src/bin/main.rs:55-136,176-190), same refusal to overwrite
 // (src/bin/main.rs:336-339,374-377,403-406) and the circuit-file default rule (src/bin/main.rs:346-357).
 // Everything arithmetic goes through include/plonkit_amd.h.
@@ -280,7 +281,9 @@ static void load_key(plk_ctx *ctx, const std::string &path, uint8_t g2[256], boo
 }
 
 static int run(int argc, char **argv) {
-    if (argc < 2) { fprintf(stderr, "plonkit (MI355X) — subcommands: analyse setup dump-lagrange prove export-verification-key verify\n"); return 2; }
+    if (argc < 2) { fprintf(stderr, "plonkit (MI355X) — subcommands: analyse setup dump-lagrange prove export-verification-key verify\n"
+                                      "                   check-key -m <key> [-l <lagrange key>] [--locate]   (the reference has no such command: is the key tau^i * G for the\n"
+                                      "                   tau of its G2 section, does the Lagrange-form key belong to it; exit 0 ok, 2 a key is refused, 101 unreadable)\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "analyse") {
         Args a = parse(argc, argv, {{"c", "circuit"}, {"o", "output"}});
@@ -515,6 +518,32 @@ static int run(int argc, char **argv) {
             plk_setup_free(s); phase("free: setup");
             plk_destroy(ctx); phase("free: context");
         }
+    } else if (cmd == "check-key") {
+        // NOT in the reference's CLI (src/bin/main.rs:27-53), whose Crs::read checks the curve equation only: plk_srs_check / plk_srs_lagrange_check
+        // with OS randomness, one line per key on stdout.  --locate is the only option without a value, so it is taken out before parse().
+        std::vector<char *> av;
+        bool locate = false;
+        for (int i = 0; i < argc; i++) { if (i >= 2 && !strcmp(argv[i], "--locate")) locate = true; else av.push_back(argv[i]); }
+        Args a = parse((int)av.size(), av.data(), {{"m", "srs_monomial_form"}, {"l", "srs_lagrange_form"}});
+        const std::string key_path = a.get("srs_monomial_form"), lag = a.get("srs_lagrange_form", "");
+        plk_ctx *ctx = open_ctx();
+        uint8_t g2[256], g2l[256];
+        load_key(ctx, key_path, g2);
+        bool refused = false;
+        int32_t valid = 0;
+        uint64_t bad = UINT64_MAX;
+        CK("check key_monomial_form", plk_srs_check(ctx, g2, nullptr, locate ? PLK_KEY_LOCATE : 0, &valid, &bad));
+        if (valid) printf("%s: ok\n", key_path.c_str());
+        else if (bad != UINT64_MAX) printf("%s: INVALID, first broken link at index %llu\n", key_path.c_str(), (unsigned long long)bad);
+        else printf("%s: INVALID\n", key_path.c_str());
+        refused |= !valid;
+        if (!lag.empty()) {
+            load_key(ctx, lag, g2l, true);
+            CK("check key_lagrange_form", plk_srs_lagrange_check(ctx, nullptr, &valid));
+            printf("%s: %s\n", lag.c_str(), valid ? "ok" : "INVALID");
+            refused |= !valid;
+        }
+        if (refused) return 2;
     } else if (cmd == "verify") {                                    // src/bin/main.rs:425-437 (no GPU involved)
         // VerifyOpts (src/bin/main.rs:125-137): the key is `-v` / `--verification_key` here, while export-verification-key
         // names its output `--vk` (src/bin/main.rs:186-187); `--vk` is kept as an alias on verify
