@@ -424,6 +424,53 @@ int32_t plk_prove_timings(const plk_ctx *ctx, double *out_ms, uint32_t cap, uint
  * reports the length.                                                                                                    */
 int32_t plk_prove_trace(plk_ctx *ctx, uint32_t which, plk_fr *out_host, uint64_t cap, uint64_t *n);
 
+/* ---- SetupForProver::validate_witness (src/plonk.rs:127-129) and the R1CS of CircomCircuit::synthesize itself (src/circom_circuit.rs:74-133) */
+/* "quickly validate whether a witness is satisfied" (src/plonk.rs:127-129), two ways.
+ *
+ * plk_validate_witness is the reference's call: the gate-level check of plk_prove on its own.  The witness front end of plk_prove
+ * (upload, the transpiler's temporaries on the host or the device) and the gate equation of every row, no key needed, nothing
+ * committed.  *valid = 1 / 0; *bad_row = the lowest failing row of the setup's gate table (rows 0 .. num_inputs - 1 are the
+ * public-input rows, the gates of constraint 0 follow), UINT64_MAX for a satisfying witness.  A setup from
+ * plk_setup_from_polynomials, a circuit without a witness, a circuit that does not match the setup, a setup that is not on the
+ * device, a commitment in flight: plk_prove's codes and words.  An unsatisfying witness is a verdict (PLK_OK), not an error.
+ *
+ * plk_r1cs is the R1CS on the device, and plk_r1cs_check_witness* ask the question on the constraints circom wrote:
+ * <A_i, w> * <B_i, w> = <C_i, w> for every i, exactly, mod r.  NO COUNTERPART IN THE REFERENCE (bellman only ever checks its own
+ * gates): neither a setup nor a key nor this library's transpiler is involved, so a proving service can screen queued witnesses
+ * with it, a circuit author learns WHICH constraint of the .r1cs broke, and its agreement with plk_validate_witness is a test of
+ * the transpiler.
+ *   plk_r1cs_upload   builds the device layout once per circuit (8-byte terms {wire, coefficient index}, the table of distinct
+ *                     coefficients, the lists of short and long linear combinations) and copies it to HBM; the circuit's witness
+ *                     is not needed and the circuit may be freed afterwards.  A term on a wire >= num_variables: PLK_ERR_FORMAT.
+ *                     Read-only after upload: one plk_r1cs may be used from several contexts of the same device, like a plk_setup.
+ *   Witness.          n >= num_variables elements, plk_fr in Montgomery form; extra ones are ignored, fewer is PLK_ERR_ARG.  On the host or
+ *                     (_dev) on the device, ordered after the work already enqueued on `stream` (NULL: the context's stream).
+ *                     WIRE 0 IS THE CONSTANT 1 WHATEVER witness[0] HOLDS (src/circom_circuit.rs:78,107-113: Index::Input(0) =
+ *                     CS::one(), w[0] is never read).  An element that some term reads and that is not a canonical residue:
+ *                     PLK_ERR_ARG, "... wire <lowest such wire> holds an element that is not a canonical residue (limbs >= r)";
+ *                     elements no term reads are not looked at.
+ *   Verdict.          The calls block.  *valid = 1 / 0, *bad_out = the lowest failing constraint or UINT64_MAX.  A constraint with an
+ *                     empty A or B and an empty C holds by arithmetic (the reference skips it, :122-123).  A wrong witness is a verdict
+ *                     (PLK_OK), not an error, as with plk_srs_check.  A commitment in flight on the context: PLK_ERR_ARG.
+ *   Memory.           The 3m values of the linear combinations and the two verdict words live in the context's staging arena (grows
+ *                     only), the host witness of plk_r1cs_check_witness beside them; nothing is allocated per call once it has grown.
+ *   plk_r1cs_long_lc_terms: linear combinations of at least this many terms are summed by a whole wave, shorter ones by one lane
+ *                     (diagnostic, for the tests: it names an internal that may change with any release).                        */
+typedef struct plk_r1cs plk_r1cs;
+int32_t plk_r1cs_upload(plk_ctx *ctx, const plk_circuit *c, plk_r1cs **out);
+void plk_r1cs_free(plk_r1cs *r);
+uint64_t plk_r1cs_num_constraints(const plk_r1cs *r);
+uint64_t plk_r1cs_num_variables(const plk_r1cs *r);
+uint32_t plk_r1cs_long_lc_terms(void);
+int32_t plk_r1cs_check_witness(plk_ctx *ctx, const plk_r1cs *r, const plk_fr *witness_host, uint64_t n,
+                               int32_t *valid, uint64_t *bad_out /* may be NULL */);
+int32_t plk_r1cs_check_witness_dev(plk_ctx *ctx, const plk_r1cs *r, const void *witness_dev, uint64_t n,
+                                   int32_t *valid, uint64_t *bad_out /* may be NULL */, void *stream);
+/* tracing hook: HIP-event times of the last plk_r1cs_check_witness* on this context, milliseconds: [0] short LCs, [1] long LCs,
+ * [2] verdict kernel, [3] the three together with the memsets between them.  Recorded only while plk_set_kernel_timing is on.  */
+int32_t plk_r1cs_last_kernel_ms(plk_ctx *ctx, float out_ms[4]);
+int32_t plk_validate_witness(plk_ctx *ctx, const plk_setup *s, const plk_circuit *c, int32_t *valid, uint64_t *bad_row /* may be NULL */);
+
 /* ---- assembled input: SetupPolynomials and the wire columns of bellman's own synthesis (src/plonk.rs:50-55,104,152-159) */
 /* plonkit's SetupForProver holds bellman's SetupPolynomials (src/plonk.rs:50-55, built by setup() at :104) and prove_by_steps takes
  * that setup plus the circuit bellman has already synthesised (:152-159).  These entry points take the same data one level below

@@ -49,6 +49,9 @@ def lib():
             L.plk_key_chunk_points.restype = ctypes.c_uint64
         if hasattr(L, "plk_setup_domain_size"):
             L.plk_setup_domain_size.restype = ctypes.c_uint64
+        L.plk_r1cs_num_constraints.restype = ctypes.c_uint64
+        L.plk_r1cs_num_variables.restype = ctypes.c_uint64
+        L.plk_r1cs_long_lc_terms.restype = ctypes.c_uint32
         _lib = L
     return _lib
 
@@ -641,6 +644,13 @@ class SetupForProver:
         return self._prove_into(lambda out, cap, n: lib().plk_prove_assembled_dev(h, self._h, arr, ctypes.c_uint64(rows), out,
                                                                                   ctypes.c_uint64(cap), ctypes.byref(n), st))
 
+    def validate_witness(self, circuit, ctx=None):
+        """SetupForProver::validate_witness (src/plonk.rs:127-129): the gate-level check of prove() on its own, no key needed.
+        Returns (valid, bad_row): bad_row is the lowest failing row of the gate table, None for a satisfying witness."""
+        valid, bad = ctypes.c_int32(0), ctypes.c_uint64(0)
+        _check(lib().plk_validate_witness((ctx or self.ctx)._h, self._h, circuit._h, ctypes.byref(valid), ctypes.byref(bad)))
+        return bool(valid.value), (bad.value if bad.value != 2**64 - 1 else None)
+
     def timings_ms(self, ctx=None):
         arr = (ctypes.c_double * 16)()
         cnt = ctypes.c_uint32(0)
@@ -658,6 +668,65 @@ class SetupForProver:
             self.close()
         except Exception:
             pass
+
+
+class R1cs:
+    """plk_r1cs: the constraints of a circuit on the device, for checking witnesses against them (no setup, no key; the circuit's own
+    witness is not needed and the circuit may be closed afterwards).  Read-only after upload: usable from several contexts of one device."""
+
+    def __init__(self, ctx, circuit):
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        _check(lib().plk_r1cs_upload(ctx._h, circuit._h, ctypes.byref(self._h)))
+
+    @property
+    def num_constraints(self):
+        return lib().plk_r1cs_num_constraints(self._h)
+
+    @property
+    def num_variables(self):
+        return lib().plk_r1cs_num_variables(self._h)
+
+    @staticmethod
+    def _verdict(rc, valid, bad):
+        _check(rc)
+        return bool(valid.value), (bad.value if bad.value != 2**64 - 1 else None)
+
+    def check(self, witness, ctx=None):
+        """witness: numpy (n, 4) uint64 Montgomery Fr, n >= num_variables; wire 0 counts as 1 whatever witness[0] holds.
+        Returns (valid, bad): bad is the lowest failing constraint, None when every constraint holds."""
+        w = _fr_vectors([witness], "R1cs.check", allow_empty=True)[0]
+        valid, bad = ctypes.c_int32(0), ctypes.c_uint64(0)
+        return self._verdict(lib().plk_r1cs_check_witness((ctx or self.ctx)._h, self._h, _np(w), ctypes.c_uint64(w.shape[0]),
+                                                          ctypes.byref(valid), ctypes.byref(bad)), valid, bad)
+
+    def check_dev(self, ptr, n, stream=None, ctx=None):
+        """the same for n elements already on the device (torch tensor / int), ordered after `stream`"""
+        valid, bad = ctypes.c_int32(0), ctypes.c_uint64(0)
+        return self._verdict(lib().plk_r1cs_check_witness_dev((ctx or self.ctx)._h, self._h, _devptr(ptr), ctypes.c_uint64(n),
+                                                              ctypes.byref(valid), ctypes.byref(bad), _stream(stream)), valid, bad)
+
+    def last_kernel_ms(self, ctx=None):
+        """HIP-event times of the last check on the context (Context.set_kernel_timing on): short LCs, long LCs, verdict, all three"""
+        arr = (ctypes.c_float * 4)()
+        _check(lib().plk_r1cs_last_kernel_ms((ctx or self.ctx)._h, arr))
+        return dict(zip(("lc_short", "lc_long", "verdict", "kernels"), [float(x) for x in arr]))
+
+    def close(self):
+        if self._h:
+            lib().plk_r1cs_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def r1cs_long_lc_terms():
+    """linear combinations of at least this many terms are summed by a whole wave (diagnostic, for the tests)"""
+    return int(lib().plk_r1cs_long_lc_terms())
 
 
 # ------------------------------------------------------------------ CPU-only helpers of the ABI

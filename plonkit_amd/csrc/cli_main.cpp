@@ -1,6 +1,6 @@
 // `plonkit` command line over the C ABI — the five prover commands of the reference's CLI
-// (src/bin/main.rs:27-53): setup, dump-lagrange, prove, export-verification-key, analyse, verify — and one the reference does not
-// have, check-key (the structure checks of include/plonkit_amd.h on a key file).
+// (src/bin/main.rs:27-53): setup, dump-lagrange, prove, export-verification-key, analyse, verify — and two the reference does not
+// have: check-key (the structure checks of include/plonkit_amd.h on a key file) and check-witness (a witness against its R1CS).
 // Same option names, short flags and defaults (src/bin/main.rs:55-136,176-190), same refusal to overwrite
 // (src/bin/main.rs:336-339,374-377,403-406) and the circuit-file default rule (src/bin/main.rs:346-357).
 // Everything arithmetic goes through include/plonkit_amd.h.
@@ -283,7 +283,9 @@ static void load_key(plk_ctx *ctx, const std::string &path, uint8_t g2[256], boo
 static int run(int argc, char **argv) {
     if (argc < 2) { fprintf(stderr, "plonkit (MI355X) — subcommands: analyse setup dump-lagrange prove export-verification-key verify\n"
                                       "                   check-key -m <key> [-l <lagrange key>] [--locate]   (the reference has no such command: is the key tau^i * G for the\n"
-                                      "                   tau of its G2 section, does the Lagrange-form key belong to it; exit 0 ok, 2 a key is refused, 101 unreadable)\n"); return 2; }
+                                      "                   tau of its G2 section, does the Lagrange-form key belong to it; exit 0 ok, 2 a key is refused, 101 unreadable)\n"
+                                      "                   check-witness -c <circuit> -w <witness>   (the reference has no such command: does the witness satisfy every\n"
+                                      "                   constraint of the R1CS, and if not which is the first that fails; no key, no setup; exit 0 ok, 2 refused, 101 unreadable)\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "analyse") {
         Args a = parse(argc, argv, {{"c", "circuit"}, {"o", "output"}});
@@ -544,6 +546,33 @@ static int run(int argc, char **argv) {
             refused |= !valid;
         }
         if (refused) return 2;
+    } else if (cmd == "check-witness") {
+        // NOT in the reference's CLI (src/bin/main.rs:27-53): SetupForProver::validate_witness (src/plonk.rs:127-129) is only reachable from Rust, and it
+        // checks bellman's gates.  This is plk_r1cs_check_witness on the constraints of the .r1cs themselves: no key, no setup, no transpiler.
+        Args a = parse(argc, argv, {{"c", "circuit"}, {"w", "witness"}});
+        std::string wf = a.get("witness", "witness.wtns");
+        plk_circuit *c = load_circuit(resolve_circuit(a), &wf);
+        // the witness as Montgomery plk_fr: through the library's own .wtns export (plk_circuit_export: one 76-byte head, then 32 little-endian
+        // canonical bytes per element), whatever format the file had
+        uint64_t len = 0;
+        CK("export witness", plk_circuit_export(c, 1, nullptr, 0, &len));
+        std::vector<uint8_t> wt(len);
+        CK("export witness", plk_circuit_export(c, 1, wt.data(), len, &len));
+        const uint64_t head = 76, n = len < head ? 0 : (len - head) / 32;
+        std::vector<plk_fr> w(n);
+        for (uint64_t i = 0; i < n; i++) {
+            uint8_t be[32];
+            for (int k = 0; k < 32; k++) be[k] = wt[head + 32 * i + 31 - k];
+            CK("witness element", plk_fr_from_bytes(be, &w[i]));
+        }
+        plk_ctx *ctx = open_ctx();
+        plk_r1cs *r = nullptr;
+        CK("upload r1cs", plk_r1cs_upload(ctx, c, &r));
+        int32_t valid = 0;
+        uint64_t bad = UINT64_MAX;
+        CK("check witness", plk_r1cs_check_witness(ctx, r, w.data(), n, &valid, &bad));
+        if (!valid) { fprintf(stderr, "constraint %llu fails\n", (unsigned long long)bad); return 2; }
+        fprintf(stderr, "witness satisfies all %llu constraints\n", (unsigned long long)plk_r1cs_num_constraints(r));
     } else if (cmd == "verify") {                                    // src/bin/main.rs:425-437 (no GPU involved)
         // VerifyOpts (src/bin/main.rs:125-137): the key is `-v` / `--verification_key` here, while export-verification-key
         // names its output `--vk` (src/bin/main.rs:186-187); `--vk` is kept as an alias on verify

@@ -131,6 +131,8 @@ struct plk_ctx {
     // intermediate vectors of the last plk_prove, still resident in prove_ws (plk_prove_trace: test / debugging hook)
     struct Trace { const plk::Fr *ptr[12] = {nullptr}; uint64_t len[12] = {0}; bool valid = false; } trace;
     bool ev_on = false;                      // record the per-slot event bracket around msm_accumulate
+    float r1cs_ms[4] = {0, 0, 0, 0};         // r1cs_check.hip: kernel times of the last witness check (recorded while ev_on)
+    bool r1cs_ms_valid = false;
     // multi-GPU commitments of the prover (plk_set_commit_shard): global index of the first resident SRS point and
     // the caller's all-ranks combiner for the Jacobian partial sums
     uint64_t shard_first = 0;

@@ -479,7 +479,9 @@ __global__ void __launch_bounds__(PT) k_eval_finish(EvalArgs a, Fr *results) {
 // ------------------------------------------------------------------- gate satisfiability
 // is_satisfied_using_one_shot_check (src/plonk.rs:128,137) on the device: every row's gate equation
 // q_a a + q_b b + q_c c + q_d d + q_m ab + q_const + q_dnext d_next + PI == 0; flag <- 1 otherwise
-__global__ void __launch_bounds__(PT) k_check_gates(CheckArgs a) {
+// ROW: the lowest failing row instead (atomicMin on one 64-bit word, as g1_decode_kernel: the answer does not depend on the launch geometry)
+template <bool ROW>
+__global__ void __launch_bounds__(PT) k_check_gates(CheckArgs a, unsigned long long *bad_row) {
     uint32_t r = blockIdx.x * PT + threadIdx.x;
     if (r >= a.n) return;
     Fr w[4];
@@ -495,7 +497,10 @@ __global__ void __launch_bounds__(PT) k_check_gates(CheckArgs a) {
         acc = add(acc, mul(qn, dn));
     }
     if (r < a.num_inputs) acc = add(acc, w[0]);
-    if (!acc.is_zero()) atomicOr(a.flag, 1u);
+    if (!acc.is_zero()) {
+        if (ROW) atomicMin(bad_row, (unsigned long long)r);
+        else atomicOr(a.flag, 1u);
+    }
 }
 
 // ------------------------------------------------------------------------- launchers
@@ -519,7 +524,12 @@ int32_t sigma_from_index(Fr *out, const uint32_t *packed, uint32_t n, uint32_t l
     return PLK_OK;
 }
 int32_t check_gates(const CheckArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL(k_check_gates, grid1(a.n), dim3(PT), 0, s, a);
+    hipLaunchKernelGGL(k_check_gates<false>, grid1(a.n), dim3(PT), 0, s, a, (unsigned long long *)nullptr);
+    PLK_HIP(hipGetLastError());
+    return PLK_OK;
+}
+int32_t check_gates_row(const CheckArgs &a, unsigned long long *bad_row, hipStream_t s) {
+    hipLaunchKernelGGL(k_check_gates<true>, grid1(a.n), dim3(PT), 0, s, a, bad_row);
     PLK_HIP(hipGetLastError());
     return PLK_OK;
 }

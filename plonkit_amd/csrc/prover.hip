@@ -882,30 +882,16 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     return PLK_OK;
 }
 
-static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
-    if (!ctx || !S || !c || !proof_out || !len) { set_error("plk_prove: bad argument"); return PLK_ERR_ARG; }
-    *len = 0;
-    if (S->from_polys) {
-        set_error("plk_prove: this setup was built from polynomials (plk_setup_from_polynomials) and has no gate structure: "
-                  "prove it from assembled columns with plk_prove_assembled / plk_prove_assembled_dev");
-        return PLK_ERR_ARG;
-    }
-    if (!c->has_witness) { set_error("plk_prove: circuit has no witness"); return PLK_ERR_ARG; }
-    PLK_HIP(hipSetDevice(ctx->device));
-    if (!ctx->srs || (!ctx->combine && ctx->srs_n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
-    if (!S->store.p) { set_error("plk_prove: the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
-    PLK_TRY(fifo_must_be_empty(ctx, "plk_prove"));
-    FifoGuard fifo_guard(ctx);
-    ctx->timings.clear();
-    ctx->trace.valid = false;
-    double t_prev = now_ms();
-    auto lap = [&]() { double t = now_ms(); ctx->timings.push_back(t - t_prev); t_prev = t; };
+// The witness front end of plk_prove and plk_validate_witness: the circom wires and the transpiler's temporaries, by variable id, in
+// W->d_values on the device (enqueued on the context's stream).  whole_workspace: the arena of a proof (prove_workspace); otherwise only
+// the values and the verdict word.  lap (may be empty) is called once, after the host part: [0] of plk_prove_timings.
+static int32_t witness_front(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, const char *who, bool whole_workspace, ProveWs *W,
+                             const std::function<void()> &lap) {
     hipStream_t st = ctx->stream;
-
     // ---- witness synthesis (host): circom wires, then the transpiler's temporaries from their recorded
     //      linear forms (the gate structure itself lives in plk_setup; the reference re-synthesises here)
     if (c->r1cs.num_variables != S->num_circuit_vars || c->witness.size() < S->num_circuit_vars) {
-        set_error("plk_prove: circuit does not match the prepared setup"); return PLK_ERR_ARG; }
+        set_error(std::string(who) + ": circuit does not match the prepared setup"); return PLK_ERR_ARG; }
     // circom wires are uploaded straight from the (page-locked) witness buffer; only the temporaries are
     // computed here, into a pinned staging area.  id 0 (dummy) is zeroed on the device.
     const uint64_t ncv = S->num_circuit_vars, n_tmp = S->num_vars - ncv;
@@ -954,13 +940,16 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
     }
     struct { uint64_t num_vars; } T;
     T.num_vars = S->num_vars;
-    lap();                                                                    // [0] witness synthesis
+    if (lap) lap();                                                           // [0] witness synthesis
 
-    const uint64_t N = S->N;
-    ProveWs W;
-    PLK_TRY(prove_workspace(ctx, S, T.num_vars, &W));
-    Fr *const d_values = W.d_values;
-    uint32_t *const d_flag = W.d_flag;
+    if (whole_workspace) PLK_TRY(prove_workspace(ctx, S, T.num_vars, W));
+    else {                                                                    // plk_validate_witness: the values and the verdict word only
+        PLK_TRY(ctx->prove_ws.reserve(((T.num_vars * sizeof(Fr) + 255) & ~(size_t)255) + 256));
+        Arena A{&ctx->prove_ws};
+        W->d_values = A.take<Fr>(T.num_vars);
+        W->d_flag = A.take<uint32_t>(64);
+    }
+    Fr *const d_values = W->d_values;
     {   // (under the circuit's lock: another context proving the SAME circuit object may be about to page-lock this buffer —
         //  not while a pageable copy of it is being staged)
         std::lock_guard<std::mutex> upload_lock(c->reg_mu);
@@ -971,6 +960,36 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
         PLK_TRY(eval_witness_runs(d_values, S->ops_dev.p, S->terms_dev.p, S->runs_dev.p, (uint32_t)S->run_start.size(), (uint32_t)S->ops.size(), (uint32_t)ncv, st));
     else if (n_tmp && tmp_on_device) PLK_TRY(eval_witness_ops(d_values, S->ops_dev.p, S->terms_dev.p, (uint32_t)S->ops.size(), (uint32_t)ncv, st));
     else if (n_tmp) PLK_HIP(hipMemcpyAsync(d_values + ncv, tmp_vals, n_tmp * sizeof(Fr), hipMemcpyHostToDevice, st));
+    return PLK_OK;
+}
+
+
+static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    if (!ctx || !S || !c || !proof_out || !len) { set_error("plk_prove: bad argument"); return PLK_ERR_ARG; }
+    *len = 0;
+    if (S->from_polys) {
+        set_error("plk_prove: this setup was built from polynomials (plk_setup_from_polynomials) and has no gate structure: "
+                  "prove it from assembled columns with plk_prove_assembled / plk_prove_assembled_dev");
+        return PLK_ERR_ARG;
+    }
+    if (!c->has_witness) { set_error("plk_prove: circuit has no witness"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    if (!ctx->srs || (!ctx->combine && ctx->srs_n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
+    if (!S->store.p) { set_error("plk_prove: the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
+    PLK_TRY(fifo_must_be_empty(ctx, "plk_prove"));
+    FifoGuard fifo_guard(ctx);
+    ctx->timings.clear();
+    ctx->trace.valid = false;
+    double t_prev = now_ms();
+    auto lap = [&]() { double t = now_ms(); ctx->timings.push_back(t - t_prev); t_prev = t; };
+    hipStream_t st = ctx->stream;
+
+    ProveWs W;
+    PLK_TRY(witness_front(ctx, S, c, "plk_prove", true, &W, lap));
+    const uint64_t N = S->N;
+    Fr *const d_values = W.d_values;
+    uint32_t *const d_flag = W.d_flag;
+    const HFr *wit = c->witness.data();
     std::vector<HFr> inputs(wit + 1, wit + 1 + S->num_inputs);
     {   // is_satisfied_using_one_shot_check (src/plonk.rs:137) on the device
         CheckArgs ca;
@@ -991,6 +1010,41 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
     F.inputs.swap(inputs);
     F.t_prev = t_prev;
     return prove_rounds(ctx, S, W, F, proof_out, cap, len);
+}
+
+// SetupForProver::validate_witness (src/plonk.rs:127-129): the witness front end of plk_prove and the gate equation of every row, on their
+// own — no key, no commitment, no round.  The verdict names the lowest failing row (the row kernel of the assembled path, assembled.hip,
+// reports the same way; here it is an atomicMin on a 64-bit word).
+static int32_t validate_witness_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, int32_t *valid, uint64_t *bad_row) {
+    if (valid) *valid = 0;
+    if (bad_row) *bad_row = ~0ull;
+    if (!ctx || !S || !c || !valid) { set_error("plk_validate_witness: bad argument"); return PLK_ERR_ARG; }
+    if (S->from_polys) {
+        set_error("plk_validate_witness: this setup was built from polynomials (plk_setup_from_polynomials) and has no gate structure: "
+                  "the assembled columns are checked by plk_prove_assembled / plk_prove_assembled_dev");
+        return PLK_ERR_ARG;
+    }
+    if (!c->has_witness) { set_error("plk_validate_witness: circuit has no witness"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    if (!S->store.p) { set_error("plk_validate_witness: the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
+    PLK_TRY(fifo_must_be_empty(ctx, "plk_validate_witness"));
+    ctx->trace.valid = false;                                                 // the workspace the trace points into is written below
+    hipStream_t st = ctx->stream;
+    ProveWs W;
+    PLK_TRY(witness_front(ctx, S, c, "plk_validate_witness", false, &W, nullptr));
+    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(W.d_flag);
+    CheckArgs ca;
+    ca.values = W.d_values; ca.n = (uint32_t)S->N; ca.num_inputs = (uint32_t)S->num_inputs; ca.flag = nullptr;
+    for (int k = 0; k < 7; k++) ca.q[k] = S->sel_vals[k];
+    for (int j = 0; j < 4; j++) ca.vars[j] = S->gate_vars[j];
+    PLK_HIP(hipMemsetAsync(d_bad, 0xff, 8, st));
+    PLK_TRY(check_gates_row(ca, d_bad, st));
+    unsigned long long bad = ~0ull;
+    PLK_HIP(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
+    PLK_HIP(hipStreamSynchronize(st));                                        // the verdict is this call's return value
+    *valid = bad == ~0ull ? 1 : 0;
+    if (bad_row) *bad_row = bad;
+    return PLK_OK;
 }
 
 
@@ -1222,6 +1276,9 @@ int32_t plk_setup_write_vk(plk_ctx *ctx, const plk_setup *s, const uint8_t g2_by
 int32_t plk_prove(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
     PLK_TRY(not_a_worker(ctx, "plk_prove"));
     return guarded("plk_prove", PLK_ERR_HIP, [&] { return prove_impl(ctx, S, c, proof_out, cap, len); });
+}
+int32_t plk_validate_witness(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, int32_t *valid, uint64_t *bad_row) {
+    return guarded("plk_validate_witness", PLK_ERR_HIP, [&] { return validate_witness_impl(ctx, S, c, valid, bad_row); });
 }
 int32_t plk_setup_from_polynomials(plk_ctx *ctx, uint64_t n, uint64_t num_inputs, const plk_fr *const selectors[6], const plk_fr *next_step_selector,
                                    const plk_fr *const sigmas[4], uint64_t len, uint32_t flags, plk_setup **out) {

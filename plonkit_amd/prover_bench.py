@@ -351,6 +351,88 @@ def run(ctx, log_n, reps=10):
                          1 << log_n, best, nonempty_commitments(proof))
 
 
+def r1cs_check(ctx, log_n, lc_terms, reps=15):
+    """plk_r1cs_check_witness_dev on the 2^log_n-gate synthetic circuit (lc_terms = 0 or 7) or, lc_terms = "poseidon", the 2^12-domain
+    Poseidon-shaped circuit of tests/gen/poseidon_like.py: HIP-event times of the three kernels (plk_r1cs_last_kernel_ms) and of the whole
+    call (events on the stream the call is given, so the verdict's way back to the host is inside), median of `reps` after a warm-up;
+    the bytes the kernels move as a share of HBM peak; and what the parent of this call offers for the same question — phase [0] plus the
+    time to the verdict of a plk_prove on an unsatisfying witness (needs a resident key of the domain's size).  Not part of bench.py."""
+    import json
+    import numpy as np
+    import torch
+    if lc_terms == "poseidon":
+        from tests.gen import poseidon_like as pl
+        ni, nv, cons, wit = pl.build(7, 84)
+        circ = _lib.Circuit(json.dumps(pl.as_circom_json(ni, nv, cons)).encode(), True, json.dumps([str(x) for x in wit]).encode(), True)
+    else:
+        circ = _lib.Circuit.synthetic_ex((1 << log_n) - 2, lc_terms=lc_terms)
+    # the witness as the Montgomery array the call takes: the .wtns export is canonical, and the conversion goes through the library's own byte
+    # codec on the host, element by element, outside every timed region
+    wtns = circ.export("wtns")
+    n = (len(wtns) - 76) // 32
+    w = np.zeros((n, 4), dtype=np.uint64)
+    raw = np.frombuffer(wtns, dtype=np.uint8, offset=76).reshape(n, 32)
+    for i in range(n):
+        w[i] = _lib.fr_from_bytes(raw[i, ::-1].tobytes())
+    t0 = time.perf_counter()
+    r = _lib.R1cs(ctx, circ)
+    upload_s = time.perf_counter() - t0
+    m, nvars = r.num_constraints, r.num_variables
+    hdr = np.frombuffer(circ.export("r1cs"), dtype=np.uint8)
+    stream = torch.cuda.Stream()
+    d_w = torch.from_numpy(w.view(np.int64)).to("cuda:%d" % ctx.device)
+    torch.cuda.synchronize()
+    ctx.set_kernel_timing(True)
+    assert r.check_dev(d_w, n, stream=stream) == (True, None)          # warm-up: the staging arena grows here
+    rows = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record(stream)
+        verdict = r.check_dev(d_w, n, stream=stream)
+        e1.record(stream)
+        wall = time.perf_counter() - t0
+        e1.synchronize()
+        assert verdict == (True, None)
+        k = r.last_kernel_ms()
+        rows.append((e0.elapsed_time(e1), wall * 1e3, k["lc_short"], k["lc_long"], k["verdict"], k["kernels"]))
+    ctx.set_kernel_timing(False)
+    med = [sorted(col)[len(col) // 2] for col in zip(*rows)]
+    # bytes: every term record once, a 32-byte witness gather per term, the offsets, lc_vals written once and read once (the coefficient table stays in cache)
+    n_terms = (len(hdr) - 112 - 8 * nvars - 12 * m) // 36                # the .r1cs export: 112 bytes of heads, 36 per term, 12 per constraint, 8 per label
+    moved = 8 * n_terms + 32 * n_terms + 8 * (3 * m + 1) + 2 * 32 * 3 * m
+    out = {"domain_log_n": log_n, "lc_terms": lc_terms, "constraints": int(m), "variables": int(nvars), "terms": int(n_terms), "upload_s": round(upload_s, 4),
+           "call_ms_events": round(med[0], 4), "call_ms_wall": round(med[1], 4), "lc_short_ms": round(med[2], 4), "lc_long_ms": round(med[3], 4),
+           "verdict_ms": round(med[4], 4), "kernels_ms": round(med[5], 4), "runs": reps, "bytes_moved": int(moved),
+           "hbm_frac_kernels": round(moved / (med[5] * 1e-3) / HBM_PEAK_BS, 4) if med[5] > 0 else None}
+    # the parent's answer to the same question: plk_prove on an unsatisfying witness, phase [0] + round 1 up to the verdict (the call returns there)
+    if ctx.srs_size() >= (1 << log_n):
+        bad = bytearray(wtns)
+        bad[76 + 32 * (n // 2)] ^= 1
+        circ_bad = _lib.Circuit(circ.export("r1cs"), False, bytes(bad), False)
+        setup = _lib.SetupForProver(ctx, circ)
+        setup.prove(circ)                                                # warm-up: workspace, tables, cached extensions
+        walls = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            try:
+                setup.prove(circ_bad)
+                raise AssertionError("the changed witness was proved")
+            except _lib.PlkError as e:
+                assert e.code == 5
+            walls.append((time.perf_counter() - t0) * 1e3)
+        out["prove_unsat_ms_wall"] = round(sorted(walls)[len(walls) // 2], 4)
+        vw = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            assert setup.validate_witness(circ_bad)[0] is False
+            vw.append((time.perf_counter() - t0) * 1e3)
+        out["validate_witness_unsat_ms_wall"] = round(sorted(vw)[len(vw) // 2], 4)
+        setup.close(); circ_bad.close()
+    r.close(); circ.close()
+    return out
+
+
 def kernel_table(ctx, device):
     """HIP-event timings of the other kernels on the path, with their algorithmic HBM bytes
     (NTT 64*M, LDE4 160*N) — the per-kernel roofline rows of DESIGN.md §4."""
