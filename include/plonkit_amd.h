@@ -471,6 +471,54 @@ int32_t plk_r1cs_check_witness_dev(plk_ctx *ctx, const plk_r1cs *r, const void *
 int32_t plk_r1cs_last_kernel_ms(plk_ctx *ctx, float out_ms[4]);
 int32_t plk_validate_witness(plk_ctx *ctx, const plk_setup *s, const plk_circuit *c, int32_t *valid, uint64_t *bad_row /* may be NULL */);
 
+/* ---- one setup, a stream of witnesses: load_witness_from_array (src/reader.rs:119-175) on the GPU, and SetupForProver::prove
+ *      (src/plonk.rs:132-159) / validate_witness (:127-129) for a witness that arrives WITHOUT its circuit.  A plk_circuit is the R1CS plus one
+ *      witness; a proving service holds one circuit (one plk_setup) and receives a witness per request, and of the circuit the prover reads
+ *      nothing but num_variables and the witness once the setup exists.
+ *
+ *   plk_fr_decode_dev / plk_fr_encode_dev: the two kernels on device pointers (16-byte aligned, else PLK_ERR_ARG), ordered on `stream` like every
+ *                _dev call.  decode: n x 32 bytes, each a little-endian canonical integer (the .wtns payload, repr.read_le + Fr::from_repr,
+ *                src/reader.rs:169-173) -> n plk_fr in Montgomery form.  It returns its verdict, so it waits for `stream`: an element >= r is
+ *                PLK_ERR_FORMAT "read witness failed: not in field", *bad_out = the LOWEST refused index and fr_dev holds zero at every refused
+ *                index; else *bad_out = UINT64_MAX.  One decode at a time per context.  encode: the inverse; limbs >= r (never a value this
+ *                library made) are encoded after one reduction.
+ *   plk_wtns_decode: the whole .wtns file in host memory (pageable is fine) -> fr_dev[0, n).  The container checks are parse_wtns_bin's
+ *                (plk_circuit_load's), in its order and with its words — "invalid file header", "unsupported file version", "invalid num
+ *                sections", "invalid section type", "invalid section len", "invalid field byte size", "invalid curve prime", "invalid witness
+ *                section size", "read witness failed: truncated" — all PLK_ERR_FORMAT, made on the host before the context is read.  *n_out =
+ *                elements in the file; fr_dev == NULL only reports it.  cap < n: PLK_ERR_ARG.  The payload starts at byte 76 of the file, which
+ *                is not 16-byte aligned: it is copied to the context's staging arena (grows only; the arena of plk_srs_load_key) and decoded
+ *                from there, nothing is allocated per call once the arena has grown.  A refused element: as plk_fr_decode_dev.  Blocks.
+ *   plk_prove_witness / _witness_dev / _wtns: the bytes plk_prove writes for a plk_circuit that holds the same witness, for the circuit the
+ *                setup was prepared from.  n >= num_variables of that circuit; extra elements are ignored (plk_prove_wtns still range-checks
+ *                every element of the file), fewer is PLK_ERR_ARG "... the witness does not match the prepared setup".  witness[0] is not read
+ *                (wire 0 is zeroed on the device, as in plk_prove); the public inputs are witness[1 .. num_inputs], which the _dev and _wtns
+ *                calls copy back before the transcript starts.  Host and _dev: an element of witness[1, num_variables) that is not a canonical
+ *                residue is PLK_ERR_ARG, "... wire <lowest such wire> holds an element that is not a canonical residue (limbs >= r)" (the
+ *                words of plk_r1cs_check_witness; a kernel finds it).  plk_prove_wtns: the container as plk_wtns_decode, and the decode
+ *                kernel's range check is that check (PLK_ERR_FORMAT, *bad_out = lowest refused element, UINT64_MAX otherwise).  A setup from
+ *                plk_setup_from_polynomials, a setup not on the device, a commitment in flight, a key too small, an unsatisfying witness
+ *                (PLK_ERR_UNSAT, no proof bytes): plk_prove's codes and words under the entry point's own name.  The host vector is never
+ *                page-locked.  _dev reads witness_dev[0, num_variables) (16-byte aligned) ordered after the work already enqueued on `stream`
+ *                (NULL: the context's stream), blocks like plk_prove and keeps no reference once it returns.  plk_prove_timings ([0] is the
+ *                witness upload / decode) and plk_prove_trace describe these proofs as any other.
+ *   plk_validate_witness_dev: plk_validate_witness's verdict and bad_row for a device witness (same length, alignment, ordering and canonical
+ *                rules as plk_prove_witness_dev).                                                                                            */
+int32_t plk_fr_decode_dev(plk_ctx *ctx, const void *bytes_dev, uint64_t n, void *fr_dev, uint64_t *bad_out /* may be NULL */, void *stream);
+int32_t plk_fr_encode_dev(plk_ctx *ctx, const void *fr_dev, uint64_t n, void *bytes_dev, void *stream);
+/* load_witness_from_array (src/reader.rs:119-175) straight into HBM */
+int32_t plk_wtns_decode(plk_ctx *ctx, const uint8_t *data, uint64_t len, void *fr_dev, uint64_t cap, uint64_t *n_out,
+                        uint64_t *bad_out /* may be NULL */, void *stream);
+/* SetupForProver::prove (src/plonk.rs:132-159) for the next witness of the circuit the setup was prepared from */
+int32_t plk_prove_witness(plk_ctx *ctx, const plk_setup *s, const plk_fr *witness_host, uint64_t n, uint8_t *proof_out, uint64_t cap, uint64_t *len);
+int32_t plk_prove_witness_dev(plk_ctx *ctx, const plk_setup *s, const void *witness_dev, uint64_t n, uint8_t *proof_out, uint64_t cap, uint64_t *len,
+                              void *stream);
+int32_t plk_prove_wtns(plk_ctx *ctx, const plk_setup *s, const uint8_t *wtns, uint64_t wtns_len, uint8_t *proof_out, uint64_t cap, uint64_t *len,
+                       uint64_t *bad_out /* may be NULL */);
+/* SetupForProver::validate_witness (src/plonk.rs:127-129) for a device witness */
+int32_t plk_validate_witness_dev(plk_ctx *ctx, const plk_setup *s, const void *witness_dev, uint64_t n, int32_t *valid,
+                                 uint64_t *bad_row /* may be NULL */, void *stream);
+
 /* ---- assembled input: SetupPolynomials and the wire columns of bellman's own synthesis (src/plonk.rs:50-55,104,152-159) */
 /* plonkit's SetupForProver holds bellman's SetupPolynomials (src/plonk.rs:50-55, built by setup() at :104) and prove_by_steps takes
  * that setup plus the circuit bellman has already synthesised (:152-159).  These entry points take the same data one level below

@@ -298,6 +298,35 @@ class Context:
     def g1_encode_dev(self, points_ptr, n, bytes_ptr, stream=None):
         _check(lib().plk_g1_encode_dev(self._h, _devptr(points_ptr), ctypes.c_uint64(n), _devptr(bytes_ptr), _stream(stream)))
 
+    # ---- witness files on the GPU (wtnsio.hip): field elements to and from their 32 little-endian file bytes
+    @staticmethod
+    def _raise_with_bad_index(rc, bad):
+        e = PlkError(rc, last_error())
+        e.bad_index = bad.value if bad.value != 2**64 - 1 else None
+        raise e
+
+    def fr_decode_dev(self, bytes_ptr, n, fr_ptr, stream=None):
+        """n x 32 little-endian canonical bytes -> n Montgomery Fr on the device; raises PlkError (`.bad_index` = the lowest element
+        >= r; zero is stored there) if an element is refused"""
+        bad = ctypes.c_uint64(0)
+        rc = lib().plk_fr_decode_dev(self._h, _devptr(bytes_ptr), ctypes.c_uint64(n), _devptr(fr_ptr), ctypes.byref(bad), _stream(stream))
+        if rc != 0:
+            self._raise_with_bad_index(rc, bad)
+
+    def fr_encode_dev(self, fr_ptr, n, bytes_ptr, stream=None):
+        _check(lib().plk_fr_encode_dev(self._h, _devptr(fr_ptr), ctypes.c_uint64(n), _devptr(bytes_ptr), _stream(stream)))
+
+    def wtns_decode(self, data, out_ptr, cap, stream=None):
+        """.wtns file bytes -> Montgomery Fr at `out_ptr` (room for `cap` elements; None: only count).  Returns (n, bad): the elements in
+        the file and None; a malformed container or an element >= r raises PlkError, the latter with `.bad_index` = the lowest such element."""
+        buf = np.frombuffer(data, dtype=np.uint8)                     # bytes, bytearray, memoryview, uint8 array: no copy
+        n, bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = lib().plk_wtns_decode(self._h, _np(buf), ctypes.c_uint64(buf.size), _devptr(out_ptr) if out_ptr is not None else None,
+                                   ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(bad), _stream(stream))
+        if rc != 0:
+            self._raise_with_bad_index(rc, bad)
+        return n.value, None
+
     def srs_lagrange_from_powers(self, log_n):
         """Crs::<Lagrange>::from_powers on the device: G1 iNTT of the first 2^log_n resident points -> the Lagrange-form key"""
         _check(lib().plk_srs_lagrange_from_powers(self._h, ctypes.c_uint32(log_n)))
@@ -649,6 +678,39 @@ class SetupForProver:
         Returns (valid, bad_row): bad_row is the lowest failing row of the gate table, None for a satisfying witness."""
         valid, bad = ctypes.c_int32(0), ctypes.c_uint64(0)
         _check(lib().plk_validate_witness((ctx or self.ctx)._h, self._h, circuit._h, ctypes.byref(valid), ctypes.byref(bad)))
+        return bool(valid.value), (bad.value if bad.value != 2**64 - 1 else None)
+
+    # ---- one setup, a stream of witnesses: the witness without its circuit (plk_prove_witness / _witness_dev / _wtns)
+    def prove_witness(self, w, ctx=None):
+        """proof.bin bytes for the next witness of this setup's circuit: numpy (n, 4) uint64 Montgomery Fr, n >= num_variables"""
+        w = _fr_vectors([w], "prove_witness", allow_empty=True)[0]
+        h = (ctx or self.ctx)._h
+        return self._prove_into(lambda out, cap, n: lib().plk_prove_witness(h, self._h, _np(w), ctypes.c_uint64(w.shape[0]), out,
+                                                                            ctypes.c_uint64(cap), ctypes.byref(n)))
+
+    def prove_witness_dev(self, ptr, n, stream=None, ctx=None):
+        """the same for n elements already on the device (torch tensor / int), ordered after `stream`"""
+        h, st = (ctx or self.ctx)._h, _stream(stream)
+        return self._prove_into(lambda out, cap, ln: lib().plk_prove_witness_dev(h, self._h, _devptr(ptr), ctypes.c_uint64(n), out,
+                                                                                 ctypes.c_uint64(cap), ctypes.byref(ln), st))
+
+    def prove_wtns(self, data, ctx=None):
+        """the same from the bytes of a .wtns file, decoded and range-checked on the device; an element >= r raises PlkError with
+        `.bad_index` = the lowest such element"""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        h, bad = (ctx or self.ctx)._h, ctypes.c_uint64(0)
+        try:
+            return self._prove_into(lambda out, cap, n: lib().plk_prove_wtns(h, self._h, _np(buf), ctypes.c_uint64(buf.size), out,
+                                                                             ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(bad)))
+        except PlkError as e:
+            e.bad_index = bad.value if bad.value != 2**64 - 1 else None
+            raise
+
+    def validate_witness_dev(self, ptr, n, stream=None, ctx=None):
+        """validate_witness for n elements already on the device; returns (valid, bad_row)"""
+        valid, bad = ctypes.c_int32(0), ctypes.c_uint64(0)
+        _check(lib().plk_validate_witness_dev((ctx or self.ctx)._h, self._h, _devptr(ptr), ctypes.c_uint64(n), ctypes.byref(valid),
+                                              ctypes.byref(bad), _stream(stream)))
         return bool(valid.value), (bad.value if bad.value != 2**64 - 1 else None)
 
     def timings_ms(self, ctx=None):

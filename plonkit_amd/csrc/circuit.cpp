@@ -262,7 +262,9 @@ bool parse_r1cs_json(const uint8_t *data, size_t len, R1cs *out) {
 }
 
 // ------------------------------------------------------------------------------ witness
-bool parse_wtns_bin(const uint8_t *data, size_t len, big_vector<HFr> *out) {
+// the container of a .wtns file (src/reader.rs:124-168) without its elements: how many there are and where the first one starts.
+// No allocation, no device: plk_wtns_decode (wtnsio.hip) makes the same checks, in the same order and with the same words, through it.
+bool wtns_container(const uint8_t *data, size_t len, uint64_t *n_out, size_t *payload_off) {
     Rd r(data, len);
     if (len < 4 || memcmp(data, "wtns", 4) != 0) { set_error("invalid file header"); return false; }
     r.off = 4;
@@ -279,9 +281,18 @@ bool parse_wtns_bin(const uint8_t *data, size_t len, big_vector<HFr> *out) {
     uint64_t sz = r.u64();
     if (!r.ok || sz != (uint64_t)wl * 32) { set_error("invalid witness section size"); return false; }
     if (!r.need(sz)) { set_error("read witness failed: truncated"); return false; }
+    *n_out = wl;
+    *payload_off = r.off;
+    return true;
+}
+
+bool parse_wtns_bin(const uint8_t *data, size_t len, big_vector<HFr> *out) {
+    uint64_t wl = 0;
+    size_t payload = 0;
+    if (!wtns_container(data, len, &wl, &payload)) return false;
     out->resize(wl);
     std::atomic<int> bad(0);
-    const uint8_t *src = data + r.off;
+    const uint8_t *src = data + payload;
     parallel_for(wl, 16384, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; i++) if (!fr_from_le32(src + 32 * i, &(*out)[i])) { bad = 1; return; }
     });

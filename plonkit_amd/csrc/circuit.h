@@ -142,6 +142,7 @@ namespace plk {
 bool parse_r1cs_bin(const uint8_t *data, size_t len, R1cs *out);
 bool parse_r1cs_json(const uint8_t *data, size_t len, R1cs *out);
 bool parse_wtns_bin(const uint8_t *data, size_t len, big_vector<HFr> *out);
+bool wtns_container(const uint8_t *data, size_t len, uint64_t *n_out, size_t *payload_off);     // the checks of parse_wtns_bin up to the elements
 bool parse_witness_json(const uint8_t *data, size_t len, big_vector<HFr> *out);
 bool fr_from_decimal(const std::string &s, HFr *out);
 

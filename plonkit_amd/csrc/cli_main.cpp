@@ -1,6 +1,7 @@
 // `plonkit` command line over the C ABI — the five prover commands of the reference's CLI
 // (src/bin/main.rs:27-53): setup, dump-lagrange, prove, export-verification-key, analyse, verify — and two the reference does not
-// have: check-key (the structure checks of include/plonkit_amd.h on a key file) and check-witness (a witness against its R1CS).
+// have: check-key (the structure checks of include/plonkit_amd.h on a key file), check-witness (a witness against its R1CS) and
+// prove-many (one key, one circuit, one setup, a proof per witness file).
 // Same option names, short flags and defaults (src/bin/main.rs:55-136,176-190), same refusal to overwrite
 // (src/bin/main.rs:336-339,374-377,403-406) and the circuit-file default rule (src/bin/main.rs:346-357).
 // Everything arithmetic goes through include/plonkit_amd.h.
@@ -285,7 +286,10 @@ static int run(int argc, char **argv) {
                                       "                   check-key -m <key> [-l <lagrange key>] [--locate]   (the reference has no such command: is the key tau^i * G for the\n"
                                       "                   tau of its G2 section, does the Lagrange-form key belong to it; exit 0 ok, 2 a key is refused, 101 unreadable)\n"
                                       "                   check-witness -c <circuit> -w <witness>   (the reference has no such command: does the witness satisfy every\n"
-                                      "                   constraint of the R1CS, and if not which is the first that fails; no key, no setup; exit 0 ok, 2 refused, 101 unreadable)\n"); return 2; }
+                                      "                   constraint of the R1CS, and if not which is the first that fails; no key, no setup; exit 0 ok, 2 refused, 101 unreadable)\n"
+                                      "                   prove-many -m <key> [-l <lagrange key>] -c <circuit> -o <dir> <witness>...   (the reference has no such command: one\n"
+                                      "                   setup, <dir>/<witness file name>.proof.bin per witness; a refused witness is reported and the run goes on;\n"
+                                      "                   exit 0 every proof written, 2 otherwise, 101 key or circuit unreadable)\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "analyse") {
         Args a = parse(argc, argv, {{"c", "circuit"}, {"o", "output"}});
@@ -573,6 +577,73 @@ static int run(int argc, char **argv) {
         CK("check witness", plk_r1cs_check_witness(ctx, r, w.data(), n, &valid, &bad));
         if (!valid) { fprintf(stderr, "constraint %llu fails\n", (unsigned long long)bad); return 2; }
         fprintf(stderr, "witness satisfies all %llu constraints\n", (unsigned long long)plk_r1cs_num_constraints(r));
+    } else if (cmd == "prove-many") {
+        // NOT in the reference's CLI (src/bin/main.rs:27-53), which is one process per proof: SetupForProver::prove (src/plonk.rs:132-159) for a
+        // stream of witnesses of ONE circuit.  Key, circuit and setup once; every witness file goes through plk_prove_wtns (decoded on the GPU), a
+        // *.json witness through the host parser and plk_prove_witness — the parser is chosen by suffix (src/reader.rs:93).  The witness files are
+        // the arguments that belong to no option, so they are taken out before parse().
+        std::vector<char *> av;
+        std::vector<std::string> witnesses;
+        for (int i = 0; i < argc; i++) {
+            if (i < 2 || argv[i][0] == '-') { av.push_back(argv[i]); if (i >= 2 && i + 1 < argc && strcmp(argv[i], "--overwrite")) av.push_back(argv[++i]); }
+            else witnesses.push_back(argv[i]);
+        }
+        Args a = parse((int)av.size(), av.data(), {{"m", "srs_monomial_form"}, {"l", "srs_lagrange_form"}, {"c", "circuit"}, {"o", "output"}});
+        const std::string key_path = a.get("srs_monomial_form"), lag = a.get("srs_lagrange_form", ""), dir = a.get("output");
+        if (witnesses.empty()) { fprintf(stderr, "error: The following required argument was not provided: <witness>...\n"); return 2; }
+        plk_circuit *c = load_circuit(resolve_circuit(a), nullptr);
+        plk_ctx *ctx = open_ctx();
+        uint8_t g2[256], g2l[256];
+        load_key(ctx, key_path, g2);
+        if (!lag.empty()) load_key(ctx, lag, g2l, true);
+        plk_setup *s = nullptr;
+        CK("prepare err", plk_setup_prepare(ctx, c, &s));
+        plk_circuit_free(c);                                         // the setup holds all the prover needs of the circuit
+        (void)mkdir(dir.c_str(), 0777);
+        size_t written = 0;
+        std::vector<uint8_t> buf(1 << 16);
+        for (const std::string &wf : witnesses) {
+            FILE *probe = fopen(wf.c_str(), "rb");
+            if (!probe) { fprintf(stderr, "%s: unable to open.\n", wf.c_str()); continue; }
+            fclose(probe);
+            const std::vector<uint8_t> w = slurp(wf, "unable to open.");
+            std::vector<plk_fr> host;                                // a json witness: parsed on the host, through the library's own loader and export
+            if (ends_with(wf, "json")) {
+                static const char one_var[] = "{\"nPubInputs\":0,\"nOutputs\":0,\"nVars\":1,\"constraints\":[]}";
+                plk_circuit *wc = nullptr;
+                uint64_t wl = 0;
+                if (plk_circuit_load((const uint8_t *)one_var, sizeof one_var - 1, 1, w.data(), w.size(), 1, &wc) != PLK_OK) {
+                    fprintf(stderr, "%s: %s\n", wf.c_str(), plk_last_error()); continue; }
+                CK("export witness", plk_circuit_export(wc, 1, nullptr, 0, &wl));
+                std::vector<uint8_t> wt(wl);
+                CK("export witness", plk_circuit_export(wc, 1, wt.data(), wl, &wl));
+                plk_circuit_free(wc);
+                const uint64_t head = 76, n = wl < head ? 0 : (wl - head) / 32;
+                host.resize(n);
+                for (uint64_t i = 0; i < n; i++) {
+                    uint8_t be[32];
+                    for (int k = 0; k < 32; k++) be[k] = wt[head + 32 * i + 31 - k];
+                    CK("witness element", plk_fr_from_bytes(be, &host[i]));
+                }
+            }
+            uint64_t len = 0, bad = UINT64_MAX;
+            auto prove = [&]() { return host.empty() ? plk_prove_wtns(ctx, s, w.data(), w.size(), buf.data(), buf.size(), &len, &bad)
+                                                     : plk_prove_witness(ctx, s, host.data(), host.size(), buf.data(), buf.size(), &len); };
+            int32_t rc = prove();
+            if (rc == PLK_ERR_ARG && len > buf.size()) { buf.resize(len); rc = prove(); }      // many public inputs: the call reports the size it needs
+            if (rc != PLK_OK) {
+                if (bad != UINT64_MAX) fprintf(stderr, "%s: %s (element %llu, status %d)\n", wf.c_str(), plk_last_error(), (unsigned long long)bad, rc);
+                else fprintf(stderr, "%s: %s (status %d)\n", wf.c_str(), plk_last_error(), rc);
+                continue;
+            }
+            const size_t slash = wf.find_last_of('/');
+            const std::string out = dir + "/" + (slash == std::string::npos ? wf : wf.substr(slash + 1)) + ".proof.bin";
+            if (!a.overwrite && exists(out)) { fprintf(stderr, "%s: duplicate proof file: %s\n", wf.c_str(), out.c_str()); continue; }
+            spit(out, buf.data(), len);
+            fprintf(stderr, "Proof saved to %s\n", out.c_str());
+            written++;
+        }
+        if (written != witnesses.size()) return 2;
     } else if (cmd == "verify") {                                    // src/bin/main.rs:425-437 (no GPU involved)
         // VerifyOpts (src/bin/main.rs:125-137): the key is `-v` / `--verification_key` here, while export-verification-key
         // names its output `--vk` (src/bin/main.rs:186-187); `--vk` is kept as an alias on verify

@@ -34,6 +34,8 @@ static const uint64_t NON_RESIDUES[4] = {1, 5, 7, 10};     // k_j (vk.bin stores
 
 static inline Fr to_dev(const HFr &h) { Fr f; memcpy(f.l, h.l, 32); return f; }
 int32_t ensure_pinned2(plk_ctx *ctx, size_t bytes);
+int32_t fr_canonical_launch(const Fr *v, uint64_t first, uint64_t n, unsigned long long *bad, hipStream_t st);                                   // wtnsio.hip
+int32_t wtns_payload_to_dev(plk_ctx *ctx, const uint8_t *payload, uint64_t n, Fr *out, uint64_t keep, unsigned long long *bad, hipStream_t st);   // wtnsio.hip
 static inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static HFr host_omega(uint32_t log_n) {
@@ -515,6 +517,9 @@ struct ProveFront {
     const HFr *inputs_pinned = nullptr;
     bool assembled = false;                  // verdict layout: circuit = one flag word; assembled = ingest_columns' two words
     bool close_perm = false;                 // sigma came from the caller: check that the permutation argument closes (round 2)
+    int wire_check = 0;                      // circuit verdict layout, second word: 1 = lowest wire that is not canonical, 2 = lowest file element >= r
+    uint64_t wire_bad = ~0ull;               // what that word held
+    const char *who = "plk_prove";
     double t_prev = 0;                       // plk_prove_timings: start of the phase in progress
 };
 
@@ -522,7 +527,16 @@ struct ProveFront {
 static int32_t front_verdict(plk_ctx *ctx, const plk_setup *S, ProveFront &F) {
     const volatile uint32_t *flag = reinterpret_cast<volatile uint32_t *>(ctx->pinned);
     if (!F.assembled) {
+        if (F.wire_check) {
+            F.wire_bad = *reinterpret_cast<const volatile uint64_t *>(flag + 2);
+            if (F.wire_bad != ~0ull && F.wire_check == 2) { set_error("read witness failed: not in field"); return PLK_ERR_FORMAT; }
+            if (F.wire_bad != ~0ull) {
+                set_error(std::string(F.who) + ": wire " + std::to_string(F.wire_bad) + " holds an element that is not a canonical residue (limbs >= r)");
+                return PLK_ERR_ARG;
+            }
+        }
         if (flag[0]) { set_error("must satisfy: witness does not satisfy the circuit"); return PLK_ERR_UNSAT; }
+        if (F.inputs_pinned) F.inputs.assign(F.inputs_pinned, F.inputs_pinned + S->num_inputs);
         return PLK_OK;
     }
     if (const uint32_t bad = flag[0]) {
@@ -882,16 +896,31 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     return PLK_OK;
 }
 
-// The witness front end of plk_prove and plk_validate_witness: the circom wires and the transpiler's temporaries, by variable id, in
+// Where the witness of a proof comes from: exactly one of the four is set.
+struct WitnessSrc {
+    const plk_circuit *c = nullptr;          // a circuit object: its witness vector, page-locked from the second proof of the object on
+    const HFr *host = nullptr;               // n Montgomery elements in host memory (the caller's buffer: never page-locked)
+    const Fr *dev = nullptr;                 // n Montgomery elements on the device, complete once the work enqueued on `caller` is
+    const uint8_t *payload = nullptr;        // the n x 32 element bytes of a .wtns file whose container has been checked (wtnsio.hip decodes them)
+    uint64_t n = 0;
+    hipStream_t caller = nullptr;
+    uint64_t *bad_out_of_file = nullptr;     // plk_prove_wtns: receives the lowest refused element of the file
+};
+
+// The witness front end of plk_prove* and plk_validate_witness*: the circom wires and the transpiler's temporaries, by variable id, in
 // W->d_values on the device (enqueued on the context's stream).  whole_workspace: the arena of a proof (prove_workspace); otherwise only
-// the values and the verdict word.  lap (may be empty) is called once, after the host part: [0] of plk_prove_timings.
-static int32_t witness_front(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, const char *who, bool whole_workspace, ProveWs *W,
-                             const std::function<void()> &lap) {
+// the values and the verdict words.  lap (may be empty) is called once, after the host part: [0] of plk_prove_timings.
+// A witness that is not a circuit object's is checked on the device: the 64-bit word at W->d_flag + 2 receives the lowest wire in
+// [1, num_variables) that is not a canonical residue (host and device vectors) or the lowest element of the file that is >= r (file
+// bytes; every element of the file is looked at).  F (may be null): the public inputs, or where they are on their way to.
+static int32_t witness_front(plk_ctx *ctx, const plk_setup *S, const WitnessSrc &src, const char *who, bool whole_workspace, ProveWs *W,
+                             const std::function<void()> &lap, ProveFront *F) {
     hipStream_t st = ctx->stream;
+    const plk_circuit *c = src.c;
     // ---- witness synthesis (host): circom wires, then the transpiler's temporaries from their recorded
     //      linear forms (the gate structure itself lives in plk_setup; the reference re-synthesises here)
-    if (c->r1cs.num_variables != S->num_circuit_vars || c->witness.size() < S->num_circuit_vars) {
-        set_error(std::string(who) + ": circuit does not match the prepared setup"); return PLK_ERR_ARG; }
+    if (c ? (c->r1cs.num_variables != S->num_circuit_vars || c->witness.size() < S->num_circuit_vars) : src.n < S->num_circuit_vars) {
+        set_error(std::string(who) + (c ? ": circuit does not match the prepared setup" : ": the witness does not match the prepared setup")); return PLK_ERR_ARG; }
     // circom wires are uploaded straight from the (page-locked) witness buffer; only the temporaries are
     // computed here, into a pinned staging area.  id 0 (dummy) is zeroed on the device.
     const uint64_t ncv = S->num_circuit_vars, n_tmp = S->num_vars - ncv;
@@ -904,7 +933,8 @@ static int32_t witness_front(plk_ctx *ctx, const plk_setup *S, const plk_circuit
     // witnesses — that the runtime locks and unlocks on its own for pageable copies; pinning and unpinning such pages behind its
     // back ended, once in two or three runs of the whole GPU test suite, in "Memory access fault by GPU ... on address <heap page>"
     // during a LATER, unrelated host-to-device copy (round 4; profiles/r04_host_register_fault.txt).  A small upload gains nothing anyway.
-    {
+    // A caller's own vector (plk_prove_witness) is never page-locked, whatever its size.
+    if (c) {
         std::lock_guard<std::mutex> reg_lock(c->reg_mu);
         const size_t wit_bytes = c->witness.size() * sizeof(HFr);
         if (!c->witness_registered && wit_bytes >= ((size_t)4 << 20) && (int)(c->proofs_started++) >= reg_mode) {
@@ -914,12 +944,13 @@ static int32_t witness_front(plk_ctx *ctx, const plk_setup *S, const plk_circuit
     }
     static const bool tmp_host_env = [] { const char *e = getenv("PLK_WITNESS_TMP_HOST"); return e && e[0] == '1'; }();      // tests: the host loop
     const bool tmp_on_device = !tmp_host_env && (S->ops_independent || S->ops_chained) && (S->ops_dev.p || S->ops.empty());
-    PLK_TRY(ensure_pinned2(ctx, (tmp_on_device ? 1 : n_tmp + 1) * sizeof(HFr)));
+    const HFr *wit = c ? c->witness.data() : src.host;                         // null: the witness is on the device, or still file bytes
+    const bool inputs_from_device = !wit && tmp_on_device && F && S->num_inputs;
+    PLK_TRY(ensure_pinned2(ctx, (tmp_on_device ? (inputs_from_device ? S->num_inputs : 1) : n_tmp + 1) * sizeof(HFr)));
     HFr *tmp_vals = reinterpret_cast<HFr *>(ctx->pinned2);
-    const HFr *wit = c->witness.data();
-    if (!tmp_on_device) {
+    auto host_temporaries = [&](const HFr *w) {
         const size_t n_ops = S->ops.size();
-        auto value_of = [&](uint32_t v) -> HFr { return v == 0 ? HFr::zero() : (v < ncv ? wit[v] : tmp_vals[v - ncv]); };
+        auto value_of = [&](uint32_t v) -> HFr { return v == 0 ? HFr::zero() : (v < ncv ? w[v] : tmp_vals[v - ncv]); };
         auto eval_range = [&](size_t lo, size_t hi) {
             for (size_t i = lo; i < hi; i++) {
                 const WitnessOp &op = S->ops[i];
@@ -937,25 +968,60 @@ static int32_t witness_front(plk_ctx *ctx, const plk_setup *S, const plk_circuit
             for (unsigned t = 0; t < nt; t++) { size_t lo = t * per, hi = std::min(n_ops, lo + per); if (lo < hi) th.emplace_back(eval_range, lo, hi); }
             for (auto &x : th) x.join();
         } else eval_range(0, n_ops);
-    }
-    struct { uint64_t num_vars; } T;
-    T.num_vars = S->num_vars;
-    if (lap) lap();                                                           // [0] witness synthesis
-
-    if (whole_workspace) PLK_TRY(prove_workspace(ctx, S, T.num_vars, W));
-    else {                                                                    // plk_validate_witness: the values and the verdict word only
-        PLK_TRY(ctx->prove_ws.reserve(((T.num_vars * sizeof(Fr) + 255) & ~(size_t)255) + 256));
+    };
+    auto workspace = [&]() -> int32_t {
+        if (whole_workspace) return prove_workspace(ctx, S, S->num_vars, W);
+        // plk_validate_witness*: the values and the verdict words only
+        PLK_TRY(ctx->prove_ws.reserve(((S->num_vars * sizeof(Fr) + 255) & ~(size_t)255) + 256));
         Arena A{&ctx->prove_ws};
-        W->d_values = A.take<Fr>(T.num_vars);
+        W->d_values = A.take<Fr>(S->num_vars);
         W->d_flag = A.take<uint32_t>(64);
+        return PLK_OK;
+    };
+    if (wit) {
+        if (!tmp_on_device) host_temporaries(wit);
+        if (lap) lap();                                                       // [0] witness synthesis
+        PLK_TRY(workspace());
+        if (c) {   // (under the circuit's lock: another context proving the SAME circuit object may be about to page-lock this buffer —
+                   //  not while a pageable copy of it is being staged)
+            std::lock_guard<std::mutex> upload_lock(c->reg_mu);
+            PLK_HIP(hipMemcpyAsync(W->d_values, wit, ncv * sizeof(Fr), hipMemcpyHostToDevice, st));
+        } else PLK_HIP(hipMemcpyAsync(W->d_values, wit, ncv * sizeof(Fr), hipMemcpyHostToDevice, st));       // pageable
+        if (F) F->inputs.assign(wit + 1, wit + 1 + S->num_inputs);
+    } else {
+        PLK_TRY(workspace());
+        unsigned long long *d_wire = reinterpret_cast<unsigned long long *>(W->d_flag + 2);
+        PLK_HIP(hipMemsetAsync(d_wire, 0xff, 8, st));
+        if (src.dev) {
+            if (src.caller && src.caller != st) {                             // ordered after what the caller has enqueued on its stream
+                if (!ctx->in_ready) PLK_HIP(hipEventCreateWithFlags(&ctx->in_ready, hipEventDisableTiming));
+                PLK_HIP(hipEventRecord(ctx->in_ready, src.caller));
+                PLK_HIP(hipStreamWaitEvent(st, ctx->in_ready, 0));
+            }
+            PLK_HIP(hipMemcpyAsync(W->d_values, src.dev, ncv * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+        } else PLK_TRY(wtns_payload_to_dev(ctx, src.payload, src.n, W->d_values, ncv, d_wire, st));
     }
     Fr *const d_values = W->d_values;
-    {   // (under the circuit's lock: another context proving the SAME circuit object may be about to page-lock this buffer —
-        //  not while a pageable copy of it is being staged)
-        std::lock_guard<std::mutex> upload_lock(c->reg_mu);
-        PLK_HIP(hipMemcpyAsync(d_values, wit, ncv * sizeof(Fr), hipMemcpyHostToDevice, st));
+    if (!c && !src.payload) {                                                 // (a file's elements have been range-checked by the decode kernel)
+        unsigned long long *d_wire = reinterpret_cast<unsigned long long *>(W->d_flag + 2);
+        if (wit) PLK_HIP(hipMemsetAsync(d_wire, 0xff, 8, st));
+        PLK_TRY(fr_canonical_launch(d_values, 1, ncv, d_wire, st));
     }
     PLK_HIP(hipMemsetAsync(d_values, 0, sizeof(Fr), st));
+    std::vector<HFr> back;
+    if (!wit) {
+        if (!tmp_on_device) {   // a setup whose temporaries need the host loop: the wires come back once
+            back.resize(ncv);
+            PLK_HIP(hipMemcpyAsync(back.data(), d_values, ncv * sizeof(Fr), hipMemcpyDeviceToHost, st));
+            PLK_HIP(hipStreamSynchronize(st));
+            host_temporaries(back.data());
+            if (F) F->inputs.assign(back.data() + 1, back.data() + 1 + S->num_inputs);
+        } else if (inputs_from_device) {                                      // the few public inputs travel behind the verdict's event
+            PLK_HIP(hipMemcpyAsync(ctx->pinned2, d_values + 1, S->num_inputs * sizeof(Fr), hipMemcpyDeviceToHost, st));
+            F->inputs_pinned = reinterpret_cast<const HFr *>(ctx->pinned2);
+        }
+        if (lap) lap();                                                       // [0] witness ingest
+    }
     if (n_tmp && tmp_on_device && S->ops_chained)
         PLK_TRY(eval_witness_runs(d_values, S->ops_dev.p, S->terms_dev.p, S->runs_dev.p, (uint32_t)S->run_start.size(), (uint32_t)S->ops.size(), (uint32_t)ncv, st));
     else if (n_tmp && tmp_on_device) PLK_TRY(eval_witness_ops(d_values, S->ops_dev.p, S->terms_dev.p, (uint32_t)S->ops.size(), (uint32_t)ncv, st));
@@ -964,19 +1030,20 @@ static int32_t witness_front(plk_ctx *ctx, const plk_setup *S, const plk_circuit
 }
 
 
-static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
-    if (!ctx || !S || !c || !proof_out || !len) { set_error("plk_prove: bad argument"); return PLK_ERR_ARG; }
+// `who`: plk_prove (a circuit object) or one of plk_prove_witness / _witness_dev / _wtns (src.c null)
+static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const WitnessSrc &src, const char *who, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    const plk_circuit *c = src.c;
     *len = 0;
     if (S->from_polys) {
-        set_error("plk_prove: this setup was built from polynomials (plk_setup_from_polynomials) and has no gate structure: "
+        set_error(std::string(who) + ": this setup was built from polynomials (plk_setup_from_polynomials) and has no gate structure: "
                   "prove it from assembled columns with plk_prove_assembled / plk_prove_assembled_dev");
         return PLK_ERR_ARG;
     }
-    if (!c->has_witness) { set_error("plk_prove: circuit has no witness"); return PLK_ERR_ARG; }
+    if (c && !c->has_witness) { set_error("plk_prove: circuit has no witness"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
     if (!ctx->srs || (!ctx->combine && ctx->srs_n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
-    if (!S->store.p) { set_error("plk_prove: the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
-    PLK_TRY(fifo_must_be_empty(ctx, "plk_prove"));
+    if (!S->store.p) { set_error(std::string(who) + ": the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
+    PLK_TRY(fifo_must_be_empty(ctx, who));
     FifoGuard fifo_guard(ctx);
     ctx->timings.clear();
     ctx->trace.valid = false;
@@ -985,12 +1052,13 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
     hipStream_t st = ctx->stream;
 
     ProveWs W;
-    PLK_TRY(witness_front(ctx, S, c, "plk_prove", true, &W, lap));
+    ProveFront F;
+    F.who = who;
+    F.wire_check = c ? 0 : (src.payload ? 2 : 1);
+    PLK_TRY(witness_front(ctx, S, src, who, true, &W, lap, &F));
     const uint64_t N = S->N;
     Fr *const d_values = W.d_values;
     uint32_t *const d_flag = W.d_flag;
-    const HFr *wit = c->witness.data();
-    std::vector<HFr> inputs(wit + 1, wit + 1 + S->num_inputs);
     {   // is_satisfied_using_one_shot_check (src/plonk.rs:137) on the device
         CheckArgs ca;
         ca.values = d_values; ca.n = (uint32_t)N; ca.num_inputs = (uint32_t)S->num_inputs; ca.flag = d_flag;
@@ -1001,37 +1069,36 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c
         // the verdict is read back into the pinned result buffer and looked at after round 1 has been enqueued (before any
         // commitment is used): the host does not stall the GPU for it.  An unsatisfied witness still ends the call with
         // PLK_ERR_UNSAT and no proof bytes — the commitments under way are drained by the FIFO guard.
-        PLK_HIP(hipMemcpyAsync(ctx->pinned, d_flag, 4, hipMemcpyDeviceToHost, st));
+        // (with a witness that was checked on the device, the word of that check travels with it: bytes 8..16)
+        PLK_HIP(hipMemcpyAsync(ctx->pinned, d_flag, F.wire_check ? 16 : 4, hipMemcpyDeviceToHost, st));
         if (!ctx->flag_ready) PLK_HIP(hipEventCreateWithFlags(&ctx->flag_ready, hipEventDisableTiming));
         PLK_HIP(hipEventRecord(ctx->flag_ready, st));
     }
     PLK_TRY(gather4_dual(W.w_vals, W.w_coef, d_values, S->gate_vars, (uint32_t)N, st));
-    ProveFront F;
-    F.inputs.swap(inputs);
     F.t_prev = t_prev;
-    return prove_rounds(ctx, S, W, F, proof_out, cap, len);
+    const int32_t rc = prove_rounds(ctx, S, W, F, proof_out, cap, len);
+    if (src.bad_out_of_file) *src.bad_out_of_file = F.wire_bad;
+    return rc;
 }
 
 // SetupForProver::validate_witness (src/plonk.rs:127-129): the witness front end of plk_prove and the gate equation of every row, on their
 // own — no key, no commitment, no round.  The verdict names the lowest failing row (the row kernel of the assembled path, assembled.hip,
 // reports the same way; here it is an atomicMin on a 64-bit word).
-static int32_t validate_witness_impl(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, int32_t *valid, uint64_t *bad_row) {
-    if (valid) *valid = 0;
-    if (bad_row) *bad_row = ~0ull;
-    if (!ctx || !S || !c || !valid) { set_error("plk_validate_witness: bad argument"); return PLK_ERR_ARG; }
+static int32_t validate_witness_impl(plk_ctx *ctx, const plk_setup *S, const WitnessSrc &src, const char *who, int32_t *valid, uint64_t *bad_row) {
+    const plk_circuit *c = src.c;
     if (S->from_polys) {
-        set_error("plk_validate_witness: this setup was built from polynomials (plk_setup_from_polynomials) and has no gate structure: "
+        set_error(std::string(who) + ": this setup was built from polynomials (plk_setup_from_polynomials) and has no gate structure: "
                   "the assembled columns are checked by plk_prove_assembled / plk_prove_assembled_dev");
         return PLK_ERR_ARG;
     }
-    if (!c->has_witness) { set_error("plk_validate_witness: circuit has no witness"); return PLK_ERR_ARG; }
+    if (c && !c->has_witness) { set_error("plk_validate_witness: circuit has no witness"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
-    if (!S->store.p) { set_error("plk_validate_witness: the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
-    PLK_TRY(fifo_must_be_empty(ctx, "plk_validate_witness"));
+    if (!S->store.p) { set_error(std::string(who) + ": the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
+    PLK_TRY(fifo_must_be_empty(ctx, who));
     ctx->trace.valid = false;                                                 // the workspace the trace points into is written below
     hipStream_t st = ctx->stream;
     ProveWs W;
-    PLK_TRY(witness_front(ctx, S, c, "plk_validate_witness", false, &W, nullptr));
+    PLK_TRY(witness_front(ctx, S, src, who, false, &W, nullptr, nullptr));
     unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(W.d_flag);
     CheckArgs ca;
     ca.values = W.d_values; ca.n = (uint32_t)S->N; ca.num_inputs = (uint32_t)S->num_inputs; ca.flag = nullptr;
@@ -1039,14 +1106,25 @@ static int32_t validate_witness_impl(plk_ctx *ctx, const plk_setup *S, const plk
     for (int j = 0; j < 4; j++) ca.vars[j] = S->gate_vars[j];
     PLK_HIP(hipMemsetAsync(d_bad, 0xff, 8, st));
     PLK_TRY(check_gates_row(ca, d_bad, st));
-    unsigned long long bad = ~0ull;
-    PLK_HIP(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
+    unsigned long long got[2] = {~0ull, ~0ull};
+    PLK_HIP(hipMemcpyAsync(got, d_bad, c ? 8 : 16, hipMemcpyDeviceToHost, st));
     PLK_HIP(hipStreamSynchronize(st));                                        // the verdict is this call's return value
-    *valid = bad == ~0ull ? 1 : 0;
-    if (bad_row) *bad_row = bad;
+    if (got[1] != ~0ull) {
+        set_error(std::string(who) + ": wire " + std::to_string(got[1]) + " holds an element that is not a canonical residue (limbs >= r)");
+        return PLK_ERR_ARG;
+    }
+    *valid = got[0] == ~0ull ? 1 : 0;
+    if (bad_row) *bad_row = got[0];
     return PLK_OK;
 }
 
+// argument checks of the entry points that take a witness without its circuit, then the shared implementation
+static int32_t prove_witness_entry(plk_ctx *ctx, const plk_setup *S, WitnessSrc src, const char *who, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    if (len) *len = 0;
+    if (!ctx || !S || !proof_out || !len || (!src.host && !src.dev && !src.payload)) { set_error(std::string(who) + ": bad argument"); return PLK_ERR_ARG; }
+    if (src.dev && ((uintptr_t)src.dev & 15u)) { set_error(std::string(who) + ": the witness must be 16-byte aligned"); return PLK_ERR_ARG; }
+    return prove_impl(ctx, S, src, who, proof_out, cap, len);
+}
 
 // ---- the assembled-input path: SetupPolynomials (src/plonk.rs:50-55,104) and prove_by_steps on a circuit bellman has synthesised
 //      (src/plonk.rs:152-159) — the setup polynomials and the four wire columns come from the caller, not from this library's transpiler
@@ -1275,10 +1353,51 @@ int32_t plk_setup_write_vk(plk_ctx *ctx, const plk_setup *s, const uint8_t g2_by
 }
 int32_t plk_prove(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
     PLK_TRY(not_a_worker(ctx, "plk_prove"));
-    return guarded("plk_prove", PLK_ERR_HIP, [&] { return prove_impl(ctx, S, c, proof_out, cap, len); });
+    return guarded("plk_prove", PLK_ERR_HIP, [&]() -> int32_t {
+        if (!ctx || !S || !c || !proof_out || !len) { set_error("plk_prove: bad argument"); return PLK_ERR_ARG; }
+        WitnessSrc src; src.c = c;
+        return prove_impl(ctx, S, src, "plk_prove", proof_out, cap, len); });
+}
+int32_t plk_prove_witness(plk_ctx *ctx, const plk_setup *S, const plk_fr *witness_host, uint64_t n, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    PLK_TRY(not_a_worker(ctx, "plk_prove_witness"));
+    return guarded("plk_prove_witness", PLK_ERR_HIP, [&] {
+        WitnessSrc src; src.host = reinterpret_cast<const HFr *>(witness_host); src.n = n;
+        return prove_witness_entry(ctx, S, src, "plk_prove_witness", proof_out, cap, len); });
+}
+int32_t plk_prove_witness_dev(plk_ctx *ctx, const plk_setup *S, const void *witness_dev, uint64_t n, uint8_t *proof_out, uint64_t cap, uint64_t *len, void *stream) {
+    PLK_TRY(not_a_worker(ctx, "plk_prove_witness_dev"));
+    return guarded("plk_prove_witness_dev", PLK_ERR_HIP, [&] {
+        WitnessSrc src; src.dev = static_cast<const Fr *>(witness_dev); src.n = n; src.caller = (hipStream_t)stream;
+        return prove_witness_entry(ctx, S, src, "plk_prove_witness_dev", proof_out, cap, len); });
+}
+int32_t plk_prove_wtns(plk_ctx *ctx, const plk_setup *S, const uint8_t *wtns, uint64_t wtns_len, uint8_t *proof_out, uint64_t cap, uint64_t *len, uint64_t *bad_out) {
+    if (bad_out) *bad_out = ~0ull;
+    PLK_TRY(not_a_worker(ctx, "plk_prove_wtns"));
+    return guarded("plk_prove_wtns", PLK_ERR_HIP, [&]() -> int32_t {
+        if (len) *len = 0;
+        if (!ctx || !S || !wtns || !proof_out || !len) { set_error("plk_prove_wtns: bad argument"); return PLK_ERR_ARG; }
+        WitnessSrc src;
+        size_t payload = 0;
+        if (!wtns_container(wtns, wtns_len, &src.n, &payload)) return PLK_ERR_FORMAT;     // plk_wtns_decode's (parse_wtns_bin's) container checks
+        src.payload = wtns + payload; src.bad_out_of_file = bad_out;
+        return prove_witness_entry(ctx, S, src, "plk_prove_wtns", proof_out, cap, len); });
 }
 int32_t plk_validate_witness(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, int32_t *valid, uint64_t *bad_row) {
-    return guarded("plk_validate_witness", PLK_ERR_HIP, [&] { return validate_witness_impl(ctx, S, c, valid, bad_row); });
+    return guarded("plk_validate_witness", PLK_ERR_HIP, [&]() -> int32_t {
+        if (valid) *valid = 0;
+        if (bad_row) *bad_row = ~0ull;
+        if (!ctx || !S || !c || !valid) { set_error("plk_validate_witness: bad argument"); return PLK_ERR_ARG; }
+        WitnessSrc src; src.c = c;
+        return validate_witness_impl(ctx, S, src, "plk_validate_witness", valid, bad_row); });
+}
+int32_t plk_validate_witness_dev(plk_ctx *ctx, const plk_setup *S, const void *witness_dev, uint64_t n, int32_t *valid, uint64_t *bad_row, void *stream) {
+    return guarded("plk_validate_witness_dev", PLK_ERR_HIP, [&]() -> int32_t {
+        if (valid) *valid = 0;
+        if (bad_row) *bad_row = ~0ull;
+        if (!ctx || !S || !witness_dev || !valid) { set_error("plk_validate_witness_dev: bad argument"); return PLK_ERR_ARG; }
+        if ((uintptr_t)witness_dev & 15u) { set_error("plk_validate_witness_dev: the witness must be 16-byte aligned"); return PLK_ERR_ARG; }
+        WitnessSrc src; src.dev = static_cast<const Fr *>(witness_dev); src.n = n; src.caller = (hipStream_t)stream;
+        return validate_witness_impl(ctx, S, src, "plk_validate_witness_dev", valid, bad_row); });
 }
 int32_t plk_setup_from_polynomials(plk_ctx *ctx, uint64_t n, uint64_t num_inputs, const plk_fr *const selectors[6], const plk_fr *next_step_selector,
                                    const plk_fr *const sigmas[4], uint64_t len, uint32_t flags, plk_setup **out) {
