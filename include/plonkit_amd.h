@@ -153,7 +153,7 @@ typedef struct plk_msm_shape {
     uint32_t window_bits, windows;       /* c and floor(254 / c) + 1                                                           */
     uint32_t bucket_sets;                /* per commitment: windows / table_copies                                             */
     uint32_t fine_bits, coarse_bins;     /* buckets per task = 2^fine_bits; bins per bucket set                                */
-    uint32_t accumulate_variant;         /* 0 equal pieces per lane, 1 the one-wave measurement build, 2 lanes own buckets     */
+    uint32_t accumulate_variant;         /* 0 equal pieces per lane, 2 lanes own buckets (1: a measurement build, retired)    */
     uint32_t prephase;                   /* 1 recoding fused with the partition (digits stay in registers), 2 through the digit array */
     uint32_t reduce_lanes;               /* per task of the bucket reduction: 4 = quads of lanes (one wave per task), 16 or 32 lanes */
     /* the last call of plk_msm_g1 / _dev / _partial_dev, if no other commitment finished since (otherwise 1 and the length):  */

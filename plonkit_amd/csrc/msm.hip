@@ -24,7 +24,7 @@
 //   * a bucket spread over many lanes (repeated scalars: all-ones, all -1) is folded by a separate small kernel
 //     (msm_fold_hot), a coarse bin spread over many tasks by another (msm_bin_fold).
 //   * per task T = sum B_f and S = sum (f+1) B_f (running sums + 32-lane shuffle scan), then per bucket set
-//     sum_t S_t, sum_t t * E_t and F_1..F_3 (msm_window_sums); the remaining shifts (2^FB, 2^8), sum u * F_u and the
+//     sum_t S_t, sum_t t * E_t and F_1..F_3 (msm_window_sums_quad); the remaining shifts (2^FB, 2^8), sum u * F_u and the
 //     Horner over the sets run on the host, where one serial EC chain is 20x faster than on a GPU lane.  The reduce
 //     kernels are chains of full additions issued from one inlined call site each.
 //   * up to 8 commitments over the same bases share every kernel launch (batch dimension), and three commitments
@@ -42,7 +42,6 @@
 #include "hostmath.h"
 #include <cstring>
 #include <cstdlib>
-#include <type_traits>
 
 namespace plk {
 
@@ -52,12 +51,10 @@ int32_t msm_small_launch(plk_ctx::MsmSlot &S, hipStream_t stream, const G1Affine
 constexpr uint32_t SM_PLANES_HOST = 17;
 // terms up to which a commitment takes it: 2^15 (measured, one at a time: 2^14 terms 0.27 against 0.62 ms, 2^15 0.35 against 0.53, 2^16 0.52 against
 // 0.54; a proof at the 2^15 domain 3.25 against 3.40 ms; at 2^16 a batch of two is SLOWER on this path — a proof 3.76 against 3.56 ms — and a batch
-// of four much slower: 4.85).  PLK_MSM_SMALL_MAX overrides (0 = never: A/B knob)
-static uint64_t msm_small_max(uint32_t batch) {
-    static const long long v = [] { const char *e = getenv("PLK_MSM_SMALL_MAX"); return e ? (long long)strtoull(e, nullptr, 10) : -1ll; }();
-    (void)batch;
-    return v >= 0 ? (uint64_t)v : (1ull << 15);
-}
+// of four much slower: 4.85)
+constexpr uint64_t MSM_SMALL_MAX = 1ull << 15;
+// terms up to which msm_accumulate is launched in the build whose lanes own the buckets of an evenly filled task (msm_accumulate.hip)
+constexpr uint64_t MSM_OWNED_MAX = 1ull << 16;
 
 // -------------------------------------------------------------------------- scalar recoding
 // Step 1: every scalar leaves Montgomery form once and is recoded into W signed c-bit digits in
@@ -528,7 +525,7 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_fold_hot(XyzzW *partials, con
 // L2 write-through traffic than the arithmetic (measured 0.60 ms for this kernel against 0.3 ms of VALU work).
 template <uint32_t FB, uint32_t RL_LOG>
 __global__ void __launch_bounds__(MSM_THREADS, 2) msm_task_reduce(const XyzzW *partials, const uint32_t *task_meta,
-                                                                   const uint32_t *task_start, XyzzW *task_out, uint32_t total_bins, uint32_t early_exit) {
+                                                                   const uint32_t *task_start, XyzzW *task_out, uint32_t total_bins) {
     constexpr uint32_t FINE = Shape<FB>::FINE, SLOT_PRIMARY = Shape<FB>::SLOT_PRIMARY, SLOT_HEAD = Shape<FB>::SLOT_HEAD, SLOT_TAIL = Shape<FB>::SLOT_TAIL,
                        SLOTS_PER_TASK = Shape<FB>::SLOTS_PER_TASK, META_PER_TASK = Shape<FB>::META_PER_TASK, RL = 1u << RL_LOG, RB = FINE / RL, RB_LOG = FB - RL_LOG;
     static_assert(FB >= RL_LOG + 1, "at least two buckets per lane");
@@ -538,7 +535,7 @@ __global__ void __launch_bounds__(MSM_THREADS, 2) msm_task_reduce(const XyzzW *p
     const bool live = task < task_start[total_bins];
     // the grid covers the UPPER BOUND of the task count (bins + entries / TASK_MAX: about twice the tasks of uniform scalars); a wave without a live task would
     // still walk the USTEPS tree steps on identities — and, from three commitments on, share its SIMD with a live wave whose every step it then doubles
-    if (early_exit && !__any(live)) return;
+    if (!__any(live)) return;
     const uint32_t *meta = task_meta + (size_t)(live ? task : 0) * META_PER_TASK;
     const uint32_t nc_raw = live ? meta[FINE + 1] : 0, nc = nc_raw & ~TASK_OWNED_BIT;
     const uint32_t mu = (nc_raw & TASK_OWNED_BIT) ? 0x7fffffffu : (nc ? (nc + MSM_THREADS - 1) / MSM_THREADS : 1);   // (owned: every bucket is whole — PRIMARY)
@@ -603,13 +600,13 @@ __global__ void __launch_bounds__(MSM_THREADS, 2) msm_task_reduce(const XyzzW *p
 // every step one four-lane addition (2.6 us for a wave alone on its SIMD against 7.3 for the lane-wise addition).  Launched for ONE commitment (1024 waves:
 // one per SIMD; 191 -> 142 us at 2^20 terms); batches keep the lane-wise kernel, whose lanes do the same work in a quarter of the lane-instructions.  The RB_LOG doublings (X + X) leave through the addition's rare branch.
 template <uint32_t FB>
-__global__ void __launch_bounds__(MSM_THREADS) msm_task_reduce_quad(const XyzzW *partials, const uint32_t *task_meta, const uint32_t *task_start, XyzzW *task_out, uint32_t total_bins, uint32_t early_exit) {
+__global__ void __launch_bounds__(MSM_THREADS) msm_task_reduce_quad(const XyzzW *partials, const uint32_t *task_meta, const uint32_t *task_start, XyzzW *task_out, uint32_t total_bins) {
     constexpr uint32_t FINE = Shape<FB>::FINE, SLOT_PRIMARY = Shape<FB>::SLOT_PRIMARY, SLOT_HEAD = Shape<FB>::SLOT_HEAD, SLOT_TAIL = Shape<FB>::SLOT_TAIL,
                        SLOTS_PER_TASK = Shape<FB>::SLOTS_PER_TASK, META_PER_TASK = Shape<FB>::META_PER_TASK, RL_LOG = 4, RL = 1u << RL_LOG, RB = FINE / RL, RB_LOG = FB - RL_LOG;
     latency_chain_priority();
     const uint32_t task = blockIdx.x * (MSM_THREADS / 64) + (threadIdx.x >> 6), sub = (threadIdx.x & 63u) >> 2, coord = threadIdx.x & 3u;
     const bool live = task < task_start[total_bins];
-    if (early_exit && !live) return;                          // (wave-uniform: one wave = one task; see msm_task_reduce)
+    if (!live) return;                                        // (wave-uniform: one wave = one task; see msm_task_reduce)
     const uint32_t *meta = task_meta + (size_t)(live ? task : 0) * META_PER_TASK;
     const uint32_t nc_raw = live ? meta[FINE + 1] : 0, nc = nc_raw & ~TASK_OWNED_BIT;
     const uint32_t mu = (nc_raw & TASK_OWNED_BIT) ? 0x7fffffffu : (nc ? (nc + MSM_THREADS - 1) / MSM_THREADS : 1);
@@ -670,7 +667,7 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_task_reduce_quad(const XyzzW 
 
 // ------------------------------------------------------------------------ bin folding
 // A coarse bin cut into many tasks (repeated scalars: all ones, all r-1, a witness of booleans put 2^20 entries into one
-// bucket of every window) would be walked task by task by ONE thread of msm_window_sums — a serial chain of full
+// bucket of every window) would be walked task by task by ONE quad of msm_window_sums_quad — a serial chain of full
 // additions (all r-1 at 2^20: 3.4 ms against 2.0 ms for uniform scalars).  The per-task sums of a bin simply add up
 // (same bucket range), so one wave per such bin folds them first: lane l takes tasks l, l + 64, .. then a shuffle tree;
 // the bin's first task receives (sum S, sum T), the others the identity.  Bins with <= BIN_FOLD_MIN tasks are left alone:
@@ -691,66 +688,24 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_bin_fold(XyzzW *task_out, con
 }
 
 // ------------------------------------------------------------------------ window reduction
-// W_w = sum_t S_t + 2^FB * sum_c c * D_c,  D_c = sum of T_t over the tasks of coarse bin c.
-// 256 threads; thread t serves bins t, t + 256, .. (nbins <= 1024: up to four of them).  With c = 256 u + t:
+// W_w = sum_t S_t + 2^FB * sum_c c * D_c,  D_c = sum of T_t over the tasks of coarse bin c.  With c = 256 u + t (nbins <= 1024: u < 4):
 //     sum_c c * D_c = sum_t t * E_t + 256 * sum_{u >= 1} u * F_u,   E_t = sum_u D_{t + 256 u},   F_u = sum_t D_{t + 256 u},
 //     sum_t t * E_t = sum_{b < 8} 2^b * G_b,                          G_b = sum of E_t over the t with bit b set.
-// One workgroup per role, side by side, each a plain tree sum (its threads first add up their own bins, then 8 tree steps):
-// role 0: sum of the S_t; roles 1..8: G_0..G_7; roles 9..: F_1.. .  Round 1 formed sum_t t * E_t with a suffix scan in one
-// workgroup (8 more dependent additions of ~8 us on the tail of every commitment); the weights 2^b, 2^FB, 2^8 and u are a
-// few dozen host operations.  Pure chains of full additions from one inlined call site (operands in registers, see
-// msm_task_reduce).  Results leave in the library's external form (canonical, R = 2^256).
+// One workgroup per role, side by side, each a plain tree sum: role 0 and the LAST role: sum of the S_t (bins below / from nbins / 2, the host
+// adds the two); roles 1..8: G_0..G_7; roles 9..: F_1.. .  Round 1 formed sum_t t * E_t with a suffix scan in one workgroup (8 more dependent
+// additions of ~8 us on the tail of every commitment); the weights 2^b, 2^FB, 2^8 and u are a few dozen host operations.  Pure chains of full
+// additions from one inlined call site (operands in registers, see msm_task_reduce).  Results leave in the library's external form
+// (canonical, R = 2^256).
 constexpr uint32_t THREADS_LOG = 8;
 static_assert((1u << THREADS_LOG) == MSM_THREADS, "THREADS_LOG");
 constexpr uint32_t WS_BIT_ROLES = THREADS_LOG, WS_FIRST_F_ROLE = 1 + WS_BIT_ROLES;
-__global__ void __launch_bounds__(MSM_THREADS, 2) msm_window_sums(const XyzzW *task_out, const uint32_t *task_start, G1Xyzz *window_out, uint32_t nbins, uint32_t roles) {
-    __shared__ __attribute__((aligned(16))) XyzzW sh[MSM_THREADS];
-    latency_chain_priority();
-    const uint32_t tid = threadIdx.x, w = blockIdx.x, role = blockIdx.y;
-    const uint32_t halves = (nbins + MSM_THREADS - 1) / MSM_THREADS;            // 1 .. 4
-    const bool takes_part = role == 0 || role >= WS_FIRST_F_ROLE || ((tid >> (role - 1)) & 1);
-    uint32_t u = role >= WS_FIRST_F_ROLE ? role - WS_FIRST_F_ROLE + 1 : 0;
-    const uint32_t u_end = !takes_part ? u : (role >= WS_FIRST_F_ROLE ? u + 1 : halves);
-    uint32_t t = 0, t_end = 0;
-    auto open_bin = [&]() {                                   // next non-empty bin of this thread
-        for (; u < u_end; u++) {
-            const uint32_t bin = tid + MSM_THREADS * u;
-            if (bin >= nbins) continue;
-            t = task_start[w * nbins + bin]; t_end = task_start[w * nbins + bin + 1];
-            if (t < t_end) return;
-        }
-        t = t_end = 0;
-    };
-    open_bin();
-    XyzzW X = xyzzw_identity();
-    uint32_t ustep = 0;
-    for (;;) {
-        const bool lockstep = __syncthreads_and(t >= t_end);  // (also the barrier that lets sh be rewritten)
-        if (lockstep && ustep == THREADS_LOG) break;
-        XyzzW O = xyzzw_identity();
-        if (!lockstep) {
-            if (t < t_end) {
-                O = load_xyzzw(task_out + 2 * (size_t)t + (role ? 1 : 0));
-                if (++t == t_end) { u++; open_bin(); }
-            }
-        } else {
-            sh[tid] = X;
-            __syncthreads();
-            const uint32_t off = (MSM_THREADS / 2) >> ustep;
-            if (tid < off) O = sh[tid + off];
-            ustep++;
-        }
-        xyzzw_add(X, O);                                      // the one addition site of the kernel
-    }
-    if (tid == 0) store_xyzz(window_out + (size_t)roles * w + role, xyzzw_export(X));
-}
 
-// The same sums by quads of lanes (late round 6; ec29_quad_dev.h, distributed form: lane r of a quad holds coordinate r of its running sum): a full
+// The sums by quads of lanes (late round 6; ec29_quad_dev.h, distributed form: lane r of a quad holds coordinate r of its running sum): a full
 // addition is four products deep instead of fourteen — 2.6 us per step for a wave that has its SIMD to itself against 7.3 — and the steps carry no
 // workgroup barrier (waves run their own bins, then ONE exchange through LDS).  One workgroup of 64 quads per (bucket set, role); role 0 is split in two
-// (bins below / from nbins / 2: the second half is the LAST role, the host adds the two) so that no quad walks more than nbins / 128 bins; the G_b roles
-// enumerate their nbins / 2 bins directly.  12 + 6 steps of 2.6 us at 1024 bins against 4 + 8 steps of 8.3 us (msm_window_sums: 100 -> ~45 us on the tail of every
-// commitment of >= 2^16 terms).
+// (bins below / from nbins / 2: the second half is the LAST role) so that no quad walks more than nbins / 128 bins; the G_b roles
+// enumerate their nbins / 2 bins directly.  12 + 6 steps of 2.6 us at 1024 bins against 4 + 8 steps of 8.3 us of the lane-wise kernel it replaced
+// (100 -> ~45 us on the tail of every commitment of >= 2^16 terms, profiles/r06b_msm_quads_ab.txt).
 __global__ void __launch_bounds__(MSM_THREADS) msm_window_sums_quad(const XyzzW *task_out, const uint32_t *task_start, G1Xyzz *window_out, uint32_t nbins, uint32_t roles) {
     __shared__ __attribute__((aligned(16))) uint32_t sh[4][4][9];
     latency_chain_priority();
@@ -841,18 +796,6 @@ static uint32_t pick_window_bits(uint64_t n, bool have_table) {
     return 17;                                                // 15 windows; 2^16 buckets = 512 coarse bins x 128
 }
 
-// Buckets per task.  64 (one task per coarse bin at the 2^20-term / one-bucket-set shape, half the bucket-reduction work)
-// whenever the coarse part then still fits the 1024 bins msm_window_sums serves; PLK_MSM_FINE_BITS overrides (A/B runs).
-static uint32_t pick_fine_bits(uint64_t n, uint32_t c) {
-    static const int probe = [] { const char *e = getenv("PLK_MSM_FINE_BITS"); return e ? atoi(e) : 0; }();
-    uint32_t fb = (probe == 6 || probe == 7) ? (uint32_t)probe : 6;
-    (void)n;
-    if (c - 1 - fb > 10) fb = FINE_BITS_MAX;                  // at most 1024 coarse bins
-    return fb;
-}
-
-int32_t ensure_pinned(plk_ctx *ctx, size_t bytes);
-
 static int32_t slot_pinned(plk_ctx::MsmSlot &S, size_t bytes) {
     if (bytes <= S.pinned_cap) return PLK_OK;
     if (S.pinned) (void)hipHostFree(S.pinned);
@@ -876,12 +819,10 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
     p.groups = p.windows / copies;                            // copies > 1 only for c = 17: 15 windows, copies | 15
     p.nbits = A.nbits;
     p.copy_stride = copies > 1 ? (uint32_t)(p.groups * A.srs_n) : 0;
-    p.fine_bits = pick_fine_bits(n, p.c);
-    p.coarse_bits = p.c - 1 - p.fine_bits;
+    p.fine_bits = FINE_BITS;
+    p.coarse_bits = p.c - 1 - p.fine_bits;                    // c is 13, 15 or 17: at most the 1024 coarse bins msm_window_sums_quad serves
     p.nbins = 1u << p.coarse_bits;
     p.batch = batch;
-    static const uint32_t probe_debug = [] { const char *e = getenv("PLK_MSM_DEBUG"); return e ? (uint32_t)atoi(e) : 0u; }();   // experiments only, read once
-    p.debug = probe_debug;
     const ScalarSet &set = A.set;
     const uint32_t total_sets = batch * p.groups, total_bins = total_sets * p.nbins, total_windows = batch * p.windows;
     const uint32_t max_tasks = total_bins + (uint32_t)(((uint64_t)total_windows * n) / TASK_MAX) + 1;
@@ -908,7 +849,6 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
     }
     // PLK_MSM_FUSED_RECODE=0 (A/B knob): the three-launch pre-phase through the digit array, as for several bucket sets
     static const bool fused_ok = [] { const char *e = getenv("PLK_MSM_FUSED_RECODE"); return !(e && e[0] == '0'); }();
-    uint32_t shape_variant = 0, shape_lanes = 0;              // (what S.shape reports, noted where it is decided)
     const uint32_t shape_prephase = (fused_ok && p.groups == 1 && p.c == 17 && p.windows == RC_WINDOWS && p.nbins <= 1024) ? 1u : 2u;
     if (shape_prephase == 1) {
         // one bucket set per commitment (the 2^20 shape): digits never leave the registers (msm_recode_count / _scatter)
@@ -930,59 +870,40 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
         hipLaunchKernelGGL(msm_partition<true>, dim3(pblocks, total_windows), dim3(PART_THREADS), plds_scatter, stream, (const int32_t *)digits, p, hist, (const uint32_t *)bin_start, entries);
     }
     if (ctx->ev_on) PLK_HIP(hipEventRecord(S.ev[0], stream));
-    // lanes per task of the bucket reduction (see msm_task_reduce): 16 for a batch of three or more commitments, 32 otherwise; PLK_MSM_RL_LOG=4|5 forces one (A/B runs)
-    static const int probe_rl = [] { const char *e = getenv("PLK_MSM_RL_LOG"); return e ? atoi(e) : 0; }();
-    // (since late round 6 also 16 when another commitment is in flight on this context: a stream of commitments is work-bound — every reduction wave displaces an
-    //  accumulation wave of the next commitment for as long as it lives — and 16 lanes per task are fewer wave-microseconds; PLK_MSM_RL_STREAM=0: 32 as before)
-    static const bool rl_stream = [] { const char *e = getenv("PLK_MSM_RL_STREAM"); return !(e && e[0] == '0'); }();
+    // commitments of <= 2^16 terms: the build whose lanes own the buckets of an evenly filled task (msm_accumulate.hip)
+    const uint32_t shape_variant = n <= MSM_OWNED_MAX ? 2u : 0u;
+    msm_accumulate_launch((int)shape_variant, max_tasks, stream, bases, (const uint32_t *)entries, (const uint32_t *)bin_start, (const uint32_t *)task_start, partials, task_meta, p);
+    if (ctx->ev_on) (void)hipEventRecord(S.ev[1], stream);
+    (void)hipEventRecord(S.acc_done, stream);
+    // The bucket reduction (see msm_task_reduce).  ONE bucket set with nothing else in flight on this context: by quads of lanes.  A batch of two is
+    // 2048 waves of quads — two per SIMD, every step twice as long: 269 us inside a proof against ~230 lane-wise; the quads do the same additions in
+    // 1.5x the lane-instructions, which a stream of commitments — whose reductions share the GPU with the next accumulation — pays for (three in flight
+    // at 2^16 terms 0.243 -> 0.255 ms, measured); and above 2^20 terms a commitment has 3 or 5 bucket sets: 5120 tasks are five waves of quads per SIMD
+    // (0.71 ms at 2^22 terms against ~0.45 lane-wise).
+    // Otherwise lane-wise: 16 lanes per task for a batch of three or more commitments or when another commitment is in flight (a stream of commitments is
+    // work-bound — every reduction wave displaces an accumulation wave of the next commitment for as long as it lives — and 16 lanes per task are fewer
+    // wave-microseconds), 32 lanes when latency is all that counts.
     const bool others_in_flight = ctx->msm_enq != ctx->msm_fin;
-    const uint32_t rl_log = (probe_rl == 4 || probe_rl == 5) ? (uint32_t)probe_rl : ((batch >= 3 || (rl_stream && others_in_flight)) ? 4u : 5u);
-    const uint32_t rblocks = ((max_tasks << rl_log) + MSM_THREADS - 1) / MSM_THREADS;
-    auto launch_shape = [&](auto fb_tag) {
-        constexpr uint32_t FB = decltype(fb_tag)::value;
-        // PLK_MSM_ONE_WAVE=1 (measurement knob): the same kernel compiled for one wave per SIMD (512 registers, no spill)
-        static const bool one_wave = getenv("PLK_MSM_ONE_WAVE") != nullptr;
-        // commitments of <= 2^16 terms: the build whose lanes own the buckets of an evenly filled task (msm_accumulate.hip; PLK_MSM_OWNED_MAX overrides, 0 = never)
-        static const long long owned_max = [] { const char *e = getenv("PLK_MSM_OWNED_MAX"); return e ? (long long)strtoull(e, nullptr, 10) : (1ll << 16); }();
-        const int variant = one_wave ? 1 : (FB == 6 && (long long)n <= owned_max ? 2 : 0);
-        shape_variant = (uint32_t)variant;
-        msm_accumulate_launch(FB, variant, max_tasks, stream, bases, (const uint32_t *)entries, (const uint32_t *)bin_start, (const uint32_t *)task_start, partials, task_meta, p);
-        if (ctx->ev_on) (void)hipEventRecord(S.ev[1], stream);
-        (void)hipEventRecord(S.acc_done, stream);
-        // ONE commitment: the bucket reduction by quads of lanes (PLK_MSM_TR_QUAD=0: the lane-wise kernel for every batch size, A/B knob).  A batch of two is
-        // 2048 waves of it — two per SIMD, every step twice as long: 269 us inside a proof against ~230 lane-wise —
-        static const bool tr_quad = [] { const char *e = getenv("PLK_MSM_TR_QUAD"); return !(e && e[0] == '0'); }();
-        static const uint32_t early_exit = [] { const char *e = getenv("PLK_MSM_REDUCE_EARLY_EXIT"); return (e && e[0] == '0') ? 0u : 1u; }();   // A/B knob: 0 = dead waves walk the tree steps (rounds 1-6)
-        // (only when no other commitment is in flight on this context: the quads do the same additions in 1.5x the lane-instructions, which a stream of
-        //  commitments — whose reductions share the GPU with the next accumulation — pays for: three in flight at 2^16 terms 0.243 -> 0.255 ms, measured)
-        // and ONE bucket set (above 2^20 terms a commitment has 3 or 5: 5120 tasks are five waves of quads per SIMD — 0.71 ms at 2^22 terms against ~0.45 lane-wise)
-        if (tr_quad && probe_rl == 0 && total_sets == 1 && ctx->msm_enq == ctx->msm_fin) {
-            shape_lanes = 4;
-            hipLaunchKernelGGL((msm_fold_hot<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
-            hipLaunchKernelGGL((msm_task_reduce_quad<FB>), dim3((max_tasks + MSM_THREADS / 64 - 1) / (MSM_THREADS / 64)), dim3(MSM_THREADS), 0, stream,
-                               (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins, early_exit);
-        } else if (rl_log == 4) {
-            shape_lanes = 16;
-            hipLaunchKernelGGL((msm_fold_hot<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
-            hipLaunchKernelGGL((msm_task_reduce<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
-                               (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins, early_exit);
-        } else {
-            shape_lanes = 32;
-            hipLaunchKernelGGL((msm_fold_hot<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
-            hipLaunchKernelGGL((msm_task_reduce<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
-                               (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins, early_exit);
-        }
-    };
-    if (p.fine_bits == 6) launch_shape(std::integral_constant<uint32_t, 6>{}); else launch_shape(std::integral_constant<uint32_t, 7>{});
+    const uint32_t shape_lanes = (total_sets == 1 && !others_in_flight) ? 4u : ((batch >= 3 || others_in_flight) ? 16u : 32u);
+    const uint32_t rblocks = (max_tasks * (shape_lanes == 16 ? 16u : 32u) + MSM_THREADS - 1) / MSM_THREADS;
+    constexpr uint32_t FB = FINE_BITS;
+    if (shape_lanes == 4) {
+        hipLaunchKernelGGL((msm_fold_hot<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
+        hipLaunchKernelGGL((msm_task_reduce_quad<FB>), dim3((max_tasks + MSM_THREADS / 64 - 1) / (MSM_THREADS / 64)), dim3(MSM_THREADS), 0, stream,
+                           (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins);
+    } else if (shape_lanes == 16) {
+        hipLaunchKernelGGL((msm_fold_hot<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
+        hipLaunchKernelGGL((msm_task_reduce<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
+                           (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins);
+    } else {
+        hipLaunchKernelGGL((msm_fold_hot<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
+        hipLaunchKernelGGL((msm_task_reduce<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
+                           (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins);
+    }
     hipLaunchKernelGGL(msm_bin_fold, dim3((total_bins + MSM_THREADS / 64 - 1) / (MSM_THREADS / 64)), dim3(MSM_THREADS), 0, stream, task_out, (const uint32_t *)task_start, total_bins);
     // points per bucket set left for the host: S (bins below nbins / 2), G_0..G_7, F_1 .., S (bins from nbins / 2)
     const uint32_t roles = WS_FIRST_F_ROLE + (p.nbins + MSM_THREADS - 1) / MSM_THREADS - 1 + 1;
-    static const bool ws_quad = [] { const char *e = getenv("PLK_MSM_WS_QUAD"); return !(e && e[0] == '0'); }();      // A/B knob: 0 = the lane-wise kernel (its last role is the identity)
-    if (ws_quad) hipLaunchKernelGGL(msm_window_sums_quad, dim3(total_sets, roles), dim3(MSM_THREADS), 0, stream, (const XyzzW *)task_out, (const uint32_t *)task_start, window_out, p.nbins, roles);
-    else {
-        PLK_HIP(hipMemsetAsync(window_out, 0, (size_t)roles * total_sets * sizeof(G1Xyzz), stream));
-        hipLaunchKernelGGL(msm_window_sums, dim3(total_sets, roles - 1), dim3(MSM_THREADS), 0, stream, (const XyzzW *)task_out, (const uint32_t *)task_start, window_out, p.nbins, roles);
-    }
+    hipLaunchKernelGGL(msm_window_sums_quad, dim3(total_sets, roles), dim3(MSM_THREADS), 0, stream, (const XyzzW *)task_out, (const uint32_t *)task_start, window_out, p.nbins, roles);
     PLK_HIP(hipGetLastError());
     PLK_TRY(slot_pinned(S, (size_t)roles * total_sets * sizeof(G1Xyzz)));
     PLK_HIP(hipMemcpyAsync(S.pinned, window_out, (size_t)roles * total_sets * sizeof(G1Xyzz), hipMemcpyDeviceToHost, stream));
@@ -1039,7 +960,7 @@ int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t b
     while ((1ull << nbits) < n) nbits++;
     // short commitments (msm_small.hip) need all 15 copies of the table: every commitment of >= 4096 terms builds them anyway; a shorter one
     // only asks for them when the key is small enough for that to be cheap (<= 2^21 points: 80 ms once per key) or has them already
-    const bool small_wanted = n >= 1 && n <= msm_small_max(batch) && table_copies_for(ctx->srs_n) == MAX_COPIES &&
+    const bool small_wanted = n >= 1 && n <= MSM_SMALL_MAX && table_copies_for(ctx->srs_n) == MAX_COPIES &&
                               (n >= 4096 || ctx->srs_n <= (1ull << 21) || (ctx->srs_w_valid && ctx->srs_w_copies == MAX_COPIES));
     const uint32_t c_bits = small_wanted ? COPY_SHIFT : (n >= 4096 ? pick_window_bits(n, table_copies_for(ctx->srs_n) > 1) : 0);
     uint32_t copies = 1;
@@ -1047,8 +968,6 @@ int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t b
         copies = table_copies_for(ctx->srs_n);
         PLK_TRY(ensure_base_table(ctx, copies, stream));
         while (copies > 1 && (MAX_COPIES % copies != 0 || ((uint64_t)copies << nbits) > (1ull << 24))) copies--;   // a divisor of 15 that fits the 24-bit (copy, index) field of an entry
-        static const int probe_copies = [] { const char *e = getenv("PLK_MSM_COPIES"); return e ? atoi(e) : 0; }();   // tuning probe, read once
-        if (probe_copies >= 1 && (uint32_t)probe_copies <= copies && MAX_COPIES % probe_copies == 0) copies = (uint32_t)probe_copies;
     } else PLK_TRY(ensure_base_table(ctx, 1, stream));
     const bool small = small_wanted && copies == MAX_COPIES;
     const G1Affine *bases = ctx->srs_w.as<G1Affine>() + base_offset;

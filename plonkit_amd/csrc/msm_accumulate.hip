@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
             if (tid + k * MSM_THREADS < nc) { const uint32_t f = ent[k] & (FINE - 1); sorted[start[f] + atomicAdd(&cursor[f], 1u)] = ent[k]; }
     }
     __syncthreads();
-    if (nc == 0 || p.debug == 3) return;                      // (debug 3: time the sort alone)
+    if (nc == 0) return;
     XyzzW *out = partials + (size_t)task * SLOTS_PER_TASK;
     const uint32_t imask = (1u << p.nbits) - 1;
     auto point_of = [&](uint32_t entry) -> const G1Affine * {          // (copy j, index i) -> address in the table
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
             acc = xyzzw_identity();
             run_start = i; b = e_cur & (FINE - 1); bend = start[b + 1];
         }
-        if (p.debug != 1) xyzzw_add_mixed(acc, cur, (e_cur & 0x80u) != 0);
+        xyzzw_add_mixed(acc, cur, (e_cur & 0x80u) != 0);
     }
     if (OWNED && own) {                                       // the quad's four sums -> one PRIMARY sum per bucket
         const uint32_t role = tid & 3u;                       // (distributed form, ec29_quad_dev.h: lane r of the quad holds coordinate r)
@@ -182,25 +182,19 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
 int32_t msm_accumulate_prepare() {
     static std::atomic<bool> attr_set{false};                 // (several contexts may commit from several host threads)
     if (attr_set) return PLK_OK;
-    PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<6>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
-    PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<7>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
-    PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<6, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
-    PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<6, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
+    PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<FINE_BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
+    PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<FINE_BITS, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
     attr_set = true;
     return PLK_OK;
 }
 
-void msm_accumulate_launch(uint32_t fine_bits, int variant, uint32_t max_tasks, hipStream_t stream, const G1Affine *bases, const uint32_t *entries,
+void msm_accumulate_launch(int variant, uint32_t max_tasks, hipStream_t stream, const G1Affine *bases, const uint32_t *entries,
                            const uint32_t *bin_start, const uint32_t *task_start, XyzzW *partials, uint32_t *task_meta, const MsmParams &p) {
     const size_t lds = CHUNK * sizeof(uint32_t);
-    if (fine_bits == 6 && variant == 2)
-        hipLaunchKernelGGL((msm_accumulate<6, 2, true>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
-    else if (fine_bits == 6 && variant == 1)
-        hipLaunchKernelGGL((msm_accumulate<6, 1>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
-    else if (fine_bits == 6)
-        hipLaunchKernelGGL((msm_accumulate<6>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
+    if (variant == 2)
+        hipLaunchKernelGGL((msm_accumulate<FINE_BITS, 2, true>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
     else
-        hipLaunchKernelGGL((msm_accumulate<7>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
+        hipLaunchKernelGGL((msm_accumulate<FINE_BITS>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
 }
 
 }  // namespace plk

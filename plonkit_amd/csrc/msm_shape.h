@@ -9,14 +9,14 @@
 namespace plk {
 
 constexpr int MSM_THREADS = 256;
-// Buckets per accumulate workgroup = 2^FB ("fine" part of the bucket index; the coarse part selects the bin).  Two shapes
-// are compiled (template parameter FB of the kernels below) and chosen per commitment by pick_fine_bits():
+// Buckets per accumulate workgroup = 2^FB ("fine" part of the bucket index; the coarse part selects the bin).  The kernels
+// keep FB as a template parameter; one shape is compiled:
 //   FB = 6: 64 buckets per task.  At c = 17 that is 1024 coarse bins of ~15 K entries at 2^20 terms = ONE task per bin,
 //           so every bucket is reduced once (65 K task-buckets) — the bucket reduction (msm_task_reduce) is not a latency
 //           detail: in VALU work it was 38 % of the accumulation (992 waves x 37 dependent full additions of 14 products
 //           against 15.7 M mixed additions of 9.3), and it shares the GPU with the next commitment's accumulation.
-//   FB = 7: 128 buckets per task, 512 bins of ~31 K entries = two tasks per bin (131 K task-buckets): the round-1 shape.
-constexpr uint32_t FINE_BITS_MAX = 7;
+//   (FB = 7, 128 buckets per task and two tasks per bin at 2^20 terms, was the round-1 shape; no window width in use needs it.)
+constexpr uint32_t FINE_BITS = 6;
 constexpr uint32_t CHUNK = 16384;                // entries per accumulate workgroup (sorted in 64 KB of LDS; two workgroups per CU)
 constexpr uint32_t DIGIT_CHUNK = 16384;            // scalars per partition workgroup (per window): 64 KB of LDS staging
 constexpr uint32_t TASK_MAX = CHUNK;
@@ -32,7 +32,6 @@ struct MsmParams {
     uint32_t coarse_bits;     // c - 1 - fine_bits
     uint32_t nbins;           // 1 << coarse_bits
     uint32_t batch;           // number of scalar vectors (same n, same bases); "global window" = m * W + w
-    uint32_t debug;           // experiments only: 1 = skip the additions (sort cost), 0 = normal
     // Shifted copies of the bases (fixed-base precomputation): window w = j*groups + g takes its points from
     // copy j*groups of the table (2^(16*j*groups) * P_i) and drops them into bucket set g, so only `groups`
     // bucket sets have to be reduced and only c*groups doublings are left for the host Horner.
@@ -75,11 +74,11 @@ template <uint32_t FB> struct Shape {
 // sum per bucket, no HEAD / TAIL pieces
 constexpr uint32_t TASK_OWNED_BIT = 0x80000000u;
 
-// kernel A (msm_accumulate.hip): one workgroup per task; fine_bits 6 or 7; variant 1 = the 512-register / one-wave-per-SIMD build
-// of the fine_bits-6 shape (measurement knob PLK_MSM_ONE_WAVE), variant 2 = the build that lets a task's lanes own its buckets when they are
-// evenly filled (commitments of <= 2^16 terms), 0 = the plain kernel
+// kernel A (msm_accumulate.hip): one workgroup per task of 2^FINE_BITS buckets; variant 0 = the plain kernel, variant 2 = the build that lets a
+// task's lanes own its buckets when they are evenly filled (commitments of <= 2^16 terms).  Variant 1 (a 512-register, one-wave-per-SIMD
+// build kept for measurements) is retired; the numbers stay as they are because plk_msm_last_shape reports them.
 int32_t msm_accumulate_prepare();                                   // dynamic-LDS attributes, once per process
-void msm_accumulate_launch(uint32_t fine_bits, int variant, uint32_t max_tasks, hipStream_t stream, const G1Affine *bases, const uint32_t *entries,
+void msm_accumulate_launch(int variant, uint32_t max_tasks, hipStream_t stream, const G1Affine *bases, const uint32_t *entries,
                            const uint32_t *bin_start, const uint32_t *task_start, XyzzW *partials, uint32_t *task_meta, const MsmParams &p);
 
 }  // namespace plk

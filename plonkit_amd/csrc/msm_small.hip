@@ -33,15 +33,15 @@ constexpr uint32_t SM_THREADS = 256;             // a workgroup owns 64 buckets 
 // 107-145 us; (3) this one — ONE list per bucket, split evenly over four lanes (lane j takes entries j, j + 4, ..): inside a bucket the balance is exact, and
 // with 4x the terms per bucket the lists are longer and relatively more even.
 constexpr uint32_t SM_CH_MIN = 64, SM_CH_MAX = 256, SM_WG_BUCKETS = 64, SM_LANES_PER_BUCKET = 4;
+constexpr uint32_t SM_WANT_WGS = 512;             // ch doubles while the accumulate grid would hold more workgroups than this (about two per CU, see above)
 static size_t sm_lds(uint32_t ch) { return (size_t)(SM_WG_BUCKETS + SM_WG_BUCKETS * (ch + 1)) * sizeof(uint32_t); }
 
 __device__ __forceinline__ void small_chain_priority() { __builtin_amdgcn_s_setprio(3); }
 
 // grid (8 G, batch): workgroup 8 g + s takes terms [g ch, (g + 1) ch) and an EIGHTH of the bucket space — s & 1: lo / hi values, s >> 1: which 64 of the 256 values.
 // bases = copy 0 of the fixed-base table at the commitment's first point; copy w lies w * copy_stride points on.
-// QUADSUM (the default; PLK_MSM_SMALL_QUADSUM=0 is the A/B knob): the four lanes of a bucket add their sums up before they store (three four-lane additions
-// on the end of the kernel): a quarter of the partial sums for msm_small_fold, whose quads walk G2 / Q of them one after the other.
-template <bool QUADSUM>
+// The four lanes of a bucket add their sums up before they store (three four-lane additions on the end of the kernel): a quarter of the partial sums
+// for msm_small_fold, whose quads walk G / Q of them one after the other (profiles/r06_small_lanes4_ab.txt).
 __global__ void __launch_bounds__(SM_THREADS, 2) msm_small_accumulate(const G1Affine *bases, ScalarSet set, uint32_t n, uint32_t ch, uint32_t copy_stride,
                                                                      XyzzW *partials, uint32_t *flag) {
     extern __shared__ uint32_t sm_lds_mem[];
@@ -82,16 +82,11 @@ __global__ void __launch_bounds__(SM_THREADS, 2) msm_small_accumulate(const G1Af
         AffW q; q.x = unpack<FqW>(cur.x); q.y = unpack<FqW>(cur.y);
         xyzzw_add_mixed(acc, q, neg);
     }
-    if (QUADSUM) {
-        // partial sums: [m][g][512 buckets]; the four sums of the quad in distributed form (ec29_quad_dev.h), three additions, each lane stores its coordinate
-        const FqW9 c1 = quad_distribute<1>(acc, sub), c2 = quad_distribute<2>(acc, sub), c3 = quad_distribute<3>(acc, sub);
-        FqW9 X = quad_distribute<0>(acc, sub);
-        for (int k = 1; k < 4; k++) X = xyzzw_add_dist(X, wsel(k == 1, c1, wsel(k == 2, c2, c3)), sub);     // (one addition site)
-        store_coord(partials + ((size_t)m * (gridDim.x >> 3) + g) * SM_BUCKETS + hi_set * 256 + eighth * 64 + bucket, sub, X);
-    } else {
-        // partial sums: [m][4 g + sub][512 buckets] — msm_small_fold sees 4 G "workgroups"
-        store_xyzzw(partials + ((size_t)m * (gridDim.x >> 3) * 4 + 4 * g + sub) * SM_BUCKETS + hi_set * 256 + eighth * 64 + bucket, acc);
-    }
+    // partial sums: [m][g][512 buckets]; the four sums of the quad in distributed form (ec29_quad_dev.h), three additions, each lane stores its coordinate
+    const FqW9 c1 = quad_distribute<1>(acc, sub), c2 = quad_distribute<2>(acc, sub), c3 = quad_distribute<3>(acc, sub);
+    FqW9 X = quad_distribute<0>(acc, sub);
+    for (int k = 1; k < 4; k++) X = xyzzw_add_dist(X, wsel(k == 1, c1, wsel(k == 2, c2, c3)), sub);     // (one addition site)
+    store_coord(partials + ((size_t)m * (gridDim.x >> 3) + g) * SM_BUCKETS + hi_set * 256 + eighth * 64 + bucket, sub, X);
 }
 
 // The two tree kernels run their full additions four lanes at a time (ec29_quad_dev.h: a quad of lanes shares one addition, four products
@@ -100,7 +95,7 @@ __global__ void __launch_bounds__(SM_THREADS, 2) msm_small_accumulate(const G1Af
 // already issues at its SIMD's rate (tools/ubench_lanes), a second wave on the SIMD doubles the time of every tree level — measured 4.5 us per level
 // with two waves per SIMD (planes of 512 threads, folds of 2048 waves) against 2.3 us alone.
 //
-// buckets[m][b] = sum of the G2 partial sums of bucket b.  Q = 2^QL quads per bucket, chosen by the launch so that batch * 512 * Q quads are about 1024
+// buckets[m][b] = sum of the G2 partial sums of bucket b (one per workgroup that took terms: G2 = ceil(n / ch)).  Q = 2^QL quads per bucket, chosen by the launch so that batch * 512 * Q quads are about 1024
 // waves: 32 quads for one commitment (two waves per bucket, the last level through LDS), 16 / 8 / 4 for batches of 2 / 3-4 / 5-8.  Quad q of a bucket takes
 // partial sums q, q + Q, .. one after the other, then a tree over the bucket's quads.  Workgroup = 128 threads = 32 quads = 32 / Q buckets.
 template <uint32_t QL>
@@ -134,7 +129,7 @@ __global__ void __launch_bounds__(128) msm_small_fold(const XyzzW *partials, uin
 // grid (17, batch), 256 threads = 64 quads: one wave per SIMD of its CU.  Plane p < 8: bit p of the lo value; plane 8 + b: bit b of the hi value (b = 8: the
 // one bucket hi = 256).  Quad q takes the q-th and the (q + 64)-th bucket of the plane; tree over the 16 quads of a wave, then over the four waves.
 constexpr uint32_t SM_PLANES = 17;
-__global__ void __launch_bounds__(256) msm_small_planes(const XyzzW *buckets, G1Xyzz *planes, const uint32_t *flag, uint32_t *flag_out, uint32_t extra) {
+__global__ void __launch_bounds__(256) msm_small_planes(const XyzzW *buckets, G1Xyzz *planes, const uint32_t *flag, uint32_t *flag_out) {
     __shared__ __attribute__((aligned(16))) uint32_t sh[4][4][9];
     small_chain_priority();
     const uint32_t p = blockIdx.x, m = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, role = tid & 3, quad = tid >> 2;
@@ -148,11 +143,11 @@ __global__ void __launch_bounds__(256) msm_small_planes(const XyzzW *buckets, G1
     FqW9 X = w_zero<FqW>();
     if (bit < 8) X = load_coord(bucket_of(quad), role);
     else if (quad == 0) X = load_coord(B + 511, role);
-    for (uint32_t k = 0; k < 7 + extra; k++) {                 // (extra: measurement knob PLK_MSM_SMALL_EXTRA — more levels that add the identity)
+    for (uint32_t k = 0; k < 7; k++) {
         FqW9 O = w_zero<FqW>();
         if (k == 0) { if (bit < 8) O = load_coord(bucket_of(quad + 64), role); }
         else if (k < 5) O = coord_shfl_xor(X, 4 << (k - 1));
-        else if (k < 7) {
+        else {
             if (k == 5) {
                 if (lane < 4) for (int i = 0; i < 9; i++) sh[wave][role][i] = X.l[i];
                 __syncthreads();
@@ -176,40 +171,30 @@ int32_t msm_small_launch(plk_ctx::MsmSlot &S, hipStream_t stream, const G1Affine
                          uint32_t batch, uint32_t n, bool ev_on, void *host_out) {
     static std::atomic<bool> attr_set{false};
     if (!attr_set) {
-        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_small_accumulate<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_lds(SM_CH_MAX)));
-        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_small_accumulate<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_lds(SM_CH_MAX)));
+        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_small_accumulate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_lds(SM_CH_MAX)));
         attr_set = true;
     }
-    static const uint32_t probe_ch = [] { const char *e = getenv("PLK_MSM_SMALL_CH"); return e ? (uint32_t)atoi(e) : 0u; }();   // A/B knob: 64, 128 or 256
-    static const uint32_t probe_extra = [] { const char *e = getenv("PLK_MSM_SMALL_EXTRA"); return e ? (uint32_t)atoi(e) : 0u; }();
-    static const uint32_t want_wgs = [] { const char *e = getenv("PLK_MSM_SMALL_WGS"); return e ? (uint32_t)atoi(e) : 512u; }();
     uint32_t ch = SM_CH_MIN;
-    while (ch < SM_CH_MAX && (uint64_t)batch * 8 * ((n + ch - 1) / ch) > want_wgs) ch <<= 1;
-    if (probe_ch == 64 || probe_ch == 128 || probe_ch == 256) ch = probe_ch;
+    while (ch < SM_CH_MAX && (uint64_t)batch * 8 * ((n + ch - 1) / ch) > SM_WANT_WGS) ch <<= 1;
     const uint32_t G = (n + ch - 1) / ch;
-    static const int probe_quadsum = [] { const char *e = getenv("PLK_MSM_SMALL_QUADSUM"); return e ? atoi(e) : -1; }();      // A/B knob: 0 never, 1 always
-    const bool quadsum = probe_quadsum != 0;
-    const uint32_t G2 = quadsum ? G : 4 * G;
-    PLK_TRY(S.e.reserve((size_t)batch * 4 * G * SM_BUCKETS * sizeof(XyzzW)));
+    PLK_TRY(S.e.reserve((size_t)batch * G * SM_BUCKETS * sizeof(XyzzW)));
     PLK_TRY(S.c.reserve((size_t)batch * SM_BUCKETS * sizeof(XyzzW) + 16));
     XyzzW *partials = S.e.as<XyzzW>(), *buckets = S.c.as<XyzzW>();
     uint32_t *flag = reinterpret_cast<uint32_t *>(buckets + (size_t)batch * SM_BUCKETS);
     G1Xyzz *planes = static_cast<G1Xyzz *>(host_out);
     PLK_HIP(hipMemsetAsync(flag, 0, 16, stream));
     if (ev_on) PLK_HIP(hipEventRecord(S.ev[0], stream));
-    if (quadsum) hipLaunchKernelGGL(msm_small_accumulate<true>, dim3(8 * G, batch), dim3(SM_THREADS), sm_lds(ch), stream, bases, set, n, ch, copy_stride, partials, flag);
-    else hipLaunchKernelGGL(msm_small_accumulate<false>, dim3(8 * G, batch), dim3(SM_THREADS), sm_lds(ch), stream, bases, set, n, ch, copy_stride, partials, flag);
+    hipLaunchKernelGGL(msm_small_accumulate, dim3(8 * G, batch), dim3(SM_THREADS), sm_lds(ch), stream, bases, set, n, ch, copy_stride, partials, flag);
     if (ev_on) (void)hipEventRecord(S.ev[1], stream);
     (void)hipEventRecord(S.acc_done, stream);
-    static const int probe_ql = [] { const char *e = getenv("PLK_MSM_SMALL_FOLD_QL"); return e ? atoi(e) : 0; }();               // A/B knob: 2 .. 5
-    const uint32_t ql = (probe_ql >= 2 && probe_ql <= 5) ? (uint32_t)probe_ql : (batch == 1 ? 5u : batch == 2 ? 4u : batch <= 4 ? 3u : 2u);
+    const uint32_t ql = batch == 1 ? 5u : batch == 2 ? 4u : batch <= 4 ? 3u : 2u;    // quads per bucket = 2^ql (see msm_small_fold)
     const dim3 fgrid(SM_BUCKETS / (32u >> ql), batch);
-    if (ql == 5) hipLaunchKernelGGL(msm_small_fold<5>, fgrid, dim3(128), 0, stream, (const XyzzW *)partials, G2, buckets);
-    else if (ql == 4) hipLaunchKernelGGL(msm_small_fold<4>, fgrid, dim3(128), 0, stream, (const XyzzW *)partials, G2, buckets);
-    else if (ql == 3) hipLaunchKernelGGL(msm_small_fold<3>, fgrid, dim3(128), 0, stream, (const XyzzW *)partials, G2, buckets);
-    else hipLaunchKernelGGL(msm_small_fold<2>, fgrid, dim3(128), 0, stream, (const XyzzW *)partials, G2, buckets);
+    if (ql == 5) hipLaunchKernelGGL(msm_small_fold<5>, fgrid, dim3(128), 0, stream, (const XyzzW *)partials, G, buckets);
+    else if (ql == 4) hipLaunchKernelGGL(msm_small_fold<4>, fgrid, dim3(128), 0, stream, (const XyzzW *)partials, G, buckets);
+    else if (ql == 3) hipLaunchKernelGGL(msm_small_fold<3>, fgrid, dim3(128), 0, stream, (const XyzzW *)partials, G, buckets);
+    else hipLaunchKernelGGL(msm_small_fold<2>, fgrid, dim3(128), 0, stream, (const XyzzW *)partials, G, buckets);
     hipLaunchKernelGGL(msm_small_planes, dim3(SM_PLANES, batch), dim3(256), 0, stream, (const XyzzW *)buckets, planes, (const uint32_t *)flag,
-                       reinterpret_cast<uint32_t *>(planes + (size_t)batch * SM_PLANES), probe_extra);
+                       reinterpret_cast<uint32_t *>(planes + (size_t)batch * SM_PLANES));
     PLK_HIP(hipGetLastError());
     return PLK_OK;
 }

@@ -746,30 +746,20 @@ static int32_t ntt_direct_table(plk_ctx *ctx, bool inverse, uint32_t log_r, uint
 // ------------------------------------------------------------------------------- driver
 static std::atomic<bool> g_attr_set{false};                    // (several contexts may transform from several host threads)
 
-// the wave-owned passes (ntt_pass_w) take every full 2048-element tile of 7..10 row bits; PLK_NTT_WAVE=0 keeps the
-// barrier-per-round kernels for everything (A/B knob)
+// the wave-owned passes (ntt_pass_w) take every full 2048-element tile of 7..10 row bits and the 4096-element tile of the 2^21-point
+// transform (digit_plan); the barrier-per-round kernels (ntt_pass_cols / ntt_pass_rows) serve every other shape
 constexpr size_t NTT_W_LDS = (size_t)36 * NTT_W_SLOTS, NTT_W_LDS_BIG = (size_t)36 * NTT_W_SLOTS_BIG;
-static bool ntt_wave_enabled() {
-    static const int on = [] { const char *e = getenv("PLK_NTT_WAVE"); return (e && e[0] == '0') ? 0 : 1; }();
-    return on != 0;
-}
-// the 4096-element tile (2^21 / 2^22-point transforms in two passes); PLK_NTT_BIG_TILE=0: three passes of 2048-element tiles as before (A/B knob)
-static bool ntt_big_tile_enabled() {
-    static const int on = [] { const char *e = getenv("PLK_NTT_BIG_TILE"); return (e && e[0] == '0') ? 0 : 1; }();
-    return on != 0 && ntt_wave_enabled();
-}
 static bool ntt_wave_shape(const NttPassArgs &a) {
     // (zero-padded inputs are taken too — `quarter`, the old kernels' copy-instead-of-butterfly shortcut for them, is simply not used;
     //  their per-element coset tables are never combined with padding)
-    if (!ntt_wave_enabled() || (a.nonzero && a.pre_direct_b[0])) return false;
+    if (a.nonzero && a.pre_direct_b[0]) return false;
     if (a.log_r + a.log_c == LOG_TILE) return a.log_r >= 7 && a.log_r <= 10;
-    return a.log_r + a.log_c == (uint32_t)NTT_LOG_TILE_BIG && a.log_r >= 10 && a.log_r <= 11 && ntt_big_tile_enabled();
+    return a.log_r + a.log_c == (uint32_t)NTT_LOG_TILE_BIG;   // 2^21 = 11 + 10 (digit_plan), nothing else plans this tile
 }
 template <bool ROWS>
 static void ntt_launch_w(const NttPassArgs &a, dim3 grid, hipStream_t stream) {
-    if (a.log_r + a.log_c == (uint32_t)NTT_LOG_TILE_BIG) {
-        if (a.log_r == 10) hipLaunchKernelGGL((ntt_pass_w<10, ROWS, NTT_LOG_TILE_BIG>), grid, dim3(2 * NTT_THREADS), NTT_W_LDS_BIG, stream, a);
-        else hipLaunchKernelGGL((ntt_pass_w<11, ROWS, NTT_LOG_TILE_BIG>), grid, dim3(2 * NTT_THREADS), NTT_W_LDS_BIG, stream, a);
+    if (a.log_r + a.log_c == (uint32_t)NTT_LOG_TILE_BIG) {        // the column pass has the 11-bit digit, the row pass the 10-bit one
+        hipLaunchKernelGGL((ntt_pass_w<ROWS ? 10 : 11, ROWS, NTT_LOG_TILE_BIG>), grid, dim3(2 * NTT_THREADS), NTT_W_LDS_BIG, stream, a);
         return;
     }
     switch (a.log_r) {
@@ -784,10 +774,10 @@ template <int LR> static hipError_t ntt_w_attr() {
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_w<LR, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_W_LDS);
 }
-template <int LR> static hipError_t ntt_w_attr_big() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_w<LR, false, NTT_LOG_TILE_BIG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_W_LDS_BIG);
+static hipError_t ntt_w_attr_big() {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_w<11, false, NTT_LOG_TILE_BIG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_W_LDS_BIG);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_w<LR, true, NTT_LOG_TILE_BIG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_W_LDS_BIG);
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_w<10, true, NTT_LOG_TILE_BIG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_W_LDS_BIG);
 }
 
 // digits of the mixed-radix plan: up to 10 bits per pass
@@ -803,10 +793,9 @@ static void digit_plan(uint32_t log_n, uint32_t d[4], uint32_t *passes) {
         for (uint32_t i = 0; i < p; i++) d[i] = log_n / p + (i < log_n % p ? 1 : 0);
         // 11-bit digits on the 4096-element tile: 2^21 = 11 + 10 in two passes instead of three (0.207 -> 0.194 ms, same box).  2^22 = 11 + 11 is NOT
         // taken: both passes then run on 64-byte row segments (C = 2) and the transform is 12 % SLOWER than three passes of the 2048-element tile
-        // (0.375 -> 0.421 ms; profiles/r06_ntt_big_tile_ab.txt) — PLK_NTT_BIG_TILE=2 forces it for that measurement
-        static const bool force22 = [] { const char *e = getenv("PLK_NTT_BIG_TILE"); return e && e[0] == '2'; }();
-        if ((log_n == 21 || (log_n == 22 && force22)) && ntt_big_tile_enabled()) {
-            d[0] = 11; d[1] = log_n - 11; d[2] = 0; *passes = 2;
+        // (0.375 -> 0.421 ms; profiles/r06_ntt_big_tile_ab.txt)
+        if (log_n == 21) {
+            d[0] = 11; d[1] = 10; d[2] = 0; *passes = 2;
             return;
         }
         if (p == 3 && log_n <= 23) {                       // leave 14 bits to passes 2 and 3: their inter-pass twiddles
@@ -856,7 +845,7 @@ static int32_t ntt_run(plk_ctx *ctx, const Fr *const *src, uint64_t nonzero, Fr 
         PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 36 << LOG_SINGLE));
         PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_cols), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
         PLK_HIP(ntt_w_attr<7>()); PLK_HIP(ntt_w_attr<8>()); PLK_HIP(ntt_w_attr<9>()); PLK_HIP(ntt_w_attr<10>());
-        PLK_HIP(ntt_w_attr_big<10>()); PLK_HIP(ntt_w_attr_big<11>());
+        PLK_HIP(ntt_w_attr_big());
         g_attr_set = true;
     }
     PowTable pre{}, post{};
@@ -938,8 +927,7 @@ __global__ void ntt_fill_coset_direct(Fr *out, PowTable t0, PowTable t1, PowTabl
 }
 static int32_t coset_direct_tables(plk_ctx *ctx, uint32_t log_n, bool inverse, const PowTable tabs[4], hipStream_t stream, const Fr *out[4]) {
     for (int k = 0; k < 4; k++) out[k] = nullptr;
-    static const bool on = [] { const char *e = getenv("PLK_NTT_COSET_DIRECT"); return !(e && e[0] == '0'); }();       // A/B knob
-    if (!on || !ntt_direct_enabled() || log_n > 24 || log_n <= POW_SPLIT) return PLK_OK;      // (<= 2^14 points: the low table alone holds the power)
+    if (!ntt_direct_enabled() || log_n > 24 || log_n <= POW_SPLIT) return PLK_OK;      // (<= 2^14 points: the low table alone holds the power)
     plk_ctx::CosetDirect &C = ctx->coset_direct[inverse ? 1 : 0];
     const size_t n = (size_t)1 << log_n;
     if (C.log_n != log_n || !C.buf.p) {

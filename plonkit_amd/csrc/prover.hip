@@ -593,8 +593,7 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     // last: stream priorities do not keep a 8192-workgroup NTT pass from taking the CUs first (measured: the pre-phase of the
     // wire commitments took 2.1 ms instead of 0.35 behind it), so the start is placed by hand where the GPU has room — the
     // bucket reduction of that commitment, the point-wise kernels of the next round and the pre-phase of its commitment.
-    static const int bg_gate_z = [] { const char *e = getenv("PLK_PROVE_BG_GATE_Z"); return e ? atoi(e) : 0; }();   // A/B knob
-    static const int bg_gate_w = [] { const char *e = getenv("PLK_PROVE_BG_GATE_W"); return e ? atoi(e) : 1; }();   // A/B knob: wire extensions behind the wires' accumulation
+    // The wire extensions start behind the wires' accumulation, z's extension behind the main stream only (see round 2).
     auto bg_after_main = [&](bool behind_accumulation) -> int32_t {
         if (!use_bg) return PLK_OK;
         PLK_HIP(hipEventRecord(ctx->bg_go, st));
@@ -616,7 +615,7 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     if (use_lagrange && (ctx->combine ? ctx->lag.n != ctx->srs_n : ctx->lag.n != N)) { set_error("Lagrange-form key has a different size than the circuit's domain"); return PLK_ERR_SRS; }
     HAffine wire_c[4];
     PLK_TRY(commit_begin(ctx, use_lagrange ? w_vals : w_coef, 4, N, use_lagrange));
-    PLK_TRY(bg_after_main(bg_gate_w != 0));
+    PLK_TRY(bg_after_main(true));
     PLK_TRY(lde4cm_batch_dev(ctx, w_coef, 4, log_n, ext, bg, bg_lane));                       // round-3 work that needs no challenge
     PLK_HIP(hipEventSynchronize(ctx->flag_ready));
     PLK_TRY(front_verdict(ctx, S, F));
@@ -641,8 +640,7 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
         // (the scans stop after their second phase when they span several blocks: the block prefixes are folded in by the product below,
         //  and C_0 — the product of all denominators — is the suffix scan's grand total, which its second phase leaves behind the prefixes)
         const Fr *pre_a = nullptr, *pre_c = nullptr;
-        static const bool fuse_scan_tail = [] { const char *e = getenv("PLK_PROVE_FUSE_SCAN_TAIL"); return !(e && e[0] == '0'); }();   // A/B knob, read once
-        PLK_TRY(scan_pair_mult(ctx, t1, t1, false, true, t2, t2, true, false, (uint32_t)N, st, fuse_scan_tail ? &pre_a : nullptr, fuse_scan_tail ? &pre_c : nullptr));
+        PLK_TRY(scan_pair_mult(ctx, t1, t1, false, true, t2, t2, true, false, (uint32_t)N, st, &pre_a, &pre_c));
         const uint32_t scan_blocks = pre_c ? (uint32_t)((N + POLY_SCAN_BLOCK - 1) / POLY_SCAN_BLOCK) : 0;
         HFr total, num_total;
         PLK_HIP(hipMemcpyAsync(total.l, pre_c ? pre_c + scan_blocks : t2, sizeof(Fr), hipMemcpyDeviceToHost, st));
@@ -673,7 +671,7 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     // while z is being committed: its extension, the public-input polynomial, and (first proof only) the constant vectors
     // (z's extension is the last thing the quotient waits for: it starts as soon as z's coefficients exist and shares the GPU
     //  with the accumulation of z's commitment — behind that accumulation it ended 0.4 ms after the commitment itself)
-    PLK_TRY(bg_after_main(bg_gate_z != 0));
+    PLK_TRY(bg_after_main(false));
     {
         const Fr *zc = z_coef;
         PLK_TRY(lde4cm_batch_dev(ctx, &zc, 1, log_n, &ext[4], bg, bg_lane));

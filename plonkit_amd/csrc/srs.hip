@@ -141,9 +141,8 @@ extern "C" int32_t plk_srs_generate(plk_ctx *ctx, uint64_t n, uint64_t start, ui
     PLK_TRY(srs_replace_guard(ctx, "plk_srs_generate"));
     PLK_HIP(hipSetDevice(ctx->device));
     PLK_TRY(ctx->srs_own.reserve(n * sizeof(G1Affine)));
-    // the XYZZ scratch is the first commitment slot's: not while a commitment is in flight (PLK_SRS_DIRECT=1: the one-kernel path, A/B knob)
-    static const bool direct_env = getenv("PLK_SRS_DIRECT") != nullptr;
-    if (!direct_env && ctx->msm_enq == ctx->msm_fin) {
+    // the XYZZ scratch is the first commitment slot's: not while a commitment is in flight (then the one-kernel path)
+    if (ctx->msm_enq == ctx->msm_fin) {
         const uint64_t chunk = n < SRS_CHUNK ? n : SRS_CHUNK;
         PLK_TRY(ctx->slot[0].e.reserve(chunk * sizeof(G1Xyzz)));
         G1Xyzz *tmp = ctx->slot[0].e.as<G1Xyzz>();

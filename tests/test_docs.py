@@ -1,5 +1,5 @@
 """-m "not gpu": the documents keep up with the code — every environment variable the library or the `plonkit` binary reads is
-listed in INTEGRATION.md's table, every entry point include/plonkit_amd.h declares is in INTEGRATION.md's index."""
+listed in INTEGRATION.md's table and every variable the table lists is read somewhere, every entry point include/plonkit_amd.h declares is in INTEGRATION.md's index."""
 import os
 import re
 
@@ -21,6 +21,19 @@ def test_every_environment_variable_is_documented():
     doc = _read("INTEGRATION.md")
     missing = sorted(v for v in read if "`%s`" % v not in doc)
     assert not missing, "read by the code, absent from INTEGRATION.md's table: %s" % missing
+    # and the converse: a row whose variable nothing reads any more is stale
+    table = doc[doc.index("## Environment variables"):]
+    table = table[:table.index("\n## ", 1)]
+    listed = set()
+    for row in table.splitlines():
+        if row.startswith("|"):
+            listed |= set(re.findall(r"`(PLK_[A-Z0-9_]+)`", row.split("|")[1]))
+    assert len(listed) >= 15, "the table scan found suspiciously few variables: %s" % sorted(listed)
+    sources = [_read("bench.py")]
+    for folder, _, names in os.walk(os.path.join(ROOT, "plonkit_amd")):
+        sources += [_read(folder, n) for n in sorted(names) if n.endswith((".hip", ".cpp", ".h", ".py"))]
+    stale = sorted(v for v in listed if not any('"%s"' % v in text for text in sources))
+    assert not stale, "listed in INTEGRATION.md's table, read nowhere in plonkit_amd/ or bench.py: %s" % stale
 
 
 def test_the_index_of_entry_points_is_current():

@@ -5,7 +5,7 @@ TAG=$1; LOGN=${2:-22}
 O=gpurun_out/$TAG; mkdir -p "$O"
 export TMPDIR=/tmp
 {
-echo "# tools/ntt_pmc2.sh $TAG $LOGN  python tools/ntt_probe.py $LOGN 20   PLK_NTT_WAVE=${PLK_NTT_WAVE:-1}"
+echo "# tools/ntt_pmc2.sh $TAG $LOGN  python tools/ntt_probe.py $LOGN 20"
 for grp in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_IFETCH SQ_IFETCH_LEVEL SQ_INSTS_VALU SQ_BUSY_CU_CYCLES SQ_CYCLES" \
            "SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_LDS_DATA_FIFO_FULL" \
            "SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_THREAD_CYCLES_VALU SQ_INST_CYCLES_SALU SQ_LEVEL_WAVES SQ_INST_LEVEL_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_VALU2" \

@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of a whole proof: working tree against ab_old (tools/ab_build.sh <commit>, built in the container), sparse and dense circuit,
-# interleaved.   usage (GPU box): tools/prove_ab.sh <tag> [extra env for the NEW arm, e.g. PLK_MSM_RL_LOG=5]
+# interleaved.   usage (GPU box): tools/prove_ab.sh <tag> [extra env for the NEW arm, e.g. PLK_PROVE_BG=0]
 out=gpurun_out/$1; mkdir -p $out; f=$out/prove_ab.txt
 for rep in 1 2 3; do
   for lc in 0 7; do

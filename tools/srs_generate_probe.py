@@ -1,5 +1,4 @@
-"""crs_42 generation time (plk_srs_generate) at a few sizes, checked against the oracle at 2^12 and by spot indices above: python tools/srs_generate_probe.py [log_n ...]
-(PLK_SRS_DIRECT=1: the one-kernel path of rounds 1-5)"""
+"""crs_42 generation time (plk_srs_generate) at a few sizes, checked against the oracle at 2^12 and by spot indices above: python tools/srs_generate_probe.py [log_n ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
