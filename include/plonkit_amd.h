@@ -368,6 +368,56 @@ int32_t plk_verify_ex(const uint8_t *vk, uint64_t vk_len, const uint8_t *proof, 
 /* e(a, g2_a) * e(b, g2_b) == 1 ?   G2 as 128 bytes x.c1|x.c0|y.c1|y.c0 big-endian (the key/vk file encoding) */
 int32_t plk_pairing_check(const plk_g1_affine *a, const uint8_t *g2_a, const plk_g1_affine *b, const uint8_t *g2_b, int32_t *is_one);
 
+/* ---- many proofs of one verification key, on the GPU (verify_many.hip).  NO COUNTERPART IN THE REFERENCE: plonk::verify (src/plonk.rs:189-210)
+ *      takes one proof on one host thread, and so does plk_verify.  These calls verify EACH proof exactly and on its own: verdict i is what
+ *      plk_verify_ex says about proof i.  No random linear combination across proofs, no shared pairing, no probabilistic bound; a bad proof
+ *      in a batch is named directly.
+ *
+ *   plk_vk_load.   Parses vk.bin exactly as plk_verify_ex does (src/plonk.rs:189-210: same refusals, same words, PLK_ERR_ARG); flags takes
+ *                PLK_VERIFY_STRICT_INPUTS, unknown bits are PLK_ERR_ARG.  Builds ON THE HOST, with the steps of pairing.cpp's Miller loop, the
+ *                line table of g2[0] and g2[1] — slope and intercept of every doubling / addition step, 64 + popcount(6u + 2 - 2^64) + 2 lines
+ *                per point — and uploads it with the key's 11 commitments and the generator.  The lines do not depend on the G1 argument, so
+ *                the device never does twist arithmetic or an Fq2 inversion, and every exceptional case of a strange G2 point (infinity, not
+ *                in the subgroup) is decided by the host code plk_verify runs.  Read-only after load: usable from several contexts of the
+ *                device it was loaded on (another device: PLK_ERR_ARG), like plk_setup.  No counterpart in the reference.
+ *   plk_verify_many.  Blocks.  verdict[i] = 1 / 0 exactly when plk_verify_ex(vk, proof_i, flags) returns PLK_OK with *valid = 1 / 0;
+ *                verdict[i] = PLK_VERDICT_MALFORMED exactly when it returns PLK_ERR_ARG for that proof — a malformed proof is a verdict and
+ *                does not end the batch.  *first_bad = the lowest i with verdict[i] != 1, else UINT64_MAX.  count == 0: PLK_OK, nothing is
+ *                launched.  Null ctx / vk / verdict / first_bad / proofs / lens / proofs[i]: PLK_ERR_ARG; a commitment in flight on the context:
+ *                PLK_ERR_ARG, as the other blocking calls.  Per proof the host (up to 16 threads) runs plk_verify_terms's code; only the proofs
+ *                it does not settle go to the device: 25 scalar multiplications, two sums, one pairing product check each.  Device memory is
+ *                the context's staging arena: it grows only, and nothing is allocated per call once it has grown (5.5 KB per proof, at most
+ *                2^16 proofs per pass).  No counterpart in the reference.
+ *                BREAK-EVEN (one MI355X, profiles/verify_many_ab.txt): a call costs ~90 ms whatever the batch up to a few thousand proofs (one
+ *                pairing lane per proof), a plk_verify 13 ms.  Measured at 1 / 16 / 256 / 4096 proofs: 90 / 92 / 91 / 120 ms against 13 / 14 /
+ *                227 / 3525 ms for a loop of plk_verify on 16 host threads — 256 is the first measured size at which this call wins (the
+ *                figures cross near 100).  Below that, prefer plk_verify on host threads.
+ *   plk_verify_many_last_ms.  With plk_set_kernel_timing on: [0] host flattening (wall clock of the host threads), then HIP-event times of
+ *                [1] upload, [2] scalar multiplications, [3] sums and XYZZ -> affine, [4] pairing checks, [5] download.  Diagnostic.
+ *   plk_pairing_check_many_dev.  The pairing kernel on its own: n independent checks e(A_i, Q_0) e(B_i, Q_1) == 1 on device arrays of
+ *                plk_g1_affine, one byte of verdict each (1 / 0), ordered on `stream` like every _dev call; pointers 16-byte aligned, else
+ *                PLK_ERR_ARG.  g2 = Q_0 | Q_1 decoded and checked as plk_pairing_check does, with the same words.  A G1 entry with x = y = 0 is
+ *                infinity (its Miller loop is 1, as on the host); a G1 entry off the curve gets verdict PLK_VERDICT_MALFORMED and the call
+ *                still returns PLK_OK.  The first call with a G2 pair the context did not see last builds that pair's table on the host and
+ *                waits for `stream` once.  No counterpart in the reference.
+ *   plk_verify_terms.  Pure CPU, no context; diagnostic like plk_msm_last_shape.  The flattened form of the two G1 arguments of the final
+ *                pairing check of plonk::verify (src/plonk.rs:189-210), one scalar (Montgomery) per distinct point:
+ *                  pg = sum_{k < 23} scalars[k] points[k]: the key's 11 commitments (selectors 0..5, next-step 6, permutations 7..10), the
+ *                       proof's 11 (wires 11..14, grand product 15, quotient 16..19, W_z 20, W_zw 21), the generator 22;
+ *                  px = scalars[23] points[23] + scalars[24] points[24] = -W_z - u W_zw;     accept iff e(pg, g2[0]) e(px, g2[1]) == 1.
+ *                *early = 0: the verdict is already "invalid" without any group arithmetic (size or input-count mismatch, z^N == 1, the
+ *                equation at z fails, the strict-inputs rule) and points / scalars are zero; *early = 1 otherwise.  Malformed key or proof:
+ *                PLK_ERR_ARG with plk_verify_ex's words.                                                                                    */
+#define PLK_VERDICT_MALFORMED 2
+typedef struct plk_vk plk_vk;
+int32_t plk_vk_load(plk_ctx *ctx, const uint8_t *vk, uint64_t vk_len, uint32_t flags, plk_vk **out);
+void plk_vk_free(plk_vk *vk);
+int32_t plk_verify_many(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict, uint64_t *first_bad);
+int32_t plk_verify_many_last_ms(plk_ctx *ctx, float out_ms[6]);
+int32_t plk_pairing_check_many_dev(plk_ctx *ctx, const void *a_dev, const void *b_dev, uint64_t n, const uint8_t g2[256], void *verdict_dev, void *stream);
+int32_t plk_verify_terms(const uint8_t *vk, uint64_t vk_len, const uint8_t *proof, uint64_t proof_len, uint32_t flags,
+                         plk_g1_affine points[25], plk_fr scalars[25], int32_t *early);
+
 /* ---- circuit pipeline: circom loaders + transpile + setup + prove ----------------------------
  * plk_circuit mirrors CircomCircuit{r1cs, witness, wire_mapping: None, aux_offset: 1}
  * (src/circom_circuit.rs:41-47).  Loaders follow src/reader.rs:178-241, src/r1cs_file.rs:100-154

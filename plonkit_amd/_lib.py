@@ -496,6 +496,17 @@ class Context:
         _check(lib().plk_g1_intt_srs_dev(self._h, ctypes.c_uint32(log_n), _devptr(out_ptr), _stream(stream)))
 
 
+    def pairing_check_many_dev(self, a_ptr, b_ptr, n, g2_bytes, verdict_ptr, stream=None):
+        """plk_pairing_check_many_dev: n checks e(A_i, Q_0) e(B_i, Q_1) == 1 on device arrays of affine points; one verdict byte each
+        (1 / 0, 2 = a point off the curve), ordered on `stream`"""
+        _check(lib().plk_pairing_check_many_dev(self._h, _devptr(a_ptr), _devptr(b_ptr), ctypes.c_uint64(n), bytes(g2_bytes), _devptr(verdict_ptr), _stream(stream)))
+
+    def verify_many_last_ms(self):
+        """plk_verify_many_last_ms (set_kernel_timing on): host flattening, upload, scalar multiplications, sums, pairing checks, download"""
+        out = (ctypes.c_float * 6)()
+        _check(lib().plk_verify_many_last_ms(self._h, out))
+        return [float(x) for x in out]
+
 # ------------------------------------------------- circuit pipeline (mirrors src/plonk.rs's API)
 class Circuit:
     """CircomCircuit{r1cs, witness, wire_mapping: None, aux_offset: 1} (src/circom_circuit.rs:41-47).
@@ -843,6 +854,54 @@ def verify(vk_bytes, proof_bytes, strict_inputs=None):
         _check(lib().plk_verify_ex(bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), bytes(proof_bytes), ctypes.c_uint64(len(proof_bytes)),
                                    ctypes.c_uint32(1 if strict_inputs else 0), ctypes.byref(valid)))
     return bool(valid.value)
+
+
+class VerificationKey:
+    """plk_vk: a verification key resident on the GPU of `ctx` with the line table of its G2 pair (plk_vk_load); verify_many checks each
+    proof exactly as `verify` does.  strict_inputs: None = as plk_verify reads the environment at load time; True / False = the flag."""
+
+    def __init__(self, ctx, vk_bytes, strict_inputs=None):
+        self._h = ctypes.c_void_p()
+        self.ctx = ctx
+        if strict_inputs is None:
+            e = os.environ.get("PLK_VERIFY_STRICT_INPUTS", "")
+            strict_inputs = bool(e) and e[0] != "0"
+        _check(lib().plk_vk_load(ctx._h, bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), ctypes.c_uint32(1 if strict_inputs else 0), ctypes.byref(self._h)))
+        self.first_bad = None
+
+    def verify_many(self, proofs, ctx=None):
+        """numpy uint8 per proof: 1 valid, 0 invalid, 2 malformed; .first_bad = lowest index that is not 1, or None"""
+        proofs = [bytes(p) for p in proofs]
+        n = len(proofs)
+        ptrs = (ctypes.c_char_p * max(n, 1))(*proofs)
+        lens = (ctypes.c_uint64 * max(n, 1))(*[len(p) for p in proofs])
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        first_bad = ctypes.c_uint64(0)
+        _check(lib().plk_verify_many((ctx or self.ctx)._h, self._h, ptrs, lens, ctypes.c_uint64(n), _np(verdict), ctypes.byref(first_bad)))
+        self.first_bad = None if first_bad.value == 2 ** 64 - 1 else int(first_bad.value)
+        return verdict[:n]
+
+    def close(self):
+        if self._h:
+            lib().plk_vk_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def verify_terms(vk_bytes, proof_bytes, strict_inputs=False):
+    """plk_verify_terms: (points [25, 8] uint64 Montgomery affine, scalars [25, 4] uint64 Montgomery, early).  pg = sum of terms 0..22,
+    px = terms 23 + 24; early False: already invalid without group arithmetic.  Pure CPU."""
+    pts = np.zeros((25, 8), dtype=np.uint64)
+    sc = np.zeros((25, 4), dtype=np.uint64)
+    early = ctypes.c_int32(0)
+    _check(lib().plk_verify_terms(bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), bytes(proof_bytes), ctypes.c_uint64(len(proof_bytes)),
+                                  ctypes.c_uint32(1 if strict_inputs else 0), _np(pts), _np(sc), ctypes.byref(early)))
+    return pts, sc, bool(early.value)
 
 
 def pairing_check(a, g2_a, b, g2_b):

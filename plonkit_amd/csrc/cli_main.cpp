@@ -1,7 +1,7 @@
 // `plonkit` command line over the C ABI — the five prover commands of the reference's CLI
 // (src/bin/main.rs:27-53): setup, dump-lagrange, prove, export-verification-key, analyse, verify — and two the reference does not
-// have: check-key (the structure checks of include/plonkit_amd.h on a key file), check-witness (a witness against its R1CS) and
-// prove-many (one key, one circuit, one setup, a proof per witness file).
+// have: check-key (the structure checks of include/plonkit_amd.h on a key file), check-witness (a witness against its R1CS),
+// prove-many (one key, one circuit, one setup, a proof per witness file) and verify-many (one verification key, a verdict per proof file).
 // Same option names, short flags and defaults (src/bin/main.rs:55-136,176-190), same refusal to overwrite
 // (src/bin/main.rs:336-339,374-377,403-406) and the circuit-file default rule (src/bin/main.rs:346-357).
 // Everything arithmetic goes through include/plonkit_amd.h.
@@ -285,6 +285,9 @@ static int run(int argc, char **argv) {
     if (argc < 2) { fprintf(stderr, "plonkit (MI355X) — subcommands: analyse setup dump-lagrange prove export-verification-key verify\n"
                                       "                   check-key -m <key> [-l <lagrange key>] [--locate]   (the reference has no such command: is the key tau^i * G for the\n"
                                       "                   tau of its G2 section, does the Lagrange-form key belong to it; exit 0 ok, 2 a key is refused, 101 unreadable)\n"
+                                      "                   verify-many -v <vk> <proof>...   (the reference has no such command: every proof of one verification key checked\n"
+                                      "                   exactly and on its own, on the GPU; one line per proof, <path>: valid | invalid | malformed; exit 0 all valid,\n"
+                                      "                   144 otherwise as verify, 101 key unreadable)\n"
                                       "                   check-witness -c <circuit> -w <witness>   (the reference has no such command: does the witness satisfy every\n"
                                       "                   constraint of the R1CS, and if not which is the first that fails; no key, no setup; exit 0 ok, 2 refused, 101 unreadable)\n"
                                       "                   prove-many -m <key> [-l <lagrange key>] -c <circuit> -o <dir> <witness>...   (the reference has no such command: one\n"
@@ -644,6 +647,31 @@ static int run(int argc, char **argv) {
             written++;
         }
         if (written != witnesses.size()) return 2;
+    } else if (cmd == "verify-many") {
+        // NOT in the reference's CLI (src/bin/main.rs:27-53): plk_vk_load + plk_verify_many over the proofs named after the options
+        std::vector<char *> av;
+        std::vector<std::string> files;
+        for (int i = 0; i < argc; i++) {
+            if (i < 2 || argv[i][0] == '-') { av.push_back(argv[i]); if (i >= 2 && i + 1 < argc) av.push_back(argv[++i]); }
+            else files.push_back(argv[i]);
+        }
+        Args a = parse((int)av.size(), av.data(), {{"v", "verification_key|vk"}});
+        if (files.empty()) { fprintf(stderr, "error: The following required argument was not provided: <proof>...\n"); return 2; }
+        const std::vector<uint8_t> vkb = slurp(a.get("verification_key", "vk.bin"), "read vk file err");
+        std::vector<std::vector<uint8_t>> proofs;
+        for (const std::string &f : files) proofs.push_back(slurp(f, "read proof file err"));
+        plk_ctx *ctx = open_ctx();
+        plk_vk *vk = nullptr;
+        const char *strict = getenv("PLK_VERIFY_STRICT_INPUTS");       // as plk_verify reads it
+        CK("read vk file err", plk_vk_load(ctx, vkb.data(), vkb.size(), (strict && strict[0] && strict[0] != '0') ? PLK_VERIFY_STRICT_INPUTS : 0u, &vk));
+        std::vector<const uint8_t *> ptrs; std::vector<uint64_t> lens;
+        static const uint8_t none = 0;
+        for (const auto &p : proofs) { ptrs.push_back(p.empty() ? &none : p.data()); lens.push_back(p.size()); }
+        std::vector<uint8_t> verdict(proofs.size());
+        uint64_t first_bad = 0;
+        CK("fail to verify proofs", plk_verify_many(ctx, vk, ptrs.data(), lens.data(), proofs.size(), verdict.data(), &first_bad));
+        for (size_t i = 0; i < files.size(); i++) printf("%s: %s\n", files[i].c_str(), verdict[i] == 1 ? "valid" : verdict[i] == 0 ? "invalid" : "malformed");
+        if (first_bad != UINT64_MAX) return 400 & 0xff;
     } else if (cmd == "verify") {                                    // src/bin/main.rs:425-437 (no GPU involved)
         // VerifyOpts (src/bin/main.rs:125-137): the key is `-v` / `--verification_key` here, while export-verification-key
         // names its output `--vk` (src/bin/main.rs:186-187); `--vk` is kept as an alias on verify

@@ -133,6 +133,11 @@ struct plk_ctx {
     bool ev_on = false;                      // record the per-slot event bracket around msm_accumulate
     float r1cs_ms[4] = {0, 0, 0, 0};         // r1cs_check.hip: kernel times of the last witness check (recorded while ev_on)
     bool r1cs_ms_valid = false;
+    float vm_ms[6] = {0, 0, 0, 0, 0, 0};     // verify_many.hip: host flattening, upload, the three kernels, download of the last plk_verify_many (recorded while ev_on)
+    bool vm_ms_valid = false;
+    plk::DevBuf pair_tab;                    // verify_many.hip: line table of the G2 pair plk_pairing_check_many_dev saw last
+    uint8_t pair_g2[256] = {};
+    bool pair_tab_valid = false;
     // multi-GPU commitments of the prover (plk_set_commit_shard): global index of the first resident SRS point and
     // the caller's all-ranks combiner for the Jacobian partial sums
     uint64_t shard_first = 0;

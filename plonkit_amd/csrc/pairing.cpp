@@ -89,22 +89,37 @@ static Fq12 line_value(const Fq2 &m, const Fq2 &xt, const Fq2 &yt, const HFq &xp
 
 struct TwistPoint { Fq2 x, y; };
 
-// f *= l_{R,R}(P);  R = 2R
-static void step_double(Fq12 &f, TwistPoint &R, const HFq &xp, const HFq &yp) {
+// the two group steps of the loop on the twist.  Each returns its line as the slope m and the intercept y_T - m x_T (T = R before the
+// step): neither depends on the G1 argument, which is what lets miller_lines tabulate a whole loop for a fixed Q (verify_many.hip)
+struct Line { Fq2 m, b; };
+static Line tangent_step(TwistPoint &R) {                               // R = 2R
     const Fq2 x2 = R.x.sqr();
     const Fq2 m = (x2 + x2 + x2) * (R.y + R.y).inv();
-    f = f * line_value(m, R.x, R.y, xp, yp);
+    const Line l = {m, R.y - m * R.x};
     const Fq2 x3 = m.sqr() - R.x - R.x;
     R.y = m * (R.x - x3) - R.y;
     R.x = x3;
+    return l;
 }
-// f *= l_{R,Q}(P);  R = R + Q   (R != +-Q for points of prime order r inside the loop)
-static void step_add(Fq12 &f, TwistPoint &R, const TwistPoint &Q, const HFq &xp, const HFq &yp) {
+static Line chord_step(TwistPoint &R, const TwistPoint &Q) {            // R = R + Q   (R != +-Q for points of prime order r inside the loop)
     const Fq2 m = (Q.y - R.y) * (Q.x - R.x).inv();
-    f = f * line_value(m, R.x, R.y, xp, yp);
+    const Line l = {m, R.y - m * R.x};
     const Fq2 x3 = m.sqr() - R.x - Q.x;
     R.y = m * (R.x - x3) - R.y;
     R.x = x3;
+    return l;
+}
+// f *= l_{R,R}(P);  R = 2R
+static void step_double(Fq12 &f, TwistPoint &R, const HFq &xp, const HFq &yp) {
+    const TwistPoint T = R;
+    const Line l = tangent_step(R);
+    f = f * line_value(l.m, T.x, T.y, xp, yp);
+}
+// f *= l_{R,Q}(P);  R = R + Q
+static void step_add(Fq12 &f, TwistPoint &R, const TwistPoint &Q, const HFq &xp, const HFq &yp) {
+    const TwistPoint T = R;
+    const Line l = chord_step(R, Q);
+    f = f * line_value(l.m, T.x, T.y, xp, yp);
 }
 
 static Fq12 miller_loop(const HAffine &P, const G2Affine &Qin) {
@@ -124,6 +139,51 @@ static Fq12 miller_loop(const HAffine &P, const G2Affine &Qin) {
     step_add(f, R, Q2n, P.x, P.y);
     return f;
 }
+
+// ---- the same loop as a table of lines for a fixed Q (plk_vk_load): 64 doublings, one addition per set bit of ATE_LOOP_LO, two Frobenius
+// corrections, in the order miller_loop takes them; entry k is {slope, intercept} of line k.  Every exceptional case of Q is decided here, by
+// the steps above, exactly as miller_loop decides it.
+uint64_t ate_loop_lo() { return ATE_LOOP_LO; }
+int miller_line_count() { return 64 + __builtin_popcountll(ATE_LOOP_LO) + 2; }
+void miller_lines(const G2Affine &Qin, Fq2 *out) {
+    const TwistPoint Q = {Qin.x, Qin.y};
+    TwistPoint R = Q;
+    int k = 0;
+    auto put = [&](const Line &l) { out[2 * k] = l.m; out[2 * k + 1] = l.b; k++; };
+    for (int i = 63; i >= 0; i--) {
+        put(tangent_step(R));
+        if ((ATE_LOOP_LO >> i) & 1) put(chord_step(R, Q));
+    }
+    const TwistPoint Q1 = {Q.x.conj() * gamma2(), Q.y.conj() * gamma3()};
+    const TwistPoint Q2n = {Q1.x.conj() * gamma2(), -(Q1.y.conj() * gamma3())};
+    put(chord_step(R, Q1));
+    put(chord_step(R, Q2n));
+}
+Fq12 miller_loop_value(const HAffine &P, const G2Affine &Q) { return miller_loop(P, Q); }
+Fq12 miller_loop_from_lines(const HAffine &P, const Fq2 *lines, bool q_inf) {
+    static const HFq nine = HFq::from_u64(9);
+    Fq12 f = Fq12::one();
+    if (P.is_inf() || q_inf) return f;
+    int k = 0;
+    auto line = [&]() {
+        const Fq2 a = lines[2 * k].scale(P.x), b = lines[2 * k + 1];
+        k++;
+        Fq12 l = Fq12::zero();
+        l.c[0] = -P.y;
+        l.c[1] = a.c0 - a.c1 * nine;  l.c[7] = a.c1;
+        l.c[3] = b.c0 - b.c1 * nine;  l.c[9] = b.c1;
+        f = f * l;
+    };
+    for (int i = 63; i >= 0; i--) {
+        f = f * f;
+        line();
+        if ((ATE_LOOP_LO >> i) & 1) line();
+    }
+    line(); line();
+    return f;
+}
+// w^p = g w with g = xi^((p-1)/6) = gamma3 / gamma2 in Fq2: the constant behind every Frobenius map of the flat representation
+Fq2 frobenius_w() { return gamma3() * gamma2().inv(); }
 
 bool pairing_product_is_one(const HAffine *g1, const G2Affine *g2, int pairs) {
     Fq12 f = Fq12::one();

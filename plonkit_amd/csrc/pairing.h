@@ -50,5 +50,15 @@ bool g2_from_bytes(const uint8_t in[128], G2Affine *out);
 // product of Miller loops over the pairs, then one final exponentiation; true when the result is 1
 bool pairing_product_is_one(const HAffine *g1, const G2Affine *g2, int pairs);
 
+
+// ---- the Miller loop of a FIXED G2 point as a table (plk_vk_load / verify_many.hip; tests/host/pairing_lines_check.cpp).  A line of the loop is
+// l = -y_P + (m x_P) w + (y_T - m x_T) w^3: its slope m and intercept y_T - m x_T do not depend on the G1 argument P.
+uint64_t ate_loop_lo();                                          // the low 64 bits of 6u + 2 (the loop walks them from bit 63 down)
+int miller_line_count();                                         // 64 doublings + popcount(ate_loop_lo()) additions + 2 Frobenius corrections
+void miller_lines(const G2Affine &Q, Fq2 *out);                  // out[2k] = slope, out[2k + 1] = intercept of line k; Q not infinity
+Fq12 miller_loop_value(const HAffine &P, const G2Affine &Q);      // the loop pairing_product_is_one runs
+Fq12 miller_loop_from_lines(const HAffine &P, const Fq2 *lines, bool q_inf);   // f <- f^2 l per step from the table
+Fq2 frobenius_w();                                               // g in Fq2 with w^p = g w
+
 }  // namespace host
 }  // namespace plk

@@ -7,6 +7,7 @@
 #include "../../include/plonkit_amd.h"
 #include "keccak.h"
 #include "pairing.h"
+#include "verify_many.h"
 #include <string>
 #include <vector>
 
@@ -191,7 +192,137 @@ bool verify_keccak(const Vk &vk, const ProofData &P, bool strict_inputs) {
     return pairing_product_is_one(g1s, vk.g2, 2);
 }
 
+// The same verifier up to the pairing, FLATTENED: every nested expression of verify_keccak above (d, agg, val) collapsed into one scalar per
+// distinct point, so that pg = sum_{k<23} s_k P_k and px = s_23 P_23 + s_24 P_24 can be formed by independent scalar multiplications
+// (verify_many.hip).  Returns false where verify_keccak returns false before any group arithmetic.  verify_keccak keeps its own arithmetic;
+// tests/test_verify_terms_host.py pins the two against each other.
+bool flatten_keccak(const Vk &vk, const ProofData &P, bool strict_inputs, HAffine pts[VERIFY_TERMS], HFr sc[VERIFY_TERMS]) {
+    const uint64_t N = vk.n + 1;
+    if (N < 2 || (N & (N - 1)) || N > (1ull << 28)) return false;
+    uint32_t log_n = 0; while ((1ull << log_n) < N) log_n++;
+    if (strict_inputs && vk.num_inputs < 1) return false;
+    if (P.n != vk.n || P.inputs.size() != vk.num_inputs) return false;
+    const HFr om = omega_of(log_n), one = HFr::one();
+    RollingKeccak tr;
+    for (const HFr &x : P.inputs) tr.absorb_fr(x);
+    for (const HAffine &c : P.wires) tr.absorb_g1(c);
+    const HFr beta = tr.challenge(), gamma = tr.challenge();
+    tr.absorb_g1(P.grand_product);
+    const HFr alpha = tr.challenge();
+    for (const HAffine &c : P.quotient) tr.absorb_g1(c);
+    const HFr z = tr.challenge();
+    HFr zN = z; for (uint32_t i = 0; i < log_n; i++) zN = zN.sqr();
+    if (zN == one) return false;
+    std::vector<HFr> lag(vk.num_inputs ? vk.num_inputs : 1);
+    { HFr wi = one; const HFr nf = HFr::from_u64(N);
+      for (uint64_t i = 0; i < lag.size(); i++) { lag[i] = wi * (zN - one) * (nf * (z - wi)).inv(); wi = wi * om; } }
+    const std::vector<HFr> &wz = P.wire_z, &sz = P.sigma_z;
+    {
+        const HFr lhs = (zN - one) * P.t_z;
+        HFr rhs = P.r_z;
+        for (uint64_t i = 0; i < vk.num_inputs; i++) rhs = rhs + lag[i] * P.inputs[i];
+        HFr zpart = P.z_zw;
+        for (int j = 0; j < 3; j++) zpart = zpart * (sz[j] * beta + gamma + wz[j]);
+        zpart = zpart * (gamma + wz[3]) * alpha;
+        rhs = rhs - zpart - lag[0] * alpha * alpha;
+        if (!(lhs == rhs)) return false;
+    }
+    for (const HFr &x : wz) tr.absorb_fr(x);
+    for (const HFr &x : P.wire_zw) tr.absorb_fr(x);
+    for (const HFr &x : sz) tr.absorb_fr(x);
+    tr.absorb_fr(P.t_z); tr.absorb_fr(P.r_z); tr.absorb_fr(P.z_zw);
+    const HFr v = tr.challenge();
+    tr.absorb_g1(P.open_z); tr.absorb_g1(P.open_zw);
+    const HFr u = tr.challenge();
+
+    // points: selectors 0..5, next_step 6, sigma 7..10 | wires 11..14, grand product 15, quotient 16..19, W_z 20, W_zw 21 | G 22 | W_z 23, W_zw 24
+    for (int j = 0; j < 6; j++) pts[j] = vk.selectors[j];
+    pts[6] = vk.next_step[0];
+    for (int j = 0; j < 4; j++) pts[7 + j] = vk.sigma[j];
+    for (int j = 0; j < 4; j++) pts[11 + j] = P.wires[j];
+    pts[15] = P.grand_product;
+    for (int j = 0; j < 4; j++) pts[16 + j] = P.quotient[j];
+    pts[20] = P.open_z; pts[21] = P.open_zw;
+    pts[22].x = HFq::from_u64(1); pts[22].y = HFq::from_u64(2);
+    pts[23] = P.open_z; pts[24] = P.open_zw;
+
+    // d = v (q_const + sum wz_j q_j + wz_0 wz_1 q_m + wire_zw q_next + gz Z - last sigma_3) + gzw Z
+    for (int j = 0; j < 4; j++) sc[j] = v * wz[j];
+    sc[4] = v * wz[0] * wz[1];
+    sc[5] = v;
+    sc[6] = v * P.wire_zw[0];
+    HFr gz = z * beta + wz[0] + gamma;
+    for (int j = 0; j < 3; j++) gz = gz * (z * vk.non_residues[j] * beta + gamma + wz[j + 1]);
+    gz = gz * alpha + lag[0] * alpha * alpha;
+    HFr v9 = one; for (int i = 0; i < 9; i++) v9 = v9 * v;
+    HFr last = one;
+    for (int j = 0; j < 3; j++) last = last * (beta * sz[j] + gamma + wz[j]);
+    last = last * beta * P.z_zw * alpha;
+    sc[10] = -(v * last);
+    sc[15] = v * gz + v9 * u;
+    // agg = t_0 + sum zN^k t_k + d + sum ch wires + sum ch sigma + ch u wires_3 - val G
+    sc[16] = one;
+    for (int k = 1; k < 4; k++) sc[16 + k] = sc[16 + k - 1] * zN;
+    HFr ch = v;
+    for (int j = 0; j < 4; j++) { ch = ch * v; sc[11 + j] = ch; }
+    for (int j = 0; j < 3; j++) { ch = ch * v; sc[7 + j] = ch; }
+    ch = ch * v; ch = ch * v;
+    sc[14] = sc[14] + ch * u;
+    ch = v;
+    HFr val = P.t_z + P.r_z * ch;
+    for (const HFr &x : wz) { ch = ch * v; val = val + x * ch; }
+    for (const HFr &x : sz) { ch = ch * v; val = val + x * ch; }
+    ch = ch * v; val = val + P.z_zw * ch * u;
+    ch = ch * v; val = val + P.wire_zw[0] * ch * u;
+    sc[22] = -val;
+    // pg = agg + z W_z + z omega u W_zw ;  px = -(W_z + u W_zw)
+    sc[20] = z; sc[21] = z * om * u;
+    sc[23] = -one; sc[24] = -u;
+    return true;
+}
+
 }  // namespace
+
+namespace plk {
+// ParsedVk is never defined: the handle is this file's Vk under a name other translation units can spell
+static const Vk &vk_of(const ParsedVk *v) { return *reinterpret_cast<const Vk *>(v); }
+ParsedVk *parsed_vk_new(const uint8_t *vk, uint64_t len) {
+    Vk *p = new Vk;
+    if (!parse_vk(vk, len, p)) { delete p; return nullptr; }
+    return reinterpret_cast<ParsedVk *>(p);
+}
+void parsed_vk_free(ParsedVk *v) { delete reinterpret_cast<Vk *>(v); }
+void parsed_vk_points(const ParsedVk *v, plk_g1_affine fixed[VERIFY_FIXED], host::G2Affine g2[2]) {
+    const Vk &k = vk_of(v);
+    for (int j = 0; j < 6; j++) memcpy(&fixed[j], &k.selectors[j], 64);
+    memcpy(&fixed[6], &k.next_step[0], 64);
+    for (int j = 0; j < 4; j++) memcpy(&fixed[7 + j], &k.sigma[j], 64);
+    HAffine G; G.x = HFq::from_u64(1); G.y = HFq::from_u64(2);
+    memcpy(&fixed[11], &G, 64);
+    g2[0] = k.g2[0]; g2[1] = k.g2[1];
+}
+int32_t verify_terms_parsed(const ParsedVk *v, const uint8_t *proof, uint64_t len, uint32_t flags, plk_g1_affine points[VERIFY_TERMS],
+                            plk_fr scalars[VERIFY_TERMS], int32_t *early) {
+    ProofData pr;
+    if (!parse_proof(proof, len, &pr)) { set_error("plk_verify: malformed proof"); return PLK_ERR_ARG; }
+    HAffine pts[VERIFY_TERMS]; HFr sc[VERIFY_TERMS];
+    memset(points, 0, VERIFY_TERMS * sizeof(plk_g1_affine)); memset(scalars, 0, VERIFY_TERMS * sizeof(plk_fr));
+    *early = flatten_keccak(vk_of(v), pr, (flags & PLK_VERIFY_STRICT_INPUTS) != 0, pts, sc) ? 1 : 0;
+    if (*early) for (int k = 0; k < VERIFY_TERMS; k++) { memcpy(&points[k], &pts[k], 64); memcpy(&scalars[k], &sc[k], 32); }
+    return PLK_OK;
+}
+}  // namespace plk
+
+PLK_API int32_t plk_verify_terms(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, uint32_t flags,
+                                 plk_g1_affine points[25], plk_fr scalars[25], int32_t *early) {
+    if (!vk_bytes || !proof_bytes || !points || !scalars || !early) { set_error("plk_verify_terms: null argument"); return PLK_ERR_ARG; }
+    if (flags & ~(uint32_t)PLK_VERIFY_STRICT_INPUTS) { set_error("plk_verify_ex: unknown flag"); return PLK_ERR_ARG; }
+    ParsedVk *v = parsed_vk_new(vk_bytes, vk_len);
+    if (!v) { set_error("plk_verify: malformed verification key"); return PLK_ERR_ARG; }
+    const int32_t rc = verify_terms_parsed(v, proof_bytes, proof_len, flags, points, scalars, early);
+    parsed_vk_free(v);
+    return rc;
+}
 
 PLK_API int32_t plk_verify_ex(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, uint32_t flags, int32_t *valid) {
     if (!vk_bytes || !proof_bytes || !valid) { set_error("plk_verify: null argument"); return PLK_ERR_ARG; }

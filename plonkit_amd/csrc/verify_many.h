@@ -1,0 +1,20 @@
+// What plk_vk_load / plk_verify_many (verify_many.hip) take from the host verifier (verify.cpp): the parsed key and the flattened form of
+// verify_keccak's two pairing arguments.  verify.cpp stays pure host code (the sanitizer build compiles it without HIP).
+#pragma once
+#include "../../include/plonkit_amd.h"
+#include "pairing.h"
+
+namespace plk {
+
+constexpr int VERIFY_TERMS = 25, VERIFY_TERMS_PG = 23, VERIFY_FIXED = 12;   // pg: 11 of the key + 11 of the proof + the generator; px: 2
+
+struct ParsedVk;                                                   // opaque: verify.cpp's parsed key
+ParsedVk *parsed_vk_new(const uint8_t *vk, uint64_t len);           // null: plk_verify_ex would say "malformed verification key"
+void parsed_vk_free(ParsedVk *v);
+// the 12 points that are the same for every proof (terms 0..10 and 22 of plk_verify_terms) and the key's G2 pair
+void parsed_vk_points(const ParsedVk *v, plk_g1_affine fixed[VERIFY_FIXED], host::G2Affine g2[2]);
+// plk_verify_terms on a parsed key; PLK_ERR_ARG "plk_verify: malformed proof" exactly when plk_verify_ex says so
+int32_t verify_terms_parsed(const ParsedVk *v, const uint8_t *proof, uint64_t len, uint32_t flags, plk_g1_affine points[VERIFY_TERMS],
+                            plk_fr scalars[VERIFY_TERMS], int32_t *early);
+
+}  // namespace plk
