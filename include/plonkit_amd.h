@@ -612,7 +612,11 @@ int32_t plk_prove_assembled_dev(plk_ctx *ctx, const plk_setup *s, const void *co
  *      from prove_by_steps src/plonk.rs:152-159): Polynomial::evaluate_at, the division by (x - z) behind the two opening
  *      proofs ((p(x) - p(z)) / (x - z), n coefficients, the top one zero), and the permutation grand product
  *      z_0 = 1, z_{i+1} = z_i * prod_j (w_j + beta k_j omega^i + gamma) / (w_j + beta sigma_j + gamma)  (SURVEY.md A.4 round 2;
- *      k = 1, 5, 7, 10; no per-element inversion: prefix x suffix products and one host inversion).  Device vectors, N = 2^log_n. */
+ *      k = 1, 5, 7, 10; no per-element inversion: prefix x suffix products and one host inversion).  Device vectors, N = 2^log_n.
+ *      plk_poly_evaluate_at_dev at z = 0 returns c_0.  plk_poly_divide_by_linear_dev refuses z = 0 with PLK_ERR_ARG (its schedule
+ *      multiplies by powers of 1/z; the quotient by x is a shift the caller can do).  plk_permutation_grand_product_dev returns
+ *      PLK_ERR_UNSAT ("grand product denominator vanished") when w_j[i] + beta sigma_j[i] + gamma = 0 for some j and some row i of
+ *      the N, the last row included; z_values_dev is unspecified then and the context stays usable. */
 int32_t plk_poly_evaluate_at_dev(plk_ctx *ctx, const void *coeffs_dev, uint64_t n, const plk_fr *z, plk_fr *out, void *stream);
 int32_t plk_poly_divide_by_linear_dev(plk_ctx *ctx, const void *coeffs_dev, uint64_t n, const plk_fr *z, void *quotient_dev, void *stream);
 int32_t plk_permutation_grand_product_dev(plk_ctx *ctx, const void *const wires_dev[4], const void *const sigmas_dev[4], const plk_fr *beta, const plk_fr *gamma,

@@ -412,6 +412,22 @@ def setup(r1cs: R1CS, T: Transpiled = None) -> Setup:
     return S
 
 
+def setup_from_values(selector_values, sigma_values, num_inputs) -> Setup:
+    """a Setup from the 7 selectors (q_a q_b q_c q_d q_m q_const q_d_next) and the 4 sigmas as Montgomery value vectors on <omega_N> in
+    row order: the same object setup() returns, for circuits that no R1CS describes"""
+    N = selector_values[0].shape[0]
+    log_n = N.bit_length() - 1
+    assert N == 1 << log_n and len(selector_values) == 7 and len(sigma_values) == 4
+    assert all(v.shape == (N, 4) for v in list(selector_values) + list(sigma_values))
+    S = Setup()
+    S.n, S.N, S.log_n, S.num_inputs = N - 1, N, log_n, num_inputs
+    S.selector_values = [np.ascontiguousarray(v, dtype=np.uint64) for v in selector_values]
+    S.sigma_values = [np.ascontiguousarray(v, dtype=np.uint64) for v in sigma_values]
+    S.selectors = [ol.ntt(v, log_n, inverse=True) for v in S.selector_values]
+    S.sigmas = [ol.ntt(v, log_n, inverse=True) for v in S.sigma_values]
+    return S
+
+
 def _rows_flat(rf: R1CSFlat, witness=None):
     """public-input rows + the C transpiler's gates, padded: vars uint32 [4, N], q [7, N, 4] (Montgomery), values"""
     n_in = rf.num_inputs - 1
@@ -583,6 +599,14 @@ def prove(r1cs: R1CS, witness, crs: Crs, S: Setup = None, return_debug=False) ->
             for j in range(4):
                 cols[j][r] = vals[g.vars[j]]
         w_vals = [ol.fr_vec(c) for c in cols]
+    return prove_columns(S, w_vals, inputs, crs, return_debug)
+
+
+def prove_columns(S: Setup, w_vals, inputs, crs: Crs, return_debug=False) -> Proof:
+    """rounds 1 to 5 from the assembled wire columns (four Montgomery arrays of N rows) and the public inputs (canonical ints): what both
+    front ends of prove() end in, and the entry for circuits given as value vectors (setup_from_values); the gate check is the caller's"""
+    N = S.N
+    assert all(v.shape == (N, 4) for v in w_vals) and len(inputs) == S.num_inputs
     log_n, log_4n = S.log_n, S.log_n + 2
     w_omega = ol.omega(log_n)
 
