@@ -943,7 +943,15 @@ int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t b
     plk_ctx::MsmSlot &S = ctx->slot[slot_index];
     auto in_flight = [&]() { ctx->fifo[ctx->msm_enq % plk_ctx::MSM_SLOTS] = (uint8_t)slot_index; S.busy = true; ctx->msm_enq++; };
     if (!S.stream) {
-        PLK_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+        // The slots' streams are created at the runtime's HIGH stream priority, all three alike.  What counts is not the priority but that the runtime
+        // keeps a pool of hardware queues per priority level: at the default level the three slots share HIP's (default: four) queues with the null
+        // stream, the context's stream and every stream of the embedding process, two slots then land on ONE hardware queue, and that queue runs its
+        // packets in order — commitment k+3's recoding waited behind the whole chain of k+2 (accumulation and reduction), the chip idled ~0.5 ms in
+        // every three commitments (kernel trace in profiles/msm_burst_priority_ab.txt: 1.51 -> 1.30 ms per 2^20 commitment with four queues per process).
+        // GPU_MAX_HW_QUEUES=8 (runtime.hip) avoids the same collision only where the caller has not set the variable.
+        int lo_prio = 0, hi_prio = 0;
+        PLK_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
+        PLK_HIP(hipStreamCreateWithPriority(&S.stream, hipStreamNonBlocking, hi_prio));
         PLK_HIP(hipEventCreateWithFlags(&S.ready, hipEventDisableTiming));
         PLK_HIP(hipEventCreateWithFlags(&S.acc_done, hipEventDisableTiming));
     }
