@@ -394,6 +394,34 @@ int32_t plk_pairing_check(const plk_g1_affine *a, const uint8_t *g2_a, const plk
  *                figures cross near 100).  Below that, prefer plk_verify on host threads.
  *   plk_verify_many_last_ms.  With plk_set_kernel_timing on: [0] host flattening (wall clock of the host threads), then HIP-event times of
  *                [1] upload, [2] scalar multiplications, [3] sums and XYZZ -> affine, [4] pairing checks, [5] download.  Diagnostic.
+ *                After plk_verify_many_packed slot [0] is the HIP-event time of the front kernel instead; the other slots keep their meaning.
+ *                plk_verify_many_dev does not wait and records no times: after it there is no timed call on the context (PLK_ERR_ARG here).
+ *   plk_verify_many_packed.  plk_verify_many from raw bytes, with the front end ON THE DEVICE: count proof.bin images back to back in host
+ *                memory, proof i = blob[off[i], off[i + 1]), off has count + 1 entries.  Blocks.  verdict[i] and *first_bad exactly as
+ *                plk_verify_many (and so as plk_verify_ex).  One lane per proof parses the bytes (the rules of plk_verify_ex's parser, 11 curve
+ *                checks), runs the Keccak transcript, checks the equation at z and writes the 25 scalars of plk_verify_terms; a lane never
+ *                reads outside its proof, whatever the counts inside it say, and proofs may start at any byte address.  Every proof of a pass
+ *                then goes through plk_verify_many's kernels — one the front end settled as 25 zero terms — and its verdict byte is written
+ *                from its state, so nothing returns to the host between the bytes and the verdicts.  Offsets that decrease or reach past
+ *                blob_len: PLK_ERR_ARG before anything is launched.  The other refusals, count == 0 and the arena as plk_verify_many; the arena
+ *                now also holds the raw bytes of a pass (about 6.7 KB per proof of 1.1 KB).  No counterpart in the reference.
+ *                BREAK-EVEN against plk_verify_many (one MI355X, profiles/verify_front_ab.txt): the front kernel is 1.6 - 1.9 ms for any batch up
+ *                to 2^16 proofs, the host front end 2 / 27 / 423 ms at 256 / 4096 / 65536.  Measured calls at those sizes: 90.5 / 91.8 / 149.6 ms
+ *                against plk_verify_many's 90.9 / 118.3 / 587.6 ms — equal at 256 (the difference is inside the spread), 4096 is the first
+ *                measured size at which this call wins by more than plk_verify_many's own spread, 3.9x at 65536.
+ *   plk_verify_many_dev.  The same with blob, offsets (8-byte aligned) and verdict bytes in DEVICE memory, ordered on `stream` like every
+ *                _dev call: it does not wait for the GPU, and no byte of it passes through the host.  An offset pair that decreases or reaches
+ *                past blob_len gives THAT proof PLK_VERDICT_MALFORMED, nothing of it is read, and its neighbours are unaffected.  Null
+ *                arguments, a key of another device, a commitment in flight: PLK_ERR_ARG; count == 0 launches nothing.
+ *                MEMORY AND ORDER.  Being the one call here that returns before its kernels end, it keeps out of the context's staging arena
+ *                (whose users each rely on the earlier ones having waited): its 5.5 KB per proof are a buffer of its own that grows only, and
+ *                its kernels run on the context's stream, after what `stream` holds at the call and before what `stream` is given next.  Any
+ *                other call on the context may follow without a wait; a second plk_verify_many_dev queues behind the first.  blob, offsets
+ *                and verdict must stay allocated until `stream` has passed the call.  No counterpart in the reference.
+ *   plk_verify_front_dev.  The front kernel on its own, as plk_pairing_check_many_dev is the pairing kernel on its own: per proof 25
+ *                plk_g1_affine and 25 plk_fr, both 16-byte aligned, and a state byte — 1: goes on to the group arithmetic, and points / scalars
+ *                equal plk_verify_terms's bit for bit; 0: settled invalid (plk_verify_terms's *early = 0); 2: malformed; for 0 and 2 points
+ *                and scalars are zero.  Ordered on `stream`.  No counterpart in the reference.
  *   plk_pairing_check_many_dev.  The pairing kernel on its own: n independent checks e(A_i, Q_0) e(B_i, Q_1) == 1 on device arrays of
  *                plk_g1_affine, one byte of verdict each (1 / 0), ordered on `stream` like every _dev call; pointers 16-byte aligned, else
  *                PLK_ERR_ARG.  g2 = Q_0 | Q_1 decoded and checked as plk_pairing_check does, with the same words.  A G1 entry with x = y = 0 is
@@ -417,6 +445,10 @@ int32_t plk_verify_many_last_ms(plk_ctx *ctx, float out_ms[6]);
 int32_t plk_pairing_check_many_dev(plk_ctx *ctx, const void *a_dev, const void *b_dev, uint64_t n, const uint8_t g2[256], void *verdict_dev, void *stream);
 int32_t plk_verify_terms(const uint8_t *vk, uint64_t vk_len, const uint8_t *proof, uint64_t proof_len, uint32_t flags,
                          plk_g1_affine points[25], plk_fr scalars[25], int32_t *early);
+int32_t plk_verify_many_packed(plk_ctx *ctx, const plk_vk *vk, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, uint64_t count, uint8_t *verdict, uint64_t *first_bad);
+int32_t plk_verify_many_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *verdict_dev, void *stream);
+int32_t plk_verify_front_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *points_dev, void *scalars_dev,
+                             void *state_dev, void *stream);
 
 /* ---- circuit pipeline: circom loaders + transpile + setup + prove ----------------------------
  * plk_circuit mirrors CircomCircuit{r1cs, witness, wire_mapping: None, aux_offset: 1}

@@ -501,8 +501,16 @@ class Context:
         (1 / 0, 2 = a point off the curve), ordered on `stream`"""
         _check(lib().plk_pairing_check_many_dev(self._h, _devptr(a_ptr), _devptr(b_ptr), ctypes.c_uint64(n), bytes(g2_bytes), _devptr(verdict_ptr), _stream(stream)))
 
+    def verify_front_dev(self, key, blob_ptr, blob_len, off_ptr, count, points_ptr, scalars_ptr, state_ptr, stream=None):
+        """plk_verify_front_dev: the verifier's front kernel on its own.  Device memory: the packed proof bytes, count + 1 uint64 offsets, and
+        per proof 25 affine points, 25 scalars (plk_verify_terms's, zero unless state is 1) and a state byte (1 goes on, 0 invalid, 2 malformed);
+        ordered on `stream`"""
+        _check(lib().plk_verify_front_dev(self._h, key._h, _devptr(blob_ptr), ctypes.c_uint64(blob_len), _devptr(off_ptr), ctypes.c_uint64(count), _devptr(points_ptr),
+                                          _devptr(scalars_ptr), _devptr(state_ptr), _stream(stream)))
+
     def verify_many_last_ms(self):
-        """plk_verify_many_last_ms (set_kernel_timing on): host flattening, upload, scalar multiplications, sums, pairing checks, download"""
+        """plk_verify_many_last_ms (set_kernel_timing on): host flattening (after verify_many_packed: the front kernel), upload, scalar
+        multiplications, sums, pairing checks, download"""
         out = (ctypes.c_float * 6)()
         _check(lib().plk_verify_many_last_ms(self._h, out))
         return [float(x) for x in out]
@@ -880,6 +888,43 @@ class VerificationKey:
         _check(lib().plk_verify_many((ctx or self.ctx)._h, self._h, ptrs, lens, ctypes.c_uint64(n), _np(verdict), ctypes.byref(first_bad)))
         self.first_bad = None if first_bad.value == 2 ** 64 - 1 else int(first_bad.value)
         return verdict[:n]
+
+    def verify_many_packed(self, blob, offsets, ctx=None):
+        """plk_verify_many_packed: proof i = blob[offsets[i]:offsets[i + 1]]; the front end runs on the GPU.  Returns and sets .first_bad as
+        verify_many; offsets that decrease or reach past the blob raise PlkError (PLK_ERR_ARG)"""
+        blob = bytes(blob)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("verify_many_packed: offsets must hold count + 1 entries")
+        n = off.size - 1
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        first_bad = ctypes.c_uint64(0)
+        _check(lib().plk_verify_many_packed((ctx or self.ctx)._h, self._h, blob, ctypes.c_uint64(len(blob)), _np(off), ctypes.c_uint64(n), _np(verdict), ctypes.byref(first_bad)))
+        self.first_bad = None if first_bad.value == 2 ** 64 - 1 else int(first_bad.value)
+        return verdict[:n]
+
+    def verify_many_dev(self, blob_tensor, offsets_tensor, stream=None, ctx=None):
+        """plk_verify_many_dev: blob (uint8) and offsets (int64 / uint64, count + 1 entries) are torch tensors on the key's GPU; returns a uint8
+        tensor of verdicts there, ordered on `stream` (default: the context's) — nothing passes through the host and nothing waits.  A bad
+        offset pair gives that proof verdict 2"""
+        import torch
+        if blob_tensor.dtype != torch.uint8 or offsets_tensor.element_size() != 8 or not blob_tensor.is_contiguous() or not offsets_tensor.is_contiguous():
+            raise ValueError("verify_many_dev: blob must be a contiguous uint8 tensor and offsets a contiguous 64-bit integer tensor")
+        dev = (ctx or self.ctx).device
+        for t in (blob_tensor, offsets_tensor):                       # a host pointer must not reach the kernel
+            if not t.is_cuda or t.device.index != dev:
+                raise ValueError("verify_many_dev: blob and offsets must be tensors on cuda:%d, the device of the key's context" % dev)
+        n = offsets_tensor.numel() - 1
+        if n < 0:
+            raise ValueError("verify_many_dev: offsets must hold count + 1 entries")
+        if stream is not None and hasattr(stream, "cuda_stream"):
+            with torch.cuda.stream(stream):                           # the verdict tensor belongs to the stream that fills it
+                verdict = torch.empty(n, dtype=torch.uint8, device=blob_tensor.device)
+        else:
+            verdict = torch.empty(n, dtype=torch.uint8, device=blob_tensor.device)
+        _check(lib().plk_verify_many_dev((ctx or self.ctx)._h, self._h, _devptr(blob_tensor), ctypes.c_uint64(blob_tensor.numel()), _devptr(offsets_tensor),
+                                         ctypes.c_uint64(n), _devptr(verdict), _stream(stream)))
+        return verdict
 
     def close(self):
         if self._h:

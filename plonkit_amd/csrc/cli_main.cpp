@@ -287,7 +287,8 @@ static int run(int argc, char **argv) {
                                       "                   tau of its G2 section, does the Lagrange-form key belong to it; exit 0 ok, 2 a key is refused, 101 unreadable)\n"
                                       "                   verify-many -v <vk> <proof>...   (the reference has no such command: every proof of one verification key checked\n"
                                       "                   exactly and on its own, on the GPU; one line per proof, <path>: valid | invalid | malformed; exit 0 all valid,\n"
-                                      "                   144 otherwise as verify, 101 key unreadable)\n"
+                                      "                   144 otherwise as verify, 101 key unreadable; --front device: the bytes are parsed, hashed\n"
+                                      "                   and flattened in a kernel instead of on host threads, same lines, same exit codes)\n"
                                       "                   check-witness -c <circuit> -w <witness>   (the reference has no such command: does the witness satisfy every\n"
                                       "                   constraint of the R1CS, and if not which is the first that fails; no key, no setup; exit 0 ok, 2 refused, 101 unreadable)\n"
                                       "                   prove-many -m <key> [-l <lagrange key>] -c <circuit> -o <dir> <witness>...   (the reference has no such command: one\n"
@@ -655,7 +656,9 @@ static int run(int argc, char **argv) {
             if (i < 2 || argv[i][0] == '-') { av.push_back(argv[i]); if (i >= 2 && i + 1 < argc) av.push_back(argv[++i]); }
             else files.push_back(argv[i]);
         }
-        Args a = parse((int)av.size(), av.data(), {{"v", "verification_key|vk"}});
+        Args a = parse((int)av.size(), av.data(), {{"v", "verification_key|vk"}, {"", "front"}});
+        const std::string front = a.get("front", "host");            // --front device: parse, transcript and scalars in a kernel (plk_verify_many_packed)
+        if (front != "host" && front != "device") { fprintf(stderr, "error: --front takes host or device\n"); return 2; }
         if (files.empty()) { fprintf(stderr, "error: The following required argument was not provided: <proof>...\n"); return 2; }
         const std::vector<uint8_t> vkb = slurp(a.get("verification_key", "vk.bin"), "read vk file err");
         std::vector<std::vector<uint8_t>> proofs;
@@ -669,7 +672,12 @@ static int run(int argc, char **argv) {
         for (const auto &p : proofs) { ptrs.push_back(p.empty() ? &none : p.data()); lens.push_back(p.size()); }
         std::vector<uint8_t> verdict(proofs.size());
         uint64_t first_bad = 0;
-        CK("fail to verify proofs", plk_verify_many(ctx, vk, ptrs.data(), lens.data(), proofs.size(), verdict.data(), &first_bad));
+        if (front == "device") {
+            std::vector<uint8_t> blob; std::vector<uint64_t> off(1, 0);
+            for (const auto &p : proofs) { blob.insert(blob.end(), p.begin(), p.end()); off.push_back(blob.size()); }
+            CK("fail to verify proofs", plk_verify_many_packed(ctx, vk, blob.empty() ? &none : blob.data(), blob.size(), off.data(), proofs.size(), verdict.data(), &first_bad));
+        } else
+            CK("fail to verify proofs", plk_verify_many(ctx, vk, ptrs.data(), lens.data(), proofs.size(), verdict.data(), &first_bad));
         for (size_t i = 0; i < files.size(); i++) printf("%s: %s\n", files[i].c_str(), verdict[i] == 1 ? "valid" : verdict[i] == 0 ? "invalid" : "malformed");
         if (first_bad != UINT64_MAX) return 400 & 0xff;
     } else if (cmd == "verify") {                                    // src/bin/main.rs:425-437 (no GPU involved)

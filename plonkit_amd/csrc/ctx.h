@@ -133,8 +133,11 @@ struct plk_ctx {
     bool ev_on = false;                      // record the per-slot event bracket around msm_accumulate
     float r1cs_ms[4] = {0, 0, 0, 0};         // r1cs_check.hip: kernel times of the last witness check (recorded while ev_on)
     bool r1cs_ms_valid = false;
-    float vm_ms[6] = {0, 0, 0, 0, 0, 0};     // verify_many.hip: host flattening, upload, the three kernels, download of the last plk_verify_many (recorded while ev_on)
+    float vm_ms[6] = {0, 0, 0, 0, 0, 0};     // verify_many.hip: host flattening (or the front kernel), upload, the three kernels, download of the last plk_verify_many / _packed (recorded while ev_on)
     bool vm_ms_valid = false;
+    plk::DevBuf vm_stage;                    // plk_verify_many_dev's working memory.  NOT `stage`: that call returns without waiting, and every user of
+                                             // `stage` relies on the earlier ones having waited (some write it on a stream the caller chooses)
+    hipEvent_t vm_in = nullptr, vm_done = nullptr;   // plk_verify_many_dev on a caller's stream: its kernels run on `stream`, which alone touches vm_stage, between these two
     plk::DevBuf pair_tab;                    // verify_many.hip: line table of the G2 pair plk_pairing_check_many_dev saw last
     uint8_t pair_g2[256] = {};
     bool pair_tab_valid = false;

@@ -301,6 +301,15 @@ void parsed_vk_points(const ParsedVk *v, plk_g1_affine fixed[VERIFY_FIXED], host
     memcpy(&fixed[11], &G, 64);
     g2[0] = k.g2[0]; g2[1] = k.g2[1];
 }
+void parsed_vk_front(const ParsedVk *v, uint64_t *n, uint64_t *num_inputs, plk_fr non_residues[3], plk_fr *omega) {
+    const Vk &k = vk_of(v);
+    *n = k.n; *num_inputs = k.num_inputs;
+    for (int j = 0; j < 3; j++) memcpy(&non_residues[j], &k.non_residues[j], 32);
+    const uint64_t N = k.n + 1;
+    HFr om = HFr::zero();                                             // a size that flatten_keccak refuses has no omega, and none is asked for
+    if (!(N < 2 || (N & (N - 1)) || N > (1ull << 28))) { uint32_t log_n = 0; while ((1ull << log_n) < N) log_n++; om = omega_of(log_n); }
+    memcpy(omega, &om, 32);
+}
 int32_t verify_terms_parsed(const ParsedVk *v, const uint8_t *proof, uint64_t len, uint32_t flags, plk_g1_affine points[VERIFY_TERMS],
                             plk_fr scalars[VERIFY_TERMS], int32_t *early) {
     ProofData pr;

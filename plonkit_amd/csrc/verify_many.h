@@ -13,6 +13,8 @@ ParsedVk *parsed_vk_new(const uint8_t *vk, uint64_t len);           // null: plk
 void parsed_vk_free(ParsedVk *v);
 // the 12 points that are the same for every proof (terms 0..10 and 22 of plk_verify_terms) and the key's G2 pair
 void parsed_vk_points(const ParsedVk *v, plk_g1_affine fixed[VERIFY_FIXED], host::G2Affine g2[2]);
+// what the device front end (verify_front_dev.h FrontVk) takes from the key: n, the input count, the non-residues and omega of the domain n + 1
+void parsed_vk_front(const ParsedVk *v, uint64_t *n, uint64_t *num_inputs, plk_fr non_residues[3], plk_fr *omega);
 // plk_verify_terms on a parsed key; PLK_ERR_ARG "plk_verify: malformed proof" exactly when plk_verify_ex says so
 int32_t verify_terms_parsed(const ParsedVk *v, const uint8_t *proof, uint64_t len, uint32_t flags, plk_g1_affine points[VERIFY_TERMS],
                             plk_fr scalars[VERIFY_TERMS], int32_t *early);

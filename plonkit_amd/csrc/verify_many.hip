@@ -3,6 +3,9 @@
 // plk_verify_ex says about proof i.  There is no random linear combination across proofs and no shared pairing.
 //
 // Host, per proof, on up to 16 threads: parse, transcript, the scalar checks, and the flattened scalars of verify.cpp (plk_verify_terms).
+// plk_verify_many_packed / plk_verify_many_dev / plk_verify_front_dev run that front end on the device instead, from the raw bytes
+// (vm_front_kernel, verify_front.hip): every proof of a pass then goes through the kernels below, a proof the front end settled as all-zero
+// terms, and vm_settle_kernel writes its verdict from the state byte.
 // Device, for the proofs that pass that:
 //   vm_mul_kernel      one (proof, term) per lane, 25 terms per proof: the GLV double-and-add of g1_mul_dev.h with four effectively affine
 //                      table entries (g1_mul_scalar_iso: 72 KB of LDS per 256 lanes, two workgroups per CU)
@@ -18,6 +21,7 @@
 #include "fq12_dev.h"
 #include "pairing_table.h"
 #include "verify_many.h"
+#include "verify_front.h"
 #include "circuit.h"
 #include <atomic>
 #include <chrono>
@@ -124,8 +128,8 @@ struct plk_vk {
     int device = 0;
     uint32_t flags = 0;
     ParsedVk *parsed = nullptr;
-    void *dev = nullptr;                                           // [PairingHead | lines | 12 fixed points]
-    size_t fixed_off = 0;
+    void *dev = nullptr;                                           // [PairingHead | lines | 12 fixed points | FrontVk]
+    size_t fixed_off = 0, front_off = 0;
 };
 
 extern "C" void plk_vk_free(plk_vk *vk) {
@@ -147,10 +151,21 @@ extern "C" int32_t plk_vk_load(plk_ctx *ctx, const uint8_t *vk_bytes, uint64_t l
     PairingHead head; std::vector<Fq> lines;
     make_pairing_table(g2, &head, &lines);
     vk->fixed_off = table_bytes(head.lines);
-    std::vector<uint8_t> img(vk->fixed_off + sizeof fixed);
+    vk->front_off = vk->fixed_off + sizeof fixed;
+    static_assert(sizeof fixed % 16 == 0 && sizeof(FrontVk) % 16 == 0, "FrontVk behind the fixed points must stay 16-byte aligned");
+    FrontVk front;                                                 // what vm_front_kernel needs from the key: sizes, flags, non-residues, omega
+    memset(&front, 0, sizeof front);
+    {
+        plk_fr nr[3], om;
+        parsed_vk_front(parsed, &front.n, &front.num_inputs, nr, &om);
+        front.flags = flags;
+        memcpy(front.non_residues, nr, sizeof nr); memcpy(&front.omega, &om, sizeof om);
+    }
+    std::vector<uint8_t> img(vk->front_off + sizeof front);
     memcpy(img.data(), &head, sizeof head);
     memcpy(img.data() + sizeof head, lines.data(), lines.size() * sizeof(Fq));
     memcpy(img.data() + vk->fixed_off, fixed, sizeof fixed);
+    memcpy(img.data() + vk->front_off, &front, sizeof front);
     int32_t rc = [&]() -> int32_t {
         PLK_HIP(hipSetDevice(ctx->device));
         PLK_HIP(hipMalloc(&vk->dev, img.size()));
@@ -287,6 +302,176 @@ extern "C" int32_t plk_verify_many(plk_ctx *ctx, const plk_vk *vk, const uint8_t
     if (rc != PLK_OK) return rc;
     for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
     return PLK_OK;
+}
+
+// ---- the front end on the device: proofs as raw bytes, packed back to back
+// One pass of cnt <= VM_CHUNK proofs whose bytes and offsets are on the device: the front kernel, then the kernels of plk_verify_many over ALL
+// cnt proofs (a settled proof is 25 zero terms: its sums are the identity), then the verdicts settled from the state bytes into `out`.
+struct VmArena {
+    G1Affine *pts; Fr *sc; XyzzW *prod; G1Xyzz *sum; G1Affine *aff; uint8_t *v, *state; char *tail;
+    static size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+    static size_t bytes(size_t m) {
+        return m * VM_PROOF_PTS * sizeof(G1Affine) + m * VERIFY_TERMS * sizeof(Fr) + m * VERIFY_TERMS * sizeof(XyzzW) + m * 2 * sizeof(G1Xyzz) + m * 2 * sizeof(G1Affine) + 2 * pad16(m);
+    }
+    VmArena(char *d, size_t m) {
+        pts = reinterpret_cast<G1Affine *>(d); d += m * VM_PROOF_PTS * sizeof(G1Affine);
+        sc = reinterpret_cast<Fr *>(d); d += m * VERIFY_TERMS * sizeof(Fr);
+        prod = reinterpret_cast<XyzzW *>(d); d += m * VERIFY_TERMS * sizeof(XyzzW);
+        sum = reinterpret_cast<G1Xyzz *>(d); d += m * 2 * sizeof(G1Xyzz);
+        aff = reinterpret_cast<G1Affine *>(d); d += m * 2 * sizeof(G1Affine);
+        v = reinterpret_cast<uint8_t *>(d); d += pad16(m);
+        state = reinterpret_cast<uint8_t *>(d); d += pad16(m);
+        tail = d;
+    }
+};
+
+template <class Mark>
+static int32_t vm_pass_from_bytes(const plk_vk *vk, const VmArena &A, const uint8_t *d_blob, uint64_t blob_len, const uint64_t *d_off, uint64_t bias, uint32_t cnt,
+                                  uint8_t *d_out, hipStream_t st, Mark mark) {
+    static std::atomic<bool> attr_set{false};
+    if (!attr_set) {
+        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vm_mul_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
+        attr_set = true;
+    }
+    const G1Affine *d_fixed = reinterpret_cast<const G1Affine *>(reinterpret_cast<const char *>(vk->dev) + vk->fixed_off);
+    const FrontVk *d_front = reinterpret_cast<const FrontVk *>(reinterpret_cast<const char *>(vk->dev) + vk->front_off);
+    PLK_TRY(front_launch(A.pts, A.sc, A.state, d_blob, blob_len, d_off, bias, cnt, d_front, d_fixed, false, st));
+    PLK_TRY(mark(2));
+    const uint32_t lanes = cnt * (uint32_t)VERIFY_TERMS;
+    hipLaunchKernelGGL(vm_mul_kernel, dim3((lanes + G1NTT_THREADS - 1) / G1NTT_THREADS), dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, A.prod, d_fixed, (const G1Affine *)A.pts,
+                       (const Fr *)A.sc, cnt);
+    PLK_HIP(hipGetLastError());
+    PLK_TRY(mark(3));
+    hipLaunchKernelGGL(vm_sum_kernel, dim3((2 * cnt + 255) / 256), dim3(256), 0, st, A.sum, (const XyzzW *)A.prod, cnt);
+    hipLaunchKernelGGL(vm_affine_kernel, dim3(((2 * cnt + VM_NORM_K - 1) / VM_NORM_K + 255) / 256), dim3(256), 0, st, A.aff, (const G1Xyzz *)A.sum, 2 * cnt);
+    PLK_HIP(hipGetLastError());
+    PLK_TRY(mark(4));
+    PLK_TRY(pairing_launch(A.v, A.aff, A.aff + 1, 2, cnt, vk->dev, st));
+    PLK_TRY(settle_launch(d_out, A.v, A.state, cnt, st));
+    return mark(5);
+}
+
+static int32_t verify_packed_impl(plk_ctx *ctx, const plk_vk *vk, const uint8_t *blob, const uint64_t *off, uint64_t count, uint8_t *verdict) {
+    const bool timed = ctx->ev_on;
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 7; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+    ctx->vm_ms_valid = false;
+    float ms[6] = {0, 0, 0, 0, 0, 0};
+    hipStream_t st = ctx->stream;
+    if (timed) for (int k = 0; k < 7; k++) PLK_HIP(hipEventCreate(&ev[k]));
+    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], st)); return PLK_OK; };
+    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
+        const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
+        const uint64_t lo = off[base], bytes = off[base + cnt] - lo;
+        // the arena of plk_verify_many, then the state bytes, the pass's cnt + 1 offsets and its raw bytes
+        const size_t b_off = VmArena::pad16(((size_t)cnt + 1) * sizeof(uint64_t));
+        PLK_TRY(ctx->stage.reserve(VmArena::bytes(cnt) + b_off + VmArena::pad16(bytes)));
+        const VmArena A(ctx->stage.as<char>(), cnt);
+        uint64_t *d_off = reinterpret_cast<uint64_t *>(A.tail);
+        uint8_t *d_blob = reinterpret_cast<uint8_t *>(A.tail + b_off);
+        PLK_TRY(mark(0));
+        PLK_HIP(hipMemcpyAsync(d_off, off + base, ((size_t)cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (bytes) PLK_HIP(hipMemcpyAsync(d_blob, blob + lo, bytes, hipMemcpyHostToDevice, st));
+        PLK_TRY(mark(1));
+        PLK_TRY(vm_pass_from_bytes(vk, A, d_blob, bytes, d_off, lo, cnt, A.v, st, mark));
+        PLK_HIP(hipMemcpyAsync(verdict + base, A.v, cnt, hipMemcpyDeviceToHost, st));
+        PLK_TRY(mark(6));
+        PLK_HIP(hipStreamSynchronize(st));
+        if (timed) {
+            static const int slot[6] = {1, 0, 2, 3, 4, 5};            // upload, front kernel, mul, sum + affine, pairing + settle, download
+            for (int k = 0; k < 6; k++) { float t = 0; PLK_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1])); ms[slot[k]] += t; }
+        }
+    }
+    if (timed) { memcpy(ctx->vm_ms, ms, sizeof ms); ctx->vm_ms_valid = true; }
+    return PLK_OK;
+}
+
+// the refusals the three calls share with plk_verify_many
+static int32_t vm_bytes_guard(const char *who, plk_ctx *ctx, const plk_vk *vk) {
+    if (vk->device != ctx->device) { set_error(std::string(who) + ": the verification key was loaded on another device"); return PLK_ERR_ARG; }
+    if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
+    return PLK_OK;
+}
+
+static int32_t verify_many_packed_body(plk_ctx *ctx, const plk_vk *vk, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, uint64_t count, uint8_t *verdict,
+                                          uint64_t *first_bad) {
+    if (!ctx || !vk || !verdict || !first_bad || (count && !off) || (blob_len && !blob)) { set_error("plk_verify_many_packed: null argument"); return PLK_ERR_ARG; }
+    PLK_TRY(vm_bytes_guard("plk_verify_many_packed", ctx, vk));
+    for (uint64_t i = 0; i < count; i++)
+        if (off[i] > off[i + 1] || off[i + 1] > blob_len) { set_error("plk_verify_many_packed: offsets decrease or reach past the blob"); return PLK_ERR_ARG; }
+    *first_bad = UINT64_MAX;
+    if (count == 0) return PLK_OK;
+    PLK_HIP(hipSetDevice(ctx->device));
+    PLK_TRY(verify_packed_impl(ctx, vk, blob, off, count, verdict));
+    for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
+    return PLK_OK;
+}
+
+extern "C" int32_t plk_verify_many_packed(plk_ctx *ctx, const plk_vk *vk, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, uint64_t count, uint8_t *verdict,
+                                          uint64_t *first_bad) {
+    try { return verify_many_packed_body(ctx, vk, blob, blob_len, off, count, verdict, first_bad); }   // no C++ exception crosses the C ABI, as plk_verify_many
+    catch (const std::exception &e) { set_error(std::string("plk_verify_many_packed: ") + e.what()); return PLK_ERR_ARG; }
+}
+
+static int32_t verify_many_dev_body(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *verdict_dev,
+                                       void *stream) {
+    if (!ctx || !vk || (count && (!off_dev || !verdict_dev)) || (blob_len && !blob_dev)) { set_error("plk_verify_many_dev: null argument"); return PLK_ERR_ARG; }
+    if ((uintptr_t)off_dev & 7) { set_error("plk_verify_many_dev: the offset table must be 8-byte aligned"); return PLK_ERR_ARG; }
+    PLK_TRY(vm_bytes_guard("plk_verify_many_dev", ctx, vk));
+    if (count == 0) return PLK_OK;
+    PLK_HIP(hipSetDevice(ctx->device));
+    ctx->vm_ms_valid = false;
+    // This call returns without waiting, so it keeps out of the staging arena, whose users each rely on the earlier ones having waited (and
+    // some write it on a stream of the caller's choice).  Its working memory is vm_stage, which only kernels on the context's stream touch:
+    // they run there after what the caller's stream holds now, the caller's stream goes on after them, and a second call queues behind the
+    // first.  Growing vm_stage frees the old block, which waits for the device.
+    hipStream_t st = ctx->stream, caller = stream ? (hipStream_t)stream : ctx->stream;
+    PLK_TRY(ctx->vm_stage.reserve(VmArena::bytes(count < VM_CHUNK ? (size_t)count : (size_t)VM_CHUNK)));
+    if (caller != st) {
+        if (!ctx->vm_in) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_in, hipEventDisableTiming));
+        if (!ctx->vm_done) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_done, hipEventDisableTiming));
+        PLK_HIP(hipEventRecord(ctx->vm_in, caller));
+        PLK_HIP(hipStreamWaitEvent(st, ctx->vm_in, 0));
+    }
+    auto mark = [](int) -> int32_t { return PLK_OK; };
+    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
+        const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
+        const VmArena A(ctx->vm_stage.as<char>(), cnt);
+        PLK_TRY(vm_pass_from_bytes(vk, A, reinterpret_cast<const uint8_t *>(blob_dev), blob_len, reinterpret_cast<const uint64_t *>(off_dev) + base, 0, cnt,
+                                   reinterpret_cast<uint8_t *>(verdict_dev) + base, st, mark));
+    }
+    if (caller != st) {
+        PLK_HIP(hipEventRecord(ctx->vm_done, st));
+        PLK_HIP(hipStreamWaitEvent(caller, ctx->vm_done, 0));
+    }
+    return PLK_OK;
+}
+
+extern "C" int32_t plk_verify_many_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *verdict_dev,
+                                       void *stream) {
+    try { return verify_many_dev_body(ctx, vk, blob_dev, blob_len, off_dev, count, verdict_dev, stream); }   // no C++ exception crosses the C ABI, as plk_verify_many
+    catch (const std::exception &e) { set_error(std::string("plk_verify_many_dev: ") + e.what()); return PLK_ERR_ARG; }
+}
+
+static int32_t verify_front_dev_body(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *points_dev,
+                                        void *scalars_dev, void *state_dev, void *stream) {
+    if (!ctx || !vk || (count && (!off_dev || !points_dev || !scalars_dev || !state_dev)) || (blob_len && !blob_dev)) { set_error("plk_verify_front_dev: null argument"); return PLK_ERR_ARG; }
+    if (((uintptr_t)off_dev & 7) || (((uintptr_t)points_dev | (uintptr_t)scalars_dev) & 15)) { set_error("plk_verify_front_dev: points and scalars must be 16-byte aligned, offsets 8-byte aligned"); return PLK_ERR_ARG; }
+    if (count > (1ull << 26)) { set_error("plk_verify_front_dev: more than 2^26 proofs"); return PLK_ERR_SIZE; }
+    PLK_TRY(vm_bytes_guard("plk_verify_front_dev", ctx, vk));
+    if (count == 0) return PLK_OK;
+    PLK_HIP(hipSetDevice(ctx->device));
+    const G1Affine *d_fixed = reinterpret_cast<const G1Affine *>(reinterpret_cast<const char *>(vk->dev) + vk->fixed_off);
+    const FrontVk *d_front = reinterpret_cast<const FrontVk *>(reinterpret_cast<const char *>(vk->dev) + vk->front_off);
+    return front_launch(reinterpret_cast<G1Affine *>(points_dev), reinterpret_cast<Fr *>(scalars_dev), reinterpret_cast<uint8_t *>(state_dev),
+                        reinterpret_cast<const uint8_t *>(blob_dev), blob_len, reinterpret_cast<const uint64_t *>(off_dev), 0, (uint32_t)count, d_front, d_fixed, true,
+                        stream ? (hipStream_t)stream : ctx->stream);
+}
+
+extern "C" int32_t plk_verify_front_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *points_dev,
+                                        void *scalars_dev, void *state_dev, void *stream) {
+    try { return verify_front_dev_body(ctx, vk, blob_dev, blob_len, off_dev, count, points_dev, scalars_dev, state_dev, stream); }   // no C++ exception crosses the C ABI, as plk_verify_many
+    catch (const std::exception &e) { set_error(std::string("plk_verify_front_dev: ") + e.what()); return PLK_ERR_ARG; }
 }
 
 extern "C" int32_t plk_verify_many_last_ms(plk_ctx *ctx, float out_ms[6]) {
