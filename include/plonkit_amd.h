@@ -344,6 +344,74 @@ int32_t plk_srs_check(plk_ctx *ctx, const uint8_t g2[256], const uint8_t seed[32
                       uint32_t flags, int32_t *valid, uint64_t *bad_out /* may be NULL */);
 int32_t plk_srs_lagrange_check(plk_ctx *ctx, const uint8_t seed[32] /* NULL: OS randomness */, int32_t *valid);
 
+/* ---- contributing a secret to a key, with a receipt anyone can check.  NO COUNTERPART IN THE REFERENCE: `plonkit setup` makes the key of the
+ *      public tau = 42 (src/plonk.rs:30-48, "development only"), and a downloaded key is read and trusted (src/reader.rs:67-89).  The step of an
+ *      updatable SRS is the third option: take any valid key of some tau, multiply tau by a secret s, throw s away.  The new key is sound for a
+ *      user who is sure that the old tau OR their own s is unknown.
+ *
+ *      plk_srs_update.  The resident monomial points P_0 .. P_{n-1} (global indexes first .. first + n - 1: a rank's slice, as
+ *      plk_srs_generate(n, start, ..)) become P'_i = s^(first + i) P_i: one GLV scalar multiplication per point on the device, the scalar formed
+ *      in the lane from a two-level table of s that is zeroed before the call returns; infinity stays infinity.  g2_new = {Q_0, s Q_1} and
+ *      receipt = S1 || S2 with S1 = s G1 (64 bytes), S2 = s Q_0 (128 bytes), in the key file's encodings, are computed on the host.
+ *      s: Montgomery form, 0 < s < r (else PLK_ERR_ARG); NULL: 32 bytes from the OS (getrandom), reduced mod r, drawn again while zero —
+ *      that s exists nowhere once the call returns (every host copy is wiped with explicit_bzero).  Ranks that update slices of one key
+ *      must use ONE s: rank 0 draws it, or every rank passes the same.
+ *      Checked before anything is computed, with nothing changed on refusal: first + n <= 2^28 (the table's reach; PLK_ERR_SIZE, checked
+ *      before s and the G2 section are looked at); the G2 section as plk_srs_check checks it (on the twist, not infinity, [r]Q = O; PLK_ERR_ARG); the key is not lent to
+ *      another context (plk_ctx_share_srs) and no commitment is in flight (PLK_ERR_ARG).  PLK_ERR_SRS: no key resident.
+ *      The result is written to a new buffer that becomes the context's OWN key after the last chunk succeeded — also when the old key was a
+ *      borrowed one or the caller's device memory (plk_srs_set_dev), which is never written.  On success the MSM table of the old key is void
+ *      and the Lagrange-form slot is cleared (the old Lagrange-form key no longer belongs).  On any failure the key, its table, the Lagrange
+ *      slot, any loan, g2_new and receipt are what they were.  Device memory of the call: the new key, an XYZZ scratch of at most 512 MiB, 1 MiB.
+ *
+ *      plk_srs_update_receipt.  The host half on its own (no device): g2_new and receipt for a given s.  A rank that updates a slice with the
+ *      s rank 0 drew uses it.  s == NULL is PLK_ERR_ARG here.
+ *
+ *      plk_srs_update_verify.  The NEW key resident, whole prefix (first = 0); old_p01 = P_0, P_1 of the old key (P_1 is not read for a
+ *      one-point key).  *valid = 1 exactly when, in this order (*reason = the first rule that failed, PLK_UPDATE_*):
+ *        - both G2 sections are sound as plk_srs_check wants them                                     PLK_UPDATE_BAD_G2
+ *        - Q_0 is unchanged                                                                           PLK_UPDATE_Q0_CHANGED
+ *        - P'_0 = P_0, on the curve and not infinity                                                  PLK_UPDATE_P0_CHANGED
+ *        - S1 decodes, is on the curve and not infinity                                               PLK_UPDATE_BAD_S1
+ *        - S2 decodes, is on the twist, in the subgroup and not infinity                              PLK_UPDATE_BAD_S2
+ *        - e(S1, Q_0) = e(P_0, S2): S1 and S2 hold the same s                                         PLK_UPDATE_RECEIPT_SPLIT
+ *        - e(P'_1, Q_0) = e(P_1, S2): the G1 side moved by s (skipped for a one-point key)            PLK_UPDATE_P1_MISMATCH
+ *        - e(P_0, Q'_1) = e(S1, Q_1): the G2 side moved by s                                          PLK_UPDATE_Q1_MISMATCH
+ *        - plk_srs_check(new key, g2_new, seed) accepts (its error bound, its seed convention)        PLK_UPDATE_KEY_STRUCTURE
+ *      The products go through the pairing of plk_verify.  WHAT THIS PROVES: the new key is a key of tau' = s tau for the s committed in
+ *      S1 / S2, and s != 0 — given that the OLD key was a valid key of tau (check it with plk_srs_check).  WHAT IT DOES NOT: it is no proof
+ *      of knowledge of s, and gives nothing against an adaptive last contributor beyond that.  The call only reads (as plk_srs_check).
+ *      A G2 section that is out of range or not on the twist is PLK_ERR_ARG with plk_srs_check's words; PLK_ERR_ARG also for null pointers
+ *      and a context that holds a slice; PLK_ERR_SRS: no key resident.  Every other wrong input is a verdict (PLK_OK, *valid = 0).
+ *
+ *      plk_srs_update_check_receipt.  The host half of the verification (no device): every rule but the last, given P'_0 and P'_1.
+ *      points = 1 for a one-point key (the [1] entries are not read), else 2.                                                               */
+enum {
+    PLK_UPDATE_OK = 0,
+    PLK_UPDATE_BAD_G2 = 1,
+    PLK_UPDATE_Q0_CHANGED = 2,
+    PLK_UPDATE_P0_CHANGED = 3,
+    PLK_UPDATE_BAD_S1 = 4,
+    PLK_UPDATE_BAD_S2 = 5,
+    PLK_UPDATE_RECEIPT_SPLIT = 6,
+    PLK_UPDATE_P1_MISMATCH = 7,
+    PLK_UPDATE_Q1_MISMATCH = 8,
+    PLK_UPDATE_KEY_STRUCTURE = 9
+};
+int32_t plk_srs_update(plk_ctx *ctx, const plk_fr *s /* Montgomery; NULL: 32 bytes from the OS, reduced, redrawn while zero */,
+                       uint64_t first, const uint8_t g2_old[256], uint8_t g2_new[256], uint8_t receipt[192]);
+/* tracing hook: HIP-event time, milliseconds, of the device work of the last successful plk_srs_update on this context (table of s, the
+ * multiplications and the affine pass of every chunk; not the allocations, not the host's G2 arithmetic).  Recorded only while
+ * plk_set_kernel_timing is on; PLK_ERR_ARG otherwise.  No counterpart in the reference.                                                  */
+int32_t plk_srs_update_last_ms(plk_ctx *ctx, float *out_ms);
+int32_t plk_srs_update_receipt(const plk_fr *s, const uint8_t g2_old[256], uint8_t g2_new[256], uint8_t receipt[192]);
+int32_t plk_srs_update_verify(plk_ctx *ctx /* NEW key resident, whole prefix, first = 0 */, const plk_g1_affine old_p01[2],
+                              const uint8_t g2_old[256], const uint8_t g2_new[256], const uint8_t receipt[192],
+                              const uint8_t seed[32] /* NULL: OS randomness */, int32_t *valid, uint32_t *reason /* may be NULL */);
+int32_t plk_srs_update_check_receipt(const plk_g1_affine old_p01[2], const plk_g1_affine new_p01[2], uint32_t points,
+                                     const uint8_t g2_old[256], const uint8_t g2_new[256], const uint8_t receipt[192],
+                                     int32_t *valid, uint32_t *reason /* may be NULL */);
+
 /* ---- RollingKeccakTranscript (src/plonk.rs:10,140,152; spec contrib/template.sol:267-307) ---- */
 typedef struct { uint8_t state0[32], state1[32]; uint32_t counter; } plk_transcript;
 void plk_transcript_init(plk_transcript *t);

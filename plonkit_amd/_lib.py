@@ -359,6 +359,36 @@ class Context:
         _check(lib().plk_srs_lagrange_check(self._h, self._seed(seed), ctypes.byref(valid)))
         return bool(valid.value)
 
+    # ---- contributing a secret to the key (srs_update.hip; the reference has no counterpart)
+    def srs_update(self, g2, s=None, first=0):
+        """resident points P_i (global indexes first + i) <- s^(first + i) P_i, the step of an updatable SRS.  `g2`: the 256 bytes of the
+        key's G2 section; `s`: 4 x uint64 Montgomery Fr, None: drawn from the OS inside the call and gone when it returns.  Returns
+        (g2_new, receipt): the new G2 section and the 192 bytes S1 || S2 that srs_update_verify checks."""
+        g2 = bytes(g2)
+        if len(g2) != 256:
+            raise ValueError("g2 must be the 256 bytes of a key file's G2 section, got %d" % len(g2))
+        sv = np.ascontiguousarray(s, dtype=np.uint64).reshape(4) if s is not None else None
+        g2_new, receipt = ctypes.create_string_buffer(256), ctypes.create_string_buffer(192)
+        _check(lib().plk_srs_update(self._h, _np(sv) if sv is not None else None, ctypes.c_uint64(first), g2, g2_new, receipt))
+        return g2_new.raw, receipt.raw
+
+    def srs_update_last_ms(self):
+        """HIP-event time of the device work of the last srs_update on the context (set_kernel_timing on)"""
+        v = ctypes.c_float(0)
+        _check(lib().plk_srs_update_last_ms(self._h, ctypes.byref(v)))
+        return v.value
+
+    def srs_update_verify(self, old_p01, g2_old, g2_new, receipt, seed=None):
+        """is the resident key (whole prefix) the key of `old_p01` (its points 0 and 1, [2, 8] uint64; [1, 8] for a one-point key) and
+        `g2_old`, updated by the s committed in `receipt`?  Returns (valid, reason): reason is one of UPDATE_REASONS, "ok" when valid."""
+        p = np.zeros((2, 8), dtype=np.uint64)
+        o = np.ascontiguousarray(old_p01, dtype=np.uint64).reshape(-1, 8)
+        p[:min(2, o.shape[0])] = o[:2]
+        g2_old, g2_new, receipt = _update_bytes(g2_old, g2_new, receipt)
+        valid, reason = ctypes.c_int32(0), ctypes.c_uint32(0)
+        _check(lib().plk_srs_update_verify(self._h, _np(p), g2_old, g2_new, receipt, self._seed(seed), ctypes.byref(valid), ctypes.byref(reason)))
+        return bool(valid.value), UPDATE_REASONS[reason.value]
+
     def set_kernel_timing(self, on=True):
         _check(lib().plk_set_kernel_timing(self._h, ctypes.c_int32(1 if on else 0)))
 
@@ -955,6 +985,40 @@ def pairing_check(a, g2_a, b, g2_b):
     a = np.ascontiguousarray(a, dtype=np.uint64); b = np.ascontiguousarray(b, dtype=np.uint64)
     _check(lib().plk_pairing_check(_np(a), bytes(g2_a), _np(b), bytes(g2_b), ctypes.byref(out)))
     return bool(out.value)
+
+
+UPDATE_REASONS = ("ok", "bad_g2", "q0_changed", "p0_changed", "bad_s1", "bad_s2", "receipt_split", "p1_mismatch", "q1_mismatch",
+                  "key_structure")                                  # PLK_UPDATE_*
+
+
+def _update_bytes(g2_old, g2_new, receipt):
+    g2_old, g2_new, receipt = bytes(g2_old), bytes(g2_new), bytes(receipt)
+    if len(g2_old) != 256 or len(g2_new) != 256 or len(receipt) != 192:
+        raise ValueError("a G2 section is 256 bytes and a receipt 192, got %d, %d and %d" % (len(g2_old), len(g2_new), len(receipt)))
+    return g2_old, g2_new, receipt
+
+
+def srs_update_receipt(s, g2_old):
+    """the host half of Context.srs_update for a given s (4 x uint64 Montgomery Fr): (g2_new, receipt).  Pure CPU."""
+    g2_old = bytes(g2_old)
+    if len(g2_old) != 256:
+        raise ValueError("g2_old must be the 256 bytes of a key file's G2 section, got %d" % len(g2_old))
+    sv = np.ascontiguousarray(s, dtype=np.uint64).reshape(4) if s is not None else None
+    g2_new, receipt = ctypes.create_string_buffer(256), ctypes.create_string_buffer(192)
+    _check(lib().plk_srs_update_receipt(_np(sv) if sv is not None else None, g2_old, g2_new, receipt))
+    return g2_new.raw, receipt.raw
+
+
+def srs_update_check_receipt(old_p01, new_p01, g2_old, g2_new, receipt):
+    """the host half of Context.srs_update_verify: every rule but the key's own structure check, given points 0 and 1 of the old and
+    of the new key ([2, 8] uint64 each; [1, 8] for a one-point key).  Returns (valid, reason).  Pure CPU."""
+    o = np.ascontiguousarray(old_p01, dtype=np.uint64).reshape(-1, 8)
+    n = np.ascontiguousarray(new_p01, dtype=np.uint64).reshape(-1, 8)
+    points = min(2, o.shape[0], n.shape[0])
+    g2_old, g2_new, receipt = _update_bytes(g2_old, g2_new, receipt)
+    valid, reason = ctypes.c_int32(0), ctypes.c_uint32(0)
+    _check(lib().plk_srs_update_check_receipt(_np(o), _np(n), ctypes.c_uint32(points), g2_old, g2_new, receipt, ctypes.byref(valid), ctypes.byref(reason)))
+    return bool(valid.value), UPDATE_REASONS[reason.value]
 
 
 def crs42_g2_bytes():

@@ -285,6 +285,11 @@ static int run(int argc, char **argv) {
     if (argc < 2) { fprintf(stderr, "plonkit (MI355X) — subcommands: analyse setup dump-lagrange prove export-verification-key verify\n"
                                       "                   check-key -m <key> [-l <lagrange key>] [--locate]   (the reference has no such command: is the key tau^i * G for the\n"
                                       "                   tau of its G2 section, does the Lagrange-form key belong to it; exit 0 ok, 2 a key is refused, 101 unreadable)\n"
+                                      "                   contribute -m <key> -o <new key> -r <receipt file> [--overwrite]   (the reference has no such command: the key is\n"
+                                      "                   checked as by check-key, then every point is multiplied by a power of a secret the OS provides and nobody keeps;\n"
+                                      "                   exit 0 written, 2 the input key is refused, 101 unreadable)\n"
+                                      "                   check-contribution -m <old key> -n <new key> -r <receipt file>   (is the new key the old one updated by the secret\n"
+                                      "                   the receipt commits to; exit 0 ok, 2 refused with the reason on one line, 101 unreadable)\n"
                                       "                   verify-many -v <vk> <proof>...   (the reference has no such command: every proof of one verification key checked\n"
                                       "                   exactly and on its own, on the GPU; one line per proof, <path>: valid | invalid | malformed; exit 0 all valid,\n"
                                       "                   144 otherwise as verify, 101 key unreadable; --front device: the bytes are parsed, hashed\n"
@@ -554,6 +559,51 @@ static int run(int argc, char **argv) {
             refused |= !valid;
         }
         if (refused) return 2;
+    } else if (cmd == "contribute") {
+        // NOT in the reference's CLI (src/bin/main.rs:27-53), which can only make the key of tau = 42 or read someone else's: plk_srs_update with an s that
+        // comes from the OS inside the library and exists nowhere afterwards (no option takes or prints it).  Updating a broken key yields a broken key, so
+        // the input goes through plk_srs_check first.
+        Args a = parse(argc, argv, {{"m", "srs_monomial_form"}, {"o", "output"}, {"r", "receipt"}});
+        const std::string key_path = a.get("srs_monomial_form"), out = a.get("output"), rcpt = a.get("receipt");
+        refuse_duplicate(a, out, "output");
+        refuse_duplicate(a, rcpt, "receipt");
+        plk_ctx *ctx = open_ctx();
+        uint8_t g2[256], g2_new[256], receipt[192];
+        load_key(ctx, key_path, g2);
+        int32_t valid = 0;
+        CK("check key_monomial_form", plk_srs_check(ctx, g2, nullptr, 0, &valid, nullptr));
+        if (!valid) { printf("%s: INVALID, not contributing to it\n", key_path.c_str()); return 2; }
+        CK("contribute", plk_srs_update(ctx, nullptr, 0, g2, g2_new, receipt));
+        uint64_t len = 0;
+        CK("serialize", plk_srs_store_key(ctx, 0, g2_new, nullptr, 0, &len));
+        std::vector<uint8_t> bytes(len);
+        CK("serialize", plk_srs_store_key(ctx, 0, g2_new, bytes.data(), len, &len));
+        spit(out, bytes.data(), len);
+        spit(rcpt, receipt, sizeof receipt);
+        fprintf(stderr, "srs_monomial_form saved to %s, receipt to %s\n", out.c_str(), rcpt.c_str());
+    } else if (cmd == "check-contribution") {
+        // NOT in the reference's CLI either: plk_srs_update_verify of the new key against points 0 and 1 and the G2 section of the old one
+        Args a = parse(argc, argv, {{"m", "srs_monomial_form"}, {"n", "new_srs_monomial_form"}, {"r", "receipt"}});
+        const std::string old_path = a.get("srs_monomial_form"), new_path = a.get("new_srs_monomial_form"), rcpt = a.get("receipt");
+        ParsedKey old_key;
+        parse_key(old_path, false, &old_key);
+        plk_g1_affine p01[2] = {};
+        for (uint64_t i = 0; i < 2 && i < old_key.n; i++) CK("read key_monomial_form err", plk_g1_from_bytes(old_key.raw.data() + 8 + 64 * i, &p01[i]));
+        const std::vector<uint8_t> receipt = slurp(rcpt, "read receipt err");
+        if (receipt.size() != 192) fatal(101, "read receipt err: " + rcpt + " holds " + std::to_string(receipt.size()) + " bytes, a receipt has 192");
+        plk_ctx *ctx = open_ctx();
+        uint8_t g2_new[256];
+        load_key(ctx, new_path, g2_new);
+        if (plk_srs_size(ctx) != old_key.n) { printf("%s: INVALID, %llu points where the old key has %llu\n", new_path.c_str(), (unsigned long long)plk_srs_size(ctx), (unsigned long long)old_key.n); return 2; }
+        int32_t valid = 0;
+        uint32_t reason = 0;
+        CK("check contribution", plk_srs_update_verify(ctx, p01, old_key.g2, g2_new, receipt.data(), nullptr, &valid, &reason));
+        static const char *const why[] = {"ok", "a G2 section holds infinity or a point outside the subgroup", "Q_0 changed", "point 0 changed (or is infinity)",
+                                          "S1 of the receipt is not a curve point, or infinity", "S2 of the receipt is not a subgroup point of the twist, or infinity",
+                                          "S1 and S2 of the receipt hold different secrets", "point 1 is not the old one times the receipt's secret",
+                                          "the G2 section is not the old one times the receipt's secret", "the new key is not the powers of the tau in its G2 section"};
+        if (!valid) { printf("%s: INVALID, %s\n", new_path.c_str(), reason < sizeof why / sizeof why[0] ? why[reason] : "unknown reason"); return 2; }
+        printf("%s: ok, %s updated by the secret of %s\n", new_path.c_str(), old_path.c_str(), rcpt.c_str());
     } else if (cmd == "check-witness") {
         // NOT in the reference's CLI (src/bin/main.rs:27-53): SetupForProver::validate_witness (src/plonk.rs:127-129) is only reachable from Rust, and it
         // checks bellman's gates.  This is plk_r1cs_check_witness on the constraints of the .r1cs themselves: no key, no setup, no transpiler.

@@ -133,6 +133,8 @@ struct plk_ctx {
     bool ev_on = false;                      // record the per-slot event bracket around msm_accumulate
     float r1cs_ms[4] = {0, 0, 0, 0};         // r1cs_check.hip: kernel times of the last witness check (recorded while ev_on)
     bool r1cs_ms_valid = false;
+    float update_ms = 0;                     // srs_update.hip: the kernels of the last plk_srs_update, table fill to last chunk (recorded while ev_on)
+    bool update_ms_valid = false;
     float vm_ms[6] = {0, 0, 0, 0, 0, 0};     // verify_many.hip: host flattening (or the front kernel), upload, the three kernels, download of the last plk_verify_many / _packed (recorded while ev_on)
     bool vm_ms_valid = false;
     plk::DevBuf vm_stage;                    // plk_verify_many_dev's working memory.  NOT `stage`: that call returns without waiting, and every user of

@@ -13,6 +13,7 @@
 #include "poly.h"
 #include "field29_dev.h"
 #include "pairing.h"
+#include "g2_host.h"
 #include "keccak.h"
 #include <cerrno>
 #include <cstring>
@@ -60,42 +61,7 @@ int32_t derive_rho(const char *tag, const uint8_t *seed, HFr *rho) {
     }
 }
 
-// Jacobian arithmetic on the twist y^2 = x^3 + 3 / xi over Fq2 (the formulas of hostmath.h's jac_double / jac_add; a = 0), for the one
-// thing the pairing code does not do: [r]Q = O.  Infinity is z = 0.  The twist has odd order, so a doubling never meets y = 0.
-struct G2Jac { Fq2 x, y, z; };
-Fq2 twice(const Fq2 &a) { return a + a; }
-G2Jac g2_double(const G2Jac &p) {
-    if (p.z.is_zero()) return p;
-    const Fq2 A = p.x.sqr(), B = p.y.sqr(), C = B.sqr();
-    const Fq2 D = twice((p.x + B).sqr() - A - C), E = twice(A) + A;
-    G2Jac r;
-    r.x = E.sqr() - twice(D);
-    r.z = twice(p.y * p.z);
-    r.y = E * (D - r.x) - twice(twice(twice(C)));
-    return r;
-}
-G2Jac g2_add(const G2Jac &p, const G2Jac &q) {
-    if (q.z.is_zero()) return p;
-    if (p.z.is_zero()) return q;
-    const Fq2 z1z1 = p.z.sqr(), z2z2 = q.z.sqr();
-    const Fq2 u1 = p.x * z2z2, u2 = q.x * z1z1, s1 = p.y * q.z * z2z2, s2 = q.y * p.z * z1z1;
-    if (u1 == u2) return (s1 == s2) ? g2_double(p) : G2Jac{Fq2::one(), Fq2::one(), Fq2::zero()};
-    const Fq2 h = u2 - u1, i = twice(h).sqr(), j = h * i, rr = twice(s2 - s1), v = u1 * i;
-    G2Jac r;
-    r.x = rr.sqr() - j - twice(v);
-    r.y = rr * (v - r.x) - twice(s1 * j);
-    r.z = ((p.z + q.z).sqr() - z1z1 - z2z2) * h;
-    return r;
-}
-bool g2_in_subgroup(const G2Affine &q) {                        // q on the twist and not infinity
-    const G2Jac base{q.x, q.y, Fq2::one()};
-    G2Jac acc{Fq2::one(), Fq2::one(), Fq2::zero()};
-    for (int i = 253; i >= 0; i--) {                            // r < 2^254
-        acc = g2_double(acc);
-        if ((FrP::P[i >> 6] >> (i & 63)) & 1) acc = g2_add(acc, base);
-    }
-    return acc.z.is_zero();
-}
+// (the twist arithmetic of the two [r]Q = O checks: g2_host.h)
 
 int32_t fetch_point(plk_ctx *ctx, uint64_t i, HAffine *p) {
     plk_g1_affine a;

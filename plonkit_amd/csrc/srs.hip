@@ -8,6 +8,7 @@
 #include "ctx.h"
 #include "ec_dev.h"
 #include "ec29_dev.h"
+#include "srs.h"
 #include <cstring>
 #include <cstdlib>
 
@@ -15,7 +16,6 @@ namespace plk {
 
 constexpr uint32_t SRS_RUN = 16;                 // the direct kernel (used when the commitment scratch is busy)
 constexpr uint32_t SRS_RUN_XYZZ = 16, SRS_NORM_K = 8;
-constexpr uint64_t SRS_CHUNK = 1ull << 22;       // points per pass through the XYZZ scratch (512 MiB)
 
 __device__ __forceinline__ G1Affine xyzz_to_affine_dev(const G1Xyzz &p) {
     G1Affine a;
@@ -98,6 +98,13 @@ __global__ void __launch_bounds__(256) srs_to_affine_kernel(G1Affine *out, const
     }
 }
 
+int32_t srs_to_affine(G1Affine *out, const G1Xyzz *in, uint64_t n, hipStream_t s) {
+    const uint64_t nthreads = (n + SRS_NORM_K - 1) / SRS_NORM_K;
+    hipLaunchKernelGGL(srs_to_affine_kernel, dim3((uint32_t)((nthreads + 255) / 256)), dim3(256), 0, s, out, in, n);
+    PLK_HIP(hipGetLastError());
+    return PLK_OK;
+}
+
 // general tau (any field element): one full double-and-add per point, no run sharing — 16x the work of the small-tau kernel,
 // still a fraction of a second at 2^20 points
 __global__ void __launch_bounds__(256) srs_powers_general_kernel(G1Affine *out, uint64_t start, uint64_t n, Fr tau) {
@@ -148,9 +155,9 @@ extern "C" int32_t plk_srs_generate(plk_ctx *ctx, uint64_t n, uint64_t start, ui
         G1Xyzz *tmp = ctx->slot[0].e.as<G1Xyzz>();
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t len = n - off < chunk ? n - off : chunk;
-            const uint64_t threads = (len + SRS_RUN_XYZZ - 1) / SRS_RUN_XYZZ, nthreads = (len + SRS_NORM_K - 1) / SRS_NORM_K;
+            const uint64_t threads = (len + SRS_RUN_XYZZ - 1) / SRS_RUN_XYZZ;
             hipLaunchKernelGGL(srs_powers_xyzz_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, ctx->stream, tmp, start + off, len, from_u64<FrParams>(tau), tau);
-            hipLaunchKernelGGL(srs_to_affine_kernel, dim3((uint32_t)((nthreads + 255) / 256)), dim3(256), 0, ctx->stream, ctx->srs_own.as<G1Affine>() + off, (const G1Xyzz *)tmp, len);
+            PLK_TRY(srs_to_affine(ctx->srs_own.as<G1Affine>() + off, tmp, len, ctx->stream));
         }
     } else {
         uint64_t threads = (n + SRS_RUN - 1) / SRS_RUN;
