@@ -518,6 +518,53 @@ int32_t plk_verify_many_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev
 int32_t plk_verify_front_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *points_dev, void *scalars_dev,
                              void *state_dev, void *stream);
 
+/* ---- a mixed batch: proofs of several verification keys in one pass, on the GPU (verify_many.hip).  NO COUNTERPART IN THE REFERENCE: plonk::verify
+ *      (src/plonk.rs:189-210) takes one key and one proof.  A verifying service sees one key per circuit, usually all made from one universal
+ *      key; a plk_verify_many call per key pays the ~90 ms floor of a call (one lane's pairing chain) once per key while most of the chip
+ *      idles.  These calls take the key PER PROOF and keep the exactness contract of the calls above: verdict i is what plk_verify_ex says about
+ *      proof i under key key_of[i], with that key's flags.  No random linear combination across proofs, no shared pairing, no regrouping by
+ *      key; lanes of one wave may hold different keys and the order of key_of does not matter.
+ *
+ *   plk_vkset_create.  Key k of the set is keys[k] (1 .. PLK_VKSET_MAX_KEYS keys of the context's device).  n_keys == 0 or above the maximum,
+ *                a null pointer, a key of another device: PLK_ERR_ARG.  Each key keeps the flags it was loaded with.  The set owns ONE device
+ *                allocation — per key the 160 bytes the front kernel needs, its 12 fixed G1 points and the index of its line table; then the
+ *                DISTINCT line tables at one stride (two keys share a table exactly when their 256 G2 bytes are equal; the tables are rebuilt
+ *                as plk_vk_load builds them) — and copies of the parsed keys, so the plk_vk objects may be freed afterwards.  Read-only after
+ *                creation: usable from several contexts of its device, like plk_vk.  No counterpart in the reference.
+ *   plk_vkset_keys, plk_vkset_tables.  The number of keys, and of distinct G2 pairs among them (diagnostic, like plk_msm_last_shape: 1 is
+ *                the common case, keys of one universal key).  0 for a null set.
+ *   plk_verify_mixed.  plk_verify_many with proof i checked under key key_of[i]: the host front end on up to 16 threads, the survivors packed
+ *                WITH their key indices, then vm_mul_mixed_kernel (terms 0..10 and 22 from the lane's key), plk_verify_many's sum and
+ *                normalisation kernels unchanged, and the pairing: with one table in the set plk_verify_many's own kernel on that table
+ *                (wave-uniform line loads); with several, vm_pairing_mixed_kernel, where every lane walks the table of its key.  Blocks.
+ *                verdict[i] and *first_bad as plk_verify_many.  A key_of[i] >= the set's key count: PLK_ERR_ARG before anything is launched.
+ *                Null arguments, count == 0, a commitment in flight, passes of 2^16 proofs and the staging arena as plk_verify_many (the arena
+ *                holds 4 more bytes per proof).  plk_verify_many_last_ms keeps its slots.  No counterpart in the reference.
+ *   plk_verify_mixed_packed.  plk_verify_many_packed likewise: the front end on the device (vm_front_mixed_kernel: the lane's FrontVk through
+ *                its key index), the offset-table rules of plk_verify_many_packed, and the key-index rule of plk_verify_mixed.  Blocks.
+ *                MEASURED (one MI355X, profiles/verify_mixed_ab.txt): one call over four keys of one G2 pair, interleaved, against four
+ *                plk_verify_many_packed calls, at 4 x 64 / 4 x 1024 / 4 x 16384 proofs: 91.0 / 92.9 / 151.7 ms against 362.5 / 365.2 / 393.1 ms.
+ *                With four G2 pairs (vm_pairing_mixed_kernel, per-lane line loads): 91.3 / 92.9 / 152.0 ms — no measurable cost.
+ *                No counterpart in the reference.
+ *   plk_verify_mixed_dev.  plk_verify_many_dev likewise: blob, offsets (8-byte aligned), key indices (uint32_t, 4-byte aligned) and verdict
+ *                bytes in DEVICE memory, ordered on `stream`, nothing waits.  The call cannot look at the indices: a proof whose key index is
+ *                out of range gets PLK_VERDICT_MALFORMED, nothing of it (not even its offset pair) is read, and its neighbours are unaffected —
+ *                the rule of a bad offset pair, which holds here too.  Memory and order as plk_verify_many_dev: the same buffer of its own, the
+ *                context's stream between two events; a second call queues behind the first, and behind a plk_verify_many_dev.
+ *                No counterpart in the reference.                                                                                            */
+typedef struct plk_vkset plk_vkset;
+#define PLK_VKSET_MAX_KEYS 1024u
+int32_t plk_vkset_create(plk_ctx *ctx, const plk_vk *const *keys, uint32_t n_keys, plk_vkset **out);
+void plk_vkset_free(plk_vkset *set);
+uint32_t plk_vkset_keys(const plk_vkset *set);
+uint32_t plk_vkset_tables(const plk_vkset *set);
+int32_t plk_verify_mixed(plk_ctx *ctx, const plk_vkset *set, const uint8_t *const *proofs, const uint64_t *lens, const uint32_t *key_of, uint64_t count, uint8_t *verdict,
+                         uint64_t *first_bad);
+int32_t plk_verify_mixed_packed(plk_ctx *ctx, const plk_vkset *set, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, const uint32_t *key_of, uint64_t count,
+                                uint8_t *verdict, uint64_t *first_bad);
+int32_t plk_verify_mixed_dev(plk_ctx *ctx, const plk_vkset *set, const void *blob_dev, uint64_t blob_len, const void *off_dev, const void *key_of_dev, uint64_t count,
+                             void *verdict_dev, void *stream);
+
 /* ---- circuit pipeline: circom loaders + transpile + setup + prove ----------------------------
  * plk_circuit mirrors CircomCircuit{r1cs, witness, wire_mapping: None, aux_offset: 1}
  * (src/circom_circuit.rs:41-47).  Loaders follow src/reader.rs:178-241, src/r1cs_file.rs:100-154

@@ -52,6 +52,9 @@ def lib():
         L.plk_r1cs_num_constraints.restype = ctypes.c_uint64
         L.plk_r1cs_num_variables.restype = ctypes.c_uint64
         L.plk_r1cs_long_lc_terms.restype = ctypes.c_uint32
+        L.plk_vkset_keys.restype = ctypes.c_uint32
+        L.plk_vkset_tables.restype = ctypes.c_uint32
+        L.plk_vkset_keys.argtypes = L.plk_vkset_tables.argtypes = L.plk_vkset_free.argtypes = [ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -959,6 +962,111 @@ class VerificationKey:
     def close(self):
         if self._h:
             lib().plk_vk_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VerificationKeySet:
+    """plk_vkset: several verification keys resident on the GPU of `ctx` as one image (plk_vkset_create); the verify_many* calls take a key
+    index per proof and answer for each proof exactly as `verify` does under that key.  `keys`: VerificationKey objects (which keep their
+    strict_inputs flag and may be closed afterwards) or vk bytes (loaded as VerificationKey(ctx, bytes) would)."""
+
+    def __init__(self, ctx, keys):
+        self._h = ctypes.c_void_p()
+        self.ctx = ctx
+        self.first_bad = None
+        keys = list(keys)
+        own = []
+        try:
+            loaded = []
+            for k in keys:
+                if not isinstance(k, VerificationKey):
+                    k = VerificationKey(ctx, k)
+                    own.append(k)
+                loaded.append(k)
+            arr = (ctypes.c_void_p * max(len(loaded), 1))(*[k._h.value for k in loaded])
+            _check(lib().plk_vkset_create(ctx._h, arr, ctypes.c_uint32(len(loaded)), ctypes.byref(self._h)))
+        finally:
+            for k in own:
+                k.close()
+
+    @property
+    def keys(self):
+        return int(lib().plk_vkset_keys(self._h))
+
+    @property
+    def tables(self):
+        """distinct G2 pairs among the keys (1: the single-key pairing kernel serves the whole set)"""
+        return int(lib().plk_vkset_tables(self._h))
+
+    @staticmethod
+    def _key_of(key_of, n, who):
+        k = np.asarray(key_of)
+        if k.ndim != 1 or k.size != n or (k.size and (k.dtype.kind not in "iu" or k.min() < 0 or k.max() > 0xffffffff)):
+            raise ValueError("%s: key_of must hold one index in [0, 2^32) per proof" % who)
+        return np.ascontiguousarray(k, dtype=np.uint32)
+
+    def verify_many(self, proofs, key_of, ctx=None):
+        """plk_verify_mixed: numpy uint8 per proof (1 valid, 0 invalid, 2 malformed) under key key_of[i]; .first_bad as VerificationKey.
+        An index that is not a key of the set raises PlkError (PLK_ERR_ARG)"""
+        proofs = [bytes(p) for p in proofs]
+        n = len(proofs)
+        keys = self._key_of(key_of, n, "verify_many")
+        ptrs = (ctypes.c_char_p * max(n, 1))(*proofs)
+        lens = (ctypes.c_uint64 * max(n, 1))(*[len(p) for p in proofs])
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        first_bad = ctypes.c_uint64(0)
+        _check(lib().plk_verify_mixed((ctx or self.ctx)._h, self._h, ptrs, lens, _np(keys), ctypes.c_uint64(n), _np(verdict), ctypes.byref(first_bad)))
+        self.first_bad = None if first_bad.value == 2 ** 64 - 1 else int(first_bad.value)
+        return verdict[:n]
+
+    def verify_many_packed(self, blob, offsets, key_of, ctx=None):
+        """plk_verify_mixed_packed: proof i = blob[offsets[i]:offsets[i + 1]] under key key_of[i]; the front end runs on the GPU"""
+        blob = bytes(blob)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("verify_many_packed: offsets must hold count + 1 entries")
+        n = off.size - 1
+        keys = self._key_of(key_of, n, "verify_many_packed")
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        first_bad = ctypes.c_uint64(0)
+        _check(lib().plk_verify_mixed_packed((ctx or self.ctx)._h, self._h, blob, ctypes.c_uint64(len(blob)), _np(off), _np(keys), ctypes.c_uint64(n), _np(verdict),
+                                             ctypes.byref(first_bad)))
+        self.first_bad = None if first_bad.value == 2 ** 64 - 1 else int(first_bad.value)
+        return verdict[:n]
+
+    def verify_many_dev(self, blob_tensor, offsets_tensor, key_of_tensor, stream=None, ctx=None):
+        """plk_verify_mixed_dev: blob (uint8), offsets (64-bit integers, count + 1 entries) and key indices (32-bit integers, count entries)
+        are torch tensors on the set's GPU; returns a uint8 tensor of verdicts there, ordered on `stream` — nothing passes through the host
+        and nothing waits.  A key index out of range, like a bad offset pair, gives that proof verdict 2"""
+        import torch
+        if (blob_tensor.dtype != torch.uint8 or offsets_tensor.element_size() != 8 or key_of_tensor.element_size() != 4 or key_of_tensor.is_floating_point()
+                or offsets_tensor.is_floating_point() or not blob_tensor.is_contiguous() or not offsets_tensor.is_contiguous() or not key_of_tensor.is_contiguous()):
+            raise ValueError("verify_many_dev: blob must be a contiguous uint8 tensor, offsets a contiguous 64-bit and key_of a contiguous 32-bit integer tensor")
+        dev = (ctx or self.ctx).device
+        for t in (blob_tensor, offsets_tensor, key_of_tensor):          # a host pointer must not reach the kernel
+            if not t.is_cuda or t.device.index != dev:
+                raise ValueError("verify_many_dev: blob, offsets and key_of must be tensors on cuda:%d, the device of the set's context" % dev)
+        n = offsets_tensor.numel() - 1
+        if n < 0 or key_of_tensor.numel() != n:
+            raise ValueError("verify_many_dev: offsets must hold count + 1 entries and key_of count")
+        if stream is not None and hasattr(stream, "cuda_stream"):
+            with torch.cuda.stream(stream):                           # the verdict tensor belongs to the stream that fills it
+                verdict = torch.empty(n, dtype=torch.uint8, device=blob_tensor.device)
+        else:
+            verdict = torch.empty(n, dtype=torch.uint8, device=blob_tensor.device)
+        _check(lib().plk_verify_mixed_dev((ctx or self.ctx)._h, self._h, _devptr(blob_tensor), ctypes.c_uint64(blob_tensor.numel()), _devptr(offsets_tensor),
+                                          _devptr(key_of_tensor), ctypes.c_uint64(n), _devptr(verdict), _stream(stream)))
+        return verdict
+
+    def close(self):
+        if self._h:
+            lib().plk_vkset_free(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

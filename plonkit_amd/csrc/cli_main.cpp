@@ -1,7 +1,8 @@
 // `plonkit` command line over the C ABI — the five prover commands of the reference's CLI
 // (src/bin/main.rs:27-53): setup, dump-lagrange, prove, export-verification-key, analyse, verify — and two the reference does not
 // have: check-key (the structure checks of include/plonkit_amd.h on a key file), check-witness (a witness against its R1CS),
-// prove-many (one key, one circuit, one setup, a proof per witness file) and verify-many (one verification key, a verdict per proof file).
+// prove-many (one key, one circuit, one setup, a proof per witness file), verify-many (one verification key, a verdict per proof file) and
+// verify-mixed (the same over several verification keys, each proof under the key named before it).
 // Same option names, short flags and defaults (src/bin/main.rs:55-136,176-190), same refusal to overwrite
 // (src/bin/main.rs:336-339,374-377,403-406) and the circuit-file default rule (src/bin/main.rs:346-357).
 // Everything arithmetic goes through include/plonkit_amd.h.
@@ -294,6 +295,9 @@ static int run(int argc, char **argv) {
                                       "                   exactly and on its own, on the GPU; one line per proof, <path>: valid | invalid | malformed; exit 0 all valid,\n"
                                       "                   144 otherwise as verify, 101 key unreadable; --front device: the bytes are parsed, hashed\n"
                                       "                   and flattened in a kernel instead of on host threads, same lines, same exit codes)\n"
+                                      "                   verify-mixed [--front host|device] -v <vk> <proof>... [-v <vk> <proof>...]...   (the reference has no such command:\n"
+                                      "                   proofs of several verification keys in one pass on the GPU, each -v naming the key of the proofs that follow\n"
+                                      "                   it; lines and exit codes as verify-many, 2 for a proof before the first -v)\n"
                                       "                   check-witness -c <circuit> -w <witness>   (the reference has no such command: does the witness satisfy every\n"
                                       "                   constraint of the R1CS, and if not which is the first that fails; no key, no setup; exit 0 ok, 2 refused, 101 unreadable)\n"
                                       "                   prove-many -m <key> [-l <lagrange key>] -c <circuit> -o <dir> <witness>...   (the reference has no such command: one\n"
@@ -728,6 +732,59 @@ static int run(int argc, char **argv) {
             CK("fail to verify proofs", plk_verify_many_packed(ctx, vk, blob.empty() ? &none : blob.data(), blob.size(), off.data(), proofs.size(), verdict.data(), &first_bad));
         } else
             CK("fail to verify proofs", plk_verify_many(ctx, vk, ptrs.data(), lens.data(), proofs.size(), verdict.data(), &first_bad));
+        for (size_t i = 0; i < files.size(); i++) printf("%s: %s\n", files[i].c_str(), verdict[i] == 1 ? "valid" : verdict[i] == 0 ? "invalid" : "malformed");
+        if (first_bad != UINT64_MAX) return 400 & 0xff;
+    } else if (cmd == "verify-mixed") {
+        // NOT in the reference's CLI (src/bin/main.rs:27-53): plk_vkset_create + plk_verify_mixed; every -v names the key of the proofs up to the next -v
+        std::string front = "host";
+        std::vector<std::string> vk_paths, files;
+        std::vector<uint32_t> key_of;
+        bool have_key = false;
+        uint32_t cur = 0;
+        for (int i = 2; i < argc; i++) {
+            const std::string arg = argv[i];
+            const bool is_v = arg == "-v" || arg == "--verification_key" || arg == "--vk";
+            if (is_v || arg == "--front") {
+                if (i + 1 >= argc) { fprintf(stderr, "error: %s needs a value\n", arg.c_str()); return 2; }
+                const std::string val = argv[++i];
+                if (!is_v) { front = val; continue; }
+                cur = 0;
+                while (cur < vk_paths.size() && vk_paths[cur] != val) cur++;       // a key named twice is loaded once
+                if (cur == vk_paths.size()) vk_paths.push_back(val);
+                have_key = true;
+            } else if (arg.size() > 1 && arg[0] == '-') {
+                fprintf(stderr, "error: Found argument '%s' which wasn't expected\n", arg.c_str()); return 2;
+            } else {
+                if (!have_key) { fprintf(stderr, "error: the proof %s comes before the first -v <vk>\n", arg.c_str()); return 2; }
+                files.push_back(arg); key_of.push_back(cur);
+            }
+        }
+        if (front != "host" && front != "device") { fprintf(stderr, "error: --front takes host or device\n"); return 2; }
+        if (files.empty()) { fprintf(stderr, "error: The following required argument was not provided: <proof>...\n"); return 2; }
+        if (vk_paths.size() > PLK_VKSET_MAX_KEYS) { fprintf(stderr, "error: more than %u verification keys\n", PLK_VKSET_MAX_KEYS); return 2; }
+        std::vector<std::vector<uint8_t>> vkb, proofs;
+        for (const std::string &f : vk_paths) vkb.push_back(slurp(f, "read vk file err"));
+        for (const std::string &f : files) proofs.push_back(slurp(f, "read proof file err"));
+        plk_ctx *ctx = open_ctx();
+        const char *strict = getenv("PLK_VERIFY_STRICT_INPUTS");       // as plk_verify reads it
+        std::vector<plk_vk *> vks(vkb.size(), nullptr);
+        for (size_t k = 0; k < vkb.size(); k++)
+            CK("read vk file err", plk_vk_load(ctx, vkb[k].data(), vkb[k].size(), (strict && strict[0] && strict[0] != '0') ? PLK_VERIFY_STRICT_INPUTS : 0u, &vks[k]));
+        plk_vkset *set = nullptr;
+        CK("fail to verify proofs", plk_vkset_create(ctx, vks.data(), (uint32_t)vks.size(), &set));
+        for (plk_vk *v : vks) plk_vk_free(v);
+        static const uint8_t none = 0;
+        std::vector<uint8_t> verdict(proofs.size());
+        uint64_t first_bad = 0;
+        if (front == "device") {
+            std::vector<uint8_t> blob; std::vector<uint64_t> off(1, 0);
+            for (const auto &p : proofs) { blob.insert(blob.end(), p.begin(), p.end()); off.push_back(blob.size()); }
+            CK("fail to verify proofs", plk_verify_mixed_packed(ctx, set, blob.empty() ? &none : blob.data(), blob.size(), off.data(), key_of.data(), proofs.size(), verdict.data(), &first_bad));
+        } else {
+            std::vector<const uint8_t *> ptrs; std::vector<uint64_t> lens;
+            for (const auto &p : proofs) { ptrs.push_back(p.empty() ? &none : p.data()); lens.push_back(p.size()); }
+            CK("fail to verify proofs", plk_verify_mixed(ctx, set, ptrs.data(), lens.data(), key_of.data(), proofs.size(), verdict.data(), &first_bad));
+        }
         for (size_t i = 0; i < files.size(); i++) printf("%s: %s\n", files[i].c_str(), verdict[i] == 1 ? "valid" : verdict[i] == 0 ? "invalid" : "malformed");
         if (first_bad != UINT64_MAX) return 400 & 0xff;
     } else if (cmd == "verify") {                                    // src/bin/main.rs:425-437 (no GPU involved)

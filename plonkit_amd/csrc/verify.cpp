@@ -292,6 +292,7 @@ ParsedVk *parsed_vk_new(const uint8_t *vk, uint64_t len) {
     return reinterpret_cast<ParsedVk *>(p);
 }
 void parsed_vk_free(ParsedVk *v) { delete reinterpret_cast<Vk *>(v); }
+ParsedVk *parsed_vk_clone(const ParsedVk *v) { return reinterpret_cast<ParsedVk *>(new Vk(vk_of(v))); }
 void parsed_vk_points(const ParsedVk *v, plk_g1_affine fixed[VERIFY_FIXED], host::G2Affine g2[2]) {
     const Vk &k = vk_of(v);
     for (int j = 0; j < 6; j++) memcpy(&fixed[j], &k.selectors[j], 64);

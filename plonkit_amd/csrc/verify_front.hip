@@ -7,9 +7,12 @@
 // writes pts[i * stride .. + stride), sc[i * 25 .. + 25) and state[i] (an ordinary byte store), nothing else.
 // One wave per workgroup, as the pairing kernel: a small batch still spreads over the CUs.  A lane's chain is ~80 permutations and
 // num_inputs + 1 inversions; lanes that settle early idle until their wave ends.
+// vm_front_mixed_kernel is the same lane code for a key set (plk_verify_mixed_packed, plk_verify_mixed_dev): the FrontVk of lane i is that of
+// key key_of[i], through vkset_lookup (vkset_dev.h).
 #include "ctx.h"
 #include "verify_front_dev.h"
 #include "verify_many.h"
+#include "vkset_dev.h"
 
 namespace plk {
 
@@ -42,6 +45,29 @@ __global__ void __launch_bounds__(VF_THREADS) vm_front_kernel(G1Affine *pts, Fr 
     state[i] = (uint8_t)st;
 }
 
+// vm_front_kernel for a key set (plk_verify_mixed*): lane i takes its FrontVk through key_of[i].  The arena layout only (11 points per proof:
+// vm_mul_mixed_kernel fetches the key's points itself).  A key index out of range gives state 2 before off[i] is read.
+__global__ void __launch_bounds__(VF_THREADS) vm_front_mixed_kernel(G1Affine *pts, Fr *sc, uint8_t *state, const uint8_t *blob, uint64_t blob_len, const uint64_t *off,
+                                                                    uint64_t bias, uint32_t count, VksetView set, const uint32_t *key_of) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    G1Affine *p = pts + (size_t)i * FRONT_PTS;
+    Fr *s = sc + (size_t)i * VERIFY_TERMS;
+    uint32_t st = FRONT_MALFORMED;
+    VksetKey key;
+    if (vkset_lookup(set, key_of[i], &key)) {
+        const FrontVk vk = *key.front;
+        const uint64_t lo = off[i], hi = off[i + 1];
+        if (lo >= bias && hi >= lo && hi - bias <= blob_len) st = flatten_front(vk, blob + (lo - bias), blob + (hi - bias), p, s);
+    }
+    if (st != FRONT_GOES_ON) {
+        const Fq zq = Fq::zero(); const Fr zr = Fr::zero();
+        for (uint32_t k = 0; k < (uint32_t)FRONT_PTS; k++) { store_fp(&p[k].x, zq); store_fp(&p[k].y, zq); }
+        for (uint32_t k = 0; k < (uint32_t)VERIFY_TERMS; k++) store_fp(&s[k], zr);
+    }
+    state[i] = (uint8_t)st;
+}
+
 __global__ void __launch_bounds__(256) vm_settle_kernel(uint8_t *verdict, const uint8_t *pairing, const uint8_t *state, uint32_t count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
@@ -53,6 +79,14 @@ int32_t front_launch(G1Affine *pts, Fr *sc, uint8_t *state, const uint8_t *blob,
                      const FrontVk *vk, const G1Affine *fixed, bool full, hipStream_t st) {
     hipLaunchKernelGGL(vm_front_kernel, dim3((count + VF_THREADS - 1) / VF_THREADS), dim3(VF_THREADS), 0, st, pts, sc, state, blob, blob_len, off, bias, count, vk, fixed,
                        full ? 1u : 0u);
+    PLK_HIP(hipGetLastError());
+    return PLK_OK;
+}
+
+int32_t front_mixed_launch(G1Affine *pts, Fr *sc, uint8_t *state, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, uint64_t bias, uint32_t count,
+                           const VksetView &set, const uint32_t *key_of, hipStream_t st) {
+    hipLaunchKernelGGL(vm_front_mixed_kernel, dim3((count + VF_THREADS - 1) / VF_THREADS), dim3(VF_THREADS), 0, st, pts, sc, state, blob, blob_len, off, bias, count, set,
+                       key_of);
     PLK_HIP(hipGetLastError());
     return PLK_OK;
 }

@@ -11,6 +11,7 @@ constexpr int VERIFY_TERMS = 25, VERIFY_TERMS_PG = 23, VERIFY_FIXED = 12;   // p
 struct ParsedVk;                                                   // opaque: verify.cpp's parsed key
 ParsedVk *parsed_vk_new(const uint8_t *vk, uint64_t len);           // null: plk_verify_ex would say "malformed verification key"
 void parsed_vk_free(ParsedVk *v);
+ParsedVk *parsed_vk_clone(const ParsedVk *v);                       // a copy of its own (plk_vkset_create: the set outlives the keys it was made from)
 // the 12 points that are the same for every proof (terms 0..10 and 22 of plk_verify_terms) and the key's G2 pair
 void parsed_vk_points(const ParsedVk *v, plk_g1_affine fixed[VERIFY_FIXED], host::G2Affine g2[2]);
 // what the device front end (verify_front_dev.h FrontVk) takes from the key: n, the input count, the non-residues and omega of the domain n + 1

@@ -13,6 +13,9 @@
 //   vm_affine_kernel   XYZZ -> affine, one inversion per 8 points (as srs_to_affine_kernel); infinity comes out as x = y = 0
 //   vm_pairing_kernel  one proof per lane: f <- f^2 l_0 l_1 over the uploaded line table, then the shortened final exponentiation of
 //                      fq12_dev.h (which decides the same predicate as pairing.cpp's; the argument is written there)
+// A key set (plk_vkset_create, plk_verify_mixed, _packed, _dev; at the end of this file) verifies proofs of several keys in one pass, the key
+// taken per proof: vm_mul_mixed_kernel and vm_pairing_mixed_kernel are the two kernels above with the key's points and line table looked up per
+// lane (vkset_dev.h), vm_front_mixed_kernel (verify_front.hip) likewise; the other kernels serve both.
 #include "ctx.h"
 #include "ec_dev.h"
 #include "ec29_dev.h"
@@ -22,10 +25,13 @@
 #include "pairing_table.h"
 #include "verify_many.h"
 #include "verify_front.h"
+#include "vkset_dev.h"
+#include "g2_host.h"
 #include "circuit.h"
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <memory>
 
 namespace plk {
 
@@ -118,6 +124,42 @@ static int32_t pairing_launch(uint8_t *verdict, const G1Affine *a, const G1Affin
     hipLaunchKernelGGL(vm_pairing_kernel, dim3((n + VM_PAIR_THREADS - 1) / VM_PAIR_THREADS), dim3(VM_PAIR_THREADS), 0, st, verdict, a, b, stride, n, head, lines);
     PLK_HIP(hipGetLastError());
     return PLK_OK;
+}
+
+// ---- a key set (plk_vkset): the same kernels with the key taken per lane through vkset_lookup (vkset_dev.h).  NO COUNTERPART IN THE REFERENCE.
+// vm_mul_kernel's body with terms 0..10 and 22 of proof p taken from key key_of[p].  A key index out of range (plk_verify_mixed_dev only: the
+// front kernel settled that proof as malformed and zeroed its scalars) reads no key and multiplies the identity.
+__global__ void __launch_bounds__(G1NTT_THREADS, 1) vm_mul_mixed_kernel(XyzzW *prod, VksetView set, const uint32_t *key_of, const G1Affine *pts, const Fr *sc, uint32_t m) {
+    extern __shared__ uint32_t g1tab[];
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m * (uint32_t)VERIFY_TERMS) return;
+    const uint32_t p = j / VERIFY_TERMS, t = j % VERIFY_TERMS;
+    VksetKey key;
+    key.fixed = nullptr;                                           // one load site below, as in vm_mul_kernel (the compiler)
+    const bool have = (t < 11 || t == 22) ? vkset_lookup(set, key_of[p], &key) : true;
+    G1Affine a; a.x = Fq::zero(); a.y = Fq::zero();
+    if (have) a = load_affine(vm_term_point(key.fixed, pts, p, t));
+    XyzzW b = xyzzw_identity();
+    if (!is_inf(a)) {
+        b.x = csub_p(w_from_s(unpack<FqW>(a.x))); b.y = csub_p(w_from_s(unpack<FqW>(a.y)));
+        b.zz = w_one<FqW>(); b.zzz = w_one<FqW>();
+    }
+    const Fr k = to_canonical(load_fp(sc + j));
+    store_xyzzw(prod + j, g1_mul_scalar_iso(b, k, g1tab));
+}
+
+// vm_pairing_kernel with head and lines of lane i's key: the lanes of a wave may walk different tables, and q_inf (so the on[] tests of
+// pairing_is_one_from_lines) may differ from lane to lane.  Launched only when the set holds more than one table.
+__global__ void __launch_bounds__(VM_PAIR_THREADS) vm_pairing_mixed_kernel(uint8_t *verdict, const G1Affine *a, const G1Affine *b, uint32_t stride, uint32_t n, VksetView set,
+                                                                           const uint32_t *key_of) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const G1Affine A = load_affine(a + (size_t)i * stride), B = load_affine(b + (size_t)i * stride);
+    uint8_t v = 2;
+    VksetKey key;
+    if (vkset_lookup(set, key_of[i], &key) && fq_on_curve(A.x, A.y) && fq_on_curve(B.x, B.y))
+        v = pairing_is_one_from_lines(A.x, A.y, B.x, B.y, key.head, key.lines) ? 1 : 0;
+    verdict[i] = v;
 }
 
 }  // namespace plk
@@ -479,4 +521,333 @@ extern "C" int32_t plk_verify_many_last_ms(plk_ctx *ctx, float out_ms[6]) {
     if (!ctx->vm_ms_valid) { set_error("plk_verify_many_last_ms: no timed plk_verify_many on this context (plk_set_kernel_timing)"); return PLK_ERR_ARG; }
     for (int k = 0; k < 6; k++) out_ms[k] = ctx->vm_ms[k];
     return PLK_OK;
+}
+
+// ---- a mixed batch: proofs of several verification keys in one pass (plk_vkset_create, plk_verify_mixed, _packed, _dev).
+// NO COUNTERPART IN THE REFERENCE.  Verdict i is what plk_verify_ex says about proof i under key key_of[i]: the calls above with the key taken
+// per proof.  The front kernel, the scalar multiplications and (when the set holds more than one G2 pair) the pairing kernel go through
+// vkset_lookup; the sums, XYZZ -> affine and the settling are the kernels above, unchanged.
+static_assert(VKSET_MAX_KEYS == PLK_VKSET_MAX_KEYS, "vkset_plan.h restates the header's bound");
+
+struct plk_vkset {
+    int device = 0;
+    std::vector<ParsedVk *> parsed;                                // per key, copies of the set's own
+    std::vector<uint32_t> flags;
+    VksetLayout layout;
+    VksetView view;                                                // device pointers into `dev`
+    void *dev = nullptr;                                           // the image of vkset_plan.h
+};
+
+extern "C" void plk_vkset_free(plk_vkset *set) {
+    if (!set) return;
+    if (set->dev) { (void)hipSetDevice(set->device); (void)hipFree(set->dev); }
+    for (ParsedVk *p : set->parsed) parsed_vk_free(p);
+    delete set;
+}
+
+extern "C" uint32_t plk_vkset_keys(const plk_vkset *set) { return set ? set->layout.n_keys : 0; }
+extern "C" uint32_t plk_vkset_tables(const plk_vkset *set) { return set ? set->layout.n_tables : 0; }
+
+static int32_t vkset_create_body(plk_ctx *ctx, const plk_vk *const *keys, uint32_t n_keys, plk_vkset **out) {
+    if (!ctx || !keys || !out) { set_error("plk_vkset_create: null argument"); return PLK_ERR_ARG; }
+    if (n_keys == 0 || n_keys > VKSET_MAX_KEYS) { set_error("plk_vkset_create: a set holds 1 to " + std::to_string(VKSET_MAX_KEYS) + " keys"); return PLK_ERR_ARG; }
+    for (uint32_t k = 0; k < n_keys; k++) {
+        if (!keys[k]) { set_error("plk_vkset_create: null argument"); return PLK_ERR_ARG; }
+        if (keys[k]->device != ctx->device) { set_error("plk_vkset_create: a verification key was loaded on another device"); return PLK_ERR_ARG; }
+    }
+    std::vector<uint8_t> g2((size_t)n_keys * VKSET_G2_BYTES);
+    for (uint32_t k = 0; k < n_keys; k++) {                          // the key's G2 pair in the file encoding, from the parsed key
+        plk_g1_affine fixed[VERIFY_FIXED]; host::G2Affine q[2];
+        parsed_vk_points(keys[k]->parsed, fixed, q);
+        host::g2_to_bytes(q[0], &g2[(size_t)k * VKSET_G2_BYTES]); host::g2_to_bytes(q[1], &g2[(size_t)k * VKSET_G2_BYTES + 128]);
+    }
+    std::vector<uint32_t> table_of, first_key;
+    const uint32_t n_tables = vkset_dedup(g2.data(), n_keys, &table_of, &first_key);
+    // the tables are rebuilt as plk_vk_load built them; the line count does not depend on the pair
+    std::vector<PairingHead> heads(n_tables);
+    std::vector<std::vector<Fq>> lines(n_tables);
+    for (uint32_t t = 0; t < n_tables; t++) {
+        plk_g1_affine fixed[VERIFY_FIXED]; host::G2Affine q[2];
+        parsed_vk_points(keys[first_key[t]]->parsed, fixed, q);
+        make_pairing_table(q, &heads[t], &lines[t]);
+        if (heads[t].lines != heads[0].lines || lines[t].size() != (size_t)heads[0].lines * 8) { set_error("plk_vkset_create: line tables of different lengths"); return PLK_ERR_HIP; }
+    }
+    std::unique_ptr<plk_vkset, void (*)(plk_vkset *)> owner(new plk_vkset, plk_vkset_free);   // freed with its cloned keys on every way out but the last
+    plk_vkset *set = owner.get();
+    set->device = ctx->device;
+    set->layout = vkset_layout(n_keys, n_tables, table_bytes(heads[0].lines));
+    const VksetLayout &L = set->layout;
+    std::vector<uint8_t> img(L.bytes, 0);
+    for (uint32_t k = 0; k < n_keys; k++) {
+        const plk_vk *vk = keys[k];
+        set->parsed.push_back(parsed_vk_clone(vk->parsed));
+        set->flags.push_back(vk->flags);
+        plk_g1_affine fixed[VERIFY_FIXED]; host::G2Affine q[2];
+        parsed_vk_points(vk->parsed, fixed, q);
+        FrontVk front;
+        memset(&front, 0, sizeof front);
+        plk_fr nr[3], om;
+        parsed_vk_front(vk->parsed, &front.n, &front.num_inputs, nr, &om);
+        front.flags = vk->flags;
+        memcpy(front.non_residues, nr, sizeof nr); memcpy(&front.omega, &om, sizeof om);
+        memcpy(img.data() + L.front_off + (size_t)k * VKSET_FRONT_BYTES, &front, sizeof front);
+        memcpy(img.data() + L.fixed_off + (size_t)k * VKSET_FIXED_BYTES, fixed, sizeof fixed);
+        memcpy(img.data() + L.index_off + (size_t)k * sizeof(uint32_t), &table_of[k], sizeof(uint32_t));
+    }
+    for (uint32_t t = 0; t < n_tables; t++) {
+        uint8_t *at = img.data() + L.tables_off + (size_t)t * L.table_stride;
+        memcpy(at, &heads[t], sizeof(PairingHead));
+        memcpy(at + sizeof(PairingHead), lines[t].data(), lines[t].size() * sizeof(Fq));
+    }
+    const int32_t rc = [&]() -> int32_t {
+        PLK_HIP(hipSetDevice(ctx->device));
+        PLK_HIP(hipMalloc(&set->dev, img.size()));
+        PLK_HIP(hipMemcpy(set->dev, img.data(), img.size(), hipMemcpyHostToDevice));
+        return PLK_OK;
+    }();
+    if (rc != PLK_OK) return rc;
+    set->view = vkset_view(set->dev, L);
+    *out = owner.release();
+    return PLK_OK;
+}
+
+extern "C" int32_t plk_vkset_create(plk_ctx *ctx, const plk_vk *const *keys, uint32_t n_keys, plk_vkset **out) {
+    try { return vkset_create_body(ctx, keys, n_keys, out); }        // no C++ exception crosses the C ABI, as plk_verify_many
+    catch (const std::exception &e) { set_error(std::string("plk_vkset_create: ") + e.what()); return PLK_ERR_ARG; }
+}
+
+// the refusals the three calls share, as vm_bytes_guard
+static int32_t vm_mixed_guard(const char *who, plk_ctx *ctx, const plk_vkset *set) {
+    if (set->device != ctx->device) { set_error(std::string(who) + ": the key set was made on another device"); return PLK_ERR_ARG; }
+    if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
+    return PLK_OK;
+}
+
+static int32_t vm_mixed_indices(const char *who, const plk_vkset *set, const uint32_t *key_of, uint64_t count) {
+    uint64_t bad = 0;
+    if (vkset_indices_ok(key_of, count, set->layout.n_keys, &bad)) return PLK_OK;
+    set_error(std::string(who) + ": key_of[" + std::to_string(bad) + "] = " + std::to_string(key_of[bad]) + " but the set holds " + std::to_string(set->layout.n_keys) + " keys");
+    return PLK_ERR_ARG;
+}
+
+// m proofs whose points, scalars and key indices are on the device: products, sums, affine pairs and the pairing verdicts into v.
+// mark(k) after the multiplications, mark(k + 1) after the sums and the normalisation.
+template <class Mark>
+static int32_t vm_mixed_group(const plk_vkset *set, XyzzW *prod, const G1Affine *pts, const Fr *sc, G1Xyzz *sum, G1Affine *aff, uint8_t *v, const uint32_t *d_key, uint32_t m,
+                              hipStream_t st, Mark mark, int k) {
+    static std::atomic<bool> attr_set{false};
+    if (!attr_set) {
+        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vm_mul_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
+        attr_set = true;
+    }
+    const uint32_t lanes = m * (uint32_t)VERIFY_TERMS;
+    hipLaunchKernelGGL(vm_mul_mixed_kernel, dim3((lanes + G1NTT_THREADS - 1) / G1NTT_THREADS), dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, prod, set->view, d_key, pts, sc, m);
+    PLK_HIP(hipGetLastError());
+    PLK_TRY(mark(k));
+    hipLaunchKernelGGL(vm_sum_kernel, dim3((2 * m + 255) / 256), dim3(256), 0, st, sum, (const XyzzW *)prod, m);
+    hipLaunchKernelGGL(vm_affine_kernel, dim3(((2 * m + VM_NORM_K - 1) / VM_NORM_K + 255) / 256), dim3(256), 0, st, aff, (const G1Xyzz *)sum, 2 * m);
+    PLK_HIP(hipGetLastError());
+    PLK_TRY(mark(k + 1));
+    // one G2 pair in the set (the common case: keys of one universal key): the single-key kernel, whose line loads are wave-uniform
+    if (set->layout.n_tables == 1) return pairing_launch(v, aff, aff + 1, 2, m, set->view.tables, st);
+    hipLaunchKernelGGL(vm_pairing_mixed_kernel, dim3((m + VM_PAIR_THREADS - 1) / VM_PAIR_THREADS), dim3(VM_PAIR_THREADS), 0, st, v, (const G1Affine *)aff,
+                       (const G1Affine *)(aff + 1), 2u, m, set->view, d_key);
+    PLK_HIP(hipGetLastError());
+    return PLK_OK;
+}
+
+static int32_t verify_mixed_impl(plk_ctx *ctx, const plk_vkset *set, const uint8_t *const *proofs, const uint64_t *lens, const uint32_t *key_of, uint64_t count,
+                                 uint8_t *verdict) {
+    using clk = std::chrono::steady_clock;
+    const bool timed = ctx->ev_on;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 6; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+    ctx->vm_ms_valid = false;
+    float ms[6] = {0, 0, 0, 0, 0, 0};
+    hipStream_t st = ctx->stream;
+    if (timed) for (int k = 0; k < 6; k++) PLK_HIP(hipEventCreate(&ev[k]));
+    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], st)); return PLK_OK; };
+    std::vector<plk_g1_affine> h_pts;
+    std::vector<plk_fr> h_sc;
+    std::vector<uint64_t> live;
+    std::vector<uint32_t> live_key;
+    std::vector<uint8_t> h_v;
+    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
+        const uint64_t cnt = count - base < VM_CHUNK ? count - base : VM_CHUNK;
+        // host: every proof of the chunk through plk_verify_terms's code under its own key; the survivors are packed in index order with their keys
+        const auto t0 = clk::now();
+        std::vector<plk_g1_affine> all_pts((size_t)cnt * VM_PROOF_PTS);
+        std::vector<plk_fr> all_sc((size_t)cnt * VERIFY_TERMS);
+        parallel_for((size_t)cnt, 1, [&](size_t lo, size_t hi) {
+            plk_g1_affine pts[VERIFY_TERMS]; plk_fr sc[VERIFY_TERMS];
+            for (size_t i = lo; i < hi; i++) {
+                int32_t early = 0;
+                const uint32_t key = key_of[base + i];
+                const int32_t rc = verify_terms_parsed(set->parsed[key], proofs[base + i], lens[base + i], set->flags[key], pts, sc, &early);
+                if (rc != PLK_OK) { verdict[base + i] = PLK_VERDICT_MALFORMED; continue; }
+                if (!early) { verdict[base + i] = 0; continue; }
+                verdict[base + i] = 0xff;                             // goes to the device
+                memcpy(&all_pts[i * VM_PROOF_PTS], &pts[11], VM_PROOF_PTS * sizeof(plk_g1_affine));
+                memcpy(&all_sc[i * VERIFY_TERMS], sc, sizeof sc);
+            }
+        }, 16);
+        vkset_compact(verdict + base, key_of + base, cnt, &live, &live_key);
+        const uint32_t m = (uint32_t)live.size();
+        h_pts.resize((size_t)m * VM_PROOF_PTS); h_sc.resize((size_t)m * VERIFY_TERMS); h_v.resize(m);
+        for (uint32_t k = 0; k < m; k++) {
+            memcpy(&h_pts[(size_t)k * VM_PROOF_PTS], &all_pts[live[k] * VM_PROOF_PTS], VM_PROOF_PTS * sizeof(plk_g1_affine));
+            memcpy(&h_sc[(size_t)k * VERIFY_TERMS], &all_sc[live[k] * VERIFY_TERMS], VERIFY_TERMS * sizeof(plk_fr));
+        }
+        ms[0] += std::chrono::duration<float, std::milli>(clk::now() - t0).count();
+        if (!m) continue;
+        // device: plk_verify_many's arena and, behind it, the survivors' key indices
+        const size_t b_pts = (size_t)m * VM_PROOF_PTS * sizeof(G1Affine), b_sc = (size_t)m * VERIFY_TERMS * sizeof(Fr), b_prod = (size_t)m * VERIFY_TERMS * sizeof(XyzzW),
+                     b_sum = (size_t)m * 2 * sizeof(G1Xyzz), b_aff = (size_t)m * 2 * sizeof(G1Affine), b_v = ((size_t)m + 15) & ~(size_t)15, b_key = (size_t)m * sizeof(uint32_t);
+        PLK_TRY(ctx->stage.reserve(b_pts + b_sc + b_prod + b_sum + b_aff + b_v + b_key));
+        char *d = ctx->stage.as<char>();
+        G1Affine *d_pts = reinterpret_cast<G1Affine *>(d);
+        Fr *d_sc = reinterpret_cast<Fr *>(d + b_pts);
+        XyzzW *d_prod = reinterpret_cast<XyzzW *>(d + b_pts + b_sc);
+        G1Xyzz *d_sum = reinterpret_cast<G1Xyzz *>(d + b_pts + b_sc + b_prod);
+        G1Affine *d_aff = reinterpret_cast<G1Affine *>(d + b_pts + b_sc + b_prod + b_sum);
+        uint8_t *d_v = reinterpret_cast<uint8_t *>(d + b_pts + b_sc + b_prod + b_sum + b_aff);
+        uint32_t *d_key = reinterpret_cast<uint32_t *>(d + b_pts + b_sc + b_prod + b_sum + b_aff + b_v);
+        PLK_TRY(mark(0));
+        PLK_HIP(hipMemcpyAsync(d_pts, h_pts.data(), b_pts, hipMemcpyHostToDevice, st));
+        PLK_HIP(hipMemcpyAsync(d_sc, h_sc.data(), b_sc, hipMemcpyHostToDevice, st));
+        PLK_HIP(hipMemcpyAsync(d_key, live_key.data(), b_key, hipMemcpyHostToDevice, st));
+        PLK_TRY(mark(1));
+        PLK_TRY(vm_mixed_group(set, d_prod, d_pts, d_sc, d_sum, d_aff, d_v, d_key, m, st, mark, 2));
+        PLK_TRY(mark(4));
+        PLK_HIP(hipMemcpyAsync(h_v.data(), d_v, m, hipMemcpyDeviceToHost, st));
+        PLK_TRY(mark(5));
+        PLK_HIP(hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < m; k++) verdict[base + live[k]] = h_v[k];
+        if (timed) for (int k = 0; k < 5; k++) { float t = 0; PLK_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1])); ms[k + 1] += t; }
+    }
+    if (timed) { memcpy(ctx->vm_ms, ms, sizeof ms); ctx->vm_ms_valid = true; }
+    return PLK_OK;
+}
+
+extern "C" int32_t plk_verify_mixed(plk_ctx *ctx, const plk_vkset *set, const uint8_t *const *proofs, const uint64_t *lens, const uint32_t *key_of, uint64_t count,
+                                    uint8_t *verdict, uint64_t *first_bad) {
+    if (!ctx || !set || !verdict || !first_bad || (count && (!proofs || !lens || !key_of))) { set_error("plk_verify_mixed: null argument"); return PLK_ERR_ARG; }
+    for (uint64_t i = 0; i < count; i++) if (!proofs[i]) { set_error("plk_verify_mixed: null argument"); return PLK_ERR_ARG; }
+    PLK_TRY(vm_mixed_guard("plk_verify_mixed", ctx, set));
+    PLK_TRY(vm_mixed_indices("plk_verify_mixed", set, key_of, count));
+    *first_bad = UINT64_MAX;
+    if (count == 0) return PLK_OK;
+    PLK_HIP(hipSetDevice(ctx->device));
+    int32_t rc = PLK_ERR_HIP;
+    try { rc = verify_mixed_impl(ctx, set, proofs, lens, key_of, count, verdict); }
+    catch (const std::exception &e) { set_error(std::string("plk_verify_mixed: ") + e.what()); return PLK_ERR_ARG; }
+    if (rc != PLK_OK) return rc;
+    for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
+    return PLK_OK;
+}
+
+// vm_pass_from_bytes for a key set: d_key holds the pass's cnt key indices
+template <class Mark>
+static int32_t vm_mixed_pass_from_bytes(const plk_vkset *set, const VmArena &A, const uint8_t *d_blob, uint64_t blob_len, const uint64_t *d_off, uint64_t bias,
+                                        const uint32_t *d_key, uint32_t cnt, uint8_t *d_out, hipStream_t st, Mark mark) {
+    PLK_TRY(front_mixed_launch(A.pts, A.sc, A.state, d_blob, blob_len, d_off, bias, cnt, set->view, d_key, st));
+    PLK_TRY(mark(2));
+    PLK_TRY(vm_mixed_group(set, A.prod, A.pts, A.sc, A.sum, A.aff, A.v, d_key, cnt, st, mark, 3));
+    PLK_TRY(settle_launch(d_out, A.v, A.state, cnt, st));
+    return mark(5);
+}
+
+static int32_t verify_mixed_packed_impl(plk_ctx *ctx, const plk_vkset *set, const uint8_t *blob, const uint64_t *off, const uint32_t *key_of, uint64_t count, uint8_t *verdict) {
+    const bool timed = ctx->ev_on;
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 7; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+    ctx->vm_ms_valid = false;
+    float ms[6] = {0, 0, 0, 0, 0, 0};
+    hipStream_t st = ctx->stream;
+    if (timed) for (int k = 0; k < 7; k++) PLK_HIP(hipEventCreate(&ev[k]));
+    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], st)); return PLK_OK; };
+    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
+        const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
+        const uint64_t lo = off[base], bytes = off[base + cnt] - lo;
+        // the arena of plk_verify_many_packed with the pass's cnt key indices between the offsets and the raw bytes
+        const size_t b_off = VmArena::pad16(((size_t)cnt + 1) * sizeof(uint64_t)), b_key = VmArena::pad16((size_t)cnt * sizeof(uint32_t));
+        PLK_TRY(ctx->stage.reserve(VmArena::bytes(cnt) + b_off + b_key + VmArena::pad16(bytes)));
+        const VmArena A(ctx->stage.as<char>(), cnt);
+        uint64_t *d_off = reinterpret_cast<uint64_t *>(A.tail);
+        uint32_t *d_key = reinterpret_cast<uint32_t *>(A.tail + b_off);
+        uint8_t *d_blob = reinterpret_cast<uint8_t *>(A.tail + b_off + b_key);
+        PLK_TRY(mark(0));
+        PLK_HIP(hipMemcpyAsync(d_off, off + base, ((size_t)cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        PLK_HIP(hipMemcpyAsync(d_key, key_of + base, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (bytes) PLK_HIP(hipMemcpyAsync(d_blob, blob + lo, bytes, hipMemcpyHostToDevice, st));
+        PLK_TRY(mark(1));
+        PLK_TRY(vm_mixed_pass_from_bytes(set, A, d_blob, bytes, d_off, lo, d_key, cnt, A.v, st, mark));
+        PLK_HIP(hipMemcpyAsync(verdict + base, A.v, cnt, hipMemcpyDeviceToHost, st));
+        PLK_TRY(mark(6));
+        PLK_HIP(hipStreamSynchronize(st));
+        if (timed) {
+            static const int slot[6] = {1, 0, 2, 3, 4, 5};            // upload, front kernel, mul, sum + affine, pairing + settle, download
+            for (int k = 0; k < 6; k++) { float t = 0; PLK_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1])); ms[slot[k]] += t; }
+        }
+    }
+    if (timed) { memcpy(ctx->vm_ms, ms, sizeof ms); ctx->vm_ms_valid = true; }
+    return PLK_OK;
+}
+
+static int32_t verify_mixed_packed_body(plk_ctx *ctx, const plk_vkset *set, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, const uint32_t *key_of, uint64_t count,
+                                        uint8_t *verdict, uint64_t *first_bad) {
+    if (!ctx || !set || !verdict || !first_bad || (count && (!off || !key_of)) || (blob_len && !blob)) { set_error("plk_verify_mixed_packed: null argument"); return PLK_ERR_ARG; }
+    PLK_TRY(vm_mixed_guard("plk_verify_mixed_packed", ctx, set));
+    for (uint64_t i = 0; i < count; i++)
+        if (off[i] > off[i + 1] || off[i + 1] > blob_len) { set_error("plk_verify_mixed_packed: offsets decrease or reach past the blob"); return PLK_ERR_ARG; }
+    PLK_TRY(vm_mixed_indices("plk_verify_mixed_packed", set, key_of, count));
+    *first_bad = UINT64_MAX;
+    if (count == 0) return PLK_OK;
+    PLK_HIP(hipSetDevice(ctx->device));
+    PLK_TRY(verify_mixed_packed_impl(ctx, set, blob, off, key_of, count, verdict));
+    for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
+    return PLK_OK;
+}
+
+extern "C" int32_t plk_verify_mixed_packed(plk_ctx *ctx, const plk_vkset *set, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, const uint32_t *key_of,
+                                           uint64_t count, uint8_t *verdict, uint64_t *first_bad) {
+    try { return verify_mixed_packed_body(ctx, set, blob, blob_len, off, key_of, count, verdict, first_bad); }   // no C++ exception crosses the C ABI, as plk_verify_many
+    catch (const std::exception &e) { set_error(std::string("plk_verify_mixed_packed: ") + e.what()); return PLK_ERR_ARG; }
+}
+
+static int32_t verify_mixed_dev_body(plk_ctx *ctx, const plk_vkset *set, const void *blob_dev, uint64_t blob_len, const void *off_dev, const void *key_of_dev, uint64_t count,
+                                     void *verdict_dev, void *stream) {
+    if (!ctx || !set || (count && (!off_dev || !key_of_dev || !verdict_dev)) || (blob_len && !blob_dev)) { set_error("plk_verify_mixed_dev: null argument"); return PLK_ERR_ARG; }
+    if (((uintptr_t)off_dev & 7) || ((uintptr_t)key_of_dev & 3)) { set_error("plk_verify_mixed_dev: the offset table must be 8-byte aligned, the key indices 4-byte aligned"); return PLK_ERR_ARG; }
+    PLK_TRY(vm_mixed_guard("plk_verify_mixed_dev", ctx, set));
+    if (count == 0) return PLK_OK;
+    PLK_HIP(hipSetDevice(ctx->device));
+    ctx->vm_ms_valid = false;
+    // memory and order exactly as plk_verify_many_dev: vm_stage, the context's stream, between the two events
+    hipStream_t st = ctx->stream, caller = stream ? (hipStream_t)stream : ctx->stream;
+    PLK_TRY(ctx->vm_stage.reserve(VmArena::bytes(count < VM_CHUNK ? (size_t)count : (size_t)VM_CHUNK)));
+    if (caller != st) {
+        if (!ctx->vm_in) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_in, hipEventDisableTiming));
+        if (!ctx->vm_done) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_done, hipEventDisableTiming));
+        PLK_HIP(hipEventRecord(ctx->vm_in, caller));
+        PLK_HIP(hipStreamWaitEvent(st, ctx->vm_in, 0));
+    }
+    auto mark = [](int) -> int32_t { return PLK_OK; };
+    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
+        const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
+        const VmArena A(ctx->vm_stage.as<char>(), cnt);
+        PLK_TRY(vm_mixed_pass_from_bytes(set, A, reinterpret_cast<const uint8_t *>(blob_dev), blob_len, reinterpret_cast<const uint64_t *>(off_dev) + base, 0,
+                                         reinterpret_cast<const uint32_t *>(key_of_dev) + base, cnt, reinterpret_cast<uint8_t *>(verdict_dev) + base, st, mark));
+    }
+    if (caller != st) {
+        PLK_HIP(hipEventRecord(ctx->vm_done, st));
+        PLK_HIP(hipStreamWaitEvent(caller, ctx->vm_done, 0));
+    }
+    return PLK_OK;
+}
+
+extern "C" int32_t plk_verify_mixed_dev(plk_ctx *ctx, const plk_vkset *set, const void *blob_dev, uint64_t blob_len, const void *off_dev, const void *key_of_dev,
+                                        uint64_t count, void *verdict_dev, void *stream) {
+    try { return verify_mixed_dev_body(ctx, set, blob_dev, blob_len, off_dev, key_of_dev, count, verdict_dev, stream); }   // no C++ exception crosses the C ABI, as plk_verify_many
+    catch (const std::exception &e) { set_error(std::string("plk_verify_mixed_dev: ") + e.what()); return PLK_ERR_ARG; }
 }
