@@ -763,11 +763,21 @@ int32_t plk_prove_assembled_dev(plk_ctx *ctx, const plk_setup *s, const void *co
  *      plk_poly_evaluate_at_dev at z = 0 returns c_0.  plk_poly_divide_by_linear_dev refuses z = 0 with PLK_ERR_ARG (its schedule
  *      multiplies by powers of 1/z; the quotient by x is a shift the caller can do).  plk_permutation_grand_product_dev returns
  *      PLK_ERR_UNSAT ("grand product denominator vanished") when w_j[i] + beta sigma_j[i] + gamma = 0 for some j and some row i of
- *      the N, the last row included; z_values_dev is unspecified then and the context stays usable. */
+ *      the N, the last row included; z_values_dev is unspecified then and the context stays usable.
+ *      plk_setup_permutation_dev is the copy-constraint permutation of plk_setup_prepare on its own (the setup calls the same code):
+ *      vars_dev[j] holds the 2^log_n uint32 variable ids of column j (a, b, c, d); id 0 is the dummy variable; every id is < num_vars —
+ *      the CALLER guarantees that, nothing checks it on the device (num_vars decides how many bits are sorted).  All occurrences of
+ *      an id, in row-major order (row by row, a to d inside a row), map each to the next and the last to the first; id 0 and single
+ *      occurrences keep the identity.  index_dev (may be NULL) receives idx[col * n + row] = col' << 30 | row', sigmas_dev (may be
+ *      NULL, not both) the four columns k_col' * omega^row' in Montgomery form.  log_n <= 26, the largest setup (SETUP_MAX_POW2).
+ *      PLK_ERR_ARG: a null pointer, log_n > 26, num_vars = 0, both outputs NULL.  Blocks until the outputs are written. */
 int32_t plk_poly_evaluate_at_dev(plk_ctx *ctx, const void *coeffs_dev, uint64_t n, const plk_fr *z, plk_fr *out, void *stream);
 int32_t plk_poly_divide_by_linear_dev(plk_ctx *ctx, const void *coeffs_dev, uint64_t n, const plk_fr *z, void *quotient_dev, void *stream);
 int32_t plk_permutation_grand_product_dev(plk_ctx *ctx, const void *const wires_dev[4], const void *const sigmas_dev[4], const plk_fr *beta, const plk_fr *gamma,
                                           uint32_t log_n, void *z_values_dev, void *stream);
+int32_t plk_setup_permutation_dev(plk_ctx *ctx, const void *const vars_dev[4], uint32_t log_n, uint64_t num_vars,
+                                  void *index_dev /* 4 * 2^log_n uint32, may be NULL */,
+                                  void *const sigmas_dev[4] /* 2^log_n plk_fr each, may be NULL */, void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

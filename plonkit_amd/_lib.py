@@ -525,6 +525,14 @@ class Context:
         b, g = np.ascontiguousarray(beta, dtype=np.uint64), np.ascontiguousarray(gamma, dtype=np.uint64)
         _check(lib().plk_permutation_grand_product_dev(self._h, w, s, _np(b), _np(g), ctypes.c_uint32(log_n), _devptr(out_ptr), _stream(stream)))
 
+    def setup_permutation_dev(self, vars_ptrs, log_n, num_vars, index_ptr=None, sigma_ptrs=None, stream=None):
+        """plk_setup_permutation_dev: the setup's copy-constraint permutation from four device columns of 2^log_n uint32 variable ids
+        (every id < num_vars, id 0 the dummy); index_ptr: 4 * 2^log_n uint32 (col' << 30 | row'), sigma_ptrs: four columns of 2^log_n Fr"""
+        v = (ctypes.c_void_p * 4)(*[_devptr(p) for p in vars_ptrs])
+        s = (ctypes.c_void_p * 4)(*[_devptr(p) for p in sigma_ptrs]) if sigma_ptrs is not None else None
+        _check(lib().plk_setup_permutation_dev(self._h, v, ctypes.c_uint32(log_n), ctypes.c_uint64(num_vars),
+                                               _devptr(index_ptr) if index_ptr is not None else None, s, _stream(stream)))
+
     def g1_intt_srs_dev(self, log_n, out_ptr, stream=None):
         _check(lib().plk_g1_intt_srs_dev(self._h, ctypes.c_uint32(log_n), _devptr(out_ptr), _stream(stream)))
 

@@ -358,6 +358,20 @@ static int32_t setup_host_impl(const plk_circuit *c, plk_setup **out) {
     return PLK_OK;
 }
 
+// The copy-constraint permutation of a setup from its 4 x N variable-index table: idx[col * N + row] = col' << 30 | row', the successor of
+// every occurrence (perm.hip), and, where sig_vals is given, sigma_col(omega^row) = k_col' * omega^row' (k = 1, 5, 7, 10).  The one place
+// that does this: the setup and plk_setup_permutation_dev both call it.  idx is the caller's (4N words); the sigma kernels are enqueued on
+// st and read idx, so the caller synchronises before releasing it.
+static int32_t setup_permutation(plk_ctx *ctx, const uint32_t *const vars[4], uint32_t log_n, uint64_t num_vars, uint32_t *idx, Fr *const sig_vals[4], hipStream_t st) {
+    const uint64_t N = 1ull << log_n;
+    PLK_TRY(build_permutation_index(ctx, vars, (uint32_t)N, num_vars, idx, st));
+    if (!sig_vals) return PLK_OK;
+    Fr kk[4];
+    for (int j = 0; j < 4; j++) kk[j] = from_u64<FrParams>(NON_RESIDUES[j]);
+    for (int j = 0; j < 4; j++) PLK_TRY(sigma_from_index(sig_vals[j], idx + (size_t)j * N, (uint32_t)N, log_n, ctx->tw_fwd, kk, st));
+    return PLK_OK;
+}
+
 static int32_t setup_upload_impl(plk_ctx *ctx, plk_setup *S) {
     if (!ctx || !S) { set_error("plk_setup_upload: bad argument"); return PLK_ERR_ARG; }
     if (S->store.p) return PLK_OK;                               // already resident
@@ -405,14 +419,10 @@ static int32_t setup_upload_impl(plk_ctx *ctx, plk_setup *S) {
     mark("selectors (upload + 7 iNTT)");
     // the permutation (rotate-left over each variable's occurrences) from the variable-index table, on the device (perm.hip)
     {
-        Fr kk[4];
-        for (int j = 0; j < 4; j++) kk[j] = from_u64<FrParams>(NON_RESIDUES[j]);
         DevBuf idx_buf;
         if ((rc = idx_buf.reserve((size_t)4 * N * 4)) != PLK_OK) return fail(rc);
-        uint32_t *idx = idx_buf.as<uint32_t>();
-        if ((rc = build_permutation_index(ctx, S->gate_vars, (uint32_t)N, S->num_vars, idx, st)) != PLK_OK) { idx_buf.release(); return fail(rc); }
+        if ((rc = setup_permutation(ctx, S->gate_vars, log_n, S->num_vars, idx_buf.as<uint32_t>(), S->sig_vals, st)) != PLK_OK) { idx_buf.release(); return fail(rc); }
         for (int j = 0; j < 4; j++) {
-            if ((rc = sigma_from_index(S->sig_vals[j], idx + (size_t)j * N, (uint32_t)N, log_n, ctx->tw_fwd, kk, st)) != PLK_OK) { idx_buf.release(); return fail(rc); }
             if (hipMemcpyAsync(S->sig_coef[j], S->sig_vals[j], N * sizeof(Fr), hipMemcpyDeviceToDevice, st) != hipSuccess) { idx_buf.release(); return fail(hip_fail(hipGetLastError(), "D2D sigma", __FILE__, __LINE__)); }
             if (log_n > 22 && (rc = ntt_dev(ctx, S->sig_coef[j], log_n, true, nullptr, st)) != PLK_OK) { idx_buf.release(); return fail(rc); }
         }
@@ -1328,6 +1338,25 @@ int32_t plk_permutation_grand_product_dev(plk_ctx *ctx, const void *const wires_
     if (hipStreamSynchronize(st) != hipSuccess && rc == PLK_OK) rc = hip_fail(hipGetLastError(), "sync", __FILE__, __LINE__);
     tmp.release();
     return rc;
+}
+
+int32_t plk_setup_permutation_dev(plk_ctx *ctx, const void *const vars_dev[4], uint32_t log_n, uint64_t num_vars, void *index_dev, void *const sigmas_dev[4], void *stream) {
+    return guarded("plk_setup_permutation_dev", PLK_ERR_HIP, [&]() -> int32_t {
+        bool ok = ctx && vars_dev && log_n <= MAX_LOG_N - 2 && num_vars != 0 && (index_dev || sigmas_dev);
+        for (int j = 0; ok && j < 4; j++) ok = vars_dev[j] && (!sigmas_dev || sigmas_dev[j]);
+        if (!ok) { set_error("plk_setup_permutation_dev: bad argument"); return PLK_ERR_ARG; }
+        PLK_HIP(hipSetDevice(ctx->device));
+        hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+        const uint64_t N = 1ull << log_n;
+        DevBuf idx_buf;                                              // the index is needed either way; the caller's memory where it is asked for
+        if (!index_dev) PLK_TRY(idx_buf.reserve((size_t)4 * N * 4));
+        const uint32_t *vars[4];
+        Fr *sig[4] = {};
+        for (int j = 0; j < 4; j++) { vars[j] = (const uint32_t *)vars_dev[j]; if (sigmas_dev) sig[j] = (Fr *)sigmas_dev[j]; }
+        int32_t rc = setup_permutation(ctx, vars, log_n, num_vars, index_dev ? (uint32_t *)index_dev : idx_buf.as<uint32_t>(), sigmas_dev ? sig : nullptr, st);
+        if (hipStreamSynchronize(st) != hipSuccess && rc == PLK_OK) rc = hip_fail(hipGetLastError(), "sync", __FILE__, __LINE__);
+        idx_buf.release();
+        return rc; });
 }
 
 // the exported entry points: no C++ exception (std::bad_alloc from a host vector of a 2^26 domain) crosses the boundary

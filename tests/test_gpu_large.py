@@ -278,6 +278,32 @@ def test_prove_large_domain_verifies(ctx24, log_n):
     setup.close(); circ.close()
 
 
+def test_setup_permutation_2pow24():
+    """the setup's permutation (perm.hip) at the smallest domain where the top level of its scan gives a thread more than one block total:
+    4n = 2^26 pairs are 16384 tiles, the (digit, tile) table 2048 blocks, two per thread of k_rs_scan_tops.  Ids up to 2^26 (four passes), one
+    hub over a whole column (2^24 occurrences across 4096 tiles); every entry of the packed index against the vectorised form of the model
+    of tests/gen/perm_cases.py (held against its plain form in tests/test_perm_cases_host.py).  The time is the host model's."""
+    import torch
+    import plonkit_amd as pa
+    from tests.gen import perm_cases as pc
+    log_n, n = pc.LARGE_LOG_N, 1 << pc.LARGE_LOG_N
+    V = pc.large_case()
+    assert V.shape == (4, n) and int(V.max()) == pc.LARGE_NUM_VARS - 1 and pc.passes(pc.LARGE_NUM_VARS) == 4 and (V[1] == pc.LARGE_HUB).all()
+    ctx = pa.Context(0)
+    d_vars = [torch.from_numpy(V[j].view(np.int32)).to("cuda:0") for j in range(4)]
+    d_idx = torch.full((4 * n,), -1, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()                                       # the library runs on its own stream
+    ctx.setup_permutation_dev(d_vars, log_n, pc.LARGE_NUM_VARS, d_idx, None)
+    got = d_idx.cpu().numpy().view(np.uint32)
+    del d_vars, d_idx
+    ctx.close()
+    torch.cuda.empty_cache()
+    want = pc.index_of_vectorised(pc.successors_vectorised(V))
+    assert want[n] == (1 << 30) | 1 and want[2 * n - 1] == 1 << 30     # the hub column: row r of b goes to row r + 1 of b, the last row to the first
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, "%d of %d entries differ, the first at idx[%d]: %#x, want %#x" % (bad.size, want.size, bad[0], got[bad[0]], want[bad[0]])
+
+
 def test_dump_lagrange_2pow20():
     """configs[3]: SRS 2^20 monomial -> Lagrange on one GPU (Crs::<Lagrange>::from_powers, src/plonk.rs:179-185)"""
     import torch
