@@ -161,6 +161,11 @@ typedef struct plk_msm_shape {
     uint64_t piece_terms;                /* terms per pass (the last one may be shorter)                                       */
 } plk_msm_shape;
 int32_t plk_msm_last_shape(plk_ctx *ctx, plk_msm_shape *out);
+/* DIAGNOSTIC like the above: 1 if the bucket accumulation of the commitment finished last ran the kernel that omits the
+ * point-at-infinity test — chosen when the resident key's MSM table holds no such point, which is established each time the
+ * table is built (every upload, load, generation or update of a key voids the table) — and 0 otherwise (a key with such a
+ * point, a commitment of <= 2^16 terms, the naive and short paths).                                                       */
+int32_t plk_msm_last_no_inf(plk_ctx *ctx, uint32_t *out);
 
 /* ---- Crs::<Lagrange>::from_powers (src/plonk.rs:179-185): inverse NTT over G1 (dump-lagrange)  */
 int32_t plk_g1_intt(plk_ctx *ctx, const plk_g1_affine *in_host, uint32_t log_n, plk_g1_affine *out_host);

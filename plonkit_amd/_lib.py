@@ -409,6 +409,13 @@ class Context:
         d["path"] = MSM_PATHS[d["path"]]
         return d
 
+    def msm_last_no_inf(self):
+        """diagnostic (plk_msm_last_no_inf): True if the accumulation of the commitment finished last ran without the point-at-infinity
+        test (the resident key's table holds no such point and the commitment took the plain kernel)"""
+        v = ctypes.c_uint32(0)
+        _check(lib().plk_msm_last_no_inf(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
     # ---- NTT
     def ntt(self, data, log_n, inverse=False, coset=None):
         """host array in, new host array out (natural order)."""

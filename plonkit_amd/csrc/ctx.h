@@ -86,11 +86,13 @@ struct plk_ctx {
     plk::DevBuf srs_w;                       // the same points in the 2^261 Montgomery domain of field29_dev.h (MSM gathers)
     bool srs_w_valid = false;
     uint32_t srs_w_copies = 0;               // shifted copies 2^(16k) * P held in srs_w (fixed-base table of the MSM)
+    bool srs_w_no_inf = false;               // srs_w holds no point at infinity: established by every build of the table (msm.hip: ensure_base_table), void
+                                             // with it (srs_w_valid) — a key can only change through srs_table_invalidate, so it cannot go stale
     // optional second key: Crs<E, CrsForLagrangeForm> (L_i(tau)*G), used by plk_prove for commit_using_values
     // (`prove -l`, src/plonk.rs:138-146).  Same fields as above; SrsSlotSwap makes it the active key for one call.
     struct LagrangeKey {
         const void *pts = nullptr; uint64_t n = 0;
-        plk::DevBuf own, w; bool w_valid = false; uint32_t w_copies = 0;
+        plk::DevBuf own, w; bool w_valid = false; uint32_t w_copies = 0; bool w_no_inf = false;
     } lag;
     // MSM: up to three commitments (or batches) may be in flight, each with its own scratch, result buffer and stream:
     // the latency-bound tail of commitment k-1 (bucket reduction) and the digit / partition kernels of k+1 then share the
@@ -111,6 +113,7 @@ struct plk_ctx {
         const void *fb_bases = nullptr, *fb_scalars[8] = {nullptr};
         uint64_t fb_srs_n = 0, fb_n = 0;
         uint32_t fb_copies = 0, fb_cbits = 0, fb_nbits = 0;
+        bool acc_no_inf = false;             // msm_accumulate ran without the is_inf(q) test (plk_msm_last_no_inf: diagnostic)
         plk_msm_shape shape = {};            // which kernels this commitment was given (plk_msm_last_shape: diagnostic, host integers only)
     } slot[MSM_SLOTS];
     uint64_t msm_enq = 0, msm_fin = 0;       // FIFO counters; commitment number k lives in slot[fifo[k % MSM_SLOTS]]
@@ -167,8 +170,8 @@ namespace plk {
 // every entry point that replaces a resident key goes through these two: the MSM table of the old key is void, and a table
 // (or key) that was only borrowed must not be written to when the next one is built
 int32_t srs_replace_guard(plk_ctx *c, const char *who, bool lagrange_only = false);   // runtime.hip: PLK_ERR_ARG while another context borrows this one's key
-inline void srs_table_invalidate(plk_ctx *c) { c->srs_w_valid = false; if (c->srs_w.borrowed) c->srs_w.release(); }
-inline void lag_table_invalidate(plk_ctx *c) { c->lag.w_valid = false; if (c->lag.w.borrowed) c->lag.w.release(); }
+inline void srs_table_invalidate(plk_ctx *c) { c->srs_w_valid = false; c->srs_w_no_inf = false; if (c->srs_w.borrowed) c->srs_w.release(); }
+inline void lag_table_invalidate(plk_ctx *c) { c->lag.w_valid = false; c->lag.w_no_inf = false; if (c->lag.w.borrowed) c->lag.w.release(); }
 void srs_return_loan(plk_ctx *c);                                 // runtime.hip
 void srs_make_loan(plk_ctx *dst, plk_ctx *src);                   // runtime.hip
 bool srs_orphan_lender(plk_ctx *c);                               // runtime.hip
@@ -184,6 +187,7 @@ struct SrsSlotSwap {
         std::swap(c->srs, c->lag.pts); std::swap(c->srs_n, c->lag.n);
         std::swap(c->srs_own, c->lag.own); std::swap(c->srs_w, c->lag.w);
         std::swap(c->srs_w_valid, c->lag.w_valid); std::swap(c->srs_w_copies, c->lag.w_copies);
+        std::swap(c->srs_w_no_inf, c->lag.w_no_inf);
     }
 };
 }  // namespace plk

@@ -104,6 +104,62 @@ PLK_HD void xyzzw_add_mixed(XyzzW &acc, const AffW &q, bool neg_q) {
     acc.zzz = zzz3;
 }
 
+// The same addition for the flat loop of msm_accumulate's plain kernel, with less work around the ten products.  The same point mod p in
+// every coordinate; the same integers, bit for bit, unless y is negated (tests/host/field29_addend_check.hip holds the earlier form).
+//   - No is_inf(q): the caller runs this only over a table that holds no point at infinity (msm.hip establishes that where it builds the
+//     table).  is_inf(acc), an OR over nine limbs in every addition, is the lane flag `fresh`: the caller sets it where it sets acc to
+//     the identity (start, after a flush); it is cleared by the first point taken and set again where the special path returns the
+//     identity.  (A hot-path result is never the identity: zz3 = 0 needs P = 0 mod p, and maybe_zero_mod_p has no false negatives.)
+//   - P = U2 + (6p - X) and R = S2 + (8p - Y) come out of the product pair itself (mulw2_add): the padded terms are addends of the high
+//     columns, whose carry chain normalises the sums, so neither sub6 nor normw follows.  Values as before: P < 7.02, R < 9.1.
+//   - The sign of y goes onto the affine operand BEFORE the product: +-y is y or the raw 2p - y (limbs <= PAD2's 2.63e9, below
+//     MULW_A_LIMB_MAX; value < 2p, so S2 < 2 * 1.3 * 0.0059 + 1 < 1.02 as before).  For a negated y this R differs from the earlier
+//     8p - Y - y*zzz by a multiple of p.
+//   - T = Q - X3 + 6p and 2p - PPP enter the fused Y3 product as they stand, without normw: they are its RIGHT operands, taken from the
+//     pads with the 2^29 bias (PAD6N, PAD2N: X3 and PPP are normalised), so their limbs stay below 1.45e9 and 1.02e9; R and Y are
+//     normalised, and a column holds at most 9 * (2^29 * 1.45e9 + 2^29 * 1.02e9 + (2^29)^2) + 2^35 < 0.79 * 2^64 (host-checked with a
+//     128-bit shadow of the chain at exactly these limbs).  With the 2^31 pads the same column reaches 1.6 * 2^64.
+// Not folded: X3 = R^2 + (4p - PPP - 2Q) needs R^2 after PPP and Q; the lockstep pairs would have to become PP alone, (PPP, Q),
+// (R^2 + addend, ZZ*PP), ZZZ*PPP alone — two single chains, whose wait states only the second wave hides, for ~25 instructions.
+PLK_HD void xyzzw_add_mixed_flag(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) {
+    if (fresh) { acc.x = q.x; acc.y = neg_q ? neg2(q.y) : q.y; acc.zz = w_one<FqW>(); acc.zzz = w_one<FqW>(); fresh = false; return; }
+    FqW9 p, r, yq;
+    {
+        FqW9 ax, ay;
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            ax.l[i] = FqW::PAD6[i] - acc.x.l[i];                         // 6p - X, 8p - Y: limbs <= the pads' (< 2^32), not normalised
+            ay.l[i] = FqW::PAD8[i] - acc.y.l[i];
+            yq.l[i] = neg_q ? FqW::PAD2[i] - q.y.l[i] : q.y.l[i];       // 2p - y (limbs <= 2.63e9 < MULW_A_LIMB_MAX, value < 2p) or y
+        }
+        mulw2_add<FqW>(q.x, acc.zz, ax, yq, acc.zzz, ay, p, r);          // P = U2 + (6p - X),  R = S2 + (8p - Y)
+    }
+    if (maybe_zero_mod_p(p)) {                               // P == +-Q: rare, kept out of the hot code
+        AffW t; t.x = q.x; t.y = normw(yq);                    // (+-y as xyzzw_add_mixed forms it: neg2(y) = normw(2p - y), y is normalised)
+        xyzzw_add_mixed_special(acc, t, false, p, r);
+        fresh = is_inf(acc);
+        return;
+    }
+    FqW9 pp, rr, ppp, qq;
+    sqrw2<FqW>(p, r, pp, rr);
+    mulw2<FqW>(p, pp, acc.x, pp, ppp, qq);
+    FqW9 x3;
+    {
+#pragma unroll
+        for (int i = 0; i < 9; i++) x3.l[i] = rr.l[i] + FqW::PAD4[i] - ppp.l[i] - 2 * qq.l[i];
+        x3 = normw(x3);
+    }
+    FqW9 zz3, zzz3;
+    mulw2<FqW>(acc.zz, pp, acc.zzz, ppp, zz3, zzz3);
+    FqW9 t, nppp;
+#pragma unroll
+    for (int i = 0; i < 9; i++) { t.l[i] = qq.l[i] + FqW::PAD6N[i] - x3.l[i]; nppp.l[i] = FqW::PAD2N[i] - ppp.l[i]; }
+    acc.y = WMA(r, t, acc.y, nppp);                           // R*(Q - X3) - Y*PPP, one reduction
+    acc.x = x3;
+    acc.zz = zz3;
+    acc.zzz = zzz3;
+}
+
 // a += b
 PLK_HD void xyzzw_add(XyzzW &a, const XyzzW &b) {
     if (is_inf(b)) return;

@@ -54,6 +54,11 @@ struct FqW {
     static constexpr uint32_t PAD4[9] = {0x81f3f51cu, 0x841182d7u, 0x91ca8d38u, 0x8b548b3fu, 0x961765dcu, 0x8b6d02feu, 0x829b8500u, 0x997098ccu, 0x00c19135u};
     static constexpr uint32_t PAD6[9] = {0x92edefaau, 0x861a4444u, 0x8aafd3d6u, 0x90fed0e1u, 0x812318ccu, 0x91238480u, 0x83e94782u, 0x9628e534u, 0x012259d2u};
     static constexpr uint32_t PAD8[9] = {0x83e7ea38u, 0x882305b2u, 0x83951a74u, 0x96a91683u, 0x8c2ecbbcu, 0x96da0601u, 0x85370a04u, 0x92e1319cu, 0x0183226fu};
+    // 2p and 6p with the lower limbs biased by 2^29 only: enough to subtract a NORMALISED value limb by limb (limbs < 2^29), and the
+    // difference keeps limbs below 2^30 (+ 2^29 with a normalised term added) — small enough to enter mul2addw as a right operand as
+    // it stands (xyzzw_add_mixed_flag; the 2^31 bias of the pads above is what a subtrahend with limbs up to 2^30 needs)
+    static constexpr uint32_t PAD2N[9] = {0x30f9fa8eu, 0x2208c16cu, 0x38e5469du, 0x25aa45a0u, 0x2b0bb2efu, 0x25b68180u, 0x214dc281u, 0x3cb84c67u, 0x0060c89bu};
+    static constexpr uint32_t PAD6N[9] = {0x32edefaau, 0x261a4447u, 0x2aafd3d9u, 0x30fed0e4u, 0x212318cfu, 0x31238483u, 0x23e94785u, 0x3628e537u, 0x012259d5u};
 };
 
 template <class WP>
@@ -238,6 +243,45 @@ PLK_HD void sqrw2(const W9<WP> &x0, const W9<WP> &x1, W9<WP> &r0, W9<WP> &r1) {
     }
     r0.l[8] = (uint32_t)acc0; r1.l[8] = (uint32_t)acc1;
 }
+// ---- the same lockstep pair with a 9-limb ADDEND folded into each chain (the mixed addition of msm_accumulate):
+//     mulw2_add: r_q = a_q * b_q * 2^-261 + A_q,  normalised,   q = 0, 1
+// A_q is any 9-limb value (limbs up to 2^32 - 1: a padded difference "PADk - x" as it stands, not normalised).  Limb j of the addend
+// joins the accumulator at column 9 + j, before the output limb j is cut off, so the column chain that normalises the product
+// normalises the sum as well: the result is bit for bit normw(addw(mulw(a, b), A)) — same integer, same (unique) normalised form —
+// without the 9 additions and the 25 instructions of normw, for 8 multiply-adds by one (the top limb is a 32-bit add).
+// Bounds: a high column k >= 9 holds at most 17 - k <= 8 products of each kind, so the addend's < 2^32 has room beside them even with
+// the left operand at MULW_A_LIMB_MAX: 8 * 3.28e9 * (2^29 - 1) + 8 * (2^29 - 1)^2 + 2^35 + 2^32 < 2^63.9.  The value must stay below
+// 2^261 and the top limb below 2^32: callers add less than 16p to a product below 1.1p.  Host-checked at the bounds
+// (tests/host/field29_addend_check.hip).
+// (the addend enters as a multiply-add by a one the compiler cannot see: the plain 64-bit addition it would otherwise form wants the
+//  addend widened to a register pair, one extra move per limb)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PLK_ADDEND(acc, x) { uint32_t one_ = 1; asm("" : "+s"(one_)); (acc) += (uint64_t)(x) * one_; }
+#else
+#define PLK_ADDEND(acc, x) { (acc) += (uint64_t)(x); }
+#endif
+#define PLK_MONT_HIGH2_ADD(k) { _Pragma("unroll") for (int i = (k) - 8; i <= 8; i++) { acc0 += (uint64_t)m0[i] * WP::P29[(k) - i]; PLK_CHAIN(acc0); acc1 += (uint64_t)m1[i] * WP::P29[(k) - i]; PLK_CHAIN(acc1); } \
+                                PLK_ADDEND(acc0, A0.l[(k) - 9]); PLK_ADDEND(acc1, A1.l[(k) - 9]); \
+                                r0.l[(k) - 9] = (uint32_t)acc0 & M29; r1.l[(k) - 9] = (uint32_t)acc1 & M29; acc0 >>= 29; acc1 >>= 29; }
+template <class WP>
+PLK_HD void mulw2_add(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &A0, const W9<WP> &a1, const W9<WP> &b1, const W9<WP> &A1, W9<WP> &r0, W9<WP> &r1) {
+    uint32_t m0[9], m1[9];
+    uint64_t acc0 = 0, acc1 = 0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
+        PLK_MONT_LOW2(k)
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) {
+#pragma unroll
+        for (int i = k - 8; i <= 8; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
+        PLK_MONT_HIGH2_ADD(k)
+    }
+    r0.l[8] = (uint32_t)acc0 + A0.l[8]; r1.l[8] = (uint32_t)acc1 + A1.l[8];
+}
+
 // a^2: the cross products a_i*a_j (i < j) are taken once against the doubled operand: 45 + 81 mads instead of 162
 template <class WP>
 PLK_HD W9<WP> sqrw(const W9<WP> &a) {

@@ -33,7 +33,7 @@ namespace plk {
 // accumulated the way msm_small.hip does it instead: the four lanes 4 b .. 4 b + 3 OWN bucket b, lane j takes entries j, j + 4, .. of its run, the quad adds
 // its four sums up (three four-lane additions) and stores ONE PRIMARY sum per bucket; the entry count in the task's meta carries bit 31, which makes the
 // two reduction kernels treat every bucket as whole.  Hot buckets (repeated scalars) fail the test and keep the equal pieces.
-template <uint32_t FB, int MINW = 2, bool OWNED = false>
+template <uint32_t FB, int MINW = 2, bool OWNED = false, bool Q_MAY_BE_INF = true>
 __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affine *bases, const uint32_t *entries,
                                                                   const uint32_t *bin_start, const uint32_t *task_start,
                                                                   XyzzW *partials, uint32_t *task_meta, MsmParams p) {
@@ -141,6 +141,37 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
     // one flat loop over the lane's piece: every lane of the wave executes the same number of mixed additions
     // in lockstep; a bucket boundary only costs the (divergent) 144-byte flush of the finished accumulator.
     // (The same loop — one mixed-addition site — serves the owned shape: first / step / last differ, and no bucket boundary is ever met.)
+    if constexpr (!OWNED && !Q_MAY_BE_INF) {
+        // The plain kernel for a table without a point at infinity (msm.hip establishes that where it builds the table).  Same flat loop
+        // as below; what differs is what each iteration carries besides the addition:
+        //   - xyzzw_add_mixed_flag: no is_inf(q), `fresh` instead of is_inf(acc), addends folded into the products (ec29_dev.h);
+        //   - the bucket of the current run and where the run began are not kept in registers: a flush reads the bucket back from the
+        //     entry before it (i == bend > lo, so there is one), and "the run began at lo" is the flag `first_run`.
+        const uint32_t lo = tid * mu < nc ? tid * mu : nc, hi = lo + mu < nc ? lo + mu : nc;
+        if (lo >= hi) return;
+        uint32_t en = sorted[lo];
+        G1Affine pt = load_affine(point_of(en));
+        uint32_t bend = start[(en & (FINE - 1)) + 1];
+        XyzzW acc = xyzzw_identity();
+        bool fresh = true, first_run = true;
+        for (uint32_t i = lo; i < hi; i++) {
+            const uint32_t e_cur = en;
+            AffW cur; cur.x = unpack<FqW>(pt.x); cur.y = unpack<FqW>(pt.y);
+            if (i + 1 < hi) { en = sorted[i + 1]; pt = load_affine(point_of(en)); }   // prefetch the next gather
+            if (i == bend) {                                      // the previous bucket ended inside this piece
+                const uint32_t b = sorted[i - 1] & (FINE - 1);
+                const bool from_prev = first_run && (start[b] < tid * mu);
+                store_xyzzw(out + (from_prev ? SLOT_HEAD + tid : SLOT_PRIMARY + b), acc);
+                acc = xyzzw_identity(); fresh = true; first_run = false;
+                bend = start[(e_cur & (FINE - 1)) + 1];
+            }
+            xyzzw_add_mixed_flag(acc, fresh, cur, (e_cur & 0x80u) != 0);
+        }
+        const uint32_t b = sorted[hi - 1] & (FINE - 1);
+        const bool from_prev = first_run && (start[b] < tid * mu), into_next = bend > hi;
+        store_xyzzw(out + (from_prev ? SLOT_HEAD + tid : (into_next ? SLOT_TAIL + tid : SLOT_PRIMARY + b)), acc);
+        return;
+    }
     const bool own = OWNED && owned;
     const uint32_t step = own ? 4u : 1u;
     uint32_t lo, hi;
@@ -184,15 +215,18 @@ int32_t msm_accumulate_prepare() {
     if (attr_set) return PLK_OK;
     PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<FINE_BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
     PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<FINE_BITS, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
+    PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msm_accumulate<FINE_BITS, 2, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK * sizeof(uint32_t)));
     attr_set = true;
     return PLK_OK;
 }
 
-void msm_accumulate_launch(int variant, uint32_t max_tasks, hipStream_t stream, const G1Affine *bases, const uint32_t *entries,
+void msm_accumulate_launch(int variant, bool no_inf, uint32_t max_tasks, hipStream_t stream, const G1Affine *bases, const uint32_t *entries,
                            const uint32_t *bin_start, const uint32_t *task_start, XyzzW *partials, uint32_t *task_meta, const MsmParams &p) {
     const size_t lds = CHUNK * sizeof(uint32_t);
     if (variant == 2)
         hipLaunchKernelGGL((msm_accumulate<FINE_BITS, 2, true>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
+    else if (no_inf)
+        hipLaunchKernelGGL((msm_accumulate<FINE_BITS, 2, false, false>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
     else
         hipLaunchKernelGGL((msm_accumulate<FINE_BITS>), dim3(max_tasks), dim3(MSM_THREADS), lds, stream, bases, entries, bin_start, task_start, partials, task_meta, p);
 }

@@ -77,8 +77,9 @@ constexpr uint32_t TASK_OWNED_BIT = 0x80000000u;
 // kernel A (msm_accumulate.hip): one workgroup per task of 2^FINE_BITS buckets; variant 0 = the plain kernel, variant 2 = the build that lets a
 // task's lanes own its buckets when they are evenly filled (commitments of <= 2^16 terms).  Variant 1 (a 512-register, one-wave-per-SIMD
 // build kept for measurements) is retired; the numbers stay as they are because plk_msm_last_shape reports them.
+// no_inf: the table holds no point at infinity (msm.hip: ensure_base_table) — variant 0 then runs the instantiation without the is_inf(q) test.
 int32_t msm_accumulate_prepare();                                   // dynamic-LDS attributes, once per process
-void msm_accumulate_launch(int variant, uint32_t max_tasks, hipStream_t stream, const G1Affine *bases, const uint32_t *entries,
+void msm_accumulate_launch(int variant, bool no_inf, uint32_t max_tasks, hipStream_t stream, const G1Affine *bases, const uint32_t *entries,
                            const uint32_t *bin_start, const uint32_t *task_start, XyzzW *partials, uint32_t *task_meta, const MsmParams &p);
 
 }  // namespace plk

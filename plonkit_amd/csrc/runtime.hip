@@ -78,7 +78,7 @@ int32_t srs_replace_guard(plk_ctx *c, const char *who, bool lagrange_only) {
         std::lock_guard<std::mutex> g(g_share_mu);
         c->srs_lender->lag_borrowers.fetch_sub(1);
         c->lag_borrowed = false;
-        c->lag.pts = nullptr; c->lag.n = 0; c->lag.w.release(); c->lag.w_valid = false; c->lag.w_copies = 0;
+        c->lag.pts = nullptr; c->lag.n = 0; c->lag.w.release(); c->lag.w_valid = false; c->lag.w_copies = 0; c->lag.w_no_inf = false;
     }
     return PLK_OK;
 }
@@ -96,8 +96,8 @@ void srs_return_loan(plk_ctx *c) {
         if (c->lag_borrowed) lender->lag_borrowers.fetch_sub(1);
         if (lender->srs_borrowers.fetch_sub(1) == 1 && lender->zombie) orphan = lender;
         c->srs_lender = nullptr;
-        c->srs = nullptr; c->srs_n = 0; c->srs_w.release(); c->srs_w_valid = false; c->srs_w_copies = 0;
-        if (c->lag_borrowed) { c->lag.pts = nullptr; c->lag.n = 0; c->lag.w.release(); c->lag.w_valid = false; c->lag.w_copies = 0; }
+        c->srs = nullptr; c->srs_n = 0; c->srs_w.release(); c->srs_w_valid = false; c->srs_w_copies = 0; c->srs_w_no_inf = false;
+        if (c->lag_borrowed) { c->lag.pts = nullptr; c->lag.n = 0; c->lag.w.release(); c->lag.w_valid = false; c->lag.w_copies = 0; c->lag.w_no_inf = false; }
         c->lag_borrowed = false;
     }
     if (orphan) free_lent(orphan);                       // the lender was destroyed before this, its last, borrower
@@ -105,9 +105,9 @@ void srs_return_loan(plk_ctx *c) {
 void srs_make_loan(plk_ctx *dst, plk_ctx *src) {         // (msm.hip plk_ctx_share_srs: the checks and the fallible steps come first)
     std::lock_guard<std::mutex> g(g_share_mu);
     dst->srs = src->srs; dst->srs_n = src->srs_n;
-    dst->srs_w.borrow(src->srs_w); dst->srs_w_valid = src->srs_w_valid; dst->srs_w_copies = src->srs_w_copies;
+    dst->srs_w.borrow(src->srs_w); dst->srs_w_valid = src->srs_w_valid; dst->srs_w_copies = src->srs_w_copies; dst->srs_w_no_inf = src->srs_w_valid && src->srs_w_no_inf;
     dst->lag.pts = src->lag.pts; dst->lag.n = src->lag.n;
-    dst->lag.w.borrow(src->lag.w); dst->lag.w_valid = src->lag.pts ? src->lag.w_valid : false; dst->lag.w_copies = src->lag.w_copies;
+    dst->lag.w.borrow(src->lag.w); dst->lag.w_valid = src->lag.pts ? src->lag.w_valid : false; dst->lag.w_copies = src->lag.w_copies; dst->lag.w_no_inf = dst->lag.w_valid && src->lag.w_no_inf;
     dst->lag_borrowed = src->lag.pts != nullptr;
     dst->srs_lender = src;
     src->srs_borrowers.fetch_add(1);
