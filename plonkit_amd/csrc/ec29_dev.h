@@ -185,6 +185,65 @@ PLK_HD void xyzzw_add(XyzzW &a, const XyzzW &b) {
     a.zzz = LM(LM(a.zzz, b.zzz), ppp);
 }
 
+// a += b for the WORK-bound bucket reduction (msm_task_reduce<.., PAIRS>: a batch of three or more, or other commitments in flight — two of
+// these chains per SIMD beside another commitment's accumulation, priced by the instructions they issue, not by their latency): the same
+// fourteen products as xyzzw_add, issued as the lockstep product-scanning pairs of the mixed addition (~205 instructions per product against
+// ~243 of a lone operand-scanning chain) and the fused Y3 as one product-scanning chain.  The same integers as xyzzw_add in all 36 limbs:
+// mulw / sqrw / mul2addw and their _os forms return the same normalised (a*b + m*p) / 2^261, and the two folds below keep the integers
+// (tests/host/field29_pairs_check.hip: > 10^5 operands as the reduction feeds them in, every chain shadowed in 128 bits).
+//   - Pairs: (U1, S1), (U2, S2), (ZZ1*ZZ2, ZZZ1*ZZZ2), (PP, RR) as squarings, (PPP, Q), (ZZ3, ZZZ3).  U1 and S1 go first because
+//   - P = U2 + (2p - U1) and R = S2 + (2p - S1) come out of the second pair itself (mulw2_add): the padded differences are addends of its
+//     high columns, whose carry chain normalises the sums — bit for bit sub2(U2, U1) and sub2(S2, S1), without their 9 additions and normw.
+//     Addend limbs <= PAD2's (< 2^32; >= 0: U1, S1 are normalised and below 2p), less than 16p added to a product below 1.1p, as mulw2_add asks.
+//   - T = Q - X3 + 6p and 2p - PPP enter the fused Y3 product as they stand, from the pads with the 2^29 bias, as in xyzzw_add_mixed_flag:
+//     right operands with limbs below 1.45e9 and 1.02e9 (X3, PPP, Q normalised) beside the normalised left operands R and S1: the column
+//     bound derived there, < 0.79 * 2^64.  mul2addw sees the same integers as with sub6 / neg2, so the result is the same.
+// Bounds.  Every other operand of every product here is NORMALISED (limbs < 2^29; the top limb too, the values being far below 2^261): the
+// coordinates come out of a product's column chain or of normw (outputs of xyzzw_add_mixed_flag, of this addition or of xyzzw_double: x,
+// y < 6p, zz, zzz < 1.3p), P and R out of the column chain of mulw2_add (P, R < 3.05p).
+//   - mulw2 / mulw2_add, left operands X1, Y1, X2, Y2, ZZ1, ZZZ1, P, U1, ZZ1*ZZ2, ZZZ1*ZZZ2: limbs < 2^29, far below MULW_A_LIMB_MAX = 3.28e9;
+//     a column holds at most 2 * 9 * (2^29 - 1)^2 + 2^35 (+ 2^32 for an addend) < 2^62.2.
+//   - sqrw2 of (P, R): the doubled limbs stay below 2^30, a column at most 9 * (2^30 * 2^29 + 2^58) + 2^35 < 2^62.8.
+// Values: U, S < 6 * 1.3 * 0.0059p + p < 1.05p; PP < 3.05^2 * 0.0059p + p < 1.06p; X3 < 5.06p; Y3 < (3.05 * 7.1 + 1.05 * 2) * 0.0059p + p < 1.2p.
+PLK_HD void xyzzw_add_pairs(XyzzW &a, const XyzzW &b) {
+    if (is_inf(b)) return;
+    if (is_inf(a)) { a = b; return; }
+    FqW9 u1, s1, p, r;
+    mulw2<FqW>(a.x, b.zz, a.y, b.zzz, u1, s1);
+    {
+        FqW9 nu, ns;
+#pragma unroll
+        for (int i = 0; i < 9; i++) { nu.l[i] = FqW::PAD2[i] - u1.l[i]; ns.l[i] = FqW::PAD2[i] - s1.l[i]; }     // 2p - U1, 2p - S1: not normalised
+        mulw2_add<FqW>(b.x, a.zz, nu, b.y, a.zzz, ns, p, r);
+    }
+    if (is_zero_mod_p(p)) {
+        if (is_zero_mod_p(r)) a = xyzzw_double(a);
+        else a = xyzzw_identity();
+        return;
+    }
+    FqW9 zz12, zzz12;
+    mulw2<FqW>(a.zz, b.zz, a.zzz, b.zzz, zz12, zzz12);
+    FqW9 pp, rr, ppp, qq;
+    // (P and R are hidden from the optimiser here: knowing from the chain's masks that their limbs are below 2^29, it widens the squarings'
+    //  doubled limbs "x << 1" to 33-bit values and pays two multiply-adds and two moves for each of ~100 products)
+#pragma unroll
+    for (int i = 0; i < 9; i++) { PLK_CHAIN(p.l[i]); PLK_CHAIN(r.l[i]); }
+    sqrw2<FqW>(p, r, pp, rr);
+    mulw2<FqW>(p, pp, u1, pp, ppp, qq);
+    FqW9 x3;
+    {
+#pragma unroll
+        for (int i = 0; i < 9; i++) x3.l[i] = rr.l[i] + FqW::PAD4[i] - ppp.l[i] - 2 * qq.l[i];
+        x3 = normw(x3);
+    }
+    FqW9 t, nppp;
+#pragma unroll
+    for (int i = 0; i < 9; i++) { t.l[i] = qq.l[i] + FqW::PAD6N[i] - x3.l[i]; nppp.l[i] = FqW::PAD2N[i] - ppp.l[i]; }
+    a.y = WMA(r, t, s1, nppp);                                // R*(Q - X3) - S1*PPP, one reduction
+    a.x = x3;
+    mulw2<FqW>(zz12, pp, zzz12, ppp, a.zz, a.zzz);
+}
+
 // storage <-> registers
 __device__ __forceinline__ AffW load_affw(const G1Affine *p) {            // packed, already in the 2^261 domain
     AffW r; r.x = unpack<FqW>(load_fp(&p->x)); r.y = unpack<FqW>(load_fp(&p->y)); return r;

@@ -592,6 +592,31 @@ PLK_HD W9<WP> mulsum3w(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &a1, con
 template <class WP> PLK_HD W9<WP> w_from_s(const W9<WP> &raw) { return mulw(raw, w_from_s_const<WP>()); }      // x*2^256 -> x*2^261 (< 1.1p)
 template <class WP> PLK_HD W9<WP> s_from_w(const W9<WP> &a) { return csub_p(mulw(a, s_from_w_const<WP>())); }   // x*2^261 -> x*2^256 canonical
 
+// Leaving the EXTERNAL Montgomery form (x * 2^256, any 256-bit value) on this layer: the canonical residue x mod p as nine normalised limbs,
+// the same integer as to_canonical() of field_dev.h gives in eight words.  One product-scanning Montgomery pass by the constant 2^5 (the
+// layer divides by 2^261): the a*b half is a_k * 2^5 in column k — nine shifts, no multiply-add — and the reduction half the usual 45 + 36.
+// Bounds: a column holds a_k * 2^5 < 2^34, at most 9 products m * p (< 2^58 each) and a carry < 2^35: below 2^62.  The value before the
+// subtraction is (32 a + m p) / 2^261 < 1 + p for a < 2^256 and m < 2^261, i.e. at most p, and the CIOS pass of to_canonical() is
+// (a + m' p) / 2^256 <= p as well: both end with one conditional subtraction, both are = a * 2^-256 (mod p) and in [0, p), hence equal.
+// 81 multiply-adds against the 64 of mul(a, 1), but none of its carry chains (tests/host/field29_pairs_check.hip compares the two).
+template <class WP, class PR>
+PLK_HD W9<WP> canonical_w(const Fp<PR> &s) {
+    const W9<WP> a = unpack<WP>(s);
+    uint32_t m[9];
+    W9<WP> r;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        acc += (uint64_t)a.l[k] << 5;
+        PLK_MONT_LOW(k)
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) PLK_MONT_HIGH(k)
+    r.l[8] = (uint32_t)acc;
+    return csub_p(r);
+}
+PLK_HD W9<FrW> fr_canonical_w(const Fr &k) { return canonical_w<FrW>(k); }
+
 using FrW9 = W9<FrW>;
 using FqW9 = W9<FqW>;
 

@@ -20,7 +20,8 @@
 //     mixed additions with XYZZ accumulators in registers, a bucket boundary inside a piece only flushes the accumulator
 //     (PRIMARY / HEAD / TAIL slots).  Points are gathered as 64-byte affine records.  All field arithmetic is the
 //     carry-free 9x29-bit layer (field29_dev.h / ec29_dev.h): product-scanning products in lockstep pairs in the mixed
-//     addition (throughput-bound), operand-scanning products in the full additions of the reduce kernels (latency-bound).
+//     addition (throughput-bound), operand-scanning products in the full additions of the reduce kernels (latency-bound) — except the
+//     16-lane msm_task_reduce of a batch or a stream, which is priced by work and takes lockstep pairs again (xyzzw_add_pairs).
 //   * a bucket spread over many lanes (repeated scalars: all-ones, all -1) is folded by a separate small kernel
 //     (msm_fold_hot), a coarse bin spread over many tasks by another (msm_bin_fold).
 //   * per task T = sum B_f and S = sum (f+1) B_f (running sums + 32-lane shuffle scan), then per bucket set
@@ -196,9 +197,11 @@ __global__ void __launch_bounds__(1024) msm_scan_bins(uint32_t *hist, uint32_t *
 // ------------------------------------------------------------------ fused recoding (one bucket set per commitment)
 // With the table of shifted copies every window of a commitment drops into ONE bucket set (groups == 1: up to 2^20 terms,
 // c = 17, 15 windows) — then a scalar's 15 entries can be produced where the scalar is read, and the int32 digit array
-// (60 B per term written by msm_digits, read twice by msm_partition) disappears: both passes read the 32-byte scalar,
-// leave Montgomery form (one product) and recode in registers.  Per term the pre-phase moves 64 B + the 60 B of entries
-// instead of 212 B, in two launches instead of three (0.22 -> ~0.1 ms in front of a 2^20-term commitment: it is on the
+// (60 B per term written by msm_digits, read twice by msm_partition) disappears: both passes read a 32-byte scalar
+// and recode in registers.  Pass 1 reads the scalar as given, leaves Montgomery form (fr_canonical_w: one reduction on the 29-bit layer) and
+// writes the canonical words for pass 2 — a stream of commitments is bound by VALU issue, and the second reduction was 207 of pass 2's
+// instructions per scalar against 32 B written and read (profiles/msm_nonloop_diet_isa.txt).  Per term the pre-phase moves 96 B + the 60 B
+// of entries instead of 212 B, in two launches instead of three (0.22 -> ~0.1 ms in front of a 2^20-term commitment: it is on the
 // critical path of every round of a proof, and in a stream of commitments its workgroups displace accumulate workgroups).
 // The workgroup of the scatter pass takes RC_SCALARS scalars x 15 windows = 15360 entries, the same LDS staging volume
 // and the same ~15-entry runs per (workgroup, coarse bin) as the per-window partition it replaces.
@@ -217,7 +220,9 @@ __device__ __forceinline__ bool wave_same_scalar(const Fr &k, bool live, uint64_
 // pass 1: coarse-bin histogram of the commitment's bucket set; RC_COUNT_PER scalars per thread keep the global atomics at
 // one per (workgroup, bin) for 4096 scalars
 constexpr int RC_COUNT_PER = 4;
-__global__ void __launch_bounds__(RC_THREADS) msm_recode_count(ScalarSet set, MsmParams p, uint32_t *hist) {
+// The scalar leaves Montgomery form HERE, once per commitment (fr_canonical_w: the 29-bit layer's reduction, no carry chains), and the canonical
+// words go to `canon` (32 B per scalar, vector m at canon + m * n) for pass 2, which would otherwise reduce every scalar a second time.
+__global__ void __launch_bounds__(RC_THREADS) msm_recode_count(ScalarSet set, MsmParams p, uint32_t *hist, Fr *canon) {
     __shared__ uint32_t lcnt[1024];
     const uint32_t tid = threadIdx.x, m = blockIdx.y;
     lcnt[tid] = 0;
@@ -239,7 +244,11 @@ __global__ void __launch_bounds__(RC_THREADS) msm_recode_count(ScalarSet set, Ms
         const bool same = wave_same_scalar(k[r], live[r], lv);
         if (!live[r]) continue;
         int32_t d[RC_WINDOWS];
-        recode17(to_canonical(k[r]), d);
+        {
+            const FrW9 kc = fr_canonical_w(k[r]);
+            store_fp(canon + (size_t)m * p.n + (blockIdx.x * RC_COUNT_PER + r) * RC_THREADS + tid, pack<FrParams>(kc));
+            recode17_w(kc, d);
+        }
         if (same) {
             if ((tid & 63) == (uint32_t)(__ffsll((unsigned long long)lv) - 1)) {
 #pragma unroll
@@ -258,7 +267,8 @@ __global__ void __launch_bounds__(RC_THREADS) msm_recode_count(ScalarSet set, Ms
 
 // pass 2: the workgroup's 15 x 1024 entries are counting-sorted by coarse bin inside LDS, one global reservation per
 // (workgroup, bin), contiguous copy-out (same scheme as msm_partition<true>)
-__global__ void __launch_bounds__(RC_THREADS) msm_recode_scatter(ScalarSet set, MsmParams p, uint32_t *cursor, const uint32_t *bin_start, uint32_t *entries) {
+// (the scalars arrive canonical, from pass 1; "the same scalar in every lane" is asked of the canonical words — all that matters is that the digits agree)
+__global__ void __launch_bounds__(RC_THREADS) msm_recode_scatter(const Fr *canon, MsmParams p, uint32_t *cursor, const uint32_t *bin_start, uint32_t *entries) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint32_t *lcnt = reinterpret_cast<uint32_t *>(smem);               // [nbins]
     uint32_t *lstart = lcnt + p.nbins;                                 // [nbins + 1]
@@ -273,9 +283,9 @@ __global__ void __launch_bounds__(RC_THREADS) msm_recode_scatter(ScalarSet set, 
     bool same = false;                                                 // every live lane of this wave holds the same scalar (see msm_recode_count)
     uint32_t lane_rank = 0, wave_live = 0;
     if (live) {
-        const Fr k = load_fp(set.v[m] + i);
+        const Fr k = load_fp(canon + (size_t)m * p.n + i);
         same = wave_same_scalar(k, true, lv);
-        recode17(to_canonical(k), d);
+        recode17(k, d);
         lane_rank = (uint32_t)__popcll(lv & ((1ull << (tid & 63)) - 1)); wave_live = (uint32_t)__popcll(lv);
     } else {
 #pragma unroll
@@ -555,7 +565,9 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_fold_hot(XyzzW *partials, con
 // step loop — every step is "X += O" or "Y += X" with the operand selected beforehand — so the operands live
 // in registers: passing two 144-byte points to an out-of-line addition through scratch memory cost more
 // L2 write-through traffic than the arithmetic (measured 0.60 ms for this kernel against 0.3 ms of VALU work).
-template <uint32_t FB, uint32_t RL_LOG>
+// PAIRS: the addition is xyzzw_add_pairs (ec29_dev.h: lockstep product-scanning pairs, 19 % fewer instructions) — the instantiation launched when the
+// reduction is work-bound (16 lanes per task, see msm_big_launch); the latency instantiation keeps the operand-scanning chains.
+template <uint32_t FB, uint32_t RL_LOG, bool PAIRS = false>
 __global__ void __launch_bounds__(MSM_THREADS, 2) msm_task_reduce(const XyzzW *partials, const uint32_t *task_meta,
                                                                    const uint32_t *task_start, XyzzW *task_out, uint32_t total_bins) {
     constexpr uint32_t FINE = Shape<FB>::FINE, SLOT_PRIMARY = Shape<FB>::SLOT_PRIMARY, SLOT_HEAD = Shape<FB>::SLOT_HEAD, SLOT_TAIL = Shape<FB>::SLOT_TAIL,
@@ -622,7 +634,7 @@ __global__ void __launch_bounds__(MSM_THREADS, 2) msm_task_reduce(const XyzzW *p
         }
         if (to_y) O = Y;
         XyzzW Tacc = X;
-        xyzzw_add(Tacc, O);                                   // the one addition site of the kernel
+        if constexpr (PAIRS) xyzzw_add_pairs(Tacc, O); else xyzzw_add(Tacc, O);      // the one addition site of the kernel
         if (to_y) Y = Tacc; else X = Tacc;
     }
     if (live && sub == 0) store_xyzzw(task_out + 2 * (size_t)task, X);
@@ -887,9 +899,11 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
         const uint32_t cblocks = (uint32_t)((n + (uint64_t)RC_THREADS * RC_COUNT_PER - 1) / ((uint64_t)RC_THREADS * RC_COUNT_PER));
         const uint32_t sblocks = (uint32_t)((n + RC_SCALARS - 1) / RC_SCALARS);
         const size_t lds = (size_t)(3 * p.nbins + 1 + RC_SCALARS * RC_WINDOWS) * sizeof(uint32_t);
-        hipLaunchKernelGGL(msm_recode_count, dim3(cblocks, batch), dim3(RC_THREADS), 0, stream, set, p, hist);
+        PLK_TRY(S.f.reserve((size_t)batch * n * sizeof(Fr)));                             // canonical scalars, pass 1 -> pass 2
+        Fr *canon = S.f.as<Fr>();
+        hipLaunchKernelGGL(msm_recode_count, dim3(cblocks, batch), dim3(RC_THREADS), 0, stream, set, p, hist, canon);
         hipLaunchKernelGGL(msm_scan_bins, dim3(1), dim3(1024), 0, stream, hist, bin_start, task_start, total_bins);
-        hipLaunchKernelGGL(msm_recode_scatter, dim3(sblocks, batch), dim3(RC_THREADS), lds, stream, set, p, hist, (const uint32_t *)bin_start, entries);
+        hipLaunchKernelGGL(msm_recode_scatter, dim3(sblocks, batch), dim3(RC_THREADS), lds, stream, (const Fr *)canon, p, hist, (const uint32_t *)bin_start, entries);
     } else {
         PLK_TRY(S.f.reserve((size_t)total_windows * n * sizeof(int32_t)));
         int32_t *digits = S.f.as<int32_t>();
@@ -915,7 +929,8 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
     // (0.71 ms at 2^22 terms against ~0.45 lane-wise).
     // Otherwise lane-wise: 16 lanes per task for a batch of three or more commitments or when another commitment is in flight (a stream of commitments is
     // work-bound — every reduction wave displaces an accumulation wave of the next commitment for as long as it lives — and 16 lanes per task are fewer
-    // wave-microseconds), 32 lanes when latency is all that counts.
+    // wave-microseconds) and the addition built from lockstep product pairs (msm_task_reduce<.., true>: 19 % fewer instructions per addition; 8 lanes per task
+    // were measured on top and lost, profiles/msm_nonloop_diet_ab.txt), 32 lanes and the latency-bound addition when latency is all that counts.
     const bool others_in_flight = ctx->msm_enq != ctx->msm_fin;
     const uint32_t shape_lanes = (total_sets == 1 && !others_in_flight) ? 4u : ((batch >= 3 || others_in_flight) ? 16u : 32u);
     const uint32_t rblocks = (max_tasks * (shape_lanes == 16 ? 16u : 32u) + MSM_THREADS - 1) / MSM_THREADS;
@@ -926,7 +941,7 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
                            (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins);
     } else if (shape_lanes == 16) {
         hipLaunchKernelGGL((msm_fold_hot<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
-        hipLaunchKernelGGL((msm_task_reduce<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
+        hipLaunchKernelGGL((msm_task_reduce<FB, 4, true>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
                            (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins);
     } else {
         hipLaunchKernelGGL((msm_fold_hot<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);

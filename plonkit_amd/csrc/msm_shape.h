@@ -60,6 +60,20 @@ PLK_HD void recode17(const Fr &k, int32_t (&d)[RC_WINDOWS]) {
         if (v >= (1u << 16) && w + 1 < RC_WINDOWS) { d[w] = (int32_t)v - (1 << 17); carry = 1; } else { d[w] = (int32_t)v; carry = 0; }
     }
 }
+// the same digits from the nine 29-bit limbs of the canonical scalar (fr_canonical_w), without packing it into words first: window w is bits
+// 17w .. 17w+16 of the same integer, which lie in limb 17w / 29 and, where they cross its end, the next one.  recode17_w(fr_canonical_w(k))
+// == recode17(to_canonical(k)) digit for digit (tests/host/field29_pairs_check.hip).
+PLK_HD void recode17_w(const FrW9 &k, int32_t (&d)[RC_WINDOWS]) {
+    uint32_t carry = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < RC_WINDOWS; w++) {
+        const uint32_t limb = (w * 17) / 29, off = (w * 17) % 29;
+        uint32_t v = k.l[limb] >> off;
+        if (off + 17 > 29 && limb + 1 < 9) v |= k.l[limb + 1] << (29 - off);
+        v = (v & ((1u << 17) - 1)) + carry;
+        if (v >= (1u << 16) && w + 1 < RC_WINDOWS) { d[w] = (int32_t)v - (1 << 17); carry = 1; } else { d[w] = (int32_t)v; carry = 0; }
+    }
+}
 
 // Per-task output of kernel A: 128 PRIMARY slots (a bucket whose run lies inside one lane's slice), and per
 // lane one HEAD slot (its first run continues a bucket begun by an earlier lane) and one TAIL slot (its last
