@@ -9,6 +9,9 @@
 //          X3 = R^2-PPP-2Q+4p < 5.5   T = Q-X3+6p < 7.05   Y3 = R*T + Y*(2p-PPP) (one reduction) < 1.5
 //   add :  U,S < 1.05  P,R < 3.05  PP < 1.06  X3 < 5.06  Y3 < 3.2
 //   dbl :  U = 2Y < 12  V < 1.85  W < 1.14  S < 1.07  M = 3X^2 < 3.7  X3 < 5.1  Y3 < 3.2
+// The two additions priced by instruction count (xyzzw_add_mixed_flag, xyzzw_add_pairs) take their products with lazy Montgomery digits
+// (field29_dev.h: *_lz): every product there is below the figure above + 2^-26 p, which no bound above notices (the tightest slack is
+// R < 9.1 of 16 for maybe_zero_mod_p); the integers are the masked forms' or, about once in 2^26 products, larger by exactly p.
 #pragma once
 #include "field29_dev.h"
 #include "ec_dev.h"
@@ -24,9 +27,16 @@ struct alignas(16) XyzzW { FqW9 x, y, zz, zzz; };              // 144 bytes
 #define WS(a) sqrw<FqW>((a))                               // normalised input; 126 mads instead of 162
 #define WMA(a, b, c, d) mul2addw<FqW>((a), (b), (c), (d))  // a*b + c*d, one reduction
 // the latency-bound chains (full addition, doubling: bucket reduction, table build) take the operand-scanning forms
+#define WMA_LZ(a, b, c, d) mul2addw_lz<FqW, LZ_ALL, LbNorm, LbT, LbNorm, LbNppp>((a), (b), (c), (d))   // the fused Y3 of the work-priced additions
 #define LM(a, b) mulw_os<FqW>((a), (b))
 #define LS(a) sqrw_os<FqW>((a))
 #define LMA(a, b, c, d) mul2addw_os<FqW>((a), (b), (c), (d))
+
+// Declared limb bounds of the operands that the lazy-digit products (field29_dev.h: *_lz) of xyzzw_add_mixed_flag and xyzzw_add_pairs take
+// un-normalised; every other operand there is LbNorm.  Each instantiation checks its exact per-column worst case at these bounds at compile time.
+struct LbSignedY { static constexpr Limbs9 B = lb_max(LbNorm::B, lb_of(FqW::PAD2)); };     // +-y: y, or 2p - y as it stands (limbs <= PAD2's)
+struct LbT { static constexpr Limbs9 B = lb_plus(lb_of(FqW::PAD6N), M29); };               // T = Q + (6p - X3) from PAD6N; Q, X3 normalised
+struct LbNppp { static constexpr Limbs9 B = lb_of(FqW::PAD2N); };                          // 2p - PPP from PAD2N; PPP normalised
 
 PLK_HD bool is_inf(const XyzzW &p) { return w_all_zero(p.zz); }
 PLK_HD bool is_inf(const AffW &p) { return w_all_zero(p.x) && w_all_zero(p.y); }
@@ -105,7 +115,7 @@ PLK_HD void xyzzw_add_mixed(XyzzW &acc, const AffW &q, bool neg_q) {
 }
 
 // The same addition for the flat loop of msm_accumulate's plain kernel, with less work around the ten products.  The same point mod p in
-// every coordinate; the same integers, bit for bit, unless y is negated (tests/host/field29_addend_check.hip holds the earlier form).
+// every coordinate (tests/host/field29_addend_check.hip holds the earlier form, tests/host/field29_lazy_digits_check.hip the one with masked digits).
 //   - No is_inf(q): the caller runs this only over a table that holds no point at infinity (msm.hip establishes that where it builds the
 //     table).  is_inf(acc), an OR over nine limbs in every addition, is the lane flag `fresh`: the caller sets it where it sets acc to
 //     the identity (start, after a flush); it is cleared by the first point taken and set again where the special path returns the
@@ -119,46 +129,71 @@ PLK_HD void xyzzw_add_mixed(XyzzW &acc, const AffW &q, bool neg_q) {
 //     pads with the 2^29 bias (PAD6N, PAD2N: X3 and PPP are normalised), so their limbs stay below 1.45e9 and 1.02e9; R and Y are
 //     normalised, and a column holds at most 9 * (2^29 * 1.45e9 + 2^29 * 1.02e9 + (2^29)^2) + 2^35 < 0.79 * 2^64 (host-checked with a
 //     128-bit shadow of the chain at exactly these limbs).  With the 2^31 pads the same column reaches 1.6 * 2^64.
+//   - Lazy Montgomery digits in all nine reductions (mulw2_add_lz, sqrw2_lz, mulw2_lz twice, mul2addw_lz; LZ_ALL: m_0..m_7 unmasked, 72
+//     v_and_b32 fewer per addition).  Every operand is normalised (LbNorm) except +-y (LbSignedY: limbs <= PAD2's), the two addends (LbAny) and
+//     the right operands T and 2p - PPP of the fused Y3 (LbT, LbNppp: the 2^29-bias pads).  Exact worst columns at those bounds, checked at
+//     compile time: 0.50 * 2^64 for the normalised products and squarings, 0.92 * 2^64 for the +-y chain with its addend, 0.85 * 2^64 for Y3.
+//     (A uniform bound over the left operand, 9 * 2.63e9 * 2^29, would put the +-y chain at 2^64.09; limb by limb PAD2 sums to 18.8e9, not 23.7e9.)
 // Not folded: X3 = R^2 + (4p - PPP - 2Q) needs R^2 after PPP and Q; the lockstep pairs would have to become PP alone, (PPP, Q),
 // (R^2 + addend, ZZ*PP), ZZZ*PPP alone — two single chains, whose wait states only the second wave hides, for ~25 instructions.
-PLK_HD void xyzzw_add_mixed_flag(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) {
-    if (fresh) { acc.x = q.x; acc.y = neg_q ? neg2(q.y) : q.y; acc.zz = w_one<FqW>(); acc.zzz = w_one<FqW>(); fresh = false; return; }
+// NXY (the loop of msm_accumulate's plain kernel): acc.x and acc.y hold NX = -X and NY = -Y (mod p) between the additions, zz and zzz as
+// they are.  The padded 6p - X and 8p - Y that P and R take as addends are then the coordinates themselves and are not formed (18
+// subtractions an iteration): P = U2 + NX, R = S2 + NY.  NQ = NX * PP = -Q, so NX3 = PPP + 2Q - R^2 = PPP - 2 NQ - R^2 + 4p, and
+// NY3 = -(R (Q - X3) - Y PPP) = R (NQ - NX3 + 6p) + NY (2p - PPP): the same fused product with the same pads.  Bounds: R^2 < 1.5p and
+// 2 NQ < 2.1p leave NX3 positive and below 5.06p, so P < 6.1p; NY3 < 1.5p, a first point enters as 2p - x and 2p -+ y (< 2p): R < 3.1p.
+// xyzzw_flip_xy converts in both directions (6p - c: an accumulator's x, y < 6p on either side) where the sum leaves the loop (the flush)
+// and around the cold P = +-Q path.  The identity is zz = 0 whatever x and y hold: the one that path returns carries 6p - 0 in both
+// and flips back to all zero (keeping it zero in place costs the hot path 24 moves: two values merge at the loop's head).
+PLK_HD XyzzW xyzzw_flip_xy(const XyzzW &a) { XyzzW r = a; r.x = sub6(w_zero<FqW>(), a.x); r.y = sub6(w_zero<FqW>(), a.y); return r; }
+template <bool NXY>
+PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) {
+    if (fresh) {
+        if constexpr (NXY) { acc.x = neg2(q.x); acc.y = neg_q ? q.y : neg2(q.y); }
+        else { acc.x = q.x; acc.y = neg_q ? neg2(q.y) : q.y; }
+        acc.zz = w_one<FqW>(); acc.zzz = w_one<FqW>(); fresh = false; return;
+    }
     FqW9 p, r, yq;
-    {
+#pragma unroll
+    for (int i = 0; i < 9; i++) yq.l[i] = neg_q ? FqW::PAD2[i] - q.y.l[i] : q.y.l[i];           // 2p - y (limbs <= 2.63e9 < MULW_A_LIMB_MAX, value < 2p) or y
+    if constexpr (NXY) mulw2_add_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbSignedY, LbNorm, LbNorm>(q.x, acc.zz, acc.x, yq, acc.zzz, acc.y, p, r);   // P = U2 + NX,  R = S2 + NY
+    else {
         FqW9 ax, ay;
 #pragma unroll
         for (int i = 0; i < 9; i++) {
             ax.l[i] = FqW::PAD6[i] - acc.x.l[i];                         // 6p - X, 8p - Y: limbs <= the pads' (< 2^32), not normalised
             ay.l[i] = FqW::PAD8[i] - acc.y.l[i];
-            yq.l[i] = neg_q ? FqW::PAD2[i] - q.y.l[i] : q.y.l[i];       // 2p - y (limbs <= 2.63e9 < MULW_A_LIMB_MAX, value < 2p) or y
         }
-        mulw2_add<FqW>(q.x, acc.zz, ax, yq, acc.zzz, ay, p, r);          // P = U2 + (6p - X),  R = S2 + (8p - Y)
+        mulw2_add_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbAny, LbSignedY, LbNorm, LbAny>(q.x, acc.zz, ax, yq, acc.zzz, ay, p, r);          // P = U2 + (6p - X),  R = S2 + (8p - Y)
     }
     if (maybe_zero_mod_p(p)) {                               // P == +-Q: rare, kept out of the hot code
         AffW t; t.x = q.x; t.y = normw(yq);                    // (+-y as xyzzw_add_mixed forms it: neg2(y) = normw(2p - y), y is normalised)
+        if constexpr (NXY) acc = xyzzw_flip_xy(acc);
         xyzzw_add_mixed_special(acc, t, false, p, r);
         fresh = is_inf(acc);
+        if constexpr (NXY) acc = xyzzw_flip_xy(acc);
         return;
     }
     FqW9 pp, rr, ppp, qq;
-    sqrw2<FqW>(p, r, pp, rr);
-    mulw2<FqW>(p, pp, acc.x, pp, ppp, qq);
+    sqrw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm>(p, r, pp, rr);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(p, pp, acc.x, pp, ppp, qq);            // (NXY: qq = NQ = -Q)
     FqW9 x3;
     {
 #pragma unroll
-        for (int i = 0; i < 9; i++) x3.l[i] = rr.l[i] + FqW::PAD4[i] - ppp.l[i] - 2 * qq.l[i];
+        for (int i = 0; i < 9; i++) x3.l[i] = NXY ? ppp.l[i] + FqW::PAD4[i] - rr.l[i] - 2 * qq.l[i] : rr.l[i] + FqW::PAD4[i] - ppp.l[i] - 2 * qq.l[i];
         x3 = normw(x3);
     }
     FqW9 zz3, zzz3;
-    mulw2<FqW>(acc.zz, pp, acc.zzz, ppp, zz3, zzz3);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(acc.zz, pp, acc.zzz, ppp, zz3, zzz3);
     FqW9 t, nppp;
 #pragma unroll
     for (int i = 0; i < 9; i++) { t.l[i] = qq.l[i] + FqW::PAD6N[i] - x3.l[i]; nppp.l[i] = FqW::PAD2N[i] - ppp.l[i]; }
-    acc.y = WMA(r, t, acc.y, nppp);                           // R*(Q - X3) - Y*PPP, one reduction
+    acc.y = WMA_LZ(r, t, acc.y, nppp);                        // R*(Q - X3) - Y*PPP, one reduction (NXY: R*(NQ - NX3) - NY*PPP = NY3)
     acc.x = x3;
     acc.zz = zz3;
     acc.zzz = zzz3;
 }
+PLK_HD void xyzzw_add_mixed_flag(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) { xyzzw_add_mixed_flag_impl<false>(acc, fresh, q, neg_q); }
+PLK_HD void xyzzw_add_mixed_nflag(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) { xyzzw_add_mixed_flag_impl<true>(acc, fresh, q, neg_q); }
 
 // a += b
 PLK_HD void xyzzw_add(XyzzW &a, const XyzzW &b) {
@@ -188,9 +223,10 @@ PLK_HD void xyzzw_add(XyzzW &a, const XyzzW &b) {
 // a += b for the WORK-bound bucket reduction (msm_task_reduce<.., PAIRS>: a batch of three or more, or other commitments in flight — two of
 // these chains per SIMD beside another commitment's accumulation, priced by the instructions they issue, not by their latency): the same
 // fourteen products as xyzzw_add, issued as the lockstep product-scanning pairs of the mixed addition (~205 instructions per product against
-// ~243 of a lone operand-scanning chain) and the fused Y3 as one product-scanning chain.  The same integers as xyzzw_add in all 36 limbs:
-// mulw / sqrw / mul2addw and their _os forms return the same normalised (a*b + m*p) / 2^261, and the two folds below keep the integers
-// (tests/host/field29_pairs_check.hip: > 10^5 operands as the reduction feeds them in, every chain shadowed in 128 bits).
+// ~243 of a lone operand-scanning chain) and the fused Y3 as one product-scanning chain.  The same residues as xyzzw_add in all four
+// coordinates, and the same integers unless a lazy multiplier passes 2^261 (then larger by p): mulw / sqrw / mul2addw and their _os forms
+// return the same normalised (a*b + m*p) / 2^261, and the two folds below keep the integers (tests/host/field29_pairs_check.hip: > 10^5
+// operands as the reduction feeds them in, every chain shadowed in 128 bits; tests/host/field29_lazy_digits_check.hip for the lazy digits).
 //   - Pairs: (U1, S1), (U2, S2), (ZZ1*ZZ2, ZZZ1*ZZZ2), (PP, RR) as squarings, (PPP, Q), (ZZ3, ZZZ3).  U1 and S1 go first because
 //   - P = U2 + (2p - U1) and R = S2 + (2p - S1) come out of the second pair itself (mulw2_add): the padded differences are addends of its
 //     high columns, whose carry chain normalises the sums — bit for bit sub2(U2, U1) and sub2(S2, S1), without their 9 additions and normw.
@@ -204,17 +240,20 @@ PLK_HD void xyzzw_add(XyzzW &a, const XyzzW &b) {
 //   - mulw2 / mulw2_add, left operands X1, Y1, X2, Y2, ZZ1, ZZZ1, P, U1, ZZ1*ZZ2, ZZZ1*ZZZ2: limbs < 2^29, far below MULW_A_LIMB_MAX = 3.28e9;
 //     a column holds at most 2 * 9 * (2^29 - 1)^2 + 2^35 (+ 2^32 for an addend) < 2^62.2.
 //   - sqrw2 of (P, R): the doubled limbs stay below 2^30, a column at most 9 * (2^30 * 2^29 + 2^58) + 2^35 < 2^62.8.
+//   - Lazy Montgomery digits in all thirteen reductions (LZ_ALL, 104 v_and_b32 fewer): the normalised operands above are LbNorm, the addends
+//     LbAny, T and 2p - PPP LbT and LbNppp; worst columns as in xyzzw_add_mixed_flag (0.50 * 2^64 normalised, 0.85 * 2^64 for Y3), checked at
+//     compile time.  Values grow by less than 2^-26 p per product: is_zero_mod_p's a < 16p holds with P, R < 3.05p as before.
 // Values: U, S < 6 * 1.3 * 0.0059p + p < 1.05p; PP < 3.05^2 * 0.0059p + p < 1.06p; X3 < 5.06p; Y3 < (3.05 * 7.1 + 1.05 * 2) * 0.0059p + p < 1.2p.
 PLK_HD void xyzzw_add_pairs(XyzzW &a, const XyzzW &b) {
     if (is_inf(b)) return;
     if (is_inf(a)) { a = b; return; }
     FqW9 u1, s1, p, r;
-    mulw2<FqW>(a.x, b.zz, a.y, b.zzz, u1, s1);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(a.x, b.zz, a.y, b.zzz, u1, s1);
     {
         FqW9 nu, ns;
 #pragma unroll
         for (int i = 0; i < 9; i++) { nu.l[i] = FqW::PAD2[i] - u1.l[i]; ns.l[i] = FqW::PAD2[i] - s1.l[i]; }     // 2p - U1, 2p - S1: not normalised
-        mulw2_add<FqW>(b.x, a.zz, nu, b.y, a.zzz, ns, p, r);
+        mulw2_add_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbAny, LbNorm, LbNorm, LbAny>(b.x, a.zz, nu, b.y, a.zzz, ns, p, r);
     }
     if (is_zero_mod_p(p)) {
         if (is_zero_mod_p(r)) a = xyzzw_double(a);
@@ -222,14 +261,14 @@ PLK_HD void xyzzw_add_pairs(XyzzW &a, const XyzzW &b) {
         return;
     }
     FqW9 zz12, zzz12;
-    mulw2<FqW>(a.zz, b.zz, a.zzz, b.zzz, zz12, zzz12);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(a.zz, b.zz, a.zzz, b.zzz, zz12, zzz12);
     FqW9 pp, rr, ppp, qq;
     // (P and R are hidden from the optimiser here: knowing from the chain's masks that their limbs are below 2^29, it widens the squarings'
     //  doubled limbs "x << 1" to 33-bit values and pays two multiply-adds and two moves for each of ~100 products)
 #pragma unroll
     for (int i = 0; i < 9; i++) { PLK_CHAIN(p.l[i]); PLK_CHAIN(r.l[i]); }
-    sqrw2<FqW>(p, r, pp, rr);
-    mulw2<FqW>(p, pp, u1, pp, ppp, qq);
+    sqrw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm>(p, r, pp, rr);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(p, pp, u1, pp, ppp, qq);
     FqW9 x3;
     {
 #pragma unroll
@@ -239,9 +278,9 @@ PLK_HD void xyzzw_add_pairs(XyzzW &a, const XyzzW &b) {
     FqW9 t, nppp;
 #pragma unroll
     for (int i = 0; i < 9; i++) { t.l[i] = qq.l[i] + FqW::PAD6N[i] - x3.l[i]; nppp.l[i] = FqW::PAD2N[i] - ppp.l[i]; }
-    a.y = WMA(r, t, s1, nppp);                                // R*(Q - X3) - S1*PPP, one reduction
+    a.y = WMA_LZ(r, t, s1, nppp);                             // R*(Q - X3) - S1*PPP, one reduction
     a.x = x3;
-    mulw2<FqW>(zz12, pp, zzz12, ppp, a.zz, a.zzz);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(zz12, pp, zzz12, ppp, a.zz, a.zzz);
 }
 
 // storage <-> registers

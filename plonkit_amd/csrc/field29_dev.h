@@ -331,6 +331,146 @@ PLK_HD W9<WP> mul2addw(const W9<WP> &a, const W9<WP> &b, const W9<WP> &c, const 
     return r;
 }
 
+// ---- LAZY MONTGOMERY DIGITS: the same lockstep products with some of the digits m_0..m_7 left UNMASKED (the additions the MSM prices by
+// the instructions they issue: xyzzw_add_mixed_flag, xyzzw_add_pairs).  A column's digit is m_k = ((uint32_t)acc * INV29) & M29, but any
+// m~_k = m_k (mod 2^29) clears the column's low 29 bits just as well: (a*b + m~*p) / 2^261 stays an exact integer congruent to a*b*2^-261,
+// and the `& M29` of that digit, one VALU instruction, is not issued.  Two things depend on the mask, and both are kept:
+//   - the VALUE of the result.  Digit 8 is always masked: with m~_0..m~_7 < 2^32 and m~_8 < 2^29, m~ = sum m~_k 2^(29 k) < 2^261 + 2^235, and
+//     m~ = m (mod 2^261), so m~ is m or m + 2^261: the result is the masked form's or that plus p EXACTLY, and it is below the masked form's
+//     bound + 2^-26 p.  Every value bound of ec29_dev.h has more slack than that.  Output limbs are normalised as before.
+//   - the 64-bit COLUMN.  An unmasked digit is up to 2^32 - 1 and the carries grow with it, so every instantiation evaluates its exact worst
+//     case at compile time (lazy_col_bound: every limb of both operands at its DECLARED bound, a Limbs9 per operand; every unmasked digit at
+//     2^32 - 1 against the actual limbs of p; the addend where there is one; the carry the worst column before it really leaves, < 2^35 with all
+//     digits masked) and a static_assert requires every column below 2^64: a form that does not fit does not compile.  The declared bounds
+//     are the caller's promise, checked on the host at exactly those limbs with a 128-bit shadow (tests/host/field29_lazy_digits_check.hip).
+// LZ is the set of unmasked digits, bit k for m_k; bit 8 and above are ignored.  LZ = 0 is the masked form, instruction for instruction.
+struct Limbs9 { uint32_t l[9]; };                              // per-limb upper bounds of an operand (inclusive)
+constexpr Limbs9 lb_uniform(uint32_t v) { return Limbs9{{v, v, v, v, v, v, v, v, v}}; }
+constexpr Limbs9 lb_of(const uint32_t (&a)[9]) { return Limbs9{{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]}}; }
+constexpr Limbs9 lb_plus(const Limbs9 &a, uint32_t v) { Limbs9 r{}; for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + v; return r; }
+constexpr bool lb_below(const Limbs9 &a, uint32_t v) { for (int i = 0; i < 9; i++) if (a.l[i] >= v) return false; return true; }
+constexpr Limbs9 lb_max(const Limbs9 &a, const Limbs9 &b) { Limbs9 r{}; for (int i = 0; i < 9; i++) r.l[i] = a.l[i] > b.l[i] ? a.l[i] : b.l[i]; return r; }
+struct LbNone { static constexpr Limbs9 B = lb_uniform(0); };                 // no such operand
+struct LbNorm { static constexpr Limbs9 B = lb_uniform(M29); };               // normalised: out of a column chain or normw, value < 2^261
+struct LbAny { static constexpr Limbs9 B = lb_uniform(0xffffffffu); };        // an addend as it stands (a padded difference, not normalised)
+constexpr unsigned LZ_ALL = 0xffu;
+constexpr bool lazy_digit(unsigned lz, int k) { return k < 8 && ((lz >> k) & 1u); }
+struct ColBound { uint64_t worst; bool fits; };                // the largest column (wrapped if it does not fit); all columns below 2^64
+// columns of a*b + c*d + m~*p (+ addend in the high columns), m~ with the digits of lz unmasked.  A squaring is a = b = the operand's bounds:
+// the doubled cross products and the square of a column sum to the same worst case.
+constexpr ColBound lazy_col_bound(const Limbs9 &a, const Limbs9 &b, const Limbs9 &c, const Limbs9 &d, const Limbs9 &addend, const uint32_t (&p)[9], unsigned lz) {
+    uint64_t carry = 0, worst = 0;
+    bool fits = true;
+    for (int k = 0; k < 17; k++) {
+        uint64_t s = carry;
+        for (int i = (k < 9 ? 0 : k - 8); i <= (k < 9 ? k : 8); i++) {
+            fits &= !__builtin_add_overflow(s, (uint64_t)a.l[k - i] * b.l[i], &s);
+            fits &= !__builtin_add_overflow(s, (uint64_t)c.l[k - i] * d.l[i], &s);
+            fits &= !__builtin_add_overflow(s, (uint64_t)(lazy_digit(lz, i) ? 0xffffffffu : M29) * p[k - i], &s);
+        }
+        if (k >= 9) fits &= !__builtin_add_overflow(s, (uint64_t)addend.l[k - 9], &s);
+        if (s > worst) worst = s;
+        carry = s >> 29;
+    }
+    return ColBound{worst, fits};
+}
+#define PLK_LZ_DIGIT(LZ, k, acc) (lazy_digit((LZ), (k)) ? (uint32_t)(acc) * WP::INV29 : ((uint32_t)(acc) * WP::INV29) & M29)
+#define PLK_MONT_LOW_LZ(k)   { _Pragma("unroll") for (int i = 0; i < (k); i++) { acc += (uint64_t)m[i] * WP::P29[(k) - i]; PLK_CHAIN(acc); } \
+                               m[k] = PLK_LZ_DIGIT(LZ, k, acc); acc += (uint64_t)m[k] * WP::P29[0]; acc >>= 29; }
+#define PLK_MONT_LOW2_LZ(k)  { _Pragma("unroll") for (int i = 0; i < (k); i++) { acc0 += (uint64_t)m0[i] * WP::P29[(k) - i]; PLK_CHAIN(acc0); acc1 += (uint64_t)m1[i] * WP::P29[(k) - i]; PLK_CHAIN(acc1); } \
+                               m0[k] = PLK_LZ_DIGIT(LZ0, k, acc0); m1[k] = PLK_LZ_DIGIT(LZ1, k, acc1); \
+                               acc0 += (uint64_t)m0[k] * WP::P29[0]; acc1 += (uint64_t)m1[k] * WP::P29[0]; acc0 >>= 29; acc1 >>= 29; }
+// mulw2 with lazy digits; LA0, LB0, LA1, LB1: the declared limb bounds of a0, b0, a1, b1
+template <class WP, unsigned LZ0, unsigned LZ1, class LA0, class LB0, class LA1, class LB1>
+PLK_HD void mulw2_lz(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &a1, const W9<WP> &b1, W9<WP> &r0, W9<WP> &r1) {
+    static_assert(lazy_col_bound(LA0::B, LB0::B, LbNone::B, LbNone::B, LbNone::B, WP::P29, LZ0).fits, "mulw2_lz: a column of chain 0 can exceed 64 bits");
+    static_assert(lazy_col_bound(LA1::B, LB1::B, LbNone::B, LbNone::B, LbNone::B, WP::P29, LZ1).fits, "mulw2_lz: a column of chain 1 can exceed 64 bits");
+    uint32_t m0[9], m1[9];
+    uint64_t acc0 = 0, acc1 = 0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
+        PLK_MONT_LOW2_LZ(k)
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) {
+#pragma unroll
+        for (int i = k - 8; i <= 8; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
+        PLK_MONT_HIGH2(k)
+    }
+    r0.l[8] = (uint32_t)acc0; r1.l[8] = (uint32_t)acc1;
+}
+// sqrw2 with lazy digits; LX0, LX1: the declared limb bounds of x0, x1 (below 2^31: the doubled limb is a 32-bit value)
+template <class WP, unsigned LZ0, unsigned LZ1, class LX0, class LX1>
+PLK_HD void sqrw2_lz(const W9<WP> &x0, const W9<WP> &x1, W9<WP> &r0, W9<WP> &r1) {
+    static_assert(lazy_col_bound(LX0::B, LX0::B, LbNone::B, LbNone::B, LbNone::B, WP::P29, LZ0).fits, "sqrw2_lz: a column of chain 0 can exceed 64 bits");
+    static_assert(lazy_col_bound(LX1::B, LX1::B, LbNone::B, LbNone::B, LbNone::B, WP::P29, LZ1).fits, "sqrw2_lz: a column of chain 1 can exceed 64 bits");
+    static_assert(lb_below(LX0::B, 1u << 31) && lb_below(LX1::B, 1u << 31), "sqrw2_lz: a doubled limb can exceed 32 bits");
+    uint32_t m0[9], m1[9], d0[9], d1[9];
+    uint64_t acc0 = 0, acc1 = 0;
+#pragma unroll
+    for (int j = 0; j < 9; j++) { d0[j] = x0.l[j] << 1; d1[j] = x1.l[j] << 1; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+#pragma unroll
+        for (int i = 0; 2 * i < k; i++) { acc0 += (uint64_t)d0[k - i] * x0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)d1[k - i] * x1.l[i]; PLK_CHAIN(acc1); }
+        if (k % 2 == 0) { acc0 += (uint64_t)x0.l[k / 2] * x0.l[k / 2]; PLK_CHAIN(acc0); acc1 += (uint64_t)x1.l[k / 2] * x1.l[k / 2]; PLK_CHAIN(acc1); }
+        PLK_MONT_LOW2_LZ(k)
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) {
+#pragma unroll
+        for (int i = k - 8; 2 * i < k; i++) { acc0 += (uint64_t)d0[k - i] * x0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)d1[k - i] * x1.l[i]; PLK_CHAIN(acc1); }
+        if (k % 2 == 0) { acc0 += (uint64_t)x0.l[k / 2] * x0.l[k / 2]; PLK_CHAIN(acc0); acc1 += (uint64_t)x1.l[k / 2] * x1.l[k / 2]; PLK_CHAIN(acc1); }
+        PLK_MONT_HIGH2(k)
+    }
+    r0.l[8] = (uint32_t)acc0; r1.l[8] = (uint32_t)acc1;
+}
+// mulw2_add with lazy digits; LAD0, LAD1: the declared limb bounds of the addends A0, A1
+template <class WP, unsigned LZ0, unsigned LZ1, class LA0, class LB0, class LAD0, class LA1, class LB1, class LAD1>
+PLK_HD void mulw2_add_lz(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &A0, const W9<WP> &a1, const W9<WP> &b1, const W9<WP> &A1, W9<WP> &r0, W9<WP> &r1) {
+    static_assert(lazy_col_bound(LA0::B, LB0::B, LbNone::B, LbNone::B, LAD0::B, WP::P29, LZ0).fits, "mulw2_add_lz: a column of chain 0 can exceed 64 bits");
+    static_assert(lazy_col_bound(LA1::B, LB1::B, LbNone::B, LbNone::B, LAD1::B, WP::P29, LZ1).fits, "mulw2_add_lz: a column of chain 1 can exceed 64 bits");
+    uint32_t m0[9], m1[9];
+    uint64_t acc0 = 0, acc1 = 0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
+        PLK_MONT_LOW2_LZ(k)
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) {
+#pragma unroll
+        for (int i = k - 8; i <= 8; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
+        PLK_MONT_HIGH2_ADD(k)
+    }
+    r0.l[8] = (uint32_t)acc0 + A0.l[8]; r1.l[8] = (uint32_t)acc1 + A1.l[8];
+}
+// mul2addw with lazy digits; LA, LB, LC, LD: the declared limb bounds of a, b, c, d
+template <class WP, unsigned LZ, class LA, class LB, class LC, class LD>
+PLK_HD W9<WP> mul2addw_lz(const W9<WP> &a, const W9<WP> &b, const W9<WP> &c, const W9<WP> &d) {
+    static_assert(lazy_col_bound(LA::B, LB::B, LC::B, LD::B, LbNone::B, WP::P29, LZ).fits, "mul2addw_lz: a column can exceed 64 bits");
+    uint32_t m[9];
+    W9<WP> r;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) { acc += (uint64_t)a.l[k - i] * b.l[i]; PLK_CHAIN(acc); acc += (uint64_t)c.l[k - i] * d.l[i]; PLK_CHAIN(acc); }
+        PLK_MONT_LOW_LZ(k)
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) {
+#pragma unroll
+        for (int i = k - 8; i <= 8; i++) { acc += (uint64_t)a.l[k - i] * b.l[i]; PLK_CHAIN(acc); acc += (uint64_t)c.l[k - i] * d.l[i]; PLK_CHAIN(acc); }
+        PLK_MONT_HIGH(k)
+    }
+    r.l[8] = (uint32_t)acc;
+    return r;
+}
+
 // ---- product by a CONSTANT that is held as three shifted copies ("tw3"): 108 multiply-adds instead of 162.
 // For a constant w keep  W_q = w * 2^(87 (q+1)) mod p  (q = 0, 1, 2; canonical, 9 limbs each).  Split the variable operand into
 // three chunks of three limbs, x = X_0 + X_1 2^87 + X_2 2^174: then  X_0 W_0 + X_1 W_1 + X_2 W_2 = x * w * 2^87 (mod p)  and all

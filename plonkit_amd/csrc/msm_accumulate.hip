@@ -144,7 +144,10 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
     if constexpr (!OWNED && !Q_MAY_BE_INF) {
         // The plain kernel for a table without a point at infinity (msm.hip establishes that where it builds the table).  Same flat loop
         // as below; what differs is what each iteration carries besides the addition:
-        //   - xyzzw_add_mixed_flag: no is_inf(q), `fresh` instead of is_inf(acc), addends folded into the products (ec29_dev.h);
+        //   - xyzzw_add_mixed_nflag: no is_inf(q), `fresh` instead of is_inf(acc), addends folded into the products, and the accumulator's
+        //     x and y carried NEGATED between the additions (ec29_dev.h); a flush stores xyzzw_flip_xy(acc), the sum itself;
+        //   - the point is carried across the iteration boundary UNPACKED (nxt): unpacking at the top of the iteration, into registers the
+        //     addition reads while the packed words of the next gather arrive, cost eight instructions an iteration;
         //   - the bucket of the current run and where the run began are not kept in registers: a flush reads the bucket back from the
         //     entry before it (i == bend > lo, so there is one), and "the run began at lo" is the flag `first_run`.
         const uint32_t lo = tid * mu < nc ? tid * mu : nc, hi = lo + mu < nc ? lo + mu : nc;
@@ -153,23 +156,25 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
         G1Affine pt = load_affine(point_of(en));
         uint32_t bend = start[(en & (FINE - 1)) + 1];
         XyzzW acc = xyzzw_identity();
+        AffW nxt; nxt.x = unpack<FqW>(pt.x); nxt.y = unpack<FqW>(pt.y);
         bool fresh = true, first_run = true;
         for (uint32_t i = lo; i < hi; i++) {
             const uint32_t e_cur = en;
-            AffW cur; cur.x = unpack<FqW>(pt.x); cur.y = unpack<FqW>(pt.y);
+            const AffW cur = nxt;
             if (i + 1 < hi) { en = sorted[i + 1]; pt = load_affine(point_of(en)); }   // prefetch the next gather
             if (i == bend) {                                      // the previous bucket ended inside this piece
                 const uint32_t b = sorted[i - 1] & (FINE - 1);
                 const bool from_prev = first_run && (start[b] < tid * mu);
-                store_xyzzw(out + (from_prev ? SLOT_HEAD + tid : SLOT_PRIMARY + b), acc);
+                store_xyzzw(out + (from_prev ? SLOT_HEAD + tid : SLOT_PRIMARY + b), xyzzw_flip_xy(acc));
                 acc = xyzzw_identity(); fresh = true; first_run = false;
                 bend = start[(e_cur & (FINE - 1)) + 1];
             }
-            xyzzw_add_mixed_flag(acc, fresh, cur, (e_cur & 0x80u) != 0);
+            xyzzw_add_mixed_nflag(acc, fresh, cur, (e_cur & 0x80u) != 0);
+            nxt.x = unpack<FqW>(pt.x); nxt.y = unpack<FqW>(pt.y);   // the prefetched point, unpacked after the addition and carried into the next iteration
         }
         const uint32_t b = sorted[hi - 1] & (FINE - 1);
         const bool from_prev = first_run && (start[b] < tid * mu), into_next = bend > hi;
-        store_xyzzw(out + (from_prev ? SLOT_HEAD + tid : (into_next ? SLOT_TAIL + tid : SLOT_PRIMARY + b)), acc);
+        store_xyzzw(out + (from_prev ? SLOT_HEAD + tid : (into_next ? SLOT_TAIL + tid : SLOT_PRIMARY + b)), xyzzw_flip_xy(acc));
         return;
     }
     const bool own = OWNED && owned;
