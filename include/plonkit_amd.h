@@ -784,6 +784,38 @@ int32_t plk_setup_permutation_dev(plk_ctx *ctx, const void *const vars_dev[4], u
                                   void *index_dev /* 4 * 2^log_n uint32, may be NULL */,
                                   void *const sigmas_dev[4] /* 2^log_n plk_fr each, may be NULL */, void *stream);
 
+/* ---- which copy constraint is broken: the exact checks behind "copy constraints: the permutation argument does not close" of
+ *      plk_prove_assembled* (prove_by_steps on a caller's sigma and columns, src/plonk.rs:152-159; bellman reports nothing here).
+ *      No key, no transcript, no beta / gamma: nothing below is probabilistic.
+ *      plk_sigma_decode_dev is the inverse of the sigmas_dev output of plk_setup_permutation_dev: every value x of the four columns
+ *      that equals k_c * omega_N^i (k = 1, 5, 7, 10, i < N = 2^log_n, Montgomery form) gives idx[col * N + row] = c << 30 | i, every
+ *      other value — 0, another coset, an element of order 2N, limbs >= r — gives 0xFFFFFFFF.  The discrete logarithm is exact
+ *      (2-power group order, one bit per step); a value counts as decoded only if the label recomputed from (c, i) equals it limb
+ *      for limb.  *bad_key (may be NULL) receives row * 4 + col of the lowest refused cell, UINT64_MAX if none.  1 <= log_n <= 26;
+ *      a null pointer or another log_n is PLK_ERR_ARG.  Blocks until the outputs are written.
+ *      The three checks return PLK_OK whenever they reached a verdict, which is out->kind (the convention of plk_validate_witness);
+ *      PLK_ERR_* is for bad arguments and HIP errors only.  "Lowest" is by row * 4 + col everywhere: row first, then a, b, c, d inside
+ *      the row — the order plk_setup_permutation_dev links occurrences in and the gate check counts rows in.
+ *      plk_setup_check_permutation looks at the setup's sigma alone (kinds 0, 1, 2): is every value a cell label, and is every cell
+ *      the image of some cell.  plk_check_copies* run those two first (kinds 1 and 2 win) and then compare every cell's value with
+ *      that of its image (kind 3).  rows and canonicity as plk_prove_assembled*: num_inputs <= rows <= N, zero beyond rows, an element
+ *      >= r is PLK_ERR_ARG.  Both kinds of setup.  When the permutation argument of plk_prove_assembled* does not close, the same
+ *      localisation runs on the columns already on the device and its finding is appended to the message:
+ *      "...; first broken copy: cell b[17] and its image c[3] hold different values", "...; sigma is not a permutation: cell a[5] is
+ *      the image of no cell", "...; sigma is not a permutation: its value at cell d[2] is not a cell label".  A proof that succeeds
+ *      launches none of this.                                                                                                        */
+typedef struct { uint32_t kind; uint32_t col, row; uint32_t col2, row2; } plk_copy_report;
+#define PLK_COPY_OK            0u
+#define PLK_COPY_NOT_A_LABEL   1u   /* sigma_col(omega^row) is no k_c * omega^i: (col,row) = lowest such cell                        */
+#define PLK_COPY_NOT_BIJECTIVE 2u   /* every value decodes, but (col,row) = lowest cell that is the image of no cell                 */
+#define PLK_COPY_BROKEN        3u   /* (col,row) = lowest cell whose value differs from that of its image (col2,row2)                */
+int32_t plk_sigma_decode_dev(plk_ctx *ctx, const void *const sigmas_dev[4], uint32_t log_n,
+                             void *index_dev /* 4 * 2^log_n uint32, the layout of plk_setup_permutation_dev */,
+                             uint64_t *bad_key /* may be NULL */, void *stream);
+int32_t plk_setup_check_permutation(plk_ctx *ctx, const plk_setup *s, plk_copy_report *out);
+int32_t plk_check_copies(plk_ctx *ctx, const plk_setup *s, const plk_fr *const columns[4], uint64_t rows, plk_copy_report *out);
+int32_t plk_check_copies_dev(plk_ctx *ctx, const plk_setup *s, const void *const columns_dev[4], uint64_t rows, plk_copy_report *out, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

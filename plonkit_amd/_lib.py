@@ -4,6 +4,7 @@ Arrays cross as numpy uint64 ([n,4] Fr Montgomery, [n,8] G1 affine, [12] Jacobia
 pointers (ints / torch tensors).  Nothing here computes: every function forwards to the C ABI, and
 a missing library or a missing GPU raises — there is no Python or CPU fallback.
 """
+import collections
 import ctypes
 import sys
 import os
@@ -115,6 +116,22 @@ class MsmShape(ctypes.Structure):
     """plk_msm_shape (include/plonkit_amd.h)"""
     _fields_ = [(k, ctypes.c_uint32) for k in ("path", "batch", "table_copies", "window_bits", "windows", "bucket_sets", "fine_bits", "coarse_bins",
                                                "accumulate_variant", "prephase", "reduce_lanes", "pieces")] + [("piece_terms", ctypes.c_uint64)]
+
+
+COPY_OK, COPY_NOT_A_LABEL, COPY_NOT_BIJECTIVE, COPY_BROKEN = 0, 1, 2, 3      # PLK_COPY_*
+
+# the verdict of the copy-constraint checks: cell = (col, row) of the lowest offender (None for COPY_OK), image = the cell sigma sends it
+# to (COPY_BROKEN only)
+CopyReport = collections.namedtuple("CopyReport", "kind cell image")
+
+
+class _CopyReportStruct(ctypes.Structure):
+    """plk_copy_report (include/plonkit_amd.h)"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("kind", "col", "row", "col2", "row2")]
+
+    def report(self):
+        return CopyReport(int(self.kind), (int(self.col), int(self.row)) if self.kind != COPY_OK else None,
+                          (int(self.col2), int(self.row2)) if self.kind == COPY_BROKEN else None)
 
 
 class Context:
@@ -540,6 +557,22 @@ class Context:
         _check(lib().plk_setup_permutation_dev(self._h, v, ctypes.c_uint32(log_n), ctypes.c_uint64(num_vars),
                                                _devptr(index_ptr) if index_ptr is not None else None, s, _stream(stream)))
 
+    def sigma_decode_dev(self, sigmas, log_n, stream=None):
+        """plk_sigma_decode_dev, the inverse of setup_permutation_dev's sigma output: four device columns of 2^log_n Fr (torch tensors /
+        ints) -> (index, bad_key).  index: an int32 torch tensor of 4 * 2^log_n words holding the uint32 bit patterns
+        idx[col * n + row] = col' << 30 | row', 0xFFFFFFFF where the value is no cell label; bad_key: row * 4 + col of the lowest such cell,
+        None when every value decodes"""
+        import torch
+        if len(sigmas) != 4:
+            raise ValueError("sigma_decode_dev: 4 sigma columns expected, got %d" % len(sigmas))
+        if not 1 <= log_n <= 26:
+            raise PlkError(1, "plk_sigma_decode_dev: bad argument")
+        s = (ctypes.c_void_p * 4)(*[_devptr(p) for p in sigmas])
+        index = torch.empty(4 << log_n, dtype=torch.int32, device="cuda:%d" % self.device)
+        bad = ctypes.c_uint64(0)
+        _check(lib().plk_sigma_decode_dev(self._h, s, ctypes.c_uint32(log_n), _devptr(index), ctypes.byref(bad), _stream(stream)))
+        return index, (bad.value if bad.value != 2**64 - 1 else None)
+
     def g1_intt_srs_dev(self, log_n, out_ptr, stream=None):
         _check(lib().plk_g1_intt_srs_dev(self._h, ctypes.c_uint32(log_n), _devptr(out_ptr), _stream(stream)))
 
@@ -739,6 +772,38 @@ class SetupForProver:
         st = _stream(stream)
         return self._prove_into(lambda out, cap, n: lib().plk_prove_assembled_dev(h, self._h, arr, ctypes.c_uint64(rows), out,
                                                                                   ctypes.c_uint64(cap), ctypes.byref(n), st))
+
+    # ---- which copy constraint is broken (plk_setup_check_permutation / plk_check_copies*): what to call when prove_assembled says
+    #      "copy constraints".  Exact checks, no key needed; every verdict is a CopyReport (kind 0 = all is well)
+    def check_permutation(self, ctx=None):
+        """is the setup's sigma a permutation of the cell labels: kind COPY_NOT_A_LABEL / COPY_NOT_BIJECTIVE with the lowest offending cell"""
+        rep = _CopyReportStruct()
+        _check(lib().plk_setup_check_permutation((ctx or self.ctx)._h, self._h, ctypes.byref(rep)))
+        return rep.report()
+
+    def check_copies(self, columns, ctx=None):
+        """the sigma checks, then every cell's value against its image's: four numpy (rows, 4) uint64 Montgomery arrays as prove_assembled
+        takes them; kind COPY_BROKEN names the lowest cell (row first, then a, b, c, d) that differs from its image"""
+        if len(columns) != 4:
+            raise ValueError("check_copies: 4 columns expected, got %d" % len(columns))
+        cols = _fr_vectors(columns, "check_copies", allow_empty=True)
+        arr = (ctypes.c_void_p * 4)(*[_np(c) for c in cols])
+        rep = _CopyReportStruct()
+        _check(lib().plk_check_copies((ctx or self.ctx)._h, self._h, arr, ctypes.c_uint64(cols[0].shape[0]), ctypes.byref(rep)))
+        return rep.report()
+
+    def check_copies_dev(self, column_tensors, stream=None, ctx=None):
+        """the same for four torch tensors on the device, (rows, 4) int64 / uint64 each, ordered on `stream`"""
+        if len(column_tensors) != 4:
+            raise ValueError("check_copies_dev: 4 column tensors expected, got %d" % len(column_tensors))
+        rows = int(column_tensors[0].shape[0])
+        for t in column_tensors:
+            if int(t.shape[0]) != rows or t.element_size() * t.numel() != 32 * rows or not t.is_contiguous():
+                raise ValueError("check_copies_dev: contiguous tensors of one length, 32 bytes per row, expected")
+        arr = (ctypes.c_void_p * 4)(*[_devptr(t) for t in column_tensors])
+        rep = _CopyReportStruct()
+        _check(lib().plk_check_copies_dev((ctx or self.ctx)._h, self._h, arr, ctypes.c_uint64(rows), ctypes.byref(rep), _stream(stream)))
+        return rep.report()
 
     def validate_witness(self, circuit, ctx=None):
         """SetupForProver::validate_witness (src/plonk.rs:127-129): the gate-level check of prove() on its own, no key needed.

@@ -103,6 +103,10 @@ struct IngestArgs {
     uint32_t *flag;
 };
 int32_t ingest_columns(const IngestArgs &a, hipStream_t s);
+// copycheck.hip: the exact copy-constraint checks behind plk_setup_check_permutation / plk_check_copies* and the failure path of
+// plk_prove_assembled*.  sigma[j] = the N values of sigma_j on <omega_N>; cols = nullptr: the two checks of sigma alone (kinds 0-2), else
+// cols[j][0, rows) are the wire columns, read as zero beyond `rows` (kind 3 as well).  Kernels on st; returns after the verdict has arrived.
+int32_t copy_check(plk_ctx *ctx, const Fr *const sigma[4], uint32_t log_n, const Fr *const cols[4], uint64_t rows, plk_copy_report *out, hipStream_t st);
 // data = the four per-coset coefficient vectors u_k of icoset4cm_dev (u_k at data + k*n) -> the 4n coefficients, natural order, in place;
 // constants in the W domain: i^-1 (i = omega_4) and s_c = 7^(-N c) / 4
 int32_t icoset_combine(Fr *data, uint32_t n, const Fr &iinv_w, const Fr s_w[4], hipStream_t s);

@@ -563,6 +563,14 @@ static int32_t front_verdict(plk_ctx *ctx, const plk_setup *S, ProveFront &F) {
     return PLK_OK;
 }
 
+// round 2's "copy constraints" message ends with what copy_check (copycheck.hip) found on the columns of the failed proof
+static void append_copy_report(std::string &msg, const plk_copy_report &r) {
+    auto cell = [](uint32_t col, uint32_t row) { return std::string(1, "abcd"[col & 3]) + "[" + std::to_string(row) + "]"; };
+    if (r.kind == PLK_COPY_BROKEN) msg += "; first broken copy: cell " + cell(r.col, r.row) + " and its image " + cell(r.col2, r.row2) + " hold different values";
+    else if (r.kind == PLK_COPY_NOT_BIJECTIVE) msg += "; sigma is not a permutation: cell " + cell(r.col, r.row) + " is the image of no cell";
+    else if (r.kind == PLK_COPY_NOT_A_LABEL) msg += "; sigma is not a permutation: its value at cell " + cell(r.col, r.row) + " is not a cell label";
+}
+
 // Rounds 1-5 and Proof::write, shared by plk_prove and plk_prove_assembled*: from the wire values a front end left in the workspace.
 static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, ProveFront &F, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
     auto lap = [&]() { double t = now_ms(); ctx->timings.push_back(t - F.t_prev); F.t_prev = t; };
@@ -664,8 +672,13 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
         if (F.close_perm) {
             if (HFr::geq_p(num_total.l)) HFr::sub_p(num_total.l);
             if (num_total != total) {
-                set_error("copy constraints: the permutation argument does not close (prod of numerators != prod of denominators at beta, gamma): "
-                          "the columns break the copy constraints of the setup's sigma");
+                std::string msg = "copy constraints: the permutation argument does not close (prod of numerators != prod of denominators at beta, gamma): "
+                                  "the columns break the copy constraints of the setup's sigma";
+                // which one: the exact checks on the columns as they sit in the workspace (only here, on the way out with an error)
+                const Fr *cols[4] = {w_vals[0], w_vals[1], w_vals[2], w_vals[3]};
+                plk_copy_report rep;
+                if (copy_check(ctx, S->sig_vals, log_n, cols, N, &rep, st) == PLK_OK) append_copy_report(msg, rep);
+                set_error(msg);
                 return PLK_ERR_UNSAT;
             }
         }
@@ -1259,6 +1272,48 @@ static int32_t prove_assembled_impl(plk_ctx *ctx, const plk_setup *S, const void
     return prove_rounds(ctx, S, W, F, proof_out, cap, len);
 }
 
+// ---- which copy constraint is broken (copycheck.hip): the setup's resident sigma values, and a caller's columns under the rules of
+//      plk_prove_assembled* (num_inputs <= rows <= N, zero beyond rows, every element canonical)
+static int32_t check_copies_impl(plk_ctx *ctx, const plk_setup *S, const void *const cols[4], bool with_cols, bool on_device, uint64_t rows, plk_copy_report *out,
+                                 hipStream_t caller, const char *who_c) {
+    const std::string who = who_c;
+    if (out) *out = plk_copy_report{PLK_COPY_OK, 0, 0, 0, 0};
+    if (!ctx || !S || !out || (with_cols && !cols)) { set_error(who + ": bad argument"); return PLK_ERR_ARG; }
+    for (int j = 0; with_cols && j < 4; j++) if (!cols[j]) { set_error(who + ": a column pointer is NULL"); return PLK_ERR_ARG; }
+    if (with_cols && (rows < S->num_inputs || rows > S->N)) { set_error(who + ": rows must satisfy num_inputs <= rows <= N"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    if (!S->store.p) { set_error(who + ": the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
+    hipStream_t st = caller ? caller : ctx->stream;
+    if (!with_cols) return copy_check(ctx, S->sig_vals, S->log_n, nullptr, 0, out, st);
+    DevBuf tmp;                                                   // the canonicity flag, then (host columns) the four uploads
+    const size_t CB = (rows * sizeof(Fr) + 255) & ~(size_t)255;
+    PLK_TRY(tmp.reserve(256 + (on_device ? 0 : 4 * CB)));
+    uint32_t *flag = tmp.as<uint32_t>();
+    const Fr *src[4];
+    int32_t rc = PLK_OK;
+    uint32_t bad = 0;
+    if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) rc = hip_fail(hipGetLastError(), "memset", __FILE__, __LINE__);
+    for (int j = 0; j < 4; j++) {
+        if (on_device) { src[j] = static_cast<const Fr *>(cols[j]); continue; }
+        Fr *d = reinterpret_cast<Fr *>((char *)tmp.p + 256 + j * CB);
+        if (rc == PLK_OK && rows && hipMemcpyAsync(d, cols[j], rows * sizeof(Fr), hipMemcpyHostToDevice, st) != hipSuccess) rc = hip_fail(hipGetLastError(), "H2D columns", __FILE__, __LINE__);
+        src[j] = d;
+    }
+    if (rc == PLK_OK) rc = check_canonical(src, 4, rows, flag, st);
+    if (rc == PLK_OK && hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = hip_fail(hipGetLastError(), "D2H", __FILE__, __LINE__);
+    if (rc == PLK_OK) rc = copy_check(ctx, S->sig_vals, S->log_n, src, rows, out, st);      // (synchronises st: `bad` has arrived)
+    else (void)hipStreamSynchronize(st);
+    tmp.release();
+    if (rc == PLK_OK && bad) {
+        std::string which;
+        for (int j = 0; j < 4; j++) if (bad >> j & 1) { which += which.empty() ? "" : ", "; which += "abcd"[j]; }
+        set_error(who + ": column " + which + " holds an element that is not a canonical residue (limbs >= r)");
+        *out = plk_copy_report{PLK_COPY_OK, 0, 0, 0, 0};
+        return PLK_ERR_ARG;
+    }
+    return rc;
+}
+
 // ---- tracing / test hooks: the vectors between the rounds, and the polynomial helpers of rounds 2, 4 and 5 on their own
 int32_t plk_prove_trace(plk_ctx *ctx, uint32_t which, plk_fr *out_host, uint64_t cap, uint64_t *n) {
     if (!ctx || !n || which >= 9) { set_error("plk_prove_trace: bad argument"); return PLK_ERR_ARG; }
@@ -1440,6 +1495,17 @@ int32_t plk_prove_assembled_dev(plk_ctx *ctx, const plk_setup *s, const void *co
     PLK_TRY(not_a_worker(ctx, "plk_prove_assembled_dev"));
     return guarded("plk_prove_assembled_dev", PLK_ERR_HIP, [&] {
         return prove_assembled_impl(ctx, s, columns_dev, true, rows, proof_out, cap, len, (hipStream_t)stream); });
+}
+int32_t plk_setup_check_permutation(plk_ctx *ctx, const plk_setup *s, plk_copy_report *out) {
+    return guarded("plk_setup_check_permutation", PLK_ERR_HIP, [&] { return check_copies_impl(ctx, s, nullptr, false, false, 0, out, nullptr, "plk_setup_check_permutation"); });
+}
+int32_t plk_check_copies(plk_ctx *ctx, const plk_setup *s, const plk_fr *const columns[4], uint64_t rows, plk_copy_report *out) {
+    return guarded("plk_check_copies", PLK_ERR_HIP, [&] {
+        return check_copies_impl(ctx, s, reinterpret_cast<const void *const *>(columns), true, false, rows, out, nullptr, "plk_check_copies"); });
+}
+int32_t plk_check_copies_dev(plk_ctx *ctx, const plk_setup *s, const void *const columns_dev[4], uint64_t rows, plk_copy_report *out, void *stream) {
+    return guarded("plk_check_copies_dev", PLK_ERR_HIP, [&] {
+        return check_copies_impl(ctx, s, columns_dev, true, true, rows, out, (hipStream_t)stream, "plk_check_copies_dev"); });
 }
 int32_t plk_comm_serve(plk_ctx *ctx, uint64_t *batches) {
     if (batches) *batches = 0;
