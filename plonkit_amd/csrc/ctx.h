@@ -11,6 +11,7 @@
 #include "../../include/plonkit_amd.h"
 #include "field_dev.h"
 #include "hostmath.h"
+#include "msm_plan.h"
 
 namespace plk {
 
@@ -98,23 +99,19 @@ struct plk_ctx {
     // the latency-bound tail of commitment k-1 (bucket reduction) and the digit / partition kernels of k+1 then share the
     // GPU with the accumulation of k, which starts the moment the previous accumulation ends.  A slot is taken lowest
     // index first, so a caller that keeps at most two in flight (the prover) never allocates the third slot's scratch.
-    static constexpr uint32_t MSM_SLOTS = 3;
+    static constexpr uint32_t MSM_SLOTS = plk::MSM_SLOTS;
     struct MsmSlot {
         plk::DevBuf a, b, c, d, e, f;
         void *pinned = nullptr; size_t pinned_cap = 0;
-        uint32_t windows = 0, c_bits = 0, pending_parts = 0, batch = 1, roles = 2, fine_bits = 7;
+        plk::MsmPlan plan = plk::msm_plan_nothing(0, 1, 0);   // which kernels the commitment it holds was given (msm_plan.h); plan.shape is what plk_msm_last_shape reports
+        // what a re-run needs beyond the plan (a short commitment whose bucket lists overflowed: msm_finish_batch)
+        const void *bases = nullptr, *scalars[plk::MSM_MAX_BATCH] = {nullptr};
         hipStream_t stream = nullptr;        // the kernels of this commitment; ordered after the caller's stream by `ready`
         hipEvent_t ready = nullptr;
         hipEvent_t acc_done = nullptr;       // recorded behind msm_accumulate: from here on the commitment only runs its latency-bound reduction
         hipEvent_t ev[2] = {nullptr, nullptr};   // optional bracket around msm_accumulate (bench roofline)
         bool busy = false;
-        // short-commitment path (msm_small.hip): what msm_finish_batch needs to run the ordinary pipeline if a bucket list overflowed
-        bool small = false;
-        const void *fb_bases = nullptr, *fb_scalars[8] = {nullptr};
-        uint64_t fb_srs_n = 0, fb_n = 0;
-        uint32_t fb_copies = 0, fb_cbits = 0, fb_nbits = 0;
         bool acc_no_inf = false;             // msm_accumulate ran without the is_inf(q) test (plk_msm_last_no_inf: diagnostic)
-        plk_msm_shape shape = {};            // which kernels this commitment was given (plk_msm_last_shape: diagnostic, host integers only)
     } slot[MSM_SLOTS];
     uint64_t msm_enq = 0, msm_fin = 0;       // FIFO counters; commitment number k lives in slot[fifo[k % MSM_SLOTS]]
     uint8_t fifo[MSM_SLOTS] = {};

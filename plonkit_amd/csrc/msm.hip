@@ -34,8 +34,11 @@
 // No MFMA (256-bit modular integers), bound by v_mad_u64_u32 issue; HBM sees the algorithmic 96 B/term plus the
 // per-window gathers (64 B x W per term) from the table.
 // Files: the accumulation kernel ("kernel A" above, step (2) of the sort) lives in msm_accumulate.hip — a translation unit
-// of its own so that it can be compiled for ILP (plonkit_amd/build.py) —, the declarations both share in msm_shape.h;
-// everything else (recoding, partition, bucket reduction, drivers, the FIFO of three slots, plk_ctx_share_srs) is here.
+// of its own so that it can be compiled for ILP (plonkit_amd/build.py) —, the device declarations both share in msm_shape.h; which kernels a
+// commitment is given (path, window bits, table copies, pre-phase, variant, reduction lanes, pieces, every buffer size) and every constant
+// that rests on is decided in msm_plan.h (msm_plan_pass / msm_plan_fallback / msm_plan_call: host-only, checked without a GPU by
+// tests/test_msm_plan_host.py); everything else (recoding, partition, bucket reduction, the drivers that launch a plan, the FIFO of three
+// slots, plk_ctx_share_srs) is here.
 #include "msm_shape.h"
 #include "msm.h"
 #include "ec29_quad_dev.h"
@@ -49,13 +52,6 @@ namespace plk {
 // msm_small.hip: the short-commitment path
 int32_t msm_small_launch(plk_ctx::MsmSlot &S, hipStream_t stream, const G1Affine *bases, uint32_t copy_stride, const ScalarSet &set,
                          uint32_t batch, uint32_t n, bool ev_on, void *host_out);
-constexpr uint32_t SM_PLANES_HOST = 17;
-// terms up to which a commitment takes it: 2^15 (measured, one at a time: 2^14 terms 0.27 against 0.62 ms, 2^15 0.35 against 0.53, 2^16 0.52 against
-// 0.54; a proof at the 2^15 domain 3.25 against 3.40 ms; at 2^16 a batch of two is SLOWER on this path — a proof 3.76 against 3.56 ms — and a batch
-// of four much slower: 4.85)
-constexpr uint64_t MSM_SMALL_MAX = 1ull << 15;
-// terms up to which msm_accumulate is launched in the build whose lanes own the buckets of an evenly filled task (msm_accumulate.hip)
-constexpr uint64_t MSM_OWNED_MAX = 1ull << 16;
 
 // -------------------------------------------------------------------------- scalar recoding
 // Step 1: every scalar leaves Montgomery form once and is recoded into W signed c-bit digits in
@@ -205,8 +201,7 @@ __global__ void __launch_bounds__(1024) msm_scan_bins(uint32_t *hist, uint32_t *
 // critical path of every round of a proof, and in a stream of commitments its workgroups displace accumulate workgroups).
 // The workgroup of the scatter pass takes RC_SCALARS scalars x 15 windows = 15360 entries, the same LDS staging volume
 // and the same ~15-entry runs per (workgroup, coarse bin) as the per-window partition it replaces.
-constexpr int RC_THREADS = 1024, RC_SCALARS = 1024;                    // (RC_WINDOWS, recode17: msm_shape.h — shared with msm_small.hip)
-static_assert(RC_WINDOWS == 254 / 17 + 1, "the fused path is the c = 17 shape");
+// (RC_THREADS, RC_SCALARS, RC_COUNT_PER, RC_WINDOWS: msm_plan.h, which sizes the grids; recode17: msm_shape.h — shared with msm_small.hip)
 
 // true for every lane of the wave iff all its live lanes hold the same scalar (then every window's digit is the same in all of them)
 __device__ __forceinline__ bool wave_same_scalar(const Fr &k, bool live, uint64_t live_mask) {
@@ -219,7 +214,6 @@ __device__ __forceinline__ bool wave_same_scalar(const Fr &k, bool live, uint64_
 
 // pass 1: coarse-bin histogram of the commitment's bucket set; RC_COUNT_PER scalars per thread keep the global atomics at
 // one per (workgroup, bin) for 4096 scalars
-constexpr int RC_COUNT_PER = 4;
 // The scalar leaves Montgomery form HERE, once per commitment (fr_canonical_w: the 29-bit layer's reduction, no carry chains), and the canonical
 // words go to `canon` (32 B per scalar, vector m at canon + m * n) for pass 2, which would otherwise reduce every scalar a second time.
 __global__ void __launch_bounds__(RC_THREADS) msm_recode_count(ScalarSet set, MsmParams p, uint32_t *hist, Fr *canon) {
@@ -392,7 +386,7 @@ __global__ void __launch_bounds__(256) srs_to_w_kernel(G1Affine *out, const G1Af
 // With all 15 copies resident a 2^20-term commitment has ONE bucket set instead of 15: the reduction
 // kernels and the host Horner shrink accordingly, the accumulate kernel gathers from a 1 GB table in
 // HBM instead of a cache-resident 64 MB one (measured: no difference, it is bound by the multiplier).
-constexpr uint32_t COPY_SHIFT = 17, MAX_COPIES = 15, NORM_K = 32;    // 15 windows of 17 bits cover the 254-bit scalars
+constexpr uint32_t NORM_K = 32;                              // (COPY_SHIFT, MAX_COPIES, table_copies_for: msm_plan.h)
 
 __global__ void __launch_bounds__(256) srs_shift_kernel(const G1Affine *prev, G1Xyzz *out, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -435,12 +429,6 @@ __global__ void __launch_bounds__(256) srs_normalise_kernel(const G1Xyzz *in, Fq
         store_fp(&out[i].x, o.x);
         store_fp(&out[i].y, o.y);
     }
-}
-
-// All 15 copies or none: a commitment that can only address 5 or 3 of them ((copy, index) must fit the 24-bit
-// field of an entry) uses every 3rd or 5th copy, so the full table serves every size.
-static uint32_t table_copies_for(uint64_t srs_n) {           // the table may take up to 32 GiB of the 288 GB
-    return (uint64_t)MAX_COPIES * srs_n * sizeof(G1Affine) <= (32ull << 30) ? MAX_COPIES : 1;
 }
 
 // Does the finished table hold a point at infinity ((0, 0): all 16 words zero, in the W domain as in the key)?  One pass over the table
@@ -506,9 +494,6 @@ static int32_t ensure_base_table(plk_ctx *ctx, uint32_t copies, hipStream_t stre
     ctx->srs_w_no_inf = found_host == 0;
     return PLK_OK;
 }
-
-static uint32_t slots_per_task(uint32_t fb) { return (1u << fb) + 2 * MSM_THREADS; }
-static uint32_t meta_per_task(uint32_t fb) { return (1u << fb) + 2; }
 
 // Kernel B0 — folds a bucket that kernel A spread over more than HOT_SPAN lanes (repeated scalars: a witness
 // full of 0/1 values) into that bucket's otherwise unused PRIMARY slot, RL lanes per task working together.
@@ -740,9 +725,7 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_bin_fold(XyzzW *task_out, con
 // additions of ~8 us on the tail of every commitment); the weights 2^b, 2^FB, 2^8 and u are a few dozen host operations.  Pure chains of full
 // additions from one inlined call site (operands in registers, see msm_task_reduce).  Results leave in the library's external form
 // (canonical, R = 2^256).
-constexpr uint32_t THREADS_LOG = 8;
-static_assert((1u << THREADS_LOG) == MSM_THREADS, "THREADS_LOG");
-constexpr uint32_t WS_BIT_ROLES = THREADS_LOG, WS_FIRST_F_ROLE = 1 + WS_BIT_ROLES;
+// (WS_BIT_ROLES, WS_FIRST_F_ROLE: msm_plan.h — the number of roles is part of a commitment's plan)
 
 // The sums by quads of lanes (late round 6; ec29_quad_dev.h, distributed form: lane r of a quad holds coordinate r of its running sum): a full
 // addition is four products deep instead of fourteen — 2.6 us per step for a wave that has its SIMD to itself against 7.3 — and the steps carry no
@@ -829,17 +812,9 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_naive(const G1Affine *bases, 
 }
 
 // ------------------------------------------------------------------------------ host side
-// Window widths are chosen among those whose top window still has many bits (254 = 19*13 + 7 = 16*15 + 14 = 15*16 + 14):
-// a top window of 1-2 bits would put every term into two or three buckets of a single bin.
-static uint32_t pick_window_bits(uint64_t n, bool have_table) {
-    // with the table of shifted copies every size is best served by 17-bit windows and one bucket set (measured
-    // against 13/15-bit windows without it: 2^12 0.50 vs 0.64 ms, 2^14 0.58 vs 0.95, 2^16 0.62 vs 0.98, 2^18 0.87 vs 1.12)
-    if (have_table) return COPY_SHIFT;
-    if (n < (1u << 17)) return 13;
-    if (n < (1u << 19)) return 15;
-    return 17;                                                // 15 windows; 2^16 buckets = 512 coarse bins x 128
-}
-
+// Nothing below decides which kernels a commitment is given: msm_plan.h does — msm_plan_pass at the enqueue, msm_plan_fallback at the finish of a
+// short commitment that overflowed, msm_plan_call per call of plk_msm_g1_partial_dev.  The functions here take the slot's plan, reserve,
+// launch and record.
 static int32_t slot_pinned(plk_ctx::MsmSlot &S, size_t bytes) {
     if (bytes <= S.pinned_cap) return PLK_OK;
     if (S.pinned) (void)hipHostFree(S.pinned);
@@ -849,33 +824,34 @@ static int32_t slot_pinned(plk_ctx::MsmSlot &S, size_t bytes) {
     return PLK_OK;
 }
 
-// the 2^20-shaped pipeline (recode / partition, accumulate, bucket reduction) for one batch on the slot's stream; everything it needs is
-// in the arguments, so that msm_finish_batch can run it again for a short commitment whose lists overflowed (msm_small.hip)
-struct BigArgs { const G1Affine *bases; uint64_t srs_n; uint32_t copies, c_bits, nbits; ScalarSet set; uint32_t batch; uint64_t n; bool no_inf = false; };
-static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t stream, const BigArgs &A) {
-    const G1Affine *bases = A.bases;
-    const uint32_t batch = A.batch, copies = A.copies;
-    const uint64_t n = A.n;
-    MsmParams p;
-    p.n = (uint32_t)n;
-    p.c = A.c_bits;
-    p.windows = 254 / p.c + 1;
-    p.groups = p.windows / copies;                            // copies > 1 only for c = 17: 15 windows, copies | 15
-    p.nbits = A.nbits;
-    p.copy_stride = copies > 1 ? (uint32_t)(p.groups * A.srs_n) : 0;
-    p.fine_bits = FINE_BITS;
-    p.coarse_bits = p.c - 1 - p.fine_bits;                    // c is 13, 15 or 17: at most the 1024 coarse bins msm_window_sums_quad serves
-    p.nbins = 1u << p.coarse_bits;
-    p.batch = batch;
-    const ScalarSet &set = A.set;
-    const uint32_t total_sets = batch * p.groups, total_bins = total_sets * p.nbins, total_windows = batch * p.windows;
-    const uint32_t max_tasks = total_bins + (uint32_t)(((uint64_t)total_windows * n) / TASK_MAX) + 1;
-    PLK_TRY(S.a.reserve((size_t)(3 * total_bins + 4) * sizeof(uint32_t)));               // hist/cursor, bin_start, task_start
-    PLK_TRY(S.b.reserve((size_t)total_windows * n * sizeof(uint32_t)));                   // entries
-    const uint32_t META_PER_TASK = meta_per_task(p.fine_bits), SLOTS_PER_TASK = slots_per_task(p.fine_bits);
-    PLK_TRY(S.c.reserve((size_t)max_tasks * 2 * sizeof(XyzzW) + (size_t)max_tasks * META_PER_TASK * 4));  // per-task (S, T) + bucket offsets
-    PLK_TRY(S.e.reserve((size_t)max_tasks * SLOTS_PER_TASK * sizeof(XyzzW)));             // lane partial sums
-    PLK_TRY(S.d.reserve((size_t)13 * total_sets * sizeof(G1Xyzz)));                    // per bucket set: sum S, G_0..G_7, F_1..F_3
+// PLK_MSM_FUSED_RECODE=0 (A/B knob): the three-launch pre-phase through the digit array, as for several bucket sets.  Read once per process
+// and handed to the plan, which reads no environment.
+static bool fused_recode_allowed() {
+    static const bool fused_ok = [] { const char *e = getenv("PLK_MSM_FUSED_RECODE"); return !(e && e[0] == '0'); }();
+    return fused_ok;
+}
+
+static ScalarSet slot_scalars(const plk_ctx::MsmSlot &S) {
+    ScalarSet set{};
+    for (uint32_t m = 0; m < S.plan.p.batch; m++) set.v[m] = static_cast<const Fr *>(S.scalars[m]);
+    return set;
+}
+
+// MSM_RUN_PIPELINE: the 2^20-shaped pipeline (recode / partition, accumulate, bucket reduction) for the slot's batch on `stream`.  Everything
+// it needs is in the slot, so that msm_finish_batch can run it for a short commitment whose lists overflowed (msm_small.hip).
+// no_inf: the key's table holds no point at infinity — the caller reads that AFTER the table is ensured; the plain accumulate kernel
+// (variant 0) then runs without its is_inf(q) test.
+static int32_t msm_pipeline_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t stream, bool no_inf) {
+    const MsmPlan &P = S.plan;
+    const MsmParams &p = P.p;
+    const G1Affine *bases = static_cast<const G1Affine *>(S.bases);
+    const ScalarSet set = slot_scalars(S);
+    const uint32_t batch = p.batch, total_bins = P.total_bins, total_windows = P.total_windows, max_tasks = P.max_tasks;
+    PLK_TRY(S.a.reserve(P.bytes_a));
+    PLK_TRY(S.b.reserve(P.bytes_b));
+    PLK_TRY(S.c.reserve(P.bytes_c));
+    PLK_TRY(S.e.reserve(P.bytes_e));
+    PLK_TRY(S.d.reserve(P.bytes_d));
     uint32_t *hist = S.a.as<uint32_t>(), *bin_start = hist + total_bins, *task_start = bin_start + total_bins + 1;
     uint32_t *entries = S.b.as<uint32_t>();
     XyzzW *task_out = S.c.as<XyzzW>();
@@ -891,55 +867,32 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
         PLK_TRY(msm_accumulate_prepare());
         attr_set = true;
     }
-    // PLK_MSM_FUSED_RECODE=0 (A/B knob): the three-launch pre-phase through the digit array, as for several bucket sets
-    static const bool fused_ok = [] { const char *e = getenv("PLK_MSM_FUSED_RECODE"); return !(e && e[0] == '0'); }();
-    const uint32_t shape_prephase = (fused_ok && p.groups == 1 && p.c == 17 && p.windows == RC_WINDOWS && p.nbins <= 1024) ? 1u : 2u;
-    if (shape_prephase == 1) {
-        // one bucket set per commitment (the 2^20 shape): digits never leave the registers (msm_recode_count / _scatter)
-        const uint32_t cblocks = (uint32_t)((n + (uint64_t)RC_THREADS * RC_COUNT_PER - 1) / ((uint64_t)RC_THREADS * RC_COUNT_PER));
-        const uint32_t sblocks = (uint32_t)((n + RC_SCALARS - 1) / RC_SCALARS);
-        const size_t lds = (size_t)(3 * p.nbins + 1 + RC_SCALARS * RC_WINDOWS) * sizeof(uint32_t);
-        PLK_TRY(S.f.reserve((size_t)batch * n * sizeof(Fr)));                             // canonical scalars, pass 1 -> pass 2
+    PLK_TRY(S.f.reserve(P.bytes_f));
+    if (P.shape.prephase == 1) {                              // fused: canonical scalars, pass 1 -> pass 2
         Fr *canon = S.f.as<Fr>();
-        hipLaunchKernelGGL(msm_recode_count, dim3(cblocks, batch), dim3(RC_THREADS), 0, stream, set, p, hist, canon);
+        hipLaunchKernelGGL(msm_recode_count, dim3(P.grid_recode_count, batch), dim3(RC_THREADS), 0, stream, set, p, hist, canon);
         hipLaunchKernelGGL(msm_scan_bins, dim3(1), dim3(1024), 0, stream, hist, bin_start, task_start, total_bins);
-        hipLaunchKernelGGL(msm_recode_scatter, dim3(sblocks, batch), dim3(RC_THREADS), lds, stream, (const Fr *)canon, p, hist, (const uint32_t *)bin_start, entries);
-    } else {
-        PLK_TRY(S.f.reserve((size_t)total_windows * n * sizeof(int32_t)));
+        hipLaunchKernelGGL(msm_recode_scatter, dim3(P.grid_recode_scatter, batch), dim3(RC_THREADS), P.lds_recode_scatter, stream, (const Fr *)canon, p, hist, (const uint32_t *)bin_start, entries);
+    } else {                                                  // through the digit array
         int32_t *digits = S.f.as<int32_t>();
-        hipLaunchKernelGGL(msm_digits, dim3((uint32_t)((n + MSM_THREADS - 1) / MSM_THREADS), batch), dim3(MSM_THREADS), 0, stream, set, p, digits);
-        const uint32_t pblocks = (uint32_t)((n + DIGIT_CHUNK - 1) / DIGIT_CHUNK);
-        const size_t plds_count = (size_t)p.nbins * sizeof(uint32_t);
-        const size_t plds_scatter = (size_t)(3 * p.nbins + 1 + DIGIT_CHUNK) * sizeof(uint32_t);
-        hipLaunchKernelGGL(msm_partition<false>, dim3(pblocks, total_windows), dim3(PART_THREADS), plds_count, stream, (const int32_t *)digits, p, hist, (const uint32_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(msm_digits, dim3(P.grid_digits, batch), dim3(MSM_THREADS), 0, stream, set, p, digits);
+        hipLaunchKernelGGL(msm_partition<false>, dim3(P.grid_partition, total_windows), dim3(PART_THREADS), P.lds_partition_count, stream, (const int32_t *)digits, p, hist, (const uint32_t *)nullptr, (uint32_t *)nullptr);
         hipLaunchKernelGGL(msm_scan_bins, dim3(1), dim3(1024), 0, stream, hist, bin_start, task_start, total_bins);
-        hipLaunchKernelGGL(msm_partition<true>, dim3(pblocks, total_windows), dim3(PART_THREADS), plds_scatter, stream, (const int32_t *)digits, p, hist, (const uint32_t *)bin_start, entries);
+        hipLaunchKernelGGL(msm_partition<true>, dim3(P.grid_partition, total_windows), dim3(PART_THREADS), P.lds_partition_scatter, stream, (const int32_t *)digits, p, hist, (const uint32_t *)bin_start, entries);
     }
     if (ctx->ev_on) PLK_HIP(hipEventRecord(S.ev[0], stream));
-    // commitments of <= 2^16 terms: the build whose lanes own the buckets of an evenly filled task (msm_accumulate.hip)
-    const uint32_t shape_variant = n <= MSM_OWNED_MAX ? 2u : 0u;
-    S.acc_no_inf = shape_variant == 0 && A.no_inf;
-    msm_accumulate_launch((int)shape_variant, S.acc_no_inf, max_tasks, stream, bases, (const uint32_t *)entries, (const uint32_t *)bin_start, (const uint32_t *)task_start, partials, task_meta, p);
+    S.acc_no_inf = P.shape.accumulate_variant == 0 && no_inf;
+    msm_accumulate_launch((int)P.shape.accumulate_variant, S.acc_no_inf, max_tasks, stream, bases, (const uint32_t *)entries, (const uint32_t *)bin_start, (const uint32_t *)task_start, partials, task_meta, p);
     if (ctx->ev_on) (void)hipEventRecord(S.ev[1], stream);
     (void)hipEventRecord(S.acc_done, stream);
-    // The bucket reduction (see msm_task_reduce).  ONE bucket set with nothing else in flight on this context: by quads of lanes.  A batch of two is
-    // 2048 waves of quads — two per SIMD, every step twice as long: 269 us inside a proof against ~230 lane-wise; the quads do the same additions in
-    // 1.5x the lane-instructions, which a stream of commitments — whose reductions share the GPU with the next accumulation — pays for (three in flight
-    // at 2^16 terms 0.243 -> 0.255 ms, measured); and above 2^20 terms a commitment has 3 or 5 bucket sets: 5120 tasks are five waves of quads per SIMD
-    // (0.71 ms at 2^22 terms against ~0.45 lane-wise).
-    // Otherwise lane-wise: 16 lanes per task for a batch of three or more commitments or when another commitment is in flight (a stream of commitments is
-    // work-bound — every reduction wave displaces an accumulation wave of the next commitment for as long as it lives — and 16 lanes per task are fewer
-    // wave-microseconds) and the addition built from lockstep product pairs (msm_task_reduce<.., true>: 19 % fewer instructions per addition; 8 lanes per task
-    // were measured on top and lost, profiles/msm_nonloop_diet_ab.txt), 32 lanes and the latency-bound addition when latency is all that counts.
-    const bool others_in_flight = ctx->msm_enq != ctx->msm_fin;
-    const uint32_t shape_lanes = (total_sets == 1 && !others_in_flight) ? 4u : ((batch >= 3 || others_in_flight) ? 16u : 32u);
-    const uint32_t rblocks = (max_tasks * (shape_lanes == 16 ? 16u : 32u) + MSM_THREADS - 1) / MSM_THREADS;
+    // the bucket reduction (see msm_task_reduce; which one: msm_plan_pipeline)
+    const uint32_t rblocks = P.grid_reduce;
     constexpr uint32_t FB = FINE_BITS;
-    if (shape_lanes == 4) {
+    if (P.shape.reduce_lanes == 4) {
         hipLaunchKernelGGL((msm_fold_hot<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
-        hipLaunchKernelGGL((msm_task_reduce_quad<FB>), dim3((max_tasks + MSM_THREADS / 64 - 1) / (MSM_THREADS / 64)), dim3(MSM_THREADS), 0, stream,
+        hipLaunchKernelGGL((msm_task_reduce_quad<FB>), dim3(P.grid_reduce_quad), dim3(MSM_THREADS), 0, stream,
                            (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins);
-    } else if (shape_lanes == 16) {
+    } else if (P.shape.reduce_lanes == 16) {
         hipLaunchKernelGGL((msm_fold_hot<FB, 4>), dim3(rblocks), dim3(MSM_THREADS), 0, stream, partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, total_bins);
         hipLaunchKernelGGL((msm_task_reduce<FB, 4, true>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
                            (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins);
@@ -948,38 +901,41 @@ static int32_t msm_big_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t str
         hipLaunchKernelGGL((msm_task_reduce<FB, 5>), dim3(rblocks), dim3(MSM_THREADS), 0, stream,
                            (const XyzzW *)partials, (const uint32_t *)task_meta, (const uint32_t *)task_start, task_out, total_bins);
     }
-    hipLaunchKernelGGL(msm_bin_fold, dim3((total_bins + MSM_THREADS / 64 - 1) / (MSM_THREADS / 64)), dim3(MSM_THREADS), 0, stream, task_out, (const uint32_t *)task_start, total_bins);
-    // points per bucket set left for the host: S (bins below nbins / 2), G_0..G_7, F_1 .., S (bins from nbins / 2)
-    const uint32_t roles = WS_FIRST_F_ROLE + (p.nbins + MSM_THREADS - 1) / MSM_THREADS - 1 + 1;
-    hipLaunchKernelGGL(msm_window_sums_quad, dim3(total_sets, roles), dim3(MSM_THREADS), 0, stream, (const XyzzW *)task_out, (const uint32_t *)task_start, window_out, p.nbins, roles);
+    hipLaunchKernelGGL(msm_bin_fold, dim3(P.grid_bin_fold), dim3(MSM_THREADS), 0, stream, task_out, (const uint32_t *)task_start, total_bins);
+    hipLaunchKernelGGL(msm_window_sums_quad, dim3(P.total_sets, P.roles), dim3(MSM_THREADS), 0, stream, (const XyzzW *)task_out, (const uint32_t *)task_start, window_out, p.nbins, P.roles);
     PLK_HIP(hipGetLastError());
-    PLK_TRY(slot_pinned(S, (size_t)roles * total_sets * sizeof(G1Xyzz)));
-    PLK_HIP(hipMemcpyAsync(S.pinned, window_out, (size_t)roles * total_sets * sizeof(G1Xyzz), hipMemcpyDeviceToHost, stream));
-    S.roles = roles;
-    S.windows = p.groups;
-    S.c_bits = p.c;
-    S.fine_bits = p.fine_bits;
-    plk_msm_shape &sh = S.shape;                              // diagnostic record (plk_msm_last_shape): the decisions taken above
-    sh.table_copies = copies; sh.window_bits = p.c; sh.windows = p.windows; sh.bucket_sets = p.groups;
-    sh.fine_bits = p.fine_bits; sh.coarse_bins = p.nbins;
-    sh.accumulate_variant = shape_variant; sh.prephase = shape_prephase; sh.reduce_lanes = shape_lanes;
+    PLK_TRY(slot_pinned(S, P.bytes_pinned));
+    PLK_HIP(hipMemcpyAsync(S.pinned, window_out, P.bytes_pinned, hipMemcpyDeviceToHost, stream));
     return PLK_OK;
 }
 
-// fewer than 4096 terms without the table's copies: one double-and-add per term (msm_naive), block sums to the host
-static int32_t msm_naive_launch(plk_ctx::MsmSlot &S, hipStream_t stream, const BigArgs &A) {
-    const uint32_t blocks = (uint32_t)((A.n + MSM_THREADS - 1) / MSM_THREADS);
-    PLK_TRY(S.d.reserve((size_t)A.batch * blocks * sizeof(G1Xyzz)));
-    for (uint32_t m = 0; m < A.batch; m++)
-        hipLaunchKernelGGL(msm_naive, dim3(blocks), dim3(MSM_THREADS), 0, stream, A.bases, A.set.v[m], (uint32_t)A.n, S.d.as<G1Xyzz>() + (size_t)m * blocks);
+// MSM_RUN_NAIVE: one double-and-add per term (msm_naive), block sums to the host
+static int32_t msm_naive_launch(plk_ctx::MsmSlot &S, hipStream_t stream) {
+    const MsmPlan &P = S.plan;
+    const uint32_t blocks = P.grid_naive;
+    PLK_TRY(S.d.reserve(P.bytes_d));
+    for (uint32_t m = 0; m < P.p.batch; m++)
+        hipLaunchKernelGGL(msm_naive, dim3(blocks), dim3(MSM_THREADS), 0, stream, static_cast<const G1Affine *>(S.bases), static_cast<const Fr *>(S.scalars[m]), P.p.n,
+                           S.d.as<G1Xyzz>() + (size_t)m * blocks);
     PLK_HIP(hipGetLastError());
     (void)hipEventRecord(S.acc_done, stream);
-    S.pending_parts = blocks;
-    S.windows = 0;
-    S.c_bits = 0;
-    PLK_TRY(slot_pinned(S, (size_t)A.batch * blocks * sizeof(G1Xyzz)));
-    PLK_HIP(hipMemcpyAsync(S.pinned, S.d.p, (size_t)A.batch * blocks * sizeof(G1Xyzz), hipMemcpyDeviceToHost, stream));
+    PLK_TRY(slot_pinned(S, P.bytes_pinned));
+    PLK_HIP(hipMemcpyAsync(S.pinned, S.d.p, P.bytes_pinned, hipMemcpyDeviceToHost, stream));
     return PLK_OK;
+}
+
+// the kernels of the slot's plan on `stream`
+static int32_t msm_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t stream, bool no_inf) {
+    const MsmPlan &P = S.plan;
+    S.acc_no_inf = false;
+    switch (P.run) {
+    case MSM_RUN_NOTHING: (void)hipEventRecord(S.acc_done, stream); return PLK_OK;
+    case MSM_RUN_NAIVE: return msm_naive_launch(S, stream);
+    case MSM_RUN_SHORT:                                       // three short launches instead of the 2^20-shaped pipeline (msm_small.hip)
+        PLK_TRY(slot_pinned(S, P.bytes_pinned));
+        return msm_small_launch(S, stream, static_cast<const G1Affine *>(S.bases), P.p.copy_stride, slot_scalars(S), P.p.batch, P.p.n, ctx->ev_on, S.pinned);
+    default: return msm_pipeline_launch(ctx, S, stream, no_inf);
+    }
 }
 
 // `caller` is the stream on which the scalars were produced; the commitment runs on its slot's own stream after an
@@ -989,7 +945,7 @@ int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t b
     uint32_t slot_index = 0;
     while (ctx->slot[slot_index].busy) slot_index++;          // lowest free slot (there is one: fewer than MSM_SLOTS are in flight)
     plk_ctx::MsmSlot &S = ctx->slot[slot_index];
-    auto in_flight = [&]() { ctx->fifo[ctx->msm_enq % plk_ctx::MSM_SLOTS] = (uint8_t)slot_index; S.busy = true; ctx->msm_enq++; };
+    // (the slot's stream and events are created before the SRS, size and batch checks)
     if (!S.stream) {
         // The slots' streams are created at the runtime's HIGH stream priority, all three alike.  What counts is not the priority but that the runtime
         // keeps a pool of hardware queues per priority level: at the default level the three slots share HIP's (default: four) queues with the null
@@ -1009,54 +965,19 @@ int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t b
     hipStream_t stream = S.stream;
     if (!ctx->srs) { set_error("msm: no SRS uploaded (plk_srs_upload)"); return PLK_ERR_SRS; }
     if (base_offset + n > ctx->srs_n) { set_error("msm: SRS too small for this commitment"); return PLK_ERR_SRS; }
-    if (n >= (1ull << 24) + 1) { set_error("msm: more than 2^24 terms in one pass (plk_msm_g1 / plk_msm_g1_dev / plk_prove split longer commitments; the enqueue and batch entry points do not)"); return PLK_ERR_SIZE; }
+    if (n > MSM_PASS_MAX_TERMS) { set_error("msm: more than 2^24 terms in one pass (plk_msm_g1 / plk_msm_g1_dev / plk_prove split longer commitments; the enqueue and batch entry points do not)"); return PLK_ERR_SIZE; }
     if (batch < 1 || batch > MSM_MAX_BATCH) { set_error("msm: batch must be 1..8"); return PLK_ERR_ARG; }
-    // resident table of the SRS in the 2^261 domain of the lazy field layer; large commitments use its shifted copies
-    uint32_t nbits = 1;
-    while ((1ull << nbits) < n) nbits++;
-    // short commitments (msm_small.hip) need all 15 copies of the table: every commitment of >= 4096 terms builds them anyway; a shorter one
-    // only asks for them when the key is small enough for that to be cheap (<= 2^21 points: 80 ms once per key) or has them already
-    const bool small_wanted = n >= 1 && n <= MSM_SMALL_MAX && table_copies_for(ctx->srs_n) == MAX_COPIES &&
-                              (n >= 4096 || ctx->srs_n <= (1ull << 21) || (ctx->srs_w_valid && ctx->srs_w_copies == MAX_COPIES));
-    const uint32_t c_bits = small_wanted ? COPY_SHIFT : (n >= 4096 ? pick_window_bits(n, table_copies_for(ctx->srs_n) > 1) : 0);
-    uint32_t copies = 1;
-    if (c_bits == COPY_SHIFT) {
-        copies = table_copies_for(ctx->srs_n);
-        PLK_TRY(ensure_base_table(ctx, copies, stream));
-        while (copies > 1 && (MAX_COPIES % copies != 0 || ((uint64_t)copies << nbits) > (1ull << 24))) copies--;   // a divisor of 15 that fits the 24-bit (copy, index) field of an entry
-    } else PLK_TRY(ensure_base_table(ctx, 1, stream));
-    const bool small = small_wanted && copies == MAX_COPIES;
-    const G1Affine *bases = ctx->srs_w.as<G1Affine>() + base_offset;
-    S.pending_parts = 0;
-    S.windows = 0;
-    S.batch = batch;
-    S.small = false;
-    S.shape = plk_msm_shape{};
-    S.acc_no_inf = false;
-    S.shape.batch = batch; S.shape.pieces = 1; S.shape.piece_terms = n;
-    if (n == 0) { (void)hipEventRecord(S.acc_done, stream); in_flight(); return PLK_OK; }
-    BigArgs A{bases, ctx->srs_n, copies, c_bits, nbits, ScalarSet{}, batch, n, ctx->srs_w_no_inf};
-    for (uint32_t m = 0; m < batch; m++) A.set.v[m] = scalars_dev[m];
-    if (n < 4096 && !small) {
-        PLK_TRY(msm_naive_launch(S, stream, A));
-        S.shape.path = PLK_MSM_PATH_NAIVE; S.shape.table_copies = 1;
-        in_flight();
-        return PLK_OK;
-    }
-    // short commitments: three short launches instead of the 2^20-shaped pipeline (msm_small.hip).  They need all 15 table copies.
-    if (small) {
-        PLK_TRY(slot_pinned(S, (size_t)MSM_MAX_BATCH * SM_PLANES_HOST * sizeof(G1Xyzz) + 16));
-        PLK_TRY(msm_small_launch(S, stream, bases, (uint32_t)ctx->srs_n, A.set, batch, (uint32_t)n, ctx->ev_on, S.pinned));
-        S.small = true;
-        S.shape.path = PLK_MSM_PATH_SHORT; S.shape.table_copies = copies;
-        S.fb_bases = bases; S.fb_srs_n = ctx->srs_n; S.fb_n = n; S.fb_copies = copies; S.fb_cbits = c_bits; S.fb_nbits = nbits;
-        for (uint32_t m = 0; m < batch; m++) S.fb_scalars[m] = scalars_dev[m];
-        in_flight();
-        return PLK_OK;
-    }
-    PLK_TRY(msm_big_launch(ctx, S, stream, A));
-    S.shape.path = PLK_MSM_PATH_ORDINARY;
-    in_flight();
+    // The plan is made from the table state as it is BEFORE ensure_base_table changes it (whether a commitment of fewer than 4096 terms takes the
+    // short path depends on what is resident), and from what is in flight before this commitment joins the FIFO.
+    const MsmPlan plan = msm_plan_pass(n, batch, ctx->srs_n, ctx->srs_w_valid, ctx->srs_w_copies, ctx->msm_enq != ctx->msm_fin, fused_recode_allowed());
+    // resident table of the SRS in the 2^261 domain of the lazy field layer; large commitments use its shifted copies.  Ensured on EVERY enqueue,
+    // zero terms and the naive path included (their bases are read from it too): 1 copy unless the window is 17 bits
+    PLK_TRY(ensure_base_table(ctx, plan.table_request, stream));
+    S.plan = plan;
+    S.bases = ctx->srs_w.as<G1Affine>() + base_offset;
+    for (uint32_t m = 0; m < batch; m++) S.scalars[m] = scalars_dev[m];
+    PLK_TRY(msm_launch(ctx, S, stream, ctx->srs_w_no_inf));   // (srs_w_no_inf: read after the table is ensured)
+    ctx->fifo[ctx->msm_enq % plk_ctx::MSM_SLOTS] = (uint8_t)slot_index; S.busy = true; ctx->msm_enq++;
     return PLK_OK;
 }
 
@@ -1086,39 +1007,40 @@ int32_t msm_finish_batch(plk_ctx *ctx, hipStream_t, host::HJac *out) {
     ctx->msm_fin++;
     S.busy = false;
     PLK_HIP(hipStreamSynchronize(S.stream));
-    if (S.small) {
-        const uint32_t flag = *reinterpret_cast<const volatile uint32_t *>(static_cast<const char *>(S.pinned) + (size_t)S.batch * SM_PLANES_HOST * sizeof(G1Xyzz));
-        if (flag) {                                           // a bucket list overflowed (msm_small.hip): the ordinary pipeline on the same inputs
-            BigArgs A{static_cast<const G1Affine *>(S.fb_bases), S.fb_srs_n, S.fb_copies, S.fb_cbits, S.fb_nbits, ScalarSet{}, S.batch, S.fb_n};
-            for (uint32_t m = 0; m < S.batch; m++) A.set.v[m] = static_cast<const Fr *>(S.fb_scalars[m]);
-            S.small = false;
-            S.shape.path = PLK_MSM_PATH_SHORT_FALLBACK;
-            if (S.fb_n < 4096) PLK_TRY(msm_naive_launch(S, S.stream, A)); else PLK_TRY(msm_big_launch(ctx, S, S.stream, A));
+    if (S.plan.run == MSM_RUN_SHORT) {
+        const uint32_t flag = *reinterpret_cast<const volatile uint32_t *>(static_cast<const char *>(S.pinned) + (size_t)S.plan.p.batch * SM_PLANES_HOST * sizeof(G1Xyzz));
+        if (flag) {
+            // a bucket list overflowed (msm_small.hip): the same inputs again by the plan of msm_plan_fallback.  "Others in flight" is what the FIFO
+            // holds NOW, after msm_fin++ above; the accumulation runs with no_inf = false
+            S.plan = msm_plan_fallback(S.plan, ctx->msm_enq != ctx->msm_fin, fused_recode_allowed());
+            PLK_TRY(msm_launch(ctx, S, S.stream, false));
             PLK_HIP(hipStreamSynchronize(S.stream));
         }
     }
-    for (uint32_t m = 0; m < S.batch; m++) {
+    const MsmPlan &P = S.plan;
+    for (uint32_t m = 0; m < P.p.batch; m++) {
         HJac acc = HJac::inf();
-        if (S.small) {
+        if (P.run == MSM_RUN_SHORT) {
             // seventeen plane sums Q_0..Q_16 per commitment: sum_b 2^b * Q_b (bits 0-7: the lo digit, 8-16: the hi digit)
             const uint64_t *raw = reinterpret_cast<const uint64_t *>(S.pinned) + (size_t)16 * SM_PLANES_HOST * m;
             for (int b = (int)SM_PLANES_HOST - 1; b >= 0; b--) acc = jac_add(jac_double(acc), xyzz_host_to_jac(raw + 16 * b));
-        } else if (S.windows) {
+        } else if (P.run == MSM_RUN_PIPELINE) {
             // per bucket set the device leaves (sum S over the lower bins, G_0..G_7, F_1, .., F_{halves-1}, sum S over the upper bins);
             // W = sum S + 2^FB * (sum_b 2^b G_b + 2^8 * sum_u u*F_u)
-            const size_t per = (size_t)16 * S.roles;
-            const uint64_t *raw = reinterpret_cast<const uint64_t *>(S.pinned) + per * m * S.windows;
-            for (int w = (int)S.windows - 1; w >= 0; w--) {
-                for (uint32_t i = 0; i < S.c_bits; i++) acc = jac_double(acc);
+            const uint32_t sets = P.p.groups, roles = P.roles;
+            const size_t per = (size_t)16 * roles;
+            const uint64_t *raw = reinterpret_cast<const uint64_t *>(S.pinned) + per * m * sets;
+            for (int w = (int)sets - 1; w >= 0; w--) {
+                for (uint32_t i = 0; i < P.p.c; i++) acc = jac_double(acc);
                 HJac run = HJac::inf(), d = HJac::inf();                  // sum_u u*F_u = sum of the suffix sums of F
-                for (uint32_t r = S.roles - 2; r >= WS_FIRST_F_ROLE; r--) { run = jac_add(run, xyzz_host_to_jac(raw + per * w + 16 * r)); d = jac_add(d, run); }
+                for (uint32_t r = roles - 2; r >= WS_FIRST_F_ROLE; r--) { run = jac_add(run, xyzz_host_to_jac(raw + per * w + 16 * r)); d = jac_add(d, run); }
                 for (int b = (int)WS_BIT_ROLES - 1; b >= 0; b--) d = jac_add(jac_double(d), xyzz_host_to_jac(raw + per * w + 16 * (1 + b)));   // Horner over the bit sums
-                for (uint32_t i = 0; i < S.fine_bits; i++) d = jac_double(d);
-                acc = jac_add(acc, jac_add(jac_add(xyzz_host_to_jac(raw + per * w), xyzz_host_to_jac(raw + per * w + 16 * (S.roles - 1))), d));   // (sum S in two halves)
+                for (uint32_t i = 0; i < P.p.fine_bits; i++) d = jac_double(d);
+                acc = jac_add(acc, jac_add(jac_add(xyzz_host_to_jac(raw + per * w), xyzz_host_to_jac(raw + per * w + 16 * (roles - 1))), d));   // (sum S in two halves)
             }
-        } else {
-            const uint64_t *raw = reinterpret_cast<const uint64_t *>(S.pinned) + (size_t)16 * m * S.pending_parts;
-            for (uint32_t i = 0; i < S.pending_parts; i++) acc = jac_add(acc, xyzz_host_to_jac(raw + 16 * i));
+        } else {                                              // the naive kernel's block sums (none for zero terms)
+            const uint64_t *raw = reinterpret_cast<const uint64_t *>(S.pinned) + (size_t)16 * m * P.grid_naive;
+            for (uint32_t i = 0; i < P.grid_naive; i++) acc = jac_add(acc, xyzz_host_to_jac(raw + 16 * i));
         }
         out[m] = acc;
     }
@@ -1126,17 +1048,8 @@ int32_t msm_finish_batch(plk_ctx *ctx, hipStream_t, host::HJac *out) {
 }
 
 int32_t msm_finish(plk_ctx *ctx, hipStream_t stream, host::HJac *out) {
-    if (ctx->msm_fin != ctx->msm_enq && ctx->front_slot().batch != 1) { set_error("msm_finish: a batch is pending"); return PLK_ERR_ARG; }
+    if (ctx->msm_fin != ctx->msm_enq && ctx->front_slot().plan.shape.batch != 1) { set_error("msm_finish: a batch is pending"); return PLK_ERR_ARG; }
     return msm_finish_batch(ctx, stream, out);
-}
-
-// From 2^23 terms on, ONE commitment is better run as 2^20-term pieces over successive SRS ranges, three pieces in flight: the
-// digit / partition kernels and the bucket reduction of a piece then overlap the accumulation of its neighbours, which a single
-// pass cannot do with itself (2^24 terms: 21.8 ms against 24.0 in one pass; at 2^22 the pieces do not pay: 6.5 against 6.15 ms,
-// profiles/r02_msm_three_in_flight_ab.txt).  Only with the table of shifted copies: an SRS of more than 2^25 points has none
-// (it would exceed 32 GiB), a 2^20-term piece then runs 19 windows instead of 15 and a 2^26-gate proof got 40 % SLOWER that way.
-uint64_t msm_pipelined_piece(const plk_ctx *ctx, uint64_t terms) {
-    return (terms >= (1ull << 23) && table_copies_for(ctx->srs_n) > 1) ? (1ull << 20) : 0;
 }
 
 }  // namespace plk
@@ -1160,7 +1073,7 @@ int32_t plk_msm_g1_enqueue_batch_dev(plk_ctx *ctx, const void *const *scalars_de
 }
 static int32_t finish_batch_checked(plk_ctx *ctx, uint32_t count, host::HJac *j) {
     if (ctx->msm_fin == ctx->msm_enq) { set_error("msm: nothing in flight"); return PLK_ERR_ARG; }
-    if (ctx->front_slot().batch != count) { set_error("plk_msm_g1_finish_batch: the commitment in flight holds a different batch size"); return PLK_ERR_ARG; }
+    if (ctx->front_slot().plan.shape.batch != count) { set_error("plk_msm_g1_finish_batch: the commitment in flight holds a different batch size"); return PLK_ERR_ARG; }
     return msm_finish_batch(ctx, nullptr, j);
 }
 int32_t plk_msm_g1_finish_batch(plk_ctx *ctx, plk_g1_jacobian *out, uint32_t count) {
@@ -1214,20 +1127,18 @@ int32_t plk_msm_g1_finish_sharded(plk_ctx *ctx, plk_g1_affine *out) {
 }
 
 int32_t plk_msm_g1_partial_dev(plk_ctx *ctx, const void *scalars_dev, uint64_t n, uint64_t base_offset, plk_g1_jacobian *out, void *stream) {
-    constexpr uint64_t PIECE = 1ull << 24;                    // one pass of the kernels takes at most 2^24 terms
-    // long commitments as short pieces, several in flight (msm_pipelined_piece); the FIFO must be empty for that (it is, unless
-    // the caller keeps commitments in flight)
-    const uint64_t pipe_piece = ctx ? msm_pipelined_piece(ctx, n) : 0;
-    const bool pipelined = pipe_piece != 0 && ctx->msm_enq == ctx->msm_fin;
-    if (n <= PIECE && !pipelined) {
+    // one pass, passes of 2^24 terms one at a time, or short pieces with several in flight — the latter only when the FIFO is empty at the
+    // call (msm_plan_call)
+    const MsmCallPlan call = msm_plan_call(n, ctx ? ctx->srs_n : 0, ctx && ctx->msm_enq == ctx->msm_fin);
+    if (call.pieces == 1) {
         PLK_TRY(plk_msm_g1_enqueue_dev(ctx, scalars_dev, n, base_offset, stream));
         return plk_msm_g1_finish(ctx, out);                   // (one pass: the slot's own record says so)
     }
     if (!ctx || !scalars_dev || !out) { set_error("plk_msm_g1: bad argument"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
     host::HJac acc = host::HJac::inf();
-    const uint64_t piece = pipelined ? pipe_piece : PIECE;
-    const uint32_t depth = pipelined ? plk_ctx::MSM_SLOTS : 1;
+    const uint64_t piece = call.piece_terms;
+    const uint32_t depth = call.depth;
     uint64_t off = 0;
     uint32_t inflight = 0;
     int32_t rc = PLK_OK;
@@ -1245,7 +1156,7 @@ int32_t plk_msm_g1_partial_dev(plk_ctx *ctx, const void *scalars_dev, uint64_t n
         if (rc == PLK_OK) acc = host::jac_add(acc, j);
     }
     if (rc != PLK_OK) return rc;
-    ctx->call_pieces = (uint32_t)((n + piece - 1) / piece); ctx->call_piece_terms = piece; ctx->call_fin = ctx->msm_fin;
+    ctx->call_pieces = (uint32_t)call.pieces; ctx->call_piece_terms = piece; ctx->call_fin = ctx->msm_fin;   // (recorded on this multi-piece path only)
     memcpy(out->x, acc.x.l, 32); memcpy(out->y, acc.y.l, 32); memcpy(out->z, acc.z.l, 32);
     return PLK_OK;
 }
@@ -1337,7 +1248,7 @@ int32_t plk_msm_last_kernel_ms(plk_ctx *ctx, float *accumulate_ms) {
 int32_t plk_msm_last_shape(plk_ctx *ctx, plk_msm_shape *out) {
     if (!ctx || !out) { set_error("plk_msm_last_shape: bad argument"); return PLK_ERR_ARG; }
     if (ctx->msm_fin == 0) { set_error("plk_msm_last_shape: no commitment finished yet"); return PLK_ERR_ARG; }
-    *out = ctx->slot[ctx->last_slot].shape;
+    *out = ctx->slot[ctx->last_slot].plan.shape;
     if (ctx->call_pieces && ctx->call_fin == ctx->msm_fin) { out->pieces = ctx->call_pieces; out->piece_terms = ctx->call_piece_terms; }
     return PLK_OK;
 }

@@ -5,40 +5,14 @@
 #include "ctx.h"
 #include "ec_dev.h"
 #include "ec29_dev.h"
+#include "msm_plan.h"
 
 namespace plk {
 
-constexpr int MSM_THREADS = 256;
-// Buckets per accumulate workgroup = 2^FB ("fine" part of the bucket index; the coarse part selects the bin).  The kernels
-// keep FB as a template parameter; one shape is compiled:
-//   FB = 6: 64 buckets per task.  At c = 17 that is 1024 coarse bins of ~15 K entries at 2^20 terms = ONE task per bin,
-//           so every bucket is reduced once (65 K task-buckets) — the bucket reduction (msm_task_reduce) is not a latency
-//           detail: in VALU work it was 38 % of the accumulation (992 waves x 37 dependent full additions of 14 products
-//           against 15.7 M mixed additions of 9.3), and it shares the GPU with the next commitment's accumulation.
-//   (FB = 7, 128 buckets per task and two tasks per bin at 2^20 terms, was the round-1 shape; no window width in use needs it.)
-constexpr uint32_t FINE_BITS = 6;
-constexpr uint32_t CHUNK = 16384;                // entries per accumulate workgroup (sorted in 64 KB of LDS; two workgroups per CU)
-constexpr uint32_t DIGIT_CHUNK = 16384;            // scalars per partition workgroup (per window): 64 KB of LDS staging
-constexpr uint32_t TASK_MAX = CHUNK;
-                   // per-chunk bucket population handled cooperatively
-
-constexpr uint32_t MSM_MAX_BATCH = 8;              // commitments sharing one pass over the same bases
-
-struct MsmParams {
-    uint32_t n;
-    uint32_t c;               // window bits
-    uint32_t windows;         // W per commitment
-    uint32_t fine_bits;       // FB: buckets per accumulate task = 2^FB
-    uint32_t coarse_bits;     // c - 1 - fine_bits
-    uint32_t nbins;           // 1 << coarse_bits
-    uint32_t batch;           // number of scalar vectors (same n, same bases); "global window" = m * W + w
-    // Shifted copies of the bases (fixed-base precomputation): window w = j*groups + g takes its points from
-    // copy j*groups of the table (2^(16*j*groups) * P_i) and drops them into bucket set g, so only `groups`
-    // bucket sets have to be reduced and only c*groups doublings are left for the host Horner.
-    uint32_t groups;          // bucket sets per commitment (= windows when there is one copy)
-    uint32_t nbits;           // entry index = (j << nbits) | i
-    uint32_t copy_stride;     // points between table copies j and j+1 (= groups * srs_n)
-};
+// Every dispatch constant (MSM_THREADS, FINE_BITS, CHUNK, MSM_MAX_BATCH, RC_WINDOWS, ...) and MsmParams: msm_plan.h, which is host-only; here is what
+// needs device types.
+static_assert(sizeof(Fr) == MSM_BYTES_FR && sizeof(G1Affine) == MSM_BYTES_AFFINE && sizeof(G1Xyzz) == MSM_BYTES_XYZZ && sizeof(XyzzW) == MSM_BYTES_XYZZW,
+              "msm_plan.h sizes the buffers with these");
 
 struct ScalarSet { const Fr *v[MSM_MAX_BATCH]; };
 
@@ -50,7 +24,6 @@ PLK_HD uint32_t extract_bits(const uint32_t *k, uint32_t pos, uint32_t c) {
     if (limb + 1 < 8) v |= (uint64_t)k[limb + 1] << 32;
     return (uint32_t)(v >> off) & ((1u << c) - 1);
 }
-constexpr int RC_WINDOWS = 15;                      // 17-bit windows over the 254-bit scalars
 // the signed digits of msm_digits for c = 17, 15 windows, in registers: d[w] in [-2^16, 2^16], top window unsigned
 PLK_HD void recode17(const Fr &k, int32_t (&d)[RC_WINDOWS]) {
     uint32_t carry = 0;

@@ -55,7 +55,7 @@ static HFr host_omega(uint32_t log_n) {
 // One MSM call takes at most 2^24 terms (24-bit index field of a bucket entry): longer vectors (domains 2^25, 2^26 —
 // SETUP_MAX_POW2 of the reference is 26) are committed in pieces against successive SRS ranges, summed on the host.
 static uint64_t msm_piece_terms() {
-    static const uint64_t v = [] { const char *e = getenv("PLK_MSM_MAX_TERMS"); uint64_t x = e ? strtoull(e, nullptr, 10) : 0; return x >= 4096 && x <= (1ull << 24) ? x : (1ull << 24); }();
+    static const uint64_t v = [] { const char *e = getenv("PLK_MSM_MAX_TERMS"); uint64_t x = e ? strtoull(e, nullptr, 10) : 0; return x >= MSM_NAIVE_BELOW && x <= MSM_PASS_MAX_TERMS ? x : MSM_PASS_MAX_TERMS; }();
     return v;                                                 // (the environment override exists for the tests)
 }
 // enqueues the pieces of `cnt` commitments over scalars[lo + ...]; every piece but the last is finished here and summed
@@ -77,7 +77,7 @@ static int32_t enqueue_pieces(plk_ctx *ctx, const Fr *const *vecs, uint32_t cnt,
     return PLK_OK;
 }
 static int32_t finish_pieces(plk_ctx *ctx, uint32_t cnt, HJac *j) {
-    if (ctx->msm_fin != ctx->msm_enq && ctx->front_slot().batch != cnt) {      // never pop somebody else's commitment
+    if (ctx->msm_fin != ctx->msm_enq && ctx->front_slot().plan.shape.batch != cnt) {      // never pop somebody else's commitment
         set_error("commitment FIFO out of step: the slot in flight holds a different batch than the prover enqueued"); return PLK_ERR_ARG; }
     PLK_TRY(msm_finish_batch(ctx, nullptr, j));
     if (!ctx->commit_pieces.empty()) {

@@ -1,12 +1,13 @@
 """-m gpu: every dispatch shape of the MSM, asserted before the answer is looked at.
 
-msm_enqueue_batch / msm_big_launch / plk_msm_g1_partial_dev (plonkit_amd/csrc/msm.hip) choose a commitment's kernels from its
-length, its batch size, the key's size, what is resident and what is in flight.  ROWS below is one table of
+msm_plan_pass / msm_plan_fallback / msm_plan_call (plonkit_amd/csrc/msm_plan.h; msm.hip launches what they plan) choose a commitment's kernels
+from its length, its batch size, the key's size, what is resident and what is in flight.  ROWS below is one table of
 (key, terms, base_offset, batch, call style, scalars, expected shape): per row the test first asserts that
 Context.msm_last_shape() (plk_msm_last_shape, a diagnostic) reports the expected shape and then that the result is the
 tau = 42 trapdoor answer (sum_i s_i 42^(off + i)) * G (Horner in the oracle's C arithmetic, ol.msm as well up to 5000 terms).
 
-The expected shapes are written by hand from the rules in msm.hip's comments and DESIGN.md section 4.2, never read from the library:
+The expected shapes are written by hand from the rules in msm_plan.h's comments and DESIGN.md section 4.2, never read from the library
+(tests/test_msm_plan_host.py checks the same table against the plan alone, without a GPU):
   * table copies of a key: 15 while 15 x 64 B x points <= 32 GiB (up to 35 791 394 points), else 1;
   * short path (msm_small.hip): 1 .. 2^15 terms on a 15-copy key, if the commitment has >= 4096 terms, or the key has <= 2^21
     points, or the 15 copies are resident already; otherwise fewer than 4096 terms take one double-and-add per term (naive);
