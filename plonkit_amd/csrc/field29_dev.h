@@ -18,6 +18,7 @@
 // at the boundary.  No MFMA: these are 29x29->58-bit integer multiply-adds on the VALU.
 #pragma once
 #include "field_dev.h"
+#include <type_traits>
 #include <utility>
 
 namespace plk {
@@ -28,7 +29,7 @@ template <int... J, class F> __device__ __forceinline__ void static_for_impl(std
 template <int N, class F> __device__ __forceinline__ void static_for(F &&f) { static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F &&>(f)); }
 
 constexpr uint32_t M29 = (1u << 29) - 1;
-constexpr uint32_t MULW_A_LIMB_MAX = 3280000000u;          // largest limb of mulw's LEFT operand (derivation at mulw)
+constexpr uint32_t MULW_A_LIMB_MAX = 3280000000u;          // largest limb of mulw's LEFT operand (the columns then just fit: asserted at mont_scan)
 
 struct FrW {
     static constexpr uint32_t P29[9] = {0x10000001u, 0x1f0fac9fu, 0x0e5c2450u, 0x07d090f3u, 0x1585d283u, 0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};
@@ -128,222 +129,53 @@ PLK_HD W9<WP> addw(const W9<WP> &a, const W9<WP> &b) {
 
 // a - b + k*p, where k*p is held with its lower limbs biased by 2^31 (PADk) so that no limb goes
 // negative; b limbs < 2^30, b < k*p.  Result normalised, value < a + k*p.
-template <class WP> PLK_HD W9<WP> sub2(const W9<WP> &a, const W9<WP> &b) {
+template <class WP, int K> PLK_HD W9<WP> sub_pad(const W9<WP> &a, const W9<WP> &b) {
+    static_assert(K == 2 || K == 4 || K == 6, "sub_pad: no pad for this multiple of p");
     W9<WP> r;
 #pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + WP::PAD2[i] - b.l[i];
+    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + (K == 2 ? WP::PAD2[i] : K == 4 ? WP::PAD4[i] : WP::PAD6[i]) - b.l[i];
     return normw(r);
 }
-template <class WP> PLK_HD W9<WP> sub4(const W9<WP> &a, const W9<WP> &b) {
-    W9<WP> r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + WP::PAD4[i] - b.l[i];
-    return normw(r);
-}
-template <class WP> PLK_HD W9<WP> sub6(const W9<WP> &a, const W9<WP> &b) {
-    W9<WP> r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + WP::PAD6[i] - b.l[i];
-    return normw(r);
-}
-// 2p - a for a < 2p (negation)
-template <class WP> PLK_HD W9<WP> neg2(const W9<WP> &a) {
-    W9<WP> r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = WP::PAD2[i] - a.l[i];
-    return normw(r);
-}
+template <class WP> PLK_HD W9<WP> sub2(const W9<WP> &a, const W9<WP> &b) { return sub_pad<WP, 2>(a, b); }
+template <class WP> PLK_HD W9<WP> sub4(const W9<WP> &a, const W9<WP> &b) { return sub_pad<WP, 4>(a, b); }
+template <class WP> PLK_HD W9<WP> sub6(const W9<WP> &a, const W9<WP> &b) { return sub_pad<WP, 6>(a, b); }
+template <class WP> PLK_HD W9<WP> neg2(const W9<WP> &a) { return sub_pad<WP, 2>(w_zero<WP>(), a); }   // 2p - a for a < 2p (negation)
 template <class WP> PLK_HD W9<WP> addn(const W9<WP> &a, const W9<WP> &b) { return normw(addw(a, b)); }
 
-// Montgomery product, radix 2^29, R' = 2^261 — PRODUCT SCANNING: the 18 columns of a*b + m*p are summed one after the
-// other in ONE 64-bit accumulator; the carry of column k (acc >> 29) is the addend of the first multiply-add of column k+1,
-// so no 64-bit addition is ever issued (operand scanning paid one v_lshl_add_u64 per row plus eight in the final
-// normalisation: 58 non-mad instructions per product against 42 here).  CHAIN() pins that association: left alone, the
-// compiler sums a column apart from the carry and joins the two with the very addition this form exists to avoid.
-// Limbs: b < 2^29 (normalised); a may be an un-normalised sum or padded difference: a column receives at most 9 products
-// a_j*b_i, 9 products m_i*p_j (both factors < 2^29) and one carry (< 2^35), so 9*A*(2^29-1) + 9*(2^29-1)^2 + 2^35 < 2^64
-// allows a-limbs up to A = 3.28e9 (MULW_A_LIMB_MAX).  The sums the kernels feed in: x + y (< 2^30), x + PAD2 - y
-// (< 2^29 + 2.66e9 = 3.19e9).  Checked on the host at the bound (tests/host/field29_check.hip).
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PLK_CHAIN(acc) asm("" : "+v"(acc))
-#else
-#define PLK_CHAIN(acc) do { } while (0)
-#endif
-// the reduction half of a column: m_k for k < 9 (and its product with p_0), then the carry; or the output limb for k >= 9
-#define PLK_MONT_LOW(k)  { _Pragma("unroll") for (int i = 0; i < (k); i++) { acc += (uint64_t)m[i] * WP::P29[(k) - i]; PLK_CHAIN(acc); } \
-                           m[k] = ((uint32_t)acc * WP::INV29) & M29; acc += (uint64_t)m[k] * WP::P29[0]; acc >>= 29; }
-#define PLK_MONT_HIGH(k) { _Pragma("unroll") for (int i = (k) - 8; i <= 8; i++) { acc += (uint64_t)m[i] * WP::P29[(k) - i]; PLK_CHAIN(acc); } \
-                           r.l[(k) - 9] = (uint32_t)acc & M29; acc >>= 29; }
-template <class WP>
-PLK_HD W9<WP> mulw(const W9<WP> &a, const W9<WP> &b) {
-    uint32_t m[9];
-    W9<WP> r;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) { acc += (uint64_t)a.l[k - i] * b.l[i]; PLK_CHAIN(acc); }
-        PLK_MONT_LOW(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; i <= 8; i++) { acc += (uint64_t)a.l[k - i] * b.l[i]; PLK_CHAIN(acc); }
-        PLK_MONT_HIGH(k)
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
-}
-// Two independent products in lockstep: the multiply-adds of the two accumulator chains alternate, so that no
-// v_mad_u64_u32 reads the result of the one issued just before it (on gfx950 that costs a wait state: the compiler
-// puts an s_nop between every pair of a single chain).
-#define PLK_MONT_LOW2(k)  { _Pragma("unroll") for (int i = 0; i < (k); i++) { acc0 += (uint64_t)m0[i] * WP::P29[(k) - i]; PLK_CHAIN(acc0); acc1 += (uint64_t)m1[i] * WP::P29[(k) - i]; PLK_CHAIN(acc1); } \
-                            m0[k] = ((uint32_t)acc0 * WP::INV29) & M29; m1[k] = ((uint32_t)acc1 * WP::INV29) & M29; \
-                            acc0 += (uint64_t)m0[k] * WP::P29[0]; acc1 += (uint64_t)m1[k] * WP::P29[0]; acc0 >>= 29; acc1 >>= 29; }
-#define PLK_MONT_HIGH2(k) { _Pragma("unroll") for (int i = (k) - 8; i <= 8; i++) { acc0 += (uint64_t)m0[i] * WP::P29[(k) - i]; PLK_CHAIN(acc0); acc1 += (uint64_t)m1[i] * WP::P29[(k) - i]; PLK_CHAIN(acc1); } \
-                            r0.l[(k) - 9] = (uint32_t)acc0 & M29; r1.l[(k) - 9] = (uint32_t)acc1 & M29; acc0 >>= 29; acc1 >>= 29; }
-template <class WP>
-PLK_HD void mulw2(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &a1, const W9<WP> &b1, W9<WP> &r0, W9<WP> &r1) {
-    uint32_t m0[9], m1[9];
-    uint64_t acc0 = 0, acc1 = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
-        PLK_MONT_LOW2(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; i <= 8; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
-        PLK_MONT_HIGH2(k)
-    }
-    r0.l[8] = (uint32_t)acc0; r1.l[8] = (uint32_t)acc1;
-}
-// two independent squarings in lockstep (see mulw2)
-template <class WP>
-PLK_HD void sqrw2(const W9<WP> &x0, const W9<WP> &x1, W9<WP> &r0, W9<WP> &r1) {
-    uint32_t m0[9], m1[9], d0[9], d1[9];
-    uint64_t acc0 = 0, acc1 = 0;
-#pragma unroll
-    for (int j = 0; j < 9; j++) { d0[j] = x0.l[j] << 1; d1[j] = x1.l[j] << 1; }
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; 2 * i < k; i++) { acc0 += (uint64_t)d0[k - i] * x0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)d1[k - i] * x1.l[i]; PLK_CHAIN(acc1); }
-        if (k % 2 == 0) { acc0 += (uint64_t)x0.l[k / 2] * x0.l[k / 2]; PLK_CHAIN(acc0); acc1 += (uint64_t)x1.l[k / 2] * x1.l[k / 2]; PLK_CHAIN(acc1); }
-        PLK_MONT_LOW2(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; 2 * i < k; i++) { acc0 += (uint64_t)d0[k - i] * x0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)d1[k - i] * x1.l[i]; PLK_CHAIN(acc1); }
-        if (k % 2 == 0) { acc0 += (uint64_t)x0.l[k / 2] * x0.l[k / 2]; PLK_CHAIN(acc0); acc1 += (uint64_t)x1.l[k / 2] * x1.l[k / 2]; PLK_CHAIN(acc1); }
-        PLK_MONT_HIGH2(k)
-    }
-    r0.l[8] = (uint32_t)acc0; r1.l[8] = (uint32_t)acc1;
-}
-// ---- the same lockstep pair with a 9-limb ADDEND folded into each chain (the mixed addition of msm_accumulate):
-//     mulw2_add: r_q = a_q * b_q * 2^-261 + A_q,  normalised,   q = 0, 1
-// A_q is any 9-limb value (limbs up to 2^32 - 1: a padded difference "PADk - x" as it stands, not normalised).  Limb j of the addend
-// joins the accumulator at column 9 + j, before the output limb j is cut off, so the column chain that normalises the product
-// normalises the sum as well: the result is bit for bit normw(addw(mulw(a, b), A)) — same integer, same (unique) normalised form —
-// without the 9 additions and the 25 instructions of normw, for 8 multiply-adds by one (the top limb is a 32-bit add).
-// Bounds: a high column k >= 9 holds at most 17 - k <= 8 products of each kind, so the addend's < 2^32 has room beside them even with
-// the left operand at MULW_A_LIMB_MAX: 8 * 3.28e9 * (2^29 - 1) + 8 * (2^29 - 1)^2 + 2^35 + 2^32 < 2^63.9.  The value must stay below
-// 2^261 and the top limb below 2^32: callers add less than 16p to a product below 1.1p.  Host-checked at the bounds
-// (tests/host/field29_addend_check.hip).
-// (the addend enters as a multiply-add by a one the compiler cannot see: the plain 64-bit addition it would otherwise form wants the
-//  addend widened to a register pair, one extra move per limb)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PLK_ADDEND(acc, x) { uint32_t one_ = 1; asm("" : "+s"(one_)); (acc) += (uint64_t)(x) * one_; }
-#else
-#define PLK_ADDEND(acc, x) { (acc) += (uint64_t)(x); }
-#endif
-#define PLK_MONT_HIGH2_ADD(k) { _Pragma("unroll") for (int i = (k) - 8; i <= 8; i++) { acc0 += (uint64_t)m0[i] * WP::P29[(k) - i]; PLK_CHAIN(acc0); acc1 += (uint64_t)m1[i] * WP::P29[(k) - i]; PLK_CHAIN(acc1); } \
-                                PLK_ADDEND(acc0, A0.l[(k) - 9]); PLK_ADDEND(acc1, A1.l[(k) - 9]); \
-                                r0.l[(k) - 9] = (uint32_t)acc0 & M29; r1.l[(k) - 9] = (uint32_t)acc1 & M29; acc0 >>= 29; acc1 >>= 29; }
-template <class WP>
-PLK_HD void mulw2_add(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &A0, const W9<WP> &a1, const W9<WP> &b1, const W9<WP> &A1, W9<WP> &r0, W9<WP> &r1) {
-    uint32_t m0[9], m1[9];
-    uint64_t acc0 = 0, acc1 = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
-        PLK_MONT_LOW2(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; i <= 8; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
-        PLK_MONT_HIGH2_ADD(k)
-    }
-    r0.l[8] = (uint32_t)acc0 + A0.l[8]; r1.l[8] = (uint32_t)acc1 + A1.l[8];
-}
-
-// a^2: the cross products a_i*a_j (i < j) are taken once against the doubled operand: 45 + 81 mads instead of 162
-template <class WP>
-PLK_HD W9<WP> sqrw(const W9<WP> &a) {
-    uint32_t m[9], a2[9];
-    W9<WP> r;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int j = 0; j < 9; j++) a2[j] = a.l[j] << 1;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; 2 * i < k; i++) { acc += (uint64_t)a2[k - i] * a.l[i]; PLK_CHAIN(acc); }
-        if (k % 2 == 0) { acc += (uint64_t)a.l[k / 2] * a.l[k / 2]; PLK_CHAIN(acc); }
-        PLK_MONT_LOW(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; 2 * i < k; i++) { acc += (uint64_t)a2[k - i] * a.l[i]; PLK_CHAIN(acc); }
-        if (k % 2 == 0) { acc += (uint64_t)a.l[k / 2] * a.l[k / 2]; PLK_CHAIN(acc); }
-        PLK_MONT_HIGH(k)
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
-}
-
-// a*b + c*d with ONE Montgomery reduction (243 mads instead of 324).  Used as a*b - c*e by passing
-// d = k*p - e.  Limbs: a, c < 2^30; b, d < 2^29.  Columns hold at most 9 * (2*2^59 + 2^58) < 2^63.4.
-template <class WP>
-PLK_HD W9<WP> mul2addw(const W9<WP> &a, const W9<WP> &b, const W9<WP> &c, const W9<WP> &d) {
-    uint32_t m[9];
-    W9<WP> r;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) { acc += (uint64_t)a.l[k - i] * b.l[i]; PLK_CHAIN(acc); acc += (uint64_t)c.l[k - i] * d.l[i]; PLK_CHAIN(acc); }
-        PLK_MONT_LOW(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; i <= 8; i++) { acc += (uint64_t)a.l[k - i] * b.l[i]; PLK_CHAIN(acc); acc += (uint64_t)c.l[k - i] * d.l[i]; PLK_CHAIN(acc); }
-        PLK_MONT_HIGH(k)
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
-}
-
-// ---- LAZY MONTGOMERY DIGITS: the same lockstep products with some of the digits m_0..m_7 left UNMASKED (the additions the MSM prices by
-// the instructions they issue: xyzzw_add_mixed_flag, xyzzw_add_pairs).  A column's digit is m_k = ((uint32_t)acc * INV29) & M29, but any
-// m~_k = m_k (mod 2^29) clears the column's low 29 bits just as well: (a*b + m~*p) / 2^261 stays an exact integer congruent to a*b*2^-261,
-// and the `& M29` of that digit, one VALU instruction, is not issued.  Two things depend on the mask, and both are kept:
+// ---- Montgomery product, radix 2^29, R' = 2^261 — PRODUCT SCANNING.  The 17 columns of a*b + m*p are summed one after the other in
+// ONE 64-bit accumulator per chain; the carry of column k (acc >> 29) is the addend of the first multiply-add of column k+1, so no 64-bit
+// addition is ever issued (operand scanning paid one v_lshl_add_u64 per row plus eight in the final normalisation: 58 non-mad
+// instructions per product against 42 here).  Columns 0..8 give the digit m_k and the carry, columns 9..16 an output limb.
+// The scan is written ONCE (mont_scan); every form below is an instantiation of it:
+//   - one chain or two in lockstep: the multiply-adds of two accumulator chains alternate one by one, so that no v_mad_u64_u32 reads the
+//     result of the one issued just before it (on gfx950 that costs a wait state: the compiler puts an s_nop between every pair of a
+//     single chain);
+//   - an OPERAND HALF per chain, which adds a column's a*b terms: T products (Products), a squaring (Squaring), a shift (Shift5);
+//   - LZ, the set of digits m_0..m_7 left UNMASKED (bit k for m_k; bit 8 and above are ignored; 0 is the masked form);
+//   - an optional 9-limb ADDEND that joins the high columns.
+// PLK_CHAIN pins the association: left alone, the compiler sums a column apart from the carry and joins the two with the very addition
+// this form exists to avoid.
+// LAZY DIGITS.  A column's digit is m_k = ((uint32_t)acc * INV29) & M29, but any m~_k = m_k (mod 2^29) clears the column's low 29 bits just
+// as well: (a*b + m~*p) / 2^261 stays an exact integer congruent to a*b*2^-261, and the `& M29` of that digit, one VALU instruction, is not
+// issued (the additions the MSM prices by the instructions they issue: xyzzw_add_mixed_flag, xyzzw_add_pairs).  Two things depend on the
+// mask, and both are kept:
 //   - the VALUE of the result.  Digit 8 is always masked: with m~_0..m~_7 < 2^32 and m~_8 < 2^29, m~ = sum m~_k 2^(29 k) < 2^261 + 2^235, and
 //     m~ = m (mod 2^261), so m~ is m or m + 2^261: the result is the masked form's or that plus p EXACTLY, and it is below the masked form's
 //     bound + 2^-26 p.  Every value bound of ec29_dev.h has more slack than that.  Output limbs are normalised as before.
-//   - the 64-bit COLUMN.  An unmasked digit is up to 2^32 - 1 and the carries grow with it, so every instantiation evaluates its exact worst
-//     case at compile time (lazy_col_bound: every limb of both operands at its DECLARED bound, a Limbs9 per operand; every unmasked digit at
-//     2^32 - 1 against the actual limbs of p; the addend where there is one; the carry the worst column before it really leaves, < 2^35 with all
-//     digits masked) and a static_assert requires every column below 2^64: a form that does not fit does not compile.  The declared bounds
-//     are the caller's promise, checked on the host at exactly those limbs with a 128-bit shadow (tests/host/field29_lazy_digits_check.hip).
-// LZ is the set of unmasked digits, bit k for m_k; bit 8 and above are ignored.  LZ = 0 is the masked form, instruction for instruction.
+//   - the 64-bit COLUMN.  Every instantiation, masked or lazy, evaluates its exact worst case at compile time (lazy_col_bound: every limb of
+//     every operand at its DECLARED bound, a Limbs9 per operand; every unmasked digit at 2^32 - 1 and every masked one at 2^29 - 1 against
+//     the actual limbs of p; the addend where there is one; the carry the worst column before it really leaves) and a static_assert
+//     requires every column below 2^64: a form that does not fit does not compile.  The declared bounds are the caller's promise, checked
+//     on the host at exactly those limbs (tests/host/field29_check.hip, field29_addend_check.hip, field29_lazy_digits_check.hip).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PLK_CHAIN(acc) asm("" : "+v"(acc))
+// (the addend enters as a multiply-add by a one the compiler cannot see: the plain 64-bit addition it would otherwise form wants the
+//  addend widened to a register pair, one extra move per limb)
+#define PLK_ADDEND(acc, x) { uint32_t one_ = 1; asm("" : "+s"(one_)); (acc) += (uint64_t)(x) * one_; }
+#else
+#define PLK_CHAIN(acc) do { } while (0)
+#define PLK_ADDEND(acc, x) { (acc) += (uint64_t)(x); }
+#endif
 struct Limbs9 { uint32_t l[9]; };                              // per-limb upper bounds of an operand (inclusive)
 constexpr Limbs9 lb_uniform(uint32_t v) { return Limbs9{{v, v, v, v, v, v, v, v, v}}; }
 constexpr Limbs9 lb_of(const uint32_t (&a)[9]) { return Limbs9{{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]}}; }
@@ -353,12 +185,15 @@ constexpr Limbs9 lb_max(const Limbs9 &a, const Limbs9 &b) { Limbs9 r{}; for (int
 struct LbNone { static constexpr Limbs9 B = lb_uniform(0); };                 // no such operand
 struct LbNorm { static constexpr Limbs9 B = lb_uniform(M29); };               // normalised: out of a column chain or normw, value < 2^261
 struct LbAny { static constexpr Limbs9 B = lb_uniform(0xffffffffu); };        // an addend as it stands (a padded difference, not normalised)
+struct LbMulwA { static constexpr Limbs9 B = lb_uniform(MULW_A_LIMB_MAX); };  // the left operand of a masked product: a sum or a padded difference
+struct LbBelow30 { static constexpr Limbs9 B = lb_uniform((1u << 30) - 1); }; // a sum of two normalised values
 constexpr unsigned LZ_ALL = 0xffu;
 constexpr bool lazy_digit(unsigned lz, int k) { return k < 8 && ((lz >> k) & 1u); }
 struct ColBound { uint64_t worst; bool fits; };                // the largest column (wrapped if it does not fit); all columns below 2^64
-// columns of a*b + c*d + m~*p (+ addend in the high columns), m~ with the digits of lz unmasked.  A squaring is a = b = the operand's bounds:
-// the doubled cross products and the square of a column sum to the same worst case.
-constexpr ColBound lazy_col_bound(const Limbs9 &a, const Limbs9 &b, const Limbs9 &c, const Limbs9 &d, const Limbs9 &addend, const uint32_t (&p)[9], unsigned lz) {
+// columns of a*b + c*d + e*f + m~*p (+ addend in the high columns), m~ with the digits of lz unmasked.  A squaring is a = b = the operand's
+// bounds: the doubled cross products and the square of a column sum to the same worst case.
+constexpr ColBound lazy_col_bound(const Limbs9 &a, const Limbs9 &b, const Limbs9 &c, const Limbs9 &d, const Limbs9 &addend, const uint32_t (&p)[9], unsigned lz,
+                                  const Limbs9 &e = LbNone::B, const Limbs9 &f = LbNone::B) {
     uint64_t carry = 0, worst = 0;
     bool fits = true;
     for (int k = 0; k < 17; k++) {
@@ -366,6 +201,7 @@ constexpr ColBound lazy_col_bound(const Limbs9 &a, const Limbs9 &b, const Limbs9
         for (int i = (k < 9 ? 0 : k - 8); i <= (k < 9 ? k : 8); i++) {
             fits &= !__builtin_add_overflow(s, (uint64_t)a.l[k - i] * b.l[i], &s);
             fits &= !__builtin_add_overflow(s, (uint64_t)c.l[k - i] * d.l[i], &s);
+            fits &= !__builtin_add_overflow(s, (uint64_t)e.l[k - i] * f.l[i], &s);
             fits &= !__builtin_add_overflow(s, (uint64_t)(lazy_digit(lz, i) ? 0xffffffffu : M29) * p[k - i], &s);
         }
         if (k >= 9) fits &= !__builtin_add_overflow(s, (uint64_t)addend.l[k - 9], &s);
@@ -375,100 +211,186 @@ constexpr ColBound lazy_col_bound(const Limbs9 &a, const Limbs9 &b, const Limbs9
     return ColBound{worst, fits};
 }
 #define PLK_LZ_DIGIT(LZ, k, acc) (lazy_digit((LZ), (k)) ? (uint32_t)(acc) * WP::INV29 : ((uint32_t)(acc) * WP::INV29) & M29)
-#define PLK_MONT_LOW_LZ(k)   { _Pragma("unroll") for (int i = 0; i < (k); i++) { acc += (uint64_t)m[i] * WP::P29[(k) - i]; PLK_CHAIN(acc); } \
-                               m[k] = PLK_LZ_DIGIT(LZ, k, acc); acc += (uint64_t)m[k] * WP::P29[0]; acc >>= 29; }
-#define PLK_MONT_LOW2_LZ(k)  { _Pragma("unroll") for (int i = 0; i < (k); i++) { acc0 += (uint64_t)m0[i] * WP::P29[(k) - i]; PLK_CHAIN(acc0); acc1 += (uint64_t)m1[i] * WP::P29[(k) - i]; PLK_CHAIN(acc1); } \
-                               m0[k] = PLK_LZ_DIGIT(LZ0, k, acc0); m1[k] = PLK_LZ_DIGIT(LZ1, k, acc1); \
-                               acc0 += (uint64_t)m0[k] * WP::P29[0]; acc1 += (uint64_t)m1[k] * WP::P29[0]; acc0 >>= 29; acc1 >>= 29; }
-// mulw2 with lazy digits; LA0, LB0, LA1, LB1: the declared limb bounds of a0, b0, a1, b1
+
+// the second chain of a scan that has only one: every step is nothing
+struct NoChain {
+    static constexpr bool FITS = true;
+    uint32_t m[9];
+    uint64_t acc;
+    PLK_HD void mad(uint64_t, uint32_t) {}
+    PLK_HD void digit(int) {}
+    PLK_HD void mp0(int) {}
+    PLK_HD void addend(int) {}
+    PLK_HD void limb(int) {}
+    PLK_HD void shift() {}
+    PLK_HD void top() {}
+};
+// one accumulator chain of the scan: its operand half, its result, its addend if LAD is not LbNone (limb j joins the accumulator at
+// column 9 + j, after the column's m*p terms and before output limb j is cut off), its digits and its accumulator
+template <class WP, unsigned LZ, class H, class LAD = LbNone>
+struct MontChain {
+    using Half = H;
+    static constexpr bool ADD = !std::is_same<LAD, LbNone>::value;
+    static constexpr bool FITS = H::bound(LAD::B, LZ).fits;
+    H h;
+    const W9<WP> *A = nullptr;
+    W9<WP> *r = nullptr;
+    uint32_t m[9];
+    uint64_t acc = 0;
+    PLK_HD void mad(uint64_t a, uint32_t b) { acc += a * b; PLK_CHAIN(acc); }
+    PLK_HD void digit(int k) { m[k] = PLK_LZ_DIGIT(LZ, k, acc); }
+    PLK_HD void mp0(int k) { acc += (uint64_t)m[k] * WP::P29[0]; }
+    PLK_HD void limb(int k) { r->l[k - 9] = (uint32_t)acc & M29; }
+    PLK_HD void shift() { acc >>= 29; }
+    PLK_HD void addend(int k) { if constexpr (ADD) PLK_ADDEND(acc, A->l[k - 9]); }
+    PLK_HD void top() { r->l[8] = (uint32_t)acc; if constexpr (ADD) r->l[8] += A->l[8]; }
+};
+// The operand halves: what column k receives besides m*p.  The scan walks i = lo .. while more(k, i, hi) and takes term<0..2>(chain, k, i)
+// of each chain in turn, then last(chain, k) where has_last<LOW>(k); prepare(chain, j) runs once per limb before the scan.  They hold no loop
+// of their own (see mont_scan); bound: the worst columns with every operand at its declared bound.
+// T = 1, 2 or 3 products a_t * b_t; x = {a_0, b_0, a_1, b_1, ...} and L their declared bounds in that order.  a_t[k - i] * b_t[i] for
+// t = 0 .. T-1, then the next i.
+template <class WP, class... L>
+struct Products {
+    static constexpr int T = sizeof...(L) / 2;
+    const W9<WP> *x[2 * T];
+    static PLK_HD bool more(int k, int i, int hi) { return i <= hi; }
+    template <int J, class C> static PLK_HD void term(C &c, int k, int i) {
+        if constexpr (J < T && !std::is_same<C, NoChain>::value) c.mad(c.h.x[2 * J]->l[k - i], c.h.x[2 * J + 1]->l[i]);
+    }
+    template <class C> static PLK_HD void prepare(C &, int) {}
+    template <class C> static PLK_HD void last(C &, int) {}
+    template <bool LOW> static PLK_HD bool has_last(int) { return false; }
+    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz) {
+        const Limbs9 b[6] = {L::B...};                         // (the pairs that are not there: zeros)
+        return lazy_col_bound(b[0], b[1], b[2], b[3], addend, WP::P29, lz, b[4], b[5]);
+    }
+};
+// x^2: the cross products x_i*x_j (i < j) are taken once against the doubled operand, then the square on an even column: 45 + 81
+// multiply-adds instead of 162.  LX: the declared bound of x (below 2^31: the doubled limb is a 32-bit value)
+template <class WP, class LX>
+struct Squaring {
+    static_assert(lb_below(LX::B, 1u << 31), "a doubled limb can exceed 32 bits");
+    const W9<WP> &x;
+    uint32_t d[9];
+    static PLK_HD bool more(int k, int i, int) { return 2 * i < k; }
+    template <int J, class C> static PLK_HD void term(C &c, int k, int i) {
+        if constexpr (J == 0 && !std::is_same<C, NoChain>::value) c.mad(c.h.d[k - i], c.h.x.l[i]);
+    }
+    template <class C> static PLK_HD void prepare(C &c, int j) { if constexpr (!std::is_same<C, NoChain>::value) c.h.d[j] = c.h.x.l[j] << 1; }
+    template <class C> static PLK_HD void last(C &c, int k) { if constexpr (!std::is_same<C, NoChain>::value) c.mad(c.h.x.l[k / 2], c.h.x.l[k / 2]); }
+    template <bool LOW> static PLK_HD bool has_last(int k) { return k % 2 == 0; }
+    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz) { return lazy_col_bound(LX::B, LX::B, LbNone::B, LbNone::B, addend, WP::P29, lz); }
+};
+// x * 2^5 (canonical_w): x_k << 5 in column k — nine shifts, no multiply-add.  As a product it is x times the limbs (32, 0, ..., 0).
+template <class WP>
+struct Shift5 {
+    const W9<WP> &x;
+    static PLK_HD bool more(int, int, int) { return false; }
+    template <int J, class C> static PLK_HD void term(C &, int, int) {}
+    template <class C> static PLK_HD void prepare(C &, int) {}
+    template <class C> static PLK_HD void last(C &c, int k) { if constexpr (!std::is_same<C, NoChain>::value) c.acc += (uint64_t)c.h.x.l[k] << 5; }
+    template <bool LOW> static PLK_HD bool has_last(int) { return LOW; }
+    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz) { return lazy_col_bound(LbNorm::B, Limbs9{{32}}, LbNone::B, LbNone::B, addend, WP::P29, lz); }
+};
+// THE scan.  Order is the contract (it is what the schedule and the register count of every hot kernel hang on): inside a column every
+// step goes chain 0, chain 1 — the operand half's terms one by one, the m*p terms one by one, then both digits, both m*p_0, both
+// shifts; in a high column both addends, both limbs, both shifts.  The chains' state (digits, accumulator) is LOCAL to this function, and
+// chain 0's result is its return value: with the state or the result of a single chain handed in from a caller the compiler schedules
+// every kernel differently (profiles/field29_engine_isa.txt).  The loops must unroll: the limb arrays are registers only then.
+template <class WP, class C0, class C1 = NoChain>
+PLK_HD auto mont_scan(const C0 &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr, W9<WP> *r1 = nullptr) {
+    static_assert(C0::FITS, "a column of chain 0 can exceed 64 bits");
+    static_assert(C1::FITS, "a column of chain 1 can exceed 64 bits");
+    using H = typename C0::Half;
+    constexpr bool ONE = std::is_same<C1, NoChain>::value;     // one chain: the result is returned; two: written to r0, r1
+    W9<WP> r;
+    C0 c0 = s0;
+    C1 c1 = s1;
+    if constexpr (ONE) c0.r = &r;
+    else { c0.r = r0; c1.r = r1; }
+#pragma unroll
+    for (int j = 0; j < 9; j++) { H::prepare(c0, j); H::prepare(c1, j); }
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+#pragma unroll
+        for (int i = 0; H::more(k, i, k); i++) { H::template term<0>(c0, k, i); H::template term<0>(c1, k, i); H::template term<1>(c0, k, i); H::template term<1>(c1, k, i); H::template term<2>(c0, k, i); H::template term<2>(c1, k, i); }
+        if (H::template has_last<true>(k)) { H::last(c0, k); H::last(c1, k); }
+#pragma unroll
+        for (int i = 0; i < k; i++) { c0.mad(c0.m[i], WP::P29[k - i]); c1.mad(c1.m[i], WP::P29[k - i]); }
+        c0.digit(k); c1.digit(k);
+        c0.mp0(k); c1.mp0(k);
+        c0.shift(); c1.shift();
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) {
+#pragma unroll
+        for (int i = k - 8; H::more(k, i, 8); i++) { H::template term<0>(c0, k, i); H::template term<0>(c1, k, i); H::template term<1>(c0, k, i); H::template term<1>(c1, k, i); H::template term<2>(c0, k, i); H::template term<2>(c1, k, i); }
+        if (H::template has_last<false>(k)) { H::last(c0, k); H::last(c1, k); }
+#pragma unroll
+        for (int i = k - 8; i <= 8; i++) { c0.mad(c0.m[i], WP::P29[k - i]); c1.mad(c1.m[i], WP::P29[k - i]); }
+        c0.addend(k); c1.addend(k);
+        c0.limb(k); c1.limb(k);
+        c0.shift(); c1.shift();
+    }
+    c0.top(); c1.top();
+    if constexpr (ONE) return r;
+}
+
+// ---- the forms with lazy digits.  LA, LB, ...: the declared limb bounds of the operands, in the order of the arguments.
+// mulw2: two independent products in lockstep
 template <class WP, unsigned LZ0, unsigned LZ1, class LA0, class LB0, class LA1, class LB1>
 PLK_HD void mulw2_lz(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &a1, const W9<WP> &b1, W9<WP> &r0, W9<WP> &r1) {
-    static_assert(lazy_col_bound(LA0::B, LB0::B, LbNone::B, LbNone::B, LbNone::B, WP::P29, LZ0).fits, "mulw2_lz: a column of chain 0 can exceed 64 bits");
-    static_assert(lazy_col_bound(LA1::B, LB1::B, LbNone::B, LbNone::B, LbNone::B, WP::P29, LZ1).fits, "mulw2_lz: a column of chain 1 can exceed 64 bits");
-    uint32_t m0[9], m1[9];
-    uint64_t acc0 = 0, acc1 = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
-        PLK_MONT_LOW2_LZ(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; i <= 8; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
-        PLK_MONT_HIGH2(k)
-    }
-    r0.l[8] = (uint32_t)acc0; r1.l[8] = (uint32_t)acc1;
+    mont_scan<WP>(MontChain<WP, LZ0, Products<WP, LA0, LB0>>{{{&a0, &b0}}}, MontChain<WP, LZ1, Products<WP, LA1, LB1>>{{{&a1, &b1}}}, &r0, &r1);
 }
-// sqrw2 with lazy digits; LX0, LX1: the declared limb bounds of x0, x1 (below 2^31: the doubled limb is a 32-bit value)
+// sqrw2: two independent squarings in lockstep
 template <class WP, unsigned LZ0, unsigned LZ1, class LX0, class LX1>
 PLK_HD void sqrw2_lz(const W9<WP> &x0, const W9<WP> &x1, W9<WP> &r0, W9<WP> &r1) {
-    static_assert(lazy_col_bound(LX0::B, LX0::B, LbNone::B, LbNone::B, LbNone::B, WP::P29, LZ0).fits, "sqrw2_lz: a column of chain 0 can exceed 64 bits");
-    static_assert(lazy_col_bound(LX1::B, LX1::B, LbNone::B, LbNone::B, LbNone::B, WP::P29, LZ1).fits, "sqrw2_lz: a column of chain 1 can exceed 64 bits");
-    static_assert(lb_below(LX0::B, 1u << 31) && lb_below(LX1::B, 1u << 31), "sqrw2_lz: a doubled limb can exceed 32 bits");
-    uint32_t m0[9], m1[9], d0[9], d1[9];
-    uint64_t acc0 = 0, acc1 = 0;
-#pragma unroll
-    for (int j = 0; j < 9; j++) { d0[j] = x0.l[j] << 1; d1[j] = x1.l[j] << 1; }
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; 2 * i < k; i++) { acc0 += (uint64_t)d0[k - i] * x0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)d1[k - i] * x1.l[i]; PLK_CHAIN(acc1); }
-        if (k % 2 == 0) { acc0 += (uint64_t)x0.l[k / 2] * x0.l[k / 2]; PLK_CHAIN(acc0); acc1 += (uint64_t)x1.l[k / 2] * x1.l[k / 2]; PLK_CHAIN(acc1); }
-        PLK_MONT_LOW2_LZ(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; 2 * i < k; i++) { acc0 += (uint64_t)d0[k - i] * x0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)d1[k - i] * x1.l[i]; PLK_CHAIN(acc1); }
-        if (k % 2 == 0) { acc0 += (uint64_t)x0.l[k / 2] * x0.l[k / 2]; PLK_CHAIN(acc0); acc1 += (uint64_t)x1.l[k / 2] * x1.l[k / 2]; PLK_CHAIN(acc1); }
-        PLK_MONT_HIGH2(k)
-    }
-    r0.l[8] = (uint32_t)acc0; r1.l[8] = (uint32_t)acc1;
+    mont_scan<WP>(MontChain<WP, LZ0, Squaring<WP, LX0>>{{x0}}, MontChain<WP, LZ1, Squaring<WP, LX1>>{{x1}}, &r0, &r1);
 }
-// mulw2_add with lazy digits; LAD0, LAD1: the declared limb bounds of the addends A0, A1
+// mulw2_add: the lockstep pair with a 9-limb ADDEND folded into each chain (the mixed addition of msm_accumulate):
+//     r_q = a_q * b_q * 2^-261 + A_q,  normalised,   q = 0, 1
+// A_q is any 9-limb value (limbs up to 2^32 - 1: a padded difference "PADk - x" as it stands, not normalised).  The column chain that
+// normalises the product normalises the sum as well: the result is bit for bit normw(addw(mulw(a, b), A)) — same integer, same (unique)
+// normalised form — without the 9 additions and the 25 instructions of normw, for 8 multiply-adds by one (the top limb is a 32-bit add).
+// The value must stay below 2^261 and the top limb below 2^32: callers add less than 16p to a product below 1.1p.
 template <class WP, unsigned LZ0, unsigned LZ1, class LA0, class LB0, class LAD0, class LA1, class LB1, class LAD1>
 PLK_HD void mulw2_add_lz(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &A0, const W9<WP> &a1, const W9<WP> &b1, const W9<WP> &A1, W9<WP> &r0, W9<WP> &r1) {
-    static_assert(lazy_col_bound(LA0::B, LB0::B, LbNone::B, LbNone::B, LAD0::B, WP::P29, LZ0).fits, "mulw2_add_lz: a column of chain 0 can exceed 64 bits");
-    static_assert(lazy_col_bound(LA1::B, LB1::B, LbNone::B, LbNone::B, LAD1::B, WP::P29, LZ1).fits, "mulw2_add_lz: a column of chain 1 can exceed 64 bits");
-    uint32_t m0[9], m1[9];
-    uint64_t acc0 = 0, acc1 = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
-        PLK_MONT_LOW2_LZ(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; i <= 8; i++) { acc0 += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc0); acc1 += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc1); }
-        PLK_MONT_HIGH2_ADD(k)
-    }
-    r0.l[8] = (uint32_t)acc0 + A0.l[8]; r1.l[8] = (uint32_t)acc1 + A1.l[8];
+    mont_scan<WP>(MontChain<WP, LZ0, Products<WP, LA0, LB0>, LAD0>{{{&a0, &b0}}, &A0}, MontChain<WP, LZ1, Products<WP, LA1, LB1>, LAD1>{{{&a1, &b1}}, &A1}, &r0, &r1);
 }
-// mul2addw with lazy digits; LA, LB, LC, LD: the declared limb bounds of a, b, c, d
+// mul2addw: a*b + c*d with ONE Montgomery reduction (243 mads instead of 324).  Used as a*b - c*e by passing d = k*p - e.
 template <class WP, unsigned LZ, class LA, class LB, class LC, class LD>
 PLK_HD W9<WP> mul2addw_lz(const W9<WP> &a, const W9<WP> &b, const W9<WP> &c, const W9<WP> &d) {
-    static_assert(lazy_col_bound(LA::B, LB::B, LC::B, LD::B, LbNone::B, WP::P29, LZ).fits, "mul2addw_lz: a column can exceed 64 bits");
-    uint32_t m[9];
-    W9<WP> r;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) { acc += (uint64_t)a.l[k - i] * b.l[i]; PLK_CHAIN(acc); acc += (uint64_t)c.l[k - i] * d.l[i]; PLK_CHAIN(acc); }
-        PLK_MONT_LOW_LZ(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; i <= 8; i++) { acc += (uint64_t)a.l[k - i] * b.l[i]; PLK_CHAIN(acc); acc += (uint64_t)c.l[k - i] * d.l[i]; PLK_CHAIN(acc); }
-        PLK_MONT_HIGH(k)
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
+    return mont_scan<WP>(MontChain<WP, LZ, Products<WP, LA, LB, LC, LD>>{{{&a, &b, &c, &d}}});
+}
+
+// ---- the masked forms: the same with no digit unmasked and the bounds of their contracts.
+// mulw(a, b): b normalised; a may be an un-normalised sum or padded difference with limbs up to MULW_A_LIMB_MAX — the sums the kernels
+// feed in: x + y (< 2^30), x + PAD2 - y (< 2^29 + 2.66e9 = 3.19e9).
+template <class WP>
+PLK_HD W9<WP> mulw(const W9<WP> &a, const W9<WP> &b) { return mont_scan<WP>(MontChain<WP, 0, Products<WP, LbMulwA, LbNorm>>{{{&a, &b}}}); }
+template <class WP>
+PLK_HD void mulw2(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &a1, const W9<WP> &b1, W9<WP> &r0, W9<WP> &r1) {
+    mulw2_lz<WP, 0, 0, LbMulwA, LbNorm, LbMulwA, LbNorm>(a0, b0, a1, b1, r0, r1);
+}
+template <class WP>
+PLK_HD void mulw2_add(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &A0, const W9<WP> &a1, const W9<WP> &b1, const W9<WP> &A1, W9<WP> &r0, W9<WP> &r1) {
+    mulw2_add_lz<WP, 0, 0, LbMulwA, LbNorm, LbAny, LbMulwA, LbNorm, LbAny>(a0, b0, A0, a1, b1, A1, r0, r1);
+}
+// normalised input
+template <class WP>
+PLK_HD W9<WP> sqrw(const W9<WP> &a) { return mont_scan<WP>(MontChain<WP, 0, Squaring<WP, LbNorm>>{{a}}); }
+template <class WP>
+PLK_HD void sqrw2(const W9<WP> &x0, const W9<WP> &x1, W9<WP> &r0, W9<WP> &r1) { sqrw2_lz<WP, 0, 0, LbNorm, LbNorm>(x0, x1, r0, r1); }
+// limbs: a, c < 2^30; b, d < 2^29
+template <class WP>
+PLK_HD W9<WP> mul2addw(const W9<WP> &a, const W9<WP> &b, const W9<WP> &c, const W9<WP> &d) {
+    return mul2addw_lz<WP, 0, LbBelow30, LbNorm, LbBelow30, LbNorm>(a, b, c, d);
+}
+// a0*b0 + a1*b1 + a2*b2 with one reduction (3*81 + 81 mads instead of 3*162).  Normalised inputs.
+template <class WP>
+PLK_HD W9<WP> mulsum3w(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &a1, const W9<WP> &b1, const W9<WP> &a2, const W9<WP> &b2) {
+    return mont_scan<WP>(MontChain<WP, 0, Products<WP, LbNorm, LbNorm, LbNorm, LbNorm, LbNorm, LbNorm>>{{{&a0, &b0, &a1, &b1, &a2, &b2}}});
 }
 
 // ---- product by a CONSTANT that is held as three shifted copies ("tw3"): 108 multiply-adds instead of 162.
@@ -485,60 +407,57 @@ PLK_HD W9<WP> mul2addw_lz(const W9<WP> &a, const W9<WP> &b, const W9<WP> &c, con
 // limbs are allowed but buy a bound of up to 19p (limbs of 3.2e9), so callers normalise first.  Output limbs are normalised.
 constexpr uint32_t MULTW3_X_LIMB_MAX = 3600000000u;
 template <class WP> struct Tw3 { uint32_t w[3][9]; };
+// one body for one product, or two by the SAME constant in lockstep (as mont_scan: the multiply-adds of the chains alternate one by
+// one, the state is local, one chain's result is the return value)
 template <class WP>
-PLK_HD W9<WP> mul_tw3(const W9<WP> &x, const Tw3<WP> &t) {
+struct Tw3Chain {
+    const W9<WP> &x;
+    W9<WP> *r = nullptr;
     uint32_t m[3];
-    W9<WP> r;
     uint64_t acc = 0;
+    PLK_HD void mad(uint64_t a, uint32_t b) { acc += a * b; PLK_CHAIN(acc); }
+    PLK_HD void xw(int j, uint32_t w) { mad(x.l[j], w); }
+    PLK_HD void digit(int k) { m[k] = ((uint32_t)acc * WP::INV29) & M29; }
+    PLK_HD void mp0(int k) { acc += (uint64_t)m[k] * WP::P29[0]; }
+    PLK_HD void limb(int j) { r->l[j] = (uint32_t)acc & M29; }
+    PLK_HD void shift() { acc >>= 29; }
+    PLK_HD void top() { r->l[8] = (uint32_t)acc; }
+};
+struct NoTw3Chain : NoChain { PLK_HD void xw(int, uint32_t) {} };
+template <class WP, class C1 = NoTw3Chain>
+PLK_HD auto mul_tw3_scan(const Tw3<WP> &t, const Tw3Chain<WP> &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr, W9<WP> *r1 = nullptr) {
+    constexpr bool ONE = std::is_same<C1, NoTw3Chain>::value;
+    W9<WP> r;
+    Tw3Chain<WP> c0 = s0;
+    C1 c1 = s1;
+    if constexpr (ONE) c0.r = &r;
+    else { c0.r = r0; c1.r = r1; }
 #pragma unroll
     for (int k = 0; k < 11; k++) {
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             if (k - i < 0 || k - i > 8) continue;
 #pragma unroll
-            for (int q = 0; q < 3; q++) { acc += (uint64_t)x.l[3 * q + i] * t.w[q][k - i]; PLK_CHAIN(acc); }
+            for (int q = 0; q < 3; q++) { c0.xw(3 * q + i, t.w[q][k - i]); c1.xw(3 * q + i, t.w[q][k - i]); }
         }
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             if (i >= k || k - i > 8) continue;
-            acc += (uint64_t)m[i] * WP::P29[k - i]; PLK_CHAIN(acc);
+            c0.mad(c0.m[i], WP::P29[k - i]); c1.mad(c1.m[i], WP::P29[k - i]);
         }
-        if (k < 3) { m[k] = ((uint32_t)acc * WP::INV29) & M29; acc += (uint64_t)m[k] * WP::P29[0]; }
-        else r.l[k - 3] = (uint32_t)acc & M29;
-        acc >>= 29;
+        if (k < 3) { c0.digit(k); c1.digit(k); c0.mp0(k); c1.mp0(k); }
+        else { c0.limb(k - 3); c1.limb(k - 3); }
+        c0.shift(); c1.shift();
     }
-    r.l[8] = (uint32_t)acc;
-    return r;
+    c0.top(); c1.top();
+    if constexpr (ONE) return r;
 }
-// two of them in lockstep with the SAME constant (the two products of a butterfly stage that share a twiddle)
+template <class WP>
+PLK_HD W9<WP> mul_tw3(const W9<WP> &x, const Tw3<WP> &t) { return mul_tw3_scan(t, Tw3Chain<WP>{x}); }
+// two of them (the two products of a butterfly stage that share a twiddle)
 template <class WP>
 PLK_HD void mul_tw3_2(const W9<WP> &x0, const W9<WP> &x1, const Tw3<WP> &t, W9<WP> &r0, W9<WP> &r1) {
-    uint32_t m0[3], m1[3];
-    uint64_t acc0 = 0, acc1 = 0;
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            if (k - i < 0 || k - i > 8) continue;
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                acc0 += (uint64_t)x0.l[3 * q + i] * t.w[q][k - i]; PLK_CHAIN(acc0);
-                acc1 += (uint64_t)x1.l[3 * q + i] * t.w[q][k - i]; PLK_CHAIN(acc1);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            if (i >= k || k - i > 8) continue;
-            acc0 += (uint64_t)m0[i] * WP::P29[k - i]; PLK_CHAIN(acc0);
-            acc1 += (uint64_t)m1[i] * WP::P29[k - i]; PLK_CHAIN(acc1);
-        }
-        if (k < 3) {
-            m0[k] = ((uint32_t)acc0 * WP::INV29) & M29; m1[k] = ((uint32_t)acc1 * WP::INV29) & M29;
-            acc0 += (uint64_t)m0[k] * WP::P29[0]; acc1 += (uint64_t)m1[k] * WP::P29[0];
-        } else { r0.l[k - 3] = (uint32_t)acc0 & M29; r1.l[k - 3] = (uint32_t)acc1 & M29; }
-        acc0 >>= 29; acc1 >>= 29;
-    }
-    r0.l[8] = (uint32_t)acc0; r1.l[8] = (uint32_t)acc1;
+    mul_tw3_scan(t, Tw3Chain<WP>{x0}, Tw3Chain<WP>{x1}, &r0, &r1);
 }
 // the three copies of a constant given in the W domain (w * 2^261, canonical): W_2 is the value itself, W_1 and W_0 are it times
 // 2^-87 and 2^-174 — products by the limb-unit vectors 2^174 and 2^87 (mulw divides by 2^261)
@@ -560,6 +479,9 @@ PLK_HD Tw3<WP> make_tw3(const W9<WP> &w_dom_w) {
 // reduction kernels are 15-20 % faster on these forms (msm_task_reduce 0.25 -> 0.21 ms, msm_window_sums 0.13 -> 0.11 at
 // 2^20 terms), while every throughput-bound kernel (NTT passes, point-wise kernels, the accumulation) is as fast or faster
 // on the product-scanning forms above.
+// They share nothing with mont_scan on purpose: the host checks hold the two formulations against each other.  (Each is written out in
+// full: with the reduction row or the normalising tail behind a shared function the g1ntt_stage kernels, g1_add_call and msm_naive come out
+// with other instruction and register counts or another schedule.)
 template <class WP>
 PLK_HD W9<WP> mulw_os(const W9<WP> &a, const W9<WP> &b) {
     uint64_t t[10];
@@ -699,35 +621,6 @@ PLK_HD bool is_zero_mod_p(const W9<WP> &a) {
 template <class WP>
 PLK_HD bool maybe_zero_mod_p(const W9<WP> &a) { return ((a.l[0] * WP::PINV0) & M29) < 16; }
 
-// a0*b0 + a1*b1 + a2*b2 with one reduction (3*81 + 81 mads instead of 3*162).  Normalised inputs; a column never
-// holds more than 9 * (3 + 1) * 2^58 < 2^64.
-template <class WP>
-PLK_HD W9<WP> mulsum3w(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &a1, const W9<WP> &b1, const W9<WP> &a2, const W9<WP> &b2) {
-    uint32_t m[9];
-    W9<WP> r;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) {
-            acc += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc); acc += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc);
-            acc += (uint64_t)a2.l[k - i] * b2.l[i]; PLK_CHAIN(acc);
-        }
-        PLK_MONT_LOW(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-        for (int i = k - 8; i <= 8; i++) {
-            acc += (uint64_t)a0.l[k - i] * b0.l[i]; PLK_CHAIN(acc); acc += (uint64_t)a1.l[k - i] * b1.l[i]; PLK_CHAIN(acc);
-            acc += (uint64_t)a2.l[k - i] * b2.l[i]; PLK_CHAIN(acc);
-        }
-        PLK_MONT_HIGH(k)
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
-}
-
 // domain changes at the boundary of the W layer (s = packed external form, R = 2^256)
 template <class WP> PLK_HD W9<WP> w_from_s(const W9<WP> &raw) { return mulw(raw, w_from_s_const<WP>()); }      // x*2^256 -> x*2^261 (< 1.1p)
 template <class WP> PLK_HD W9<WP> s_from_w(const W9<WP> &a) { return csub_p(mulw(a, s_from_w_const<WP>())); }   // x*2^261 -> x*2^256 canonical
@@ -735,25 +628,14 @@ template <class WP> PLK_HD W9<WP> s_from_w(const W9<WP> &a) { return csub_p(mulw
 // Leaving the EXTERNAL Montgomery form (x * 2^256, any 256-bit value) on this layer: the canonical residue x mod p as nine normalised limbs,
 // the same integer as to_canonical() of field_dev.h gives in eight words.  One product-scanning Montgomery pass by the constant 2^5 (the
 // layer divides by 2^261): the a*b half is a_k * 2^5 in column k — nine shifts, no multiply-add — and the reduction half the usual 45 + 36.
-// Bounds: a column holds a_k * 2^5 < 2^34, at most 9 products m * p (< 2^58 each) and a carry < 2^35: below 2^62.  The value before the
+// The columns fit with room to spare (asserted at mont_scan, like every form's).  The value before the
 // subtraction is (32 a + m p) / 2^261 < 1 + p for a < 2^256 and m < 2^261, i.e. at most p, and the CIOS pass of to_canonical() is
 // (a + m' p) / 2^256 <= p as well: both end with one conditional subtraction, both are = a * 2^-256 (mod p) and in [0, p), hence equal.
 // 81 multiply-adds against the 64 of mul(a, 1), but none of its carry chains (tests/host/field29_pairs_check.hip compares the two).
 template <class WP, class PR>
 PLK_HD W9<WP> canonical_w(const Fp<PR> &s) {
     const W9<WP> a = unpack<WP>(s);
-    uint32_t m[9];
-    W9<WP> r;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        acc += (uint64_t)a.l[k] << 5;
-        PLK_MONT_LOW(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) PLK_MONT_HIGH(k)
-    r.l[8] = (uint32_t)acc;
-    return csub_p(r);
+    return csub_p(mont_scan<WP>(MontChain<WP, 0, Shift5<WP>>{{a}}));
 }
 PLK_HD W9<FrW> fr_canonical_w(const Fr &k) { return canonical_w<FrW>(k); }
 

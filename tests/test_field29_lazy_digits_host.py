@@ -85,3 +85,28 @@ void f(const FqW9 &a, const FqW9 &b, FqW9 &r0, FqW9 &r1) { mulw2_lz<FqW, %s, 0u,
     assert ok, err
     ok, err = compiles("LZ_ALL")
     assert not ok and "a column of chain 0 can exceed 64 bits" in err, err
+
+
+def test_a_masked_form_past_its_left_operand_bound_does_not_compile(tmp_path):
+    """the masked forms are the same engine with no digit unmasked and their contracts as declared bounds: mulw2 is this instantiation
+    with the left operands at MULW_A_LIMB_MAX, which fits; any 32-bit limb on the left does not"""
+    body = """#include "field29_dev.h"
+using namespace plk;
+struct LbLeft { static constexpr Limbs9 B = lb_uniform(%s); };
+void f(const FqW9 &a, const FqW9 &b, FqW9 &r0, FqW9 &r1) { mulw2_lz<FqW, 0u, 0u, LbLeft, LbNorm, LbNorm, LbNorm>(a, b, a, b, r0, r1); }
+void g(const FqW9 &a, const FqW9 &b, FqW9 &r0, FqW9 &r1) { mulw2<FqW>(a, b, a, b, r0, r1); }
+// the bound the masked wrappers declare for their left operand is the documented constant, limb for limb, and the right one is normalised
+constexpr bool all_equal(const Limbs9 &b, uint32_t v) { for (int i = 0; i < 9; i++) if (b.l[i] != v) return false; return true; }
+static_assert(all_equal(LbMulwA::B, MULW_A_LIMB_MAX) && all_equal(LbNorm::B, M29), "the masked forms' declared contract");
+static_assert(lazy_col_bound(LbMulwA::B, LbNorm::B, LbNone::B, LbNone::B, LbNone::B, FqW::P29, 0).fits, "fits at the bound");
+"""
+    def compiles(left):
+        src = tmp_path / "masked.hip"
+        src.write_text(body % left)
+        r = subprocess.run(["hipcc", "--offload-host-only", "-fsyntax-only", "-std=c++17", "-I", CSRC, str(src)],
+                           capture_output=True, text=True, timeout=300)
+        return r.returncode == 0, r.stderr
+    ok, err = compiles("MULW_A_LIMB_MAX")
+    assert ok, err
+    ok, err = compiles("0xffffffffu")
+    assert not ok and "a column of chain 0 can exceed 64 bits" in err, err
