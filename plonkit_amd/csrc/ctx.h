@@ -12,6 +12,7 @@
 #include "field_dev.h"
 #include "hostmath.h"
 #include "msm_plan.h"
+#include "ntt_dispatch.h"
 
 namespace plk {
 
@@ -30,11 +31,7 @@ int32_t hip_fail(hipError_t e, const char *what, const char *file, int line);
         if (_rc != PLK_OK) return _rc;        \
     } while (0)
 
-constexpr uint32_t MAX_LOG_N = 28;          // 2-adicity of Fr
-constexpr uint32_t POW_SPLIT = 14;          // two-level power tables: e = hi * 2^14 + lo
-constexpr uint32_t POW_TAB = 1u << POW_SPLIT;
-
-// base^e for e < 2^28 as lo[e & 16383] * hi[e >> 14]
+// base^e for e < 2^28 as lo[e & 16383] * hi[e >> 14] (MAX_LOG_N, POW_SPLIT: ntt_dispatch.h)
 struct PowTable {
     const Fr *lo = nullptr;
     const Fr *hi = nullptr;
@@ -68,10 +65,8 @@ struct plk_ctx {
     plk::PowTable tw_fwd_w, tw_inv_w;        // the same powers in the 2^261 domain of field29_dev.h (NTT passes)
     std::map<std::vector<uint32_t>, plk::PowTable> coset_tabs;   // keyed by the 8 limbs of the shift
     std::vector<void *> coset_allocs;
-    std::map<uint32_t, void *> ntt_direct;                       // ntt.hip: inter-pass twiddle tables by (direction, digit plan)
-    size_t ntt_direct_bytes = 0;                                 // what they hold together (capped: ntt.hip, PLK_NTT_DIRECT_CAP_MB)
-    std::map<uint32_t, uint64_t> ntt_direct_used;                // per table: value of ntt_direct_clock at its last request (eviction order)
-    std::map<uint32_t, size_t> ntt_direct_size;
+    struct NttDirect { void *buf; size_t bytes; uint64_t used; };   // `used`: value of ntt_direct_clock at the table's last request (eviction order)
+    std::map<uint32_t, NttDirect> ntt_direct;                    // ntt.hip: inter-pass twiddle tables by ntt_table_key, capped together (PLK_NTT_DIRECT_CAP_MB)
     uint64_t ntt_direct_clock = 0;
     struct CosetDirect { plk::DevBuf buf; uint32_t log_n = 0; } coset_direct[2];   // ntt.hip: coset-shift powers of the extensions as tables ([1]: inverse)
     std::map<std::vector<uint32_t>, plk::Fr> inv_cache;

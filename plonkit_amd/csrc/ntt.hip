@@ -6,8 +6,8 @@
 // the coset generator 7 are those of SURVEY.md A.2/A.4.
 //
 // Design (MI355X-first, not a translation of bellman's thread-split FFT):
-//   * n = 2^log_n is factored into p <= 3 digits of <= 10 bits: n = R1*R2*..*Rp (mixed-radix Cooley-Tukey,
-//     "four-step" generalised): two passes up to 2^20, three beyond.  Pass i transforms digit i for every
+//   * n = 2^log_n is factored into p <= 3 digits of <= 10 bits — 11 + 10 at 2^21 —: n = R1*R2*..*Rp (mixed-radix Cooley-Tukey,
+//     "four-step" generalised): two passes up to 2^21, three beyond (ntt_dispatch.h).  Pass i transforms digit i for every
 //     combination of the other digits; between passes the element (k_i, m) is multiplied by omega_L^(k_i*m).
 //   * A workgroup (512 threads) owns a tile of 2048 elements = R rows x C adjacent columns (C*32 B contiguous
 //     per row), stages it in LDS as 9 x 29-bit limbs in two 16-byte planes and one 4-byte plane, and runs the
@@ -41,11 +41,7 @@
 
 namespace plk {
 
-constexpr int NTT_THREADS = 512;               // 8 waves per workgroup, 2 workgroups per CU (LDS): 4 waves per SIMD
-constexpr int LOG_TILE = 11;                   // 2048 elements per workgroup
-constexpr int LOG_SINGLE = 11;                 // largest transform done by one workgroup in one pass (ntt_pass_rows)
-
-constexpr uint32_t NTT_MAX_BATCH = 16;         // transforms of equal shape sharing one launch per pass (blockIdx.y)
+// (NTT_THREADS, LOG_TILE, LOG_SINGLE, NTT_MAX_BATCH and every other constant of the dispatch: ntt_dispatch.h)
 struct NttPassArgs {
     const Fr *in_b[NTT_MAX_BATCH];             // per transform of the batch: where this pass reads ...
     Fr *out_b[NTT_MAX_BATCH];                  // ... and writes
@@ -62,7 +58,8 @@ struct NttPassArgs {
     const Fr *tw_direct;                       // optional (ntt_pass_cols): the inter-pass twiddles of this pass as a table,
                                                // entry (k << log_inner | column), W domain, 1/n folded in on inverse transforms
     uint32_t quarter;                          // first pass of an LDE by 4 with an even number of stages: only every fourth
-                                               // (bit-reversed) row is non-zero, the first pair of stages is a broadcast
+                                               // (bit-reversed) row is non-zero, the first pair of stages is a broadcast.  ntt_pass_cols
+                                               // only, and one shape: 4n = 2^12, the 6 + 6 plan (ntt_dispatch.h)
     const Fr *pre_direct_b[NTT_MAX_BATCH];     // optional, per transform: pre^i as a table of its own (W domain), index = element index:
     const Fr *post_direct_b[NTT_MAX_BATCH];    // one load + one product per element instead of two loads + two products (the composition
 };                                             // lo[e & 16383] * hi[e >> 14] is itself a product) — the coset shifts of the prover's extensions
@@ -291,7 +288,8 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_rows(NttPassArgs a) {
 //   * LDS is laid out the way the reader reads it: 64 consecutive 16-byte words per instruction, no bank conflicts on either
 //     side (pads per round from the plan), one address register with immediate offsets.
 // The old kernels (ntt_pass_cols / ntt_pass_rows) keep the shapes this one does not take: transforms of <= 2^11 points, 6-bit passes
-// (2^12, 2^13), and passes whose inter-pass twiddle table does not fit the cap.
+// (2^12, 2^13), and a zero-padded first pass that reads a per-element input table (ntt_dispatch.h; no caller asks for one).  Whether a pass
+// has its inter-pass twiddle table plays no part: without one this kernel composes the twiddles (tw_direct null).
 __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -687,58 +685,43 @@ __global__ void ntt_fill_direct(Fr *out, PowTable tw, uint32_t log_r, uint32_t l
     store_fp(out + i, pack<FrParams>(csub_p(v)));
 }
 
-constexpr uint32_t NTT_DIRECT_MAX_LOG = 25;
-
+// the two environment switches of the tables, read once; the plan (ntt_dispatch.h) is handed their values
 static bool ntt_direct_enabled() {
     static const int on = [] { const char *e = getenv("PLK_NTT_DIRECT"); return (e && e[0] == '0') ? 0 : 1; }();
     return on != 0;
 }
+static size_t ntt_direct_cap() {
+    static const size_t cap = [] { const char *e = getenv("PLK_NTT_DIRECT_CAP_MB"); size_t mb = e ? strtoull(e, nullptr, 10) : 0; return (mb ? mb : NTT_DIRECT_CAP_DEFAULT_MB) << 20; }();
+    return cap;
+}
 
-// returns nullptr (and PLK_OK) when the pass should compose its twiddles
-static int32_t ntt_direct_table(plk_ctx *ctx, bool inverse, uint32_t log_r, uint32_t log_inner, bool scaled, uint32_t log_n,
-                                hipStream_t stream, const Fr **out) {
+// The table pass q of plan P wants (q.wants_table).  Returns nullptr (and PLK_OK) when the pass should compose its twiddles instead: the cap
+// (ntt_plan_eviction) or the device memory has no room for the table.
+static int32_t ntt_direct_table(plk_ctx *ctx, const NttPlan &P, const NttPassPlan &q, hipStream_t stream, const Fr **out) {
     *out = nullptr;
-    const uint32_t bits = log_r + log_inner;
-    if (!ntt_direct_enabled() || MAX_LOG_N - bits >= POW_SPLIT || bits > NTT_DIRECT_MAX_LOG) return PLK_OK;
-    const uint32_t key = (inverse ? 1u << 31 : 0) | (scaled ? log_n << 16 : 0) | log_r << 8 | log_inner;
-    ctx->ntt_direct_clock++;
-    auto it = ctx->ntt_direct.find(key);
-    if (it != ctx->ntt_direct.end()) { ctx->ntt_direct_used[key] = ctx->ntt_direct_clock; *out = static_cast<const Fr *>(it->second); return PLK_OK; }
-    // A long-lived context that proves many domain sizes would otherwise collect tables for ever (up to 1 GiB each).  When the next
-    // one would take the total past the cap, the tables that have not been asked for during the last NTT_DIRECT_KEEP requests (about
-    // two proofs' worth) go, oldest first, until it fits — after the device has drained, since passes in flight on any stream may
-    // still be reading them.  Tables of the plan in use are never dropped: if they alone fill the cap (a small
-    // PLK_NTT_DIRECT_CAP_MB, or one proof whose shapes exceed it) the new pass composes its twiddles instead — round 3 dropped
-    // everything, which made such a proof rebuild its tables, and stall every stream, on every pass.
-    static const size_t cap = [] { const char *e = getenv("PLK_NTT_DIRECT_CAP_MB"); size_t mb = e ? strtoull(e, nullptr, 10) : 0; return (mb ? mb : 6144) << 20; }();
-    const size_t want = sizeof(Fr) << bits;
-    if (ctx->ntt_direct_bytes + want > cap) {
-        constexpr uint64_t NTT_DIRECT_KEEP = 96;
-        std::vector<std::pair<uint64_t, uint32_t>> idle;             // (last use, key) of the evictable tables
-        for (auto &kv : ctx->ntt_direct) { const uint64_t u = ctx->ntt_direct_used[kv.first]; if (u + NTT_DIRECT_KEEP < ctx->ntt_direct_clock) idle.emplace_back(u, kv.first); }
-        std::sort(idle.begin(), idle.end());
-        size_t freed = 0;
-        for (auto &e : idle) { if (ctx->ntt_direct_bytes - freed + want <= cap) break; freed += ctx->ntt_direct_size[e.second]; }
-        if (ctx->ntt_direct_bytes - freed + want > cap) return PLK_OK;            // the tables in use fill the cap: compose
-        PLK_HIP(hipDeviceSynchronize());
-        for (auto &e : idle) {
-            if (ctx->ntt_direct_bytes + want <= cap) break;
-            (void)hipFree(ctx->ntt_direct[e.second]);
-            ctx->ntt_direct_bytes -= ctx->ntt_direct_size[e.second];
-            ctx->ntt_direct.erase(e.second); ctx->ntt_direct_used.erase(e.second); ctx->ntt_direct_size.erase(e.second);
-        }
+    const uint64_t now = ++ctx->ntt_direct_clock;
+    auto it = ctx->ntt_direct.find(q.table_key);
+    if (it != ctx->ntt_direct.end()) { it->second.used = now; *out = static_cast<const Fr *>(it->second.buf); return PLK_OK; }
+    const size_t want = sizeof(Fr) << q.table_bits;
+    std::vector<NttResident> resident;
+    for (auto &kv : ctx->ntt_direct) resident.push_back(NttResident{kv.first, kv.second.used, kv.second.bytes});
+    std::vector<uint32_t> drop(resident.size());
+    const int drops = ntt_plan_eviction(resident.data(), resident.size(), now, want, ntt_direct_cap(), drop.data());
+    if (drops == NTT_EVICT_COMPOSE) return PLK_OK;
+    if (drops > 0) PLK_HIP(hipDeviceSynchronize());        // passes in flight on any stream may still be reading the tables that go
+    for (int i = 0; i < drops; i++) {
+        auto gone = ctx->ntt_direct.find(drop[i]);
+        (void)hipFree(gone->second.buf);
+        ctx->ntt_direct.erase(gone);
     }
     Fr *buf = nullptr;
     if (hipMalloc(&buf, want) != hipSuccess) { (void)hipGetLastError(); return PLK_OK; }   // no room: compose
-    const PowTable &tw = inverse ? ctx->tw_inv_w : ctx->tw_fwd_w;
-    hipLaunchKernelGGL(ntt_fill_direct, dim3((uint32_t)((((size_t)1 << bits) + 255) / 256)), dim3(256), 0, stream, buf, tw, log_r, log_inner,
-                       scaled ? ctx->n_inv_w[log_n] : Fr::zero(), scaled ? 1u : 0u);
+    const PowTable &tw = P.inverse ? ctx->tw_inv_w : ctx->tw_fwd_w;
+    hipLaunchKernelGGL(ntt_fill_direct, dim3((uint32_t)((((size_t)1 << q.table_bits) + 255) / 256)), dim3(256), 0, stream, buf, tw, q.log_r, q.log_inner,
+                       q.table_scaled ? ctx->n_inv_w[P.log_n] : Fr::zero(), q.table_scaled);
     PLK_HIP(hipGetLastError());
     PLK_HIP(hipStreamSynchronize(stream));                 // other streams may use the table right after this call
-    ctx->ntt_direct[key] = buf;
-    ctx->ntt_direct_used[key] = ctx->ntt_direct_clock;
-    ctx->ntt_direct_size[key] = want;
-    ctx->ntt_direct_bytes += want;
+    ctx->ntt_direct[q.table_key] = plk_ctx::NttDirect{buf, want, now};
     *out = buf;
     return PLK_OK;
 }
@@ -746,28 +729,26 @@ static int32_t ntt_direct_table(plk_ctx *ctx, bool inverse, uint32_t log_r, uint
 // ------------------------------------------------------------------------------- driver
 static std::atomic<bool> g_attr_set{false};                    // (several contexts may transform from several host threads)
 
-// the wave-owned passes (ntt_pass_w) take every full 2048-element tile of 7..10 row bits and the 4096-element tile of the 2^21-point
-// transform (digit_plan); the barrier-per-round kernels (ntt_pass_cols / ntt_pass_rows) serve every other shape
-constexpr size_t NTT_W_LDS = (size_t)36 * NTT_W_SLOTS, NTT_W_LDS_BIG = (size_t)36 * NTT_W_SLOTS_BIG;
-static bool ntt_wave_shape(const NttPassArgs &a) {
-    // (zero-padded inputs are taken too — `quarter`, the old kernels' copy-instead-of-butterfly shortcut for them, is simply not used;
-    //  their per-element coset tables are never combined with padding)
-    if (a.nonzero && a.pre_direct_b[0]) return false;
-    if (a.log_r + a.log_c == LOG_TILE) return a.log_r >= 7 && a.log_r <= 10;
-    return a.log_r + a.log_c == (uint32_t)NTT_LOG_TILE_BIG;   // 2^21 = 11 + 10 (digit_plan), nothing else plans this tile
-}
+// one pass of a plan (ntt_dispatch.h), by its (family, role, row bits, tile): twelve kernels
 template <bool ROWS>
-static void ntt_launch_w(const NttPassArgs &a, dim3 grid, hipStream_t stream) {
-    if (a.log_r + a.log_c == (uint32_t)NTT_LOG_TILE_BIG) {        // the column pass has the 11-bit digit, the row pass the 10-bit one
-        hipLaunchKernelGGL((ntt_pass_w<ROWS ? 10 : 11, ROWS, NTT_LOG_TILE_BIG>), grid, dim3(2 * NTT_THREADS), NTT_W_LDS_BIG, stream, a);
-        return;
-    }
-    switch (a.log_r) {
-        case 7: hipLaunchKernelGGL((ntt_pass_w<7, ROWS>), grid, dim3(NTT_THREADS), NTT_W_LDS, stream, a); break;
-        case 8: hipLaunchKernelGGL((ntt_pass_w<8, ROWS>), grid, dim3(NTT_THREADS), NTT_W_LDS, stream, a); break;
-        case 9: hipLaunchKernelGGL((ntt_pass_w<9, ROWS>), grid, dim3(NTT_THREADS), NTT_W_LDS, stream, a); break;
-        default: hipLaunchKernelGGL((ntt_pass_w<10, ROWS>), grid, dim3(NTT_THREADS), NTT_W_LDS, stream, a); break;
-    }
+static int32_t ntt_launch(const NttPassPlan &q, const NttPassArgs &a, uint32_t count, hipStream_t stream) {
+    const dim3 grid(q.grid_x, count), block(q.block);
+    const uint32_t big_bits = ROWS ? 10 : 11;               // 11 + 10: the column pass has the 11-bit digit, the row pass the 10-bit one
+    if (q.family == NTT_FAMILY_BARRIER) {
+        if (ROWS) hipLaunchKernelGGL(ntt_pass_rows, grid, block, q.lds_bytes, stream, a);
+        else hipLaunchKernelGGL(ntt_pass_cols, grid, block, q.lds_bytes, stream, a);
+    } else if (q.log_tile == (uint32_t)NTT_LOG_TILE_BIG && q.row_bits == big_bits) {
+        hipLaunchKernelGGL((ntt_pass_w<ROWS ? 10 : 11, ROWS, NTT_LOG_TILE_BIG>), grid, block, q.lds_bytes, stream, a);
+    } else if (q.log_tile == (uint32_t)NTT_LOG_TILE) {
+        switch (q.row_bits) {
+            case 7: hipLaunchKernelGGL((ntt_pass_w<7, ROWS>), grid, block, q.lds_bytes, stream, a); break;
+            case 8: hipLaunchKernelGGL((ntt_pass_w<8, ROWS>), grid, block, q.lds_bytes, stream, a); break;
+            case 9: hipLaunchKernelGGL((ntt_pass_w<9, ROWS>), grid, block, q.lds_bytes, stream, a); break;
+            case 10: hipLaunchKernelGGL((ntt_pass_w<10, ROWS>), grid, block, q.lds_bytes, stream, a); break;
+            default: set_error("ntt: the plan asks for a kernel that is not built"); return PLK_ERR_ARG;
+        }
+    } else { set_error("ntt: the plan asks for a kernel that is not built"); return PLK_ERR_ARG; }
+    return PLK_OK;
 }
 template <int LR> static hipError_t ntt_w_attr() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_w<LR, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_W_LDS);
@@ -778,31 +759,6 @@ static hipError_t ntt_w_attr_big() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_w<11, false, NTT_LOG_TILE_BIG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_W_LDS_BIG);
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_w<10, true, NTT_LOG_TILE_BIG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_W_LDS_BIG);
-}
-
-// digits of the mixed-radix plan: up to 10 bits per pass
-static void digit_plan(uint32_t log_n, uint32_t d[4], uint32_t *passes) {
-    d[0] = d[1] = d[2] = d[3] = 0;
-    uint32_t p = 1;
-    // one pass — ONE workgroup holds the whole transform in LDS — up to 2^11 points.  2^12 points in one workgroup (147 KB of the CU's 160 KB, the kernel
-    // handles it) was tried in round 6 and is SLOWER than two passes of two workgroups: 62 against 37 us per transform, same box (six rounds of two
-    // radix-4 groups per thread on one CU against two launches of three rounds on two)
-    if (log_n <= LOG_SINGLE) d[0] = log_n;
-    else {
-        p = (log_n + 9) / 10;                              // up to 10 bits per pass: 2^20 = 10 + 10 (two passes)
-        for (uint32_t i = 0; i < p; i++) d[i] = log_n / p + (i < log_n % p ? 1 : 0);
-        // 11-bit digits on the 4096-element tile: 2^21 = 11 + 10 in two passes instead of three (0.207 -> 0.194 ms, same box).  2^22 = 11 + 11 is NOT
-        // taken: both passes then run on 64-byte row segments (C = 2) and the transform is 12 % SLOWER than three passes of the 2048-element tile
-        // (0.375 -> 0.421 ms; profiles/r06_ntt_big_tile_ab.txt)
-        if (log_n == 21) {
-            d[0] = 11; d[1] = 10; d[2] = 0; *passes = 2;
-            return;
-        }
-        if (p == 3 && log_n <= 23) {                       // leave 14 bits to passes 2 and 3: their inter-pass twiddles
-            d[0] = log_n - 14; d[1] = 7; d[2] = 7;         // then come straight out of the hi table (ntt_pass_cols)
-        }
-    }
-    *passes = p;
 }
 
 // src: where the first pass reads (data itself for an in-place transform); nonzero: see NttPassArgs.
@@ -820,15 +776,22 @@ int32_t ntt_dev(plk_ctx *ctx, Fr *data, uint32_t log_n, bool inverse, const Fr *
     return ntt_run(ctx, &src, 0, &data, 1, log_n, inverse, coset, stream, 0);
 }
 
-int32_t ntt_batch_dev(plk_ctx *ctx, Fr *const *data, uint32_t count, uint32_t log_n, bool inverse, const Fr *coset, hipStream_t stream, uint32_t lane) {
+// in place, `per` transforms per launch
+static int32_t ntt_batch_by(plk_ctx *ctx, uint32_t per, Fr *const *data, uint32_t count, uint32_t log_n, bool inverse, const Fr *coset, hipStream_t stream, uint32_t lane) {
     for (uint32_t done = 0; done < count;) {
-        const uint32_t b = count - done > NTT_MAX_BATCH ? NTT_MAX_BATCH : count - done;
+        const uint32_t b = count - done > per ? per : count - done;
         const Fr *src[NTT_MAX_BATCH];
         for (uint32_t k = 0; k < b; k++) src[k] = data[done + k];
         PLK_TRY(ntt_run(ctx, src, 0, data + done, b, log_n, inverse, coset, stream, lane));
         done += b;
     }
     return PLK_OK;
+}
+int32_t ntt_batch_dev(plk_ctx *ctx, Fr *const *data, uint32_t count, uint32_t log_n, bool inverse, const Fr *coset, hipStream_t stream, uint32_t lane) {
+    return ntt_batch_by(ctx, ntt_batch_per_launch(NTT_BATCH_PLAIN, log_n), data, count, log_n, inverse, coset, stream, lane);
+}
+int32_t ntt_columns_dev(plk_ctx *ctx, Fr *const *data, uint32_t count, uint32_t log_n, bool inverse, hipStream_t stream) {
+    return ntt_batch_by(ctx, ntt_batch_per_launch(NTT_BATCH_PROVER, log_n), data, count, log_n, inverse, nullptr, stream, 0);
 }
 
 // pre_each / post_each: one input- / output-scaling table per transform of the batch (the four cosets of lde4cm_batch_dev and
@@ -842,8 +805,8 @@ static int32_t ntt_run(plk_ctx *ctx, const Fr *const *src, uint64_t nonzero, Fr 
     if (log_n == 0) return PLK_OK;
     PLK_TRY(ntt_init_tables(ctx));
     if (!g_attr_set) {
-        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 36 << LOG_SINGLE));
-        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_cols), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_LDS_ROWS));
+        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ntt_pass_cols), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_LDS_COLS));
         PLK_HIP(ntt_w_attr<7>()); PLK_HIP(ntt_w_attr<8>()); PLK_HIP(ntt_w_attr<9>()); PLK_HIP(ntt_w_attr<10>());
         PLK_HIP(ntt_w_attr_big());
         g_attr_set = true;
@@ -853,60 +816,42 @@ static int32_t ntt_run(plk_ctx *ctx, const Fr *const *src, uint64_t nonzero, Fr 
         if (!inverse) PLK_TRY(ntt_coset_table(ctx, *coset, &pre));
         else PLK_TRY(ntt_coset_table(ctx, cached_inverse(ctx, *coset), &post));
     }
-    uint32_t d[4], p;
-    digit_plan(log_n, d, &p);
-    const uint32_t log_tile = (p == 2 && d[0] == 11) ? (uint32_t)NTT_LOG_TILE_BIG : (uint32_t)LOG_TILE;     // 11-bit digits: the 4096-element tile
-    const size_t n = (size_t)1 << log_n;
-    if (p > 1) PLK_TRY(ctx->ntt_scratch[lane].reserve((size_t)count * n * sizeof(Fr)));
+    // the plan: every decision about the passes (ntt_dispatch.h)
+    const bool has_pre = pre_each || (coset && !inverse), has_post = post_each || (coset && inverse);
+    const NttPlan P = ntt_plan(log_n, count, inverse, nonzero, pre_direct ? NTT_SCALE_PER_ELEMENT : (has_pre ? NTT_SCALE_TWO_LEVEL : NTT_SCALE_NONE),
+                               post_direct ? NTT_SCALE_PER_ELEMENT : (has_post ? NTT_SCALE_TWO_LEVEL : NTT_SCALE_NONE), ntt_direct_enabled());
+    // the ping-pong scratch
+    if (P.scratch_bytes) PLK_TRY(ctx->ntt_scratch[lane].reserve(P.scratch_bytes));
     Fr *const scratch = ctx->ntt_scratch[lane].as<Fr>();
+    const size_t n = (size_t)1 << log_n;
 
     NttPassArgs a{};
     a.log_n = log_n;
     a.tw = inverse ? ctx->tw_inv_w : ctx->tw_fwd_w;
-    // ping-pong: pass 1 data -> scratch, middle passes in place in scratch, last pass scratch -> data
-    uint32_t rem = log_n;
-    bool scale_folded = false;
-    for (uint32_t i = 0; i + 1 < p; i++) {
-        rem -= d[i];
-        for (uint32_t b = 0; b < count; b++) { a.in_b[b] = (i == 0) ? src[b] : scratch + (size_t)b * n; a.out_b[b] = scratch + (size_t)b * n; }
-        a.nonzero = (i == 0) ? (uint32_t)nonzero : 0;
-        a.log_r = d[i]; a.log_inner = rem;
-        a.log_c = (log_tile - d[i]) < rem ? (log_tile - d[i]) : rem;
-        for (uint32_t b = 0; b < count; b++) a.pre_b[b] = (i == 0) ? (pre_each ? pre_each[b] : pre) : PowTable{};
-        for (uint32_t b = 0; b < count; b++) a.post_b[b] = PowTable{};
-        for (uint32_t b = 0; b < count; b++) { a.pre_direct_b[b] = (i == 0 && pre_direct) ? pre_direct[b] : nullptr; a.post_direct_b[b] = nullptr; }
-        a.has_scale = 0;
-        PLK_TRY(ntt_direct_table(ctx, inverse, d[i], rem, inverse && i == 0, log_n, stream, &a.tw_direct));
-        if (a.tw_direct && inverse && i == 0) scale_folded = true;
-        a.quarter = (i == 0 && nonzero && nonzero == (n >> 2) && !(d[0] & 1) && d[0] >= 2) ? 1 : 0;
-        uint32_t tiles = (uint32_t)(n >> (a.log_r + a.log_c));
-        size_t lds = (size_t)36 << (a.log_r + a.log_c);
-        if (ntt_wave_shape(a)) ntt_launch_w<false>(a, dim3(tiles, count), stream);
-        else hipLaunchKernelGGL(ntt_pass_cols, dim3(tiles, count), dim3(NTT_THREADS), lds, stream, a);
-    }
-    {
-        // (a single pass is one workgroup per transform that has read ALL of its input into LDS — a barrier — before its first store: in place is safe,
-        //  no detour through the scratch buffer and no copy launch behind it)
-        for (uint32_t b = 0; b < count; b++) { a.in_b[b] = (p == 1) ? src[b] : scratch + (size_t)b * n; a.out_b[b] = data[b]; }
-        a.nonzero = (p == 1) ? (uint32_t)nonzero : 0;
-        a.log_r = d[p - 1];
-        if (p == 1) { a.log_r1 = 0; a.log_m1 = a.log_m2 = 0; a.log_c = 0; }
-        else {
-            a.log_r1 = d[0];
-            a.log_m1 = p >= 3 ? d[1] : 0;
-            a.log_m2 = p >= 4 ? d[2] : 0;
-            a.log_c = (log_tile - a.log_r) < d[0] ? (log_tile - a.log_r) : d[0];
+    bool first_table = false;
+    for (uint32_t i = 0; i < P.passes; i++) {
+        const NttPassPlan &q = P.pass[i];
+        // the table the pass wants, if there is room for it
+        a.tw_direct = nullptr;
+        if (q.wants_table) PLK_TRY(ntt_direct_table(ctx, P, q, stream, &a.tw_direct));
+        if (i == 0) first_table = a.tw_direct != nullptr;
+        // its arguments
+        for (uint32_t b = 0; b < count; b++) {
+            a.in_b[b] = q.reads == NTT_AT_SOURCE ? src[b] : scratch + (size_t)b * n;
+            a.out_b[b] = q.writes == NTT_AT_DATA ? data[b] : scratch + (size_t)b * n;
+            a.pre_b[b] = q.pre != NTT_SCALE_NONE ? (pre_each ? pre_each[b] : pre) : PowTable{};
+            a.post_b[b] = q.post != NTT_SCALE_NONE ? (post_each ? post_each[b] : post) : PowTable{};
+            a.pre_direct_b[b] = q.pre == NTT_SCALE_PER_ELEMENT ? pre_direct[b] : nullptr;
+            a.post_direct_b[b] = q.post == NTT_SCALE_PER_ELEMENT ? post_direct[b] : nullptr;
         }
-        for (uint32_t b = 0; b < count; b++) a.pre_b[b] = (p == 1) ? (pre_each ? pre_each[b] : pre) : PowTable{};
-        for (uint32_t b = 0; b < count; b++) a.post_b[b] = post_each ? post_each[b] : post;
-        for (uint32_t b = 0; b < count; b++) { a.pre_direct_b[b] = (p == 1 && pre_direct) ? pre_direct[b] : nullptr; a.post_direct_b[b] = post_direct ? post_direct[b] : nullptr; }
-        a.tw_direct = nullptr; a.quarter = 0;
-        a.has_scale = (inverse && !scale_folded) ? 1 : 0;
+        a.log_r = q.log_r; a.log_c = q.log_c; a.log_inner = q.log_inner;
+        a.log_r1 = q.log_r1; a.log_m1 = q.log_m1; a.log_m2 = q.log_m2;
+        a.nonzero = q.nonzero; a.quarter = q.quarter;
+        a.has_scale = q.role == NTT_ROLE_ROWS ? ntt_plan_has_scale(P, first_table) : 0;
         if (a.has_scale) a.scale = ctx->n_inv_w[log_n];
-        uint32_t tiles = (uint32_t)(n >> (a.log_r + a.log_c));
-        size_t lds = (size_t)36 << (a.log_r + a.log_c);
-        if (p > 1 && ntt_wave_shape(a)) ntt_launch_w<true>(a, dim3(tiles, count), stream);
-        else hipLaunchKernelGGL(ntt_pass_rows, dim3(tiles, count), dim3(NTT_THREADS), lds, stream, a);
+        // the launch
+        if (q.role == NTT_ROLE_ROWS) PLK_TRY(ntt_launch<true>(q, a, count, stream));
+        else PLK_TRY(ntt_launch<false>(q, a, count, stream));
     }
     PLK_HIP(hipGetLastError());
     return PLK_OK;
@@ -927,7 +872,7 @@ __global__ void ntt_fill_coset_direct(Fr *out, PowTable t0, PowTable t1, PowTabl
 }
 static int32_t coset_direct_tables(plk_ctx *ctx, uint32_t log_n, bool inverse, const PowTable tabs[4], hipStream_t stream, const Fr *out[4]) {
     for (int k = 0; k < 4; k++) out[k] = nullptr;
-    if (!ntt_direct_enabled() || log_n > 24 || log_n <= POW_SPLIT) return PLK_OK;      // (<= 2^14 points: the low table alone holds the power)
+    if (!ntt_coset_direct_wanted(log_n, ntt_direct_enabled())) return PLK_OK;
     plk_ctx::CosetDirect &C = ctx->coset_direct[inverse ? 1 : 0];
     const size_t n = (size_t)1 << log_n;
     if (C.log_n != log_n || !C.buf.p) {
@@ -951,8 +896,8 @@ int32_t lde4_batch_dev(plk_ctx *ctx, const Fr *const *coeffs, uint32_t count, ui
     // coefficients where they are and treats every index >= n as zero (no copy, no memset, no scaling of zeros)
     for (uint32_t k = 0; k < count; k++) if (coeffs[k] == out_4n[k]) { set_error("lde4: input and output must not alias"); return PLK_ERR_ARG; }
     Fr g = from_u64<FrParams>(7);
-    // one launch per pass for the whole batch while its ping-pong scratch stays below 2 GiB (count x 4n x 32 B)
-    const uint32_t per = log_n + 2 <= 22 ? NTT_MAX_BATCH : (log_n + 2 <= 24 ? 4 : 1);
+    // one launch per pass for the whole batch while its ping-pong scratch stays within 2 GiB (count x 4n x 32 B)
+    const uint32_t per = ntt_batch_per_launch(NTT_BATCH_LDE4, log_n);
     for (uint32_t done = 0; done < count;) {
         const uint32_t b = count - done > per ? per : count - done;
         PLK_TRY(ntt_run(ctx, coeffs + done, n, out_4n + done, b, log_n + 2, false, &g, stream, lane));
@@ -1006,8 +951,7 @@ int32_t lde4cm_batch_dev(plk_ctx *ctx, const Fr *const *coeffs, uint32_t count, 
     const Fr *direct[4];
     PLK_TRY(coset_direct_tables(ctx, log_n, false, pre, stream, direct));
     // polynomials per launch: 4 transforms each, at most NTT_MAX_BATCH per launch and 2 GiB of ping-pong scratch
-    uint32_t per = NTT_MAX_BATCH / 4;
-    while (per > 1 && (size_t)per * 4 * n * sizeof(Fr) > ((size_t)2 << 30)) per--;
+    const uint32_t per = ntt_batch_per_launch(NTT_BATCH_LDE4CM, log_n);
     for (uint32_t done = 0; done < count;) {
         const uint32_t b = count - done > per ? per : count - done;
         const Fr *src[NTT_MAX_BATCH]; Fr *dst[NTT_MAX_BATCH]; PowTable pe[NTT_MAX_BATCH]; const Fr *pd[NTT_MAX_BATCH];

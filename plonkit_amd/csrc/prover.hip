@@ -422,12 +422,13 @@ static int32_t setup_upload_impl(plk_ctx *ctx, plk_setup *S) {
         DevBuf idx_buf;
         if ((rc = idx_buf.reserve((size_t)4 * N * 4)) != PLK_OK) return fail(rc);
         if ((rc = setup_permutation(ctx, S->gate_vars, log_n, S->num_vars, idx_buf.as<uint32_t>(), S->sig_vals, st)) != PLK_OK) { idx_buf.release(); return fail(rc); }
+        // one launch per pass for the four of them where the batch scratch is small; above, each column is transformed behind its own copy
+        const bool singly = ntt_batch_per_launch(NTT_BATCH_PROVER, log_n) == 1;
         for (int j = 0; j < 4; j++) {
             if (hipMemcpyAsync(S->sig_coef[j], S->sig_vals[j], N * sizeof(Fr), hipMemcpyDeviceToDevice, st) != hipSuccess) { idx_buf.release(); return fail(hip_fail(hipGetLastError(), "D2D sigma", __FILE__, __LINE__)); }
-            if (log_n > 22 && (rc = ntt_dev(ctx, S->sig_coef[j], log_n, true, nullptr, st)) != PLK_OK) { idx_buf.release(); return fail(rc); }
+            if (singly && (rc = ntt_columns_dev(ctx, &S->sig_coef[j], 1, log_n, true, st)) != PLK_OK) { idx_buf.release(); return fail(rc); }
         }
-        // (one launch per pass for the four of them where the batch scratch is small)
-        if (log_n <= 22 && (rc = ntt_batch_dev(ctx, S->sig_coef, 4, log_n, true, nullptr, st, 0)) != PLK_OK) { idx_buf.release(); return fail(rc); }
+        if (!singly && (rc = ntt_columns_dev(ctx, S->sig_coef, 4, log_n, true, st)) != PLK_OK) { idx_buf.release(); return fail(rc); }
         hipError_t e = hipStreamSynchronize(st);
         idx_buf.release();
         if (e != hipSuccess) return fail(hip_fail(e, "sync", __FILE__, __LINE__));
@@ -625,8 +626,7 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
 
 
     // ---- round 1: wire polynomials, 4 x iNTT(N) in one launch per pass, 4 x MSM(N)
-    if (log_n <= 22) PLK_TRY(ntt_batch_dev(ctx, w_coef, 4, log_n, true, nullptr, st, 0));
-    else for (int j = 0; j < 4; j++) PLK_TRY(ntt_dev(ctx, w_coef[j], log_n, true, nullptr, st));
+    PLK_TRY(ntt_columns_dev(ctx, w_coef, 4, log_n, true, st));
     // with a Lagrange-form key of the domain's size resident (`prove -l`, src/plonk.rs:138-146) the witness and
     // grand-product polynomials are committed from their evaluations, as bellman's prove() does; same proof bytes
     const bool use_lagrange = ctx->lag.pts != nullptr;
@@ -1196,8 +1196,7 @@ static int32_t setup_polys_impl(plk_ctx *ctx, uint64_t n, uint64_t num_inputs, c
     PLK_TRY(check_canonical(given, 11, len, flag, st));
     for (int i = 0; i < 11; i++) PLK_HIP(hipMemcpyAsync(derived[i], given[i], N * sizeof(Fr), hipMemcpyDeviceToDevice, st));
     // (four transforms per launch where the batch scratch is small, one at a time above, as the circuit path's setup does)
-    if (log_n <= 22) for (int i = 0; i < 11; i += 4) PLK_TRY(ntt_batch_dev(ctx, derived + i, 11 - i < 4 ? 11 - i : 4, log_n, values, nullptr, st, 0));
-    else for (int i = 0; i < 11; i++) PLK_TRY(ntt_dev(ctx, derived[i], log_n, values, nullptr, st));
+    PLK_TRY(ntt_columns_dev(ctx, derived, 11, log_n, values, st));
     uint32_t bad = 0;
     PLK_HIP(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st));
     PLK_HIP(hipStreamSynchronize(st));

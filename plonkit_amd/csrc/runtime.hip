@@ -190,7 +190,7 @@ void plk_destroy(plk_ctx *ctx) {
     srs_return_loan(ctx);
     const bool lent = srs_orphan_lender(ctx);            // borrowers alive: their commitments read this context's key and tables at any time
     for (void *p : ctx->coset_allocs) (void)hipFree(p);
-    for (auto &kv : ctx->ntt_direct) (void)hipFree(kv.second);
+    for (auto &kv : ctx->ntt_direct) (void)hipFree(kv.second.buf);
     ctx->coset_direct[0].buf.release(); ctx->coset_direct[1].buf.release();
     ctx->tables.release(); ctx->ntt_scratch[0].release(); ctx->ntt_scratch[1].release();
     if (!lent) { ctx->srs_own.release(); ctx->srs_w.release(); ctx->lag.own.release(); ctx->lag.w.release(); }

@@ -13,6 +13,16 @@ pytestmark = pytest.mark.gpu
 from oracle import oracle_lib as ol
 from oracle.oracle_lib import R_MOD
 
+# the sizes of the NTT tests below; tests/test_ntt_dispatch_host.py runs them through the dispatch plan (plonkit_amd/csrc/ntt_dispatch.h) and checks that,
+# with those of tests/test_gpu_large.py, they launch every kernel instantiation the plan can name
+NTT_ORACLE_LOG_N = [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 18, 19]
+NTT_EXTREME_LOG_N = [11, 13, 14, 15, 16, 17, 18, 19, 20, 21]
+NTT_COSET_LOG_N = [3, 9, 12, 15, 17, 19, 21]
+NTT_LARGE_PROPERTIES_LOG_N = [20, 21, 22, 23, 25]
+LDE4_LOG_N = [3, 10, 14]
+LDE4CM_SHAPES = [(1, 1), (3, 2), (10, 4), (11, 1), (12, 5), (16, 4), (20, 4)]
+ICOSET4CM_LOG_N = [1, 3, 9, 10, 11, 12, 16, 20]
+
 
 @pytest.fixture(scope="module")
 def ctx():
@@ -29,14 +39,14 @@ def _rand_fr(n, seed):
     return a
 
 
-@pytest.mark.parametrize("log_n", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 18, 19])
+@pytest.mark.parametrize("log_n", NTT_ORACLE_LOG_N)
 def test_ntt_matches_oracle(ctx, log_n):
     a = _rand_fr(1 << log_n, 100 + log_n)
     assert np.array_equal(ctx.ntt(a, log_n), ol.ntt(a, log_n))
     assert np.array_equal(ctx.ntt(a, log_n, inverse=True), ol.ntt(a, log_n, inverse=True))
 
 
-@pytest.mark.parametrize("log_n", [11, 13, 14, 15, 16, 17, 18, 19, 20, 21])
+@pytest.mark.parametrize("log_n", NTT_EXTREME_LOG_N)
 def test_ntt_extreme_residues(ctx, log_n):
     """the lazy bounds of the butterflies at their worst inputs (random vectors of `_rand_fr` stay below 2^252): every element r - 1, r - 1
     alternating with 0 at stride 1 and at the stride of the first pass, residues within 2^16 of r, and all zeros — plain, inverse and
@@ -61,7 +71,7 @@ def test_ntt_extreme_residues(ctx, log_n):
         assert np.array_equal(ctx.ntt(a, log_n, coset=ol.fr_mont(7)), ol.ntt(a, log_n, coset=7))
 
 
-@pytest.mark.parametrize("log_n", [3, 9, 12, 15, 17, 19, 21])
+@pytest.mark.parametrize("log_n", NTT_COSET_LOG_N)
 def test_coset_ntt_and_roundtrip(ctx, log_n):
     a = _rand_fr(1 << log_n, 7 + log_n)
     g = ol.fr_mont(7)
@@ -72,7 +82,7 @@ def test_coset_ntt_and_roundtrip(ctx, log_n):
     assert np.array_equal(ctx.ntt(a, log_n, inverse=True, coset=ol.fr_mont(other)), ol.ntt(a, log_n, inverse=True, coset=other))
 
 
-@pytest.mark.parametrize("log_n", [20, 21, 22, 23, 25])
+@pytest.mark.parametrize("log_n", NTT_LARGE_PROPERTIES_LOG_N)
 def test_ntt_large_properties(ctx, log_n):
     """full BASELINE size and every plan above it that nothing else runs (2^21 = 11 + 10 on the 4096-element tile, 2^23 = 9 + 7 + 7,
     2^25 = 9 + 8 + 8): oracle parity up to 2^21, plus size-independent properties (round trip, linearity, evaluation at a point)."""
@@ -89,7 +99,7 @@ def test_ntt_large_properties(ctx, log_n):
         assert ol.fr_ints(fa[k:k + 1])[0] == ol.poly_eval(a, pow(w, k, R_MOD))
 
 
-@pytest.mark.parametrize("log_n", [3, 10, 14])
+@pytest.mark.parametrize("log_n", LDE4_LOG_N)
 def test_lde4(ctx, log_n):
     a = _rand_fr(1 << log_n, 40 + log_n)
     ext = np.zeros((4 << log_n, 4), dtype=np.uint64)
@@ -97,7 +107,7 @@ def test_lde4(ctx, log_n):
     assert np.array_equal(ctx.lde4(a, log_n), ol.ntt(ext, log_n + 2, coset=7))
 
 
-@pytest.mark.parametrize("log_n,count", [(1, 1), (3, 2), (10, 4), (11, 1), (12, 5), (16, 4), (20, 4)])
+@pytest.mark.parametrize("log_n,count", LDE4CM_SHAPES)
 def test_lde4_coset_major(ctx, log_n, count):
     """the layout of the prover's round 3 (lde4cm_batch_dev: four n-point coset transforms per polynomial, up to four
     polynomials per launch): out[k*n + r] must be the natural-order extension's element 4r + k — against the oracle's
@@ -126,7 +136,7 @@ def test_lde4_coset_major(ctx, log_n, count):
             assert np.array_equal(got[k], nat[:, k, :]), (p, k)
 
 
-@pytest.mark.parametrize("log_n", [1, 3, 9, 10, 11, 12, 16, 20])
+@pytest.mark.parametrize("log_n", ICOSET4CM_LOG_N)
 def test_icoset4_coset_major(ctx, log_n):
     """the coset iNTT of the prover's round 3 (icoset4cm_dev + k_icoset_combine): a random polynomial of 4n coefficients is
     evaluated on 7*<omega_4n> by the natural-order coset NTT (pinned to the oracle above), its values are put in coset-major

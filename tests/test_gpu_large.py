@@ -22,6 +22,10 @@ pytestmark = pytest.mark.gpu
 from oracle import oracle_lib as ol
 from oracle.oracle_lib import R_MOD
 
+# the sizes of the NTT tests below (tests/test_ntt_dispatch_host.py: which kernels of the dispatch plan they launch)
+NTT_TWO_ADICITY_LOG_N = [27, 28]
+NTT_WORST_CASE_LOG_N = [22, 23, 25]
+NTT_RECURSIVE_LOG_N = [24, 26]
 
 def _rand_fr(n, seed):
     rng = np.random.default_rng(seed)
@@ -74,7 +78,7 @@ def test_msm_2pow24_trapdoor(ctx24, kind):
     assert np.array_equal(pa.g1_sum_jacobian(np.stack([lo, hi])), want)
 
 
-@pytest.mark.parametrize("log_n", [27, 28])
+@pytest.mark.parametrize("log_n", NTT_TWO_ADICITY_LOG_N)
 def test_ntt_up_to_the_two_adicity_of_fr(log_n):
     """plk_ntt's largest sizes (2^28 = the 2-adicity of Fr; error code 2 above it): a sparse polynomial against its
     closed form at eight indices, plain and on the coset 7 * <omega>, and the round trip of a dense random vector compared on the device"""
@@ -122,7 +126,7 @@ def test_ntt_up_to_the_two_adicity_of_fr(log_n):
     torch.cuda.empty_cache()
 
 
-@pytest.mark.parametrize("log_n", [22, 23, 25])
+@pytest.mark.parametrize("log_n", NTT_WORST_CASE_LOG_N)
 def test_ntt_worst_case_residues_above_the_oracle_sizes(log_n):
     """the inputs the lazy bounds of the butterflies were written for, at the three-pass plans the oracle cannot re-run in test time: 2^22 = 8 + 7 + 7 and
     2^23 = 9 + 7 + 7 (ntt_pass_cols in the middle) and 2^25 = 9 + 8 + 8.  EVERY output element is compared, on the device, against a closed form
@@ -211,7 +215,7 @@ def test_ntt_worst_case_residues_above_the_oracle_sizes(log_n):
     torch.cuda.empty_cache()
 
 
-@pytest.mark.parametrize("log_n", [24, 26])
+@pytest.mark.parametrize("log_n", NTT_RECURSIVE_LOG_N)
 def test_ntt_recursive_prover_shapes(log_n):
     """NTT 2^24 (N) and 2^26 (4N) of the recursive circuit: round trip, linearity, evaluation at four points"""
     import torch
