@@ -144,8 +144,15 @@ PLK_HD void xyzzw_add_mixed(XyzzW &acc, const AffW &q, bool neg_q) {
 // xyzzw_flip_xy converts in both directions (6p - c: an accumulator's x, y < 6p on either side) where the sum leaves the loop (the flush)
 // and around the cold P = +-Q path.  The identity is zz = 0 whatever x and y hold: the one that path returns carries 6p - 0 in both
 // and flips back to all zero (keeping it zero in place costs the hot path 24 moves: two values merge at the loop's head).
+// SF (the loop of msm_accumulate's plain kernel, together with NXY): the SHARED FACTOR PP = P^2 is the right operand of three products - PPP = P PP,
+// Q = X1 PP (here NQ = NX PP), ZZ3 = ZZ1 PP - and is reduced once for the three: A_PP = PP 2^-116 mod p (make_tw2_a, 39 multiply-adds), then each is a
+// tw2 product (field29_dev.h: 126 multiply-adds instead of 162), (PPP, NQ) as a lockstep pair and ZZ3 beside the plain product ZZZ3 = ZZZ1 PPP
+// (mul_tw2_mulw).  1483 -> 1414 multiply-adds an addition.  The same residues in all four coordinates, not the same integers.  Operands: P, NX, ZZ1 and
+// PP are normalised (out of a column chain or normw), A_PP is LbTw2A; worst column 0.43 * 2^64, checked at compile time.  Values: a tw2 result is below
+// z w / 2^261 + A / 2^29 + p (1 + 2^-26), i.e. the bound of the mulw2_lz it replaces + 2^-28 p: PPP < 1.06, Q < 1.05, ZZ3 < 1.01 as in the table above
+// (tests/host/field29_shared_factor_check.hip: chains of 250 additions from accumulators at the coordinate bounds, this form beside <true, false>).
 PLK_HD XyzzW xyzzw_flip_xy(const XyzzW &a) { XyzzW r = a; r.x = sub6(w_zero<FqW>(), a.x); r.y = sub6(w_zero<FqW>(), a.y); return r; }
-template <bool NXY>
+template <bool NXY, bool SF = false>
 PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) {
     if (fresh) {
         if constexpr (NXY) { acc.x = neg2(q.x); acc.y = neg_q ? q.y : neg2(q.y); }
@@ -175,6 +182,11 @@ PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bo
     }
     FqW9 pp, rr, ppp, qq;
     sqrw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm>(p, r, pp, rr);
+    FqW9 a_pp;
+    if constexpr (SF) {
+        a_pp = make_tw2_a<FqW>(pp);
+        mul_tw2_2<FqW, TW2_LZ_ALL, TW2_LZ_ALL>(p, a_pp, pp, acc.x, a_pp, pp, ppp, qq);
+    } else
     mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(p, pp, acc.x, pp, ppp, qq);            // (NXY: qq = NQ = -Q)
     FqW9 x3;
     {
@@ -183,6 +195,9 @@ PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bo
         x3 = normw(x3);
     }
     FqW9 zz3, zzz3;
+    if constexpr (SF) {
+        mul_tw2_mulw<FqW, TW2_LZ_ALL, LZ_ALL>(acc.zz, a_pp, pp, acc.zzz, ppp, zz3, zzz3);
+    } else
     mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(acc.zz, pp, acc.zzz, ppp, zz3, zzz3);
     FqW9 t, nppp;
 #pragma unroll
@@ -193,7 +208,7 @@ PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bo
     acc.zzz = zzz3;
 }
 PLK_HD void xyzzw_add_mixed_flag(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) { xyzzw_add_mixed_flag_impl<false>(acc, fresh, q, neg_q); }
-PLK_HD void xyzzw_add_mixed_nflag(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) { xyzzw_add_mixed_flag_impl<true>(acc, fresh, q, neg_q); }
+PLK_HD void xyzzw_add_mixed_nflag(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) { xyzzw_add_mixed_flag_impl<true, true>(acc, fresh, q, neg_q); }
 
 // a += b
 PLK_HD void xyzzw_add(XyzzW &a, const XyzzW &b) {

@@ -471,6 +471,197 @@ PLK_HD Tw3<WP> make_tw3(const W9<WP> &w_dom_w) {
     return t;
 }
 
+// ---- product by a SHARED FACTOR that is held in two forms ("tw2"): 126 multiply-adds instead of 162.
+// For a factor w (W domain, normalised) that is the right operand of several products keep, beside w itself,
+//     A = w * 2^-116 mod p = (W_lo + m p) / 2^116 + W_hi        (make_tw2_a: W_lo = limbs 0..3 of w, W_hi = limbs 4..8; FOUR Montgomery steps)
+// and split the variable operand after four limbs, z = Z_0 + Z_1 2^116 (Z_0 = limbs 0..3, Z_1 = limbs 4..8).  Z_0 A + Z_1 w = z w 2^-116 (mod p)
+// and both partial products start at column 0, so FIVE Montgomery steps divide the remaining 2^145 out:
+//     tw2(z; A, w) = (Z_0 A + Z_1 w + m p) / 2^145  =  z * w * 2^-261 (mod p) — what mulw(z, w) is,   36 + 45 + 45 multiply-adds, 13 columns.
+// (The 4 + 5 split is what lets the second form be w as it stands; 5 + 4 would need w * 2^29 mod p.)  A costs 36 multiply-adds by p and three
+// by one (limbs 1..3 of w join their columns as PLK_ADDEND; limb 0 starts the chain; W_hi is added limb by limb AFTER the chain, so A's limbs
+// 0..4 are below 2^30 and not normalised — LbTw2A): a factor used three times (PP in the mixed addition) pays it back twice over.
+// Lazy digits as in mont_scan: the top digit (3 for A, 4 for tw2) is always masked, the others may stay unmasked (bit k of LZ for m_k), so
+// m~ < 2^(29 D) (1 + 2^-26) for D digits.  Values, for normalised z and w:
+//     A < w / 2^116 + p (1 + 2^-26)                                 (W_lo / 2^116 < 1; in the W domain w < 2^261, so A < 1.0001 p)
+//     tw2 < z w / 2^261 + A / 2^29 + p (1 + 2^-26)                  (Z_0 < 2^116, Z_1 2^116 <= z): the bound of mulw2_lz + 2^-28 p.
+// Columns: at most 4 products z * A, 5 products z * w, 5 products m~ * p and a carry; every instantiation evaluates its exact worst case at the
+// declared limb bounds at compile time (tw2_col_bound, tw2a_col_bound — lazy_col_bound's method) and does not compile if a column can reach 2^64.
+// A sibling of mont_scan, as mul_tw3_scan is: the column ranges and the number of digits differ, and mont_scan's text is what the schedule of
+// every hot kernel hangs on.  Chain order inside a column is mont_scan's (chain 0, chain 1, one step each).
+struct LbTw2A { static constexpr Limbs9 B = Limbs9{{(1u << 30) - 1, (1u << 30) - 1, (1u << 30) - 1, (1u << 30) - 1, (1u << 30) - 1, M29, M29, M29, M29}}; };
+constexpr unsigned TW2_LZ_ALL = 0xfu;                          // tw2: m_0..m_3 unmasked
+constexpr unsigned TW2A_LZ_ALL = 0x7u;                         // make_tw2_a: m_0..m_2 unmasked
+constexpr ColBound tw2_col_bound(const Limbs9 &z, const Limbs9 &a, const Limbs9 &w, const uint32_t (&p)[9], unsigned lz) {
+    uint64_t carry = 0, worst = 0;
+    bool fits = true;
+    for (int k = 0; k < 13; k++) {
+        uint64_t s = carry;
+        for (int i = 0; i < 4; i++) if (k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)z.l[i] * a.l[k - i], &s);
+        for (int i = 0; i < 5; i++) if (k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)z.l[4 + i] * w.l[k - i], &s);
+        for (int i = 0; i < 5; i++) if (k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)(i < 4 && ((lz >> i) & 1u) ? 0xffffffffu : M29) * p[k - i], &s);
+        if (s > worst) worst = s;
+        carry = s >> 29;
+    }
+    return ColBound{worst, fits};
+}
+constexpr ColBound tw2a_col_bound(const Limbs9 &w, const uint32_t (&p)[9], unsigned lz) {
+    uint64_t carry = 0, worst = 0;
+    bool fits = true;
+    for (int k = 0; k < 12; k++) {
+        uint64_t s = carry;
+        if (k < 4) fits &= !__builtin_add_overflow(s, (uint64_t)w.l[k], &s);
+        for (int i = 0; i < 4; i++) if (k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)(i < 3 && ((lz >> i) & 1u) ? 0xffffffffu : M29) * p[k - i], &s);
+        if (s > worst) worst = s;
+        carry = s >> 29;
+    }
+    return ColBound{worst, fits};
+}
+// A = w * 2^-116 mod p.  LW: the declared bound of w (its limbs 4..8 below 2^29 for LbTw2A to hold: static_assert).  One chain: every
+// multiply-add reads the one before it.
+template <class WP, unsigned LZ = TW2A_LZ_ALL, class LW = LbNorm>
+PLK_HD W9<WP> make_tw2_a(const W9<WP> &w) {
+    static_assert(tw2a_col_bound(LW::B, WP::P29, LZ).fits, "a column of make_tw2_a can exceed 64 bits");
+    static_assert(lb_below(LW::B, 1u << 29), "make_tw2_a: the high limbs of w are added to normalised limbs and must stay below 2^30");
+    W9<WP> r;
+    uint32_t m[4];
+    uint64_t acc = w.l[0];
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        if (k > 0 && k < 4) PLK_ADDEND(acc, w.l[k]);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (i >= k || k - i > 8) continue;
+            acc += (uint64_t)m[i] * WP::P29[k - i]; PLK_CHAIN(acc);
+        }
+        if (k < 4) {
+            m[k] = (k < 3 && ((LZ >> k) & 1u)) ? (uint32_t)acc * WP::INV29 : ((uint32_t)acc * WP::INV29) & M29;
+            acc += (uint64_t)m[k] * WP::P29[0];
+        } else r.l[k - 4] = (uint32_t)acc & M29;
+        acc >>= 29;
+    }
+    r.l[8] = (uint32_t)acc;
+#pragma unroll
+    for (int j = 0; j < 5; j++) r.l[j] += w.l[4 + j];
+    return r;
+}
+// one accumulator chain of the tw2 scan: z, the two forms of its factor, the result
+template <class WP, unsigned LZ, class LZV, class LA, class LW>
+struct Tw2Chain {
+    static constexpr bool FITS = tw2_col_bound(LZV::B, LA::B, LW::B, WP::P29, LZ).fits;
+    const W9<WP> &z, &a, &w;
+    W9<WP> *r = nullptr;
+    uint32_t m[5];
+    uint64_t acc = 0;
+    PLK_HD void mad(uint64_t x, uint32_t y) { acc += x * y; PLK_CHAIN(acc); }
+    PLK_HD void za(int i, int j) { mad(z.l[i], a.l[j]); }
+    PLK_HD void zw(int i, int j) { mad(z.l[4 + i], w.l[j]); }
+    PLK_HD void digit(int k) { m[k] = (k < 4 && ((LZ >> k) & 1u)) ? (uint32_t)acc * WP::INV29 : ((uint32_t)acc * WP::INV29) & M29; }
+    PLK_HD void mp0(int k) { acc += (uint64_t)m[k] * WP::P29[0]; }
+    PLK_HD void limb(int j) { r->l[j] = (uint32_t)acc & M29; }
+    PLK_HD void shift() { acc >>= 29; }
+    PLK_HD void top() { r->l[8] = (uint32_t)acc; }
+};
+struct NoTw2Chain : NoChain { PLK_HD void za(int, int) {} PLK_HD void zw(int, int) {} };
+template <class WP, class C0, class C1 = NoTw2Chain>
+PLK_HD auto mul_tw2_scan(const C0 &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr, W9<WP> *r1 = nullptr) {
+    static_assert(C0::FITS, "a column of chain 0 can exceed 64 bits");
+    static_assert(C1::FITS, "a column of chain 1 can exceed 64 bits");
+    constexpr bool ONE = std::is_same<C1, NoTw2Chain>::value;
+    W9<WP> r;
+    C0 c0 = s0;
+    C1 c1 = s1;
+    if constexpr (ONE) c0.r = &r;
+    else { c0.r = r0; c1.r = r1; }
+#pragma unroll
+    for (int k = 0; k < 13; k++) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (k - i < 0 || k - i > 8) continue;
+            c0.za(i, k - i); c1.za(i, k - i);
+        }
+#pragma unroll
+        for (int i = 0; i < 5; i++) {
+            if (k - i < 0 || k - i > 8) continue;
+            c0.zw(i, k - i); c1.zw(i, k - i);
+        }
+#pragma unroll
+        for (int i = 0; i < 5; i++) {
+            if (i >= k || k - i > 8) continue;
+            c0.mad(c0.m[i], WP::P29[k - i]); c1.mad(c1.m[i], WP::P29[k - i]);
+        }
+        if (k < 5) { c0.digit(k); c1.digit(k); c0.mp0(k); c1.mp0(k); }
+        else { c0.limb(k - 5); c1.limb(k - 5); }
+        c0.shift(); c1.shift();
+    }
+    c0.top(); c1.top();
+    if constexpr (ONE) return r;
+}
+// z * w * 2^-261 (mod p) with a = make_tw2_a(w); LZV, LA, LW: the declared limb bounds of z, a, w
+template <class WP, unsigned LZ = 0, class LZV = LbNorm, class LA = LbTw2A, class LW = LbNorm>
+PLK_HD W9<WP> mul_tw2(const W9<WP> &z, const W9<WP> &a, const W9<WP> &w) { return mul_tw2_scan<WP>(Tw2Chain<WP, LZ, LZV, LA, LW>{z, a, w}); }
+// two in lockstep, each by a factor of its own (the same one twice where two products share it)
+template <class WP, unsigned LZ0, unsigned LZ1, class LZV0 = LbNorm, class LZV1 = LbNorm, class LA = LbTw2A, class LW = LbNorm>
+PLK_HD void mul_tw2_2(const W9<WP> &z0, const W9<WP> &a0, const W9<WP> &w0, const W9<WP> &z1, const W9<WP> &a1, const W9<WP> &w1, W9<WP> &r0, W9<WP> &r1) {
+    mul_tw2_scan<WP>(Tw2Chain<WP, LZ0, LZV0, LA, LW>{z0, a0, w0}, Tw2Chain<WP, LZ1, LZV1, LA, LW>{z1, a1, w1}, &r0, &r1);
+}
+// a tw2 product (chain 0, 13 columns) in lockstep with a plain Montgomery product a * b (chain 1, a MontChain over ONE product, 17 columns): for
+// a pair of which only one factor has its second form.  Column k of both is issued together, the multiply-adds alternating one by one while
+// both have some left (term t of column k of each chain, in the order of their own scans); columns 13..16 are chain 1's alone.
+// (term t of a column as a compile-time code, kind * 16 + i, or -1 past the column's last: left to the optimiser the scan stays a rolled loop)
+constexpr int tw2_term_code(int k, int t) {
+    int n = 0;
+    for (int i = 0; i < 4; i++) if (k - i >= 0 && k - i <= 8) { if (n == t) return i; n++; }
+    for (int i = 0; i < 5; i++) if (k - i >= 0 && k - i <= 8) { if (n == t) return 16 + i; n++; }
+    for (int i = 0; i < 5; i++) if (i < k && k - i <= 8) { if (n == t) return 32 + i; n++; }
+    return -1;
+}
+constexpr int mont_term_code(int k, int t) {
+    const int lo = k < 9 ? 0 : k - 8, hi = k < 9 ? k : 8;
+    int n = 0;
+    for (int i = lo; i <= hi; i++) { if (n == t) return i; n++; }
+    for (int i = lo; i <= hi && i < k; i++) { if (n == t) return 16 + i; n++; }
+    return -1;
+}
+// (static_for for code that the host checks compile too)
+template <int... J, class F> PLK_HD void static_for_hd_impl(std::integer_sequence<int, J...>, F &&f) { (f(std::integral_constant<int, J>{}), ...); }
+template <int N, class F> PLK_HD void static_for_hd(F &&f) { static_for_hd_impl(std::make_integer_sequence<int, N>{}, static_cast<F &&>(f)); }
+template <class WP, class CT, class CM>
+PLK_HD void mul_tw2_mulw_scan(const CT &s0, const CM &s1, W9<WP> *r0, W9<WP> *r1) {
+    static_assert(CT::FITS, "a column of chain 0 can exceed 64 bits");
+    static_assert(CM::FITS, "a column of chain 1 can exceed 64 bits");
+    static_assert(CM::Half::T == 1 && !CM::ADD, "chain 1 is one product without an addend");
+    CT c0 = s0;
+    CM c1 = s1;
+    c0.r = r0; c1.r = r1;
+    static_for_hd<17>([&](auto K) {
+        constexpr int k = decltype(K)::value;
+        static_for_hd<18>([&](auto T) {
+            constexpr int t = decltype(T)::value;
+            constexpr int e0 = k < 13 ? tw2_term_code(k, t) : -1, e1 = mont_term_code(k, t);
+            if constexpr (e0 >= 32) c0.mad(c0.m[e0 - 32], WP::P29[k - (e0 - 32)]);
+            else if constexpr (e0 >= 16) c0.zw(e0 - 16, k - (e0 - 16));
+            else if constexpr (e0 >= 0) c0.za(e0, k - e0);
+            if constexpr (e1 >= 16) c1.mad(c1.m[e1 - 16], WP::P29[k - (e1 - 16)]);
+            else if constexpr (e1 >= 0) c1.mad(c1.h.x[0]->l[k - e1], c1.h.x[1]->l[e1]);
+        });
+        if constexpr (k < 5) c0.digit(k);
+        if constexpr (k < 9) c1.digit(k);
+        if constexpr (k < 5) c0.mp0(k);
+        if constexpr (k < 9) c1.mp0(k);
+        if constexpr (k >= 5 && k < 13) c0.limb(k - 5);
+        if constexpr (k >= 9) c1.limb(k);
+        if constexpr (k < 13) c0.shift();
+        c1.shift();
+        if constexpr (k == 12) c0.top();
+    });
+    c1.top();
+}
+// r0 = tw2(z; a, w), r1 = x * y * 2^-261, in lockstep
+template <class WP, unsigned LZ0, unsigned LZ1, class LZV = LbNorm, class LX = LbNorm, class LY = LbNorm, class LA = LbTw2A, class LW = LbNorm>
+PLK_HD void mul_tw2_mulw(const W9<WP> &z, const W9<WP> &a, const W9<WP> &w, const W9<WP> &x, const W9<WP> &y, W9<WP> &r0, W9<WP> &r1) {
+    mul_tw2_mulw_scan<WP>(Tw2Chain<WP, LZ0, LZV, LA, LW>{z, a, w}, MontChain<WP, LZ1, Products<WP, LX, LY>>{{{&x, &y}}}, &r0, &r1);
+}
+
 // ---- OPERAND-SCANNING forms of the same three products (identical results, bit for bit): ten independent 64-bit
 // column accumulators per row instead of one chain.  They issue 16 more instructions per product (the carries join their
 // columns through v_lshl_add_u64), but a wave that has its SIMD to itself — the bucket-reduction kernels of the MSM are
