@@ -167,6 +167,37 @@ int32_t plk_msm_last_shape(plk_ctx *ctx, plk_msm_shape *out);
  * point, a commitment of <= 2^16 terms, the naive and short paths).                                                       */
 int32_t plk_msm_last_no_inf(plk_ctx *ctx, uint32_t *out);
 
+/* ---- multiexp::dense_multiexp(&worker, bases, scalars) with the bases as an argument: out = sum_{i<n} scalars[i] * bases[i] for points that
+ *      are NOT the resident key.  Every plk_msm_g1* call above sums against the resident key and reads it through the fixed-base table (15
+ *      shifted copies of the key: 0.94 GiB and ~40 ms at 2^20 points) — right for a prover that commits to one key thousands of times, wrong
+ *      for a one-off sum, and no answer at all for points that must not become the key.  These calls keep no table and need no key:
+ *      a front kernel converts the caller's points into a scratch of 64 B per term of the pass (never cached across calls: the caller's
+ *      memory may change), and the pass runs the shape of a key without shifted copies — fewer than 4096 terms: one double-and-add per
+ *      term; otherwise 13-bit windows below 2^17 terms, 15-bit below 2^19, 17-bit from there, one bucket set per window (plk_msm_last_shape
+ *      reports the pass: table_copies = 1).  Costs: DESIGN.md §4.2c.
+ *      Bases: the key's in-memory form, 64 bytes x ‖ y Montgomery, (0, 0) = infinity.  Scalars: Montgomery Fr, as for plk_msm_g1_dev.
+ *      n = 0 gives infinity and launches nothing.  Synchronous like plk_msm_g1_dev; the work is ordered after `stream` (NULL: the context's).
+ *      plk_msm_g1_bases (host pointers: 96 B per term through the context's staging buffer) and _bases_dev cut vectors above 2^24 terms into
+ *      passes of 2^24, one at a time, and add the partial sums on the host; _bases_batch_dev (`count` <= 8 scalar vectors against the same
+ *      bases, one pass of the kernels, `out` holds count points) returns PLK_ERR_SIZE above 2^24 terms, as plk_msm_g1_batch_dev does.
+ *      NO KEY NEEDS TO BE RESIDENT, and nothing about the resident key(s), their table(s), the Lagrange slot or any loan changes: the calls
+ *      are allowed on a context whose key is lent or borrowed (plk_ctx_share_srs).  They do not join the FIFO of _enqueue / _finish: a
+ *      commitment still in flight on the context is PLK_ERR_ARG.  PLK_ERR_ARG also: null ctx / out, a null pointer with n > 0, a device
+ *      pointer that is not 16-byte aligned, unknown flag bits, `count` outside 1..8.
+ *      Without PLK_MSM_CHECK_BASES the bases are taken on trust, exactly as plk_srs_upload takes a key: a point off the curve gives some
+ *      point, never a fault; *bad_out = UINT64_MAX.  With it every base must be (0, 0) or have x, y < q and y^2 = x^3 + 3 (checked by the
+ *      front kernel, before any commitment kernel is launched; a vector of several passes is checked whole first, at the price of converting
+ *      it twice): otherwise PLK_ERR_FORMAT with plk_g1_decode_dev's words, *bad_out = the LOWEST refused index, `out` untouched.
+ *      The scratch grows only and is freed with the context; a call that had to grow it beyond 2^20 points' worth (64 MiB) frees it before
+ *      it returns (1 GiB at 2^24 terms is not left attached to a long-lived context).                                                       */
+#define PLK_MSM_CHECK_BASES 1u   /* refuse a base that is neither (0, 0) nor a curve point with coordinates below q */
+int32_t plk_msm_g1_bases(plk_ctx *ctx, const plk_g1_affine *bases_host, const plk_fr *scalars_host, uint64_t n,
+                         uint32_t flags, plk_g1_affine *out, uint64_t *bad_out /* may be NULL */);
+int32_t plk_msm_g1_bases_dev(plk_ctx *ctx, const void *bases_dev, const void *scalars_dev, uint64_t n,
+                             uint32_t flags, plk_g1_affine *out, uint64_t *bad_out /* may be NULL */, void *stream);
+int32_t plk_msm_g1_bases_batch_dev(plk_ctx *ctx, const void *bases_dev, const void *const *scalars_dev, uint32_t count,
+                                   uint64_t n, uint32_t flags, plk_g1_affine *out, uint64_t *bad_out /* may be NULL */, void *stream);
+
 /* ---- Crs::<Lagrange>::from_powers (src/plonk.rs:179-185): inverse NTT over G1 (dump-lagrange)  */
 int32_t plk_g1_intt(plk_ctx *ctx, const plk_g1_affine *in_host, uint32_t log_n, plk_g1_affine *out_host);
 /* same, from the first 2^log_n points of the resident SRS into a device buffer (64 B per point) */
@@ -348,6 +379,16 @@ int32_t plk_srs_lagrange_from_powers(plk_ctx *ctx, uint32_t log_n);
 int32_t plk_srs_check(plk_ctx *ctx, const uint8_t g2[256], const uint8_t seed[32] /* NULL: OS randomness */,
                       uint32_t flags, int32_t *valid, uint64_t *bad_out /* may be NULL */);
 int32_t plk_srs_lagrange_check(plk_ctx *ctx, const uint8_t seed[32] /* NULL: OS randomness */, int32_t *valid);
+/* plk_srs_check for a CANDIDATE key: n points in device memory (the key's in-memory form, 16-byte aligned) that are NOT installed — to judge a
+ * key before it replaces the resident one, on a context whose key is lent, or in the middle of proving.  Same rules, same rho
+ * ("plk_srs_check" ‖ seed), same one-commitment form, same flags, codes and verdict convention: for the same points, g2 and seed it returns
+ * the *valid and *bad_out of plk_srs_check on those points made resident.  The commitment and the sub-range commitments of the bisection go
+ * through plk_msm_g1_bases_dev's path (points_dev + lo), P_0 and P_{n-1} are read from points_dev: no key needs to be resident, nothing
+ * resident changes and NO FIXED-BASE TABLE IS BUILT.  Waits for `stream` (NULL: the context's), then runs on the context's stream.
+ * PLK_ERR_ARG as plk_srs_check, and for a null or misaligned points_dev; PLK_ERR_SRS: n = 0.  Workspace as plk_srs_check; the converted
+ * points follow the scratch rule of plk_msm_g1_bases_dev, once for the whole call.                                                          */
+int32_t plk_srs_check_points_dev(plk_ctx *ctx, const void *points_dev, uint64_t n, const uint8_t g2[256], const uint8_t seed[32] /* NULL: OS randomness */,
+                                 uint32_t flags, int32_t *valid, uint64_t *bad_out /* may be NULL */, void *stream);
 
 /* ---- contributing a secret to a key, with a receipt anyone can check.  NO COUNTERPART IN THE REFERENCE: `plonkit setup` makes the key of the
  *      public tau = 42 (src/plonk.rs:30-48, "development only"), and a downloaded key is read and trusted (src/reader.rs:67-89).  The step of an

@@ -373,6 +373,17 @@ class Context:
         _check(lib().plk_srs_check(self._h, g2, self._seed(seed), ctypes.c_uint32(2 if locate else 0), ctypes.byref(valid), ctypes.byref(bad)))
         return bool(valid.value), (bad.value if bad.value != 2**64 - 1 else None)
 
+    def srs_check_points_dev(self, ptr, n, g2_bytes, seed=None, locate=False, stream=None):
+        """srs_check for `n` points in device memory (the key's form) that are NOT installed: the same (valid, bad_index) as srs_check on
+        those points made resident.  No key needs to be resident, nothing resident changes and no fixed-base table is built."""
+        g2 = bytes(g2_bytes)
+        if len(g2) != 256:
+            raise ValueError("g2_bytes must be the 256 bytes of a key file's G2 section, got %d" % len(g2))
+        valid, bad = ctypes.c_int32(0), ctypes.c_uint64(0)
+        _check(lib().plk_srs_check_points_dev(self._h, _devptr(ptr), ctypes.c_uint64(n), g2, self._seed(seed), ctypes.c_uint32(2 if locate else 0),
+                                              ctypes.byref(valid), ctypes.byref(bad), _stream(stream)))
+        return bool(valid.value), (bad.value if bad.value != 2**64 - 1 else None)
+
     def srs_lagrange_check(self, seed=None):
         """does the resident Lagrange-form key belong to the resident monomial key (same tau, same domain, same order)?"""
         valid = ctypes.c_int32(0)
@@ -487,6 +498,37 @@ class Context:
         out = np.zeros((len(ptrs), 8), dtype=np.uint64)
         _check(lib().plk_msm_g1_batch_dev(self._h, arr, ctypes.c_uint32(len(ptrs)), ctypes.c_uint64(n), ctypes.c_uint64(base_offset), _np(out), _stream(stream)))
         return out
+
+    # ---- MSM against caller-supplied bases: no resident key, no fixed-base table (plk_msm_g1_bases*)
+    def _bases_result(self, rc, bad, out):
+        if rc != 0:
+            self._raise_with_bad_index(rc, bad)                       # a refused base (check=True): PlkError with `.bad_index`
+        return out
+
+    def msm_bases(self, bases, scalars, check=False):
+        """sum_i scalars[i] * bases[i] for host arrays: bases (n, 8) uint64 in the key's form (x ‖ y Montgomery, zeros = infinity), scalars
+        (n, 4) uint64 Montgomery Fr.  check=True refuses a base that is not on the curve: PlkError with `.bad_index` = the lowest such index."""
+        b = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 8)
+        s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        if b.shape[0] != s.shape[0]:
+            raise ValueError("msm_bases: %d bases and %d scalars" % (b.shape[0], s.shape[0]))
+        out, bad = np.zeros(8, dtype=np.uint64), ctypes.c_uint64(0)
+        rc = lib().plk_msm_g1_bases(self._h, _np(b), _np(s), ctypes.c_uint64(s.shape[0]), ctypes.c_uint32(1 if check else 0), _np(out), ctypes.byref(bad))
+        return self._bases_result(rc, bad, out)
+
+    def msm_bases_dev(self, bases_ptr, scalars_ptr, n, check=False, stream=None):
+        out, bad = np.zeros(8, dtype=np.uint64), ctypes.c_uint64(0)
+        rc = lib().plk_msm_g1_bases_dev(self._h, _devptr(bases_ptr), _devptr(scalars_ptr), ctypes.c_uint64(n), ctypes.c_uint32(1 if check else 0),
+                                        _np(out), ctypes.byref(bad), _stream(stream))
+        return self._bases_result(rc, bad, out)
+
+    def msm_bases_batch_dev(self, bases_ptr, scalar_ptrs, n, check=False, stream=None):
+        """several scalar vectors (same length) against the same caller-supplied bases in one pass; returns [count, 8] affine points"""
+        arr = (ctypes.c_void_p * len(scalar_ptrs))(*[_devptr(p) for p in scalar_ptrs])
+        out, bad = np.zeros((len(scalar_ptrs), 8), dtype=np.uint64), ctypes.c_uint64(0)
+        rc = lib().plk_msm_g1_bases_batch_dev(self._h, _devptr(bases_ptr), arr, ctypes.c_uint32(len(scalar_ptrs)), ctypes.c_uint64(n),
+                                              ctypes.c_uint32(1 if check else 0), _np(out), ctypes.byref(bad), _stream(stream))
+        return self._bases_result(rc, bad, out)
 
     def msm_partial_dev(self, ptr, n, base_offset=0, stream=None):
         out = np.zeros(12, dtype=np.uint64)

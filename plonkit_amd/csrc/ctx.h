@@ -114,6 +114,7 @@ struct plk_ctx {
     uint32_t call_pieces = 0;                // plk_msm_g1_partial_dev: passes of its last call, their length, and msm_fin when it returned
     uint64_t call_piece_terms = 0, call_fin = 0;
     MsmSlot &front_slot() { return slot[fifo[msm_fin % MSM_SLOTS]]; }
+    plk::DevBuf bases_w;                     // msm.hip: caller-supplied bases of the current pass in the 2^261 domain (plk_msm_g1_bases*); never kept across calls
     plk::DevBuf prove_ws;                    // workspace of the prover rounds (grows only)
     plk::DevBuf poly_tmp, poly_tmp2;         // scan block totals / evaluation partials
     plk::DevBuf stage;                       // host<->device staging for the host-pointer API

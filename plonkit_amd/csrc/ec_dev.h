@@ -29,6 +29,18 @@ struct alignas(16) G1Jac { Fq x, y, z; };
 
 PLK_HD bool is_inf(const G1Affine &p) { return p.x.is_zero() && p.y.is_zero(); }
 PLK_HD bool is_inf(const G1Xyzz &p) { return p.zz.is_zero(); }
+// y^2 = x^3 + 3 on Montgomery coordinates below q (keyio.hip: decode; msm.hip: checked caller-supplied bases).  (0, 0) is NOT on the curve.
+PLK_HD bool g1_on_curve(const G1Affine &p) {
+    const Fq one = Fq::one();
+    return sqr(p.y) == add(mul(sqr(p.x), p.x), add(add(one, one), one));
+}
+// v < q as an integer (a borrow out of the top limb of v - q)
+PLK_HD bool fq_below_modulus(const Fq &v) {
+    uint64_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { const uint64_t d = (uint64_t)v.l[i] - FqParams::P[i] - br; br = (d >> 32) & 1; }
+    return br != 0;
+}
 PLK_HD G1Xyzz xyzz_identity() { G1Xyzz r; r.x = Fq::zero(); r.y = Fq::zero(); r.zz = Fq::zero(); r.zzz = Fq::zero(); return r; }
 PLK_HD G1Xyzz xyzz_from_affine(const G1Affine &p) {
     if (is_inf(p)) return xyzz_identity();

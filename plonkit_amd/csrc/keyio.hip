@@ -54,8 +54,7 @@ __global__ void __launch_bounds__(256) g1_decode_kernel(const u32x4 *__restrict_
         ok = xin && yin && !(x.is_zero() && y.is_zero());   // (0, 0) without the flag is an ordinary point, and not on the curve
         if (ok) {
             p.x = from_canonical(x); p.y = from_canonical(y);
-            const Fq one = Fq::one();
-            ok = sqr(p.y) == add(mul(sqr(p.x), p.x), add(add(one, one), one));       // y^2 = x^3 + 3
+            ok = g1_on_curve(p);                            // y^2 = x^3 + 3 (ec_dev.h)
             if (!ok) { p.x = Fq::zero(); p.y = Fq::zero(); }
         }
     }

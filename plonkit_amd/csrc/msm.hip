@@ -38,7 +38,8 @@
 // commitment is given (path, window bits, table copies, pre-phase, variant, reduction lanes, pieces, every buffer size) and every constant
 // that rests on is decided in msm_plan.h (msm_plan_pass / msm_plan_fallback / msm_plan_call: host-only, checked without a GPU by
 // tests/test_msm_plan_host.py); everything else (recoding, partition, bucket reduction, the drivers that launch a plan, the FIFO of three
-// slots, plk_ctx_share_srs) is here.
+// slots, plk_ctx_share_srs) is here — and so are the commitments against bases that are NOT the key (plk_msm_g1_bases*: bases_to_w_kernel converts
+// the caller's points, msm_plan_bases_pass plans a pass without a table, msm_bases_commit runs it through the same slots).
 #include "msm_shape.h"
 #include "msm.h"
 #include "ec29_quad_dev.h"
@@ -369,13 +370,39 @@ __device__ __noinline__ void xyzzw_double_call(XyzzW *a) { XyzzW t = *a; *a = xy
 __device__ __forceinline__ void xyzzw_add_nl(XyzzW &a, const XyzzW &b) { xyzzw_add_call(&a, &b); }
 __device__ __forceinline__ XyzzW xyzzw_double_nl(const XyzzW &a) { XyzzW t = a; xyzzw_double_call(&t); return t; }
 
+// a point in the key's form (Montgomery, R = 2^256) as the 64-byte record the accumulation, the short path and msm_naive gather
+__device__ __forceinline__ G1Affine affine_to_w(const G1Affine &p) {
+    G1Affine o;
+    o.x = pack<FqParams>(csub_p(w_from_s(unpack<FqW>(p.x))));
+    o.y = pack<FqParams>(csub_p(w_from_s(unpack<FqW>(p.y))));
+    return o;
+}
+
 __global__ void __launch_bounds__(256) srs_to_w_kernel(G1Affine *out, const G1Affine *in, uint64_t n) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     G1Affine p = load_affine(in + i);
-    G1Affine o;
-    o.x = pack<FqParams>(csub_p(w_from_s(unpack<FqW>(p.x))));
-    o.y = pack<FqParams>(csub_p(w_from_s(unpack<FqW>(p.y))));
+    G1Affine o = affine_to_w(p);
+    store_fp(&out[i].x, o.x);
+    store_fp(&out[i].y, o.y);
+}
+
+// Front kernel of the commitments against caller-supplied bases (plk_msm_g1_bases*): the caller's points, which are no key and have no table,
+// into the scratch the pass gathers from.  One lane per point, four dwordx4 loads and four dwordx4 stores with a 64-byte lane stride (every
+// byte of every line used, as keyio.hip's decode): 128 B of traffic per point and nothing to stage.  CHECK: a point must be (0, 0) or have
+// both coordinates below q and lie on the curve — what plk_g1_decode_dev accepts, on the form it produces; the verdict of the whole vector is
+// the LOWEST refused index (atomicMin on one 64-bit word), whatever the launch geometry.  A refused point is converted like any other: the
+// host reads the word before it launches anything that would gather it.
+template <bool CHECK>
+__global__ void __launch_bounds__(256) bases_to_w_kernel(G1Affine *__restrict__ out, const G1Affine *__restrict__ in, uint64_t n, unsigned long long *bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const G1Affine p = load_affine(in + i);
+    if (CHECK) {
+        const bool ok = is_inf(p) || (fq_below_modulus(p.x) && fq_below_modulus(p.y) && g1_on_curve(p));
+        if (!ok) atomicMin(bad, (unsigned long long)i);
+    }
+    const G1Affine o = affine_to_w(p);
     store_fp(&out[i].x, o.x);
     store_fp(&out[i].y, o.y);
 }
@@ -938,14 +965,8 @@ static int32_t msm_launch(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t stream,
     }
 }
 
-// `caller` is the stream on which the scalars were produced; the commitment runs on its slot's own stream after an
-// event recorded there.  The caller must leave the scalars alone until the matching msm_finish_batch.
-int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t batch, uint64_t n, uint64_t base_offset, hipStream_t caller) {
-    if (ctx->msm_enq - ctx->msm_fin >= plk_ctx::MSM_SLOTS) { set_error("msm: " + std::to_string(plk_ctx::MSM_SLOTS) + " commitments are already in flight (call the finish function first)"); return PLK_ERR_ARG; }
-    uint32_t slot_index = 0;
-    while (ctx->slot[slot_index].busy) slot_index++;          // lowest free slot (there is one: fewer than MSM_SLOTS are in flight)
-    plk_ctx::MsmSlot &S = ctx->slot[slot_index];
-    // (the slot's stream and events are created before the SRS, size and batch checks)
+// the slot's stream and events (created at its first use), and its stream ordered after `caller`
+static int32_t slot_open(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t caller) {
     if (!S.stream) {
         // The slots' streams are created at the runtime's HIGH stream priority, all three alike.  What counts is not the priority but that the runtime
         // keeps a pool of hardware queues per priority level: at the default level the three slots share HIP's (default: four) queues with the null
@@ -962,6 +983,17 @@ int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t b
     if (ctx->ev_on && !S.ev[0]) { PLK_HIP(hipEventCreate(&S.ev[0])); PLK_HIP(hipEventCreate(&S.ev[1])); }
     PLK_HIP(hipEventRecord(S.ready, caller));
     PLK_HIP(hipStreamWaitEvent(S.stream, S.ready, 0));
+    return PLK_OK;
+}
+
+// `caller` is the stream on which the scalars were produced; the commitment runs on its slot's own stream after an
+// event recorded there.  The caller must leave the scalars alone until the matching msm_finish_batch.
+int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t batch, uint64_t n, uint64_t base_offset, hipStream_t caller) {
+    if (ctx->msm_enq - ctx->msm_fin >= plk_ctx::MSM_SLOTS) { set_error("msm: " + std::to_string(plk_ctx::MSM_SLOTS) + " commitments are already in flight (call the finish function first)"); return PLK_ERR_ARG; }
+    uint32_t slot_index = 0;
+    while (ctx->slot[slot_index].busy) slot_index++;          // lowest free slot (there is one: fewer than MSM_SLOTS are in flight)
+    plk_ctx::MsmSlot &S = ctx->slot[slot_index];
+    PLK_TRY(slot_open(ctx, S, caller));                       // (before the SRS, size and batch checks)
     hipStream_t stream = S.stream;
     if (!ctx->srs) { set_error("msm: no SRS uploaded (plk_srs_upload)"); return PLK_ERR_SRS; }
     if (base_offset + n > ctx->srs_n) { set_error("msm: SRS too small for this commitment"); return PLK_ERR_SRS; }
@@ -1050,6 +1082,74 @@ int32_t msm_finish_batch(plk_ctx *ctx, hipStream_t, host::HJac *out) {
 int32_t msm_finish(plk_ctx *ctx, hipStream_t stream, host::HJac *out) {
     if (ctx->msm_fin != ctx->msm_enq && ctx->front_slot().plan.shape.batch != 1) { set_error("msm_finish: a batch is pending"); return PLK_ERR_ARG; }
     return msm_finish_batch(ctx, stream, out);
+}
+
+// ------------------------------------------------------------------------ caller-supplied bases
+// sum_i scalars[i] * bases[i] for points that are no key (plk_msm_g1_bases*, plk_srs_check_points_dev).  Nothing resident is read or written:
+// the front kernel converts the pass's points into ctx->bases_w (64 B per term, never kept across calls: the caller's memory may change), the
+// slot's plan is msm_plan_bases_pass — one copy, so no table — and the slot machinery above runs it with the infinity test (no_inf = false;
+// finding out whether the bases hold infinity would cost a synchronisation).  The callers have established that nothing is in flight, so the
+// lowest slot is free; it is taken and finished before the function returns.
+static int32_t bases_front(plk_ctx *ctx, hipStream_t stream, const G1Affine *in, uint64_t n, bool check, uint64_t *bad) {
+    *bad = MSM_BASES_NONE;
+    PLK_TRY(ctx->bases_w.reserve((size_t)n * sizeof(G1Affine)));
+    const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
+    if (!check) {
+        hipLaunchKernelGGL(bases_to_w_kernel<false>, grid, block, 0, stream, ctx->bases_w.as<G1Affine>(), in, n, (unsigned long long *)nullptr);
+        PLK_HIP(hipGetLastError());
+        return PLK_OK;
+    }
+    PLK_TRY(ctx->key_bad.reserve(16));
+    unsigned long long word = MSM_BASES_NONE;
+    PLK_HIP(hipMemsetAsync(ctx->key_bad.p, 0xff, 8, stream));
+    hipLaunchKernelGGL(bases_to_w_kernel<true>, grid, block, 0, stream, ctx->bases_w.as<G1Affine>(), in, n, ctx->key_bad.as<unsigned long long>());
+    PLK_HIP(hipGetLastError());
+    PLK_HIP(hipMemcpyAsync(&word, ctx->key_bad.p, 8, hipMemcpyDeviceToHost, stream));
+    PLK_HIP(hipStreamSynchronize(stream));                    // the verdict decides whether anything else is launched
+    *bad = word;
+    return PLK_OK;
+}
+
+int32_t msm_bases_commit(plk_ctx *ctx, const void *bases_dev, const Fr *const *scalars_dev, uint32_t batch, uint64_t n, bool check, uint64_t *bad,
+                         hipStream_t caller, host::HJac *out) {
+    *bad = MSM_BASES_NONE;
+    if (ctx->msm_enq != ctx->msm_fin) { set_error("msm: a commitment is still in flight on this context"); return PLK_ERR_ARG; }
+    if (batch < 1 || batch > MSM_MAX_BATCH) { set_error("msm: batch must be 1..8"); return PLK_ERR_ARG; }
+    const MsmCallPlan call = msm_plan_bases_call(n);
+    if (call.pieces > 1 && batch != 1) { set_error("msm: more than 2^24 terms in one pass (plk_msm_g1_bases / plk_msm_g1_bases_dev split longer commitments; the batch entry point does not)"); return PLK_ERR_SIZE; }
+    const uint32_t slot_index = 0;
+    plk_ctx::MsmSlot &S = ctx->slot[slot_index];
+    PLK_TRY(slot_open(ctx, S, caller));
+    const G1Affine *bases = static_cast<const G1Affine *>(bases_dev);
+    const auto refused = [&](uint64_t index) { *bad = index; set_error("read key err: point not on curve"); return PLK_ERR_FORMAT; };
+    // several passes, checked: every pass is checked before the first commitment kernel runs (one more conversion of each pass)
+    if (check && call.pieces > 1)
+        for (uint64_t off = 0; off < n; off += call.piece_terms) {
+            uint64_t b;
+            PLK_TRY(bases_front(ctx, S.stream, bases + off, n - off < call.piece_terms ? n - off : call.piece_terms, true, &b));
+            if (b != MSM_BASES_NONE) return refused(off + b);
+        }
+    host::HJac acc[MSM_MAX_BATCH];
+    for (uint32_t k = 0; k < batch; k++) acc[k] = host::HJac::inf();
+    for (uint64_t piece = 0, off = 0; piece < call.pieces; piece++, off += call.piece_terms) {
+        const uint64_t m = n - off < call.piece_terms ? n - off : call.piece_terms;
+        if (m) {
+            uint64_t b;
+            PLK_TRY(bases_front(ctx, S.stream, bases + off, m, check && call.pieces == 1, &b));
+            if (b != MSM_BASES_NONE) return refused(off + b);
+        }
+        S.plan = msm_plan_bases_pass(m, batch, fused_recode_allowed());
+        S.bases = ctx->bases_w.p;
+        for (uint32_t k = 0; k < batch; k++) S.scalars[k] = scalars_dev[k] ? scalars_dev[k] + off : nullptr;
+        PLK_TRY(msm_launch(ctx, S, S.stream, false));
+        ctx->fifo[ctx->msm_enq % plk_ctx::MSM_SLOTS] = (uint8_t)slot_index; S.busy = true; ctx->msm_enq++;
+        host::HJac j[MSM_MAX_BATCH];
+        PLK_TRY(msm_finish_batch(ctx, nullptr, j));
+        for (uint32_t k = 0; k < batch; k++) acc[k] = host::jac_add(acc[k], j[k]);
+    }
+    if (call.pieces > 1) { ctx->call_pieces = (uint32_t)call.pieces; ctx->call_piece_terms = call.piece_terms; ctx->call_fin = ctx->msm_fin; }
+    for (uint32_t k = 0; k < batch; k++) out[k] = acc[k];
+    return PLK_OK;
 }
 
 }  // namespace plk
@@ -1192,6 +1292,56 @@ int32_t plk_msm_g1(plk_ctx *ctx, const plk_fr *scalars, uint64_t n, uint64_t bas
     PLK_TRY(ctx->stage.reserve(n * sizeof(plk_fr) + 32));
     PLK_HIP(hipMemcpyAsync(ctx->stage.p, scalars, n * sizeof(plk_fr), hipMemcpyHostToDevice, ctx->stream));
     return plk_msm_g1_dev(ctx, ctx->stage.p, n, base_offset, out, nullptr);
+}
+
+// ---- commitments against caller-supplied bases (msm_bases_commit above)
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+static int32_t bases_entry(const char *who, plk_ctx *ctx, const void *bases_dev, const void *const *scalars_dev, uint32_t count, uint64_t n, uint32_t flags,
+                           plk_g1_affine *out, uint64_t *bad_out, hipStream_t stream) {
+    if (bad_out) *bad_out = MSM_BASES_NONE;
+    bool bad_arg = !ctx || !out || !scalars_dev || (flags & ~PLK_MSM_CHECK_BASES) || count < 1 || count > MSM_MAX_BATCH || (n && !bases_dev) || !aligned16(bases_dev);
+    for (uint32_t k = 0; !bad_arg && k < count; k++) bad_arg = (n && !scalars_dev[k]) || !aligned16(scalars_dev[k]);
+    if (bad_arg) { set_error(std::string(who) + ": bad argument"); return PLK_ERR_ARG; }
+    if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment is still in flight on this context"); return PLK_ERR_ARG; }
+    if (count > 1 && n > MSM_PASS_MAX_TERMS) { set_error(std::string(who) + ": more than 2^24 terms in one pass (plk_msm_g1_bases and plk_msm_g1_bases_dev split longer commitments)"); return PLK_ERR_SIZE; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    BasesScratchLoan loan(ctx);
+    host::HJac j[MSM_MAX_BATCH];
+    uint64_t bad = MSM_BASES_NONE;
+    const int32_t rc = msm_bases_commit(ctx, bases_dev, reinterpret_cast<const Fr *const *>(scalars_dev), count, n, (flags & PLK_MSM_CHECK_BASES) != 0, &bad,
+                                        stream ? stream : ctx->stream, j);
+    if (bad_out) *bad_out = bad;
+    if (rc != PLK_OK) return rc;                              // (`out` is untouched)
+    for (uint32_t k = 0; k < count; k++) {
+        const host::HAffine a = host::jac_to_affine(j[k]);
+        memcpy(out[k].x, a.x.l, 32); memcpy(out[k].y, a.y.l, 32);
+    }
+    return PLK_OK;
+}
+
+int32_t plk_msm_g1_bases_dev(plk_ctx *ctx, const void *bases_dev, const void *scalars_dev, uint64_t n, uint32_t flags, plk_g1_affine *out, uint64_t *bad_out, void *stream) {
+    return bases_entry("plk_msm_g1_bases_dev", ctx, bases_dev, &scalars_dev, 1, n, flags, out, bad_out, (hipStream_t)stream);
+}
+
+int32_t plk_msm_g1_bases_batch_dev(plk_ctx *ctx, const void *bases_dev, const void *const *scalars_dev, uint32_t count, uint64_t n, uint32_t flags, plk_g1_affine *out,
+                                   uint64_t *bad_out, void *stream) {
+    return bases_entry("plk_msm_g1_bases_batch_dev", ctx, bases_dev, scalars_dev, count, n, flags, out, bad_out, (hipStream_t)stream);
+}
+
+// host pointers: 96 B per term through the context's staging buffer, then the call above on the context's stream
+int32_t plk_msm_g1_bases(plk_ctx *ctx, const plk_g1_affine *bases, const plk_fr *scalars, uint64_t n, uint32_t flags, plk_g1_affine *out, uint64_t *bad_out) {
+    if (bad_out) *bad_out = MSM_BASES_NONE;
+    if (!ctx || !out || (n && (!bases || !scalars)) || (flags & ~PLK_MSM_CHECK_BASES)) { set_error("plk_msm_g1_bases: bad argument"); return PLK_ERR_ARG; }
+    if (ctx->msm_enq != ctx->msm_fin) { set_error("plk_msm_g1_bases: a commitment is still in flight on this context"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    PLK_TRY(ctx->stage.reserve(n * (sizeof(plk_g1_affine) + sizeof(plk_fr)) + 32));
+    char *bases_dev = ctx->stage.as<char>(), *scalars_dev = bases_dev + n * sizeof(plk_g1_affine);
+    if (n) {
+        PLK_HIP(hipMemcpyAsync(bases_dev, bases, n * sizeof(plk_g1_affine), hipMemcpyHostToDevice, ctx->stream));
+        PLK_HIP(hipMemcpyAsync(scalars_dev, scalars, n * sizeof(plk_fr), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const void *sv = scalars_dev;
+    return bases_entry("plk_msm_g1_bases", ctx, bases_dev, &sv, 1, n, flags, out, bad_out, nullptr);
 }
 
 int32_t plk_srs_precompute(plk_ctx *ctx) {

@@ -7,6 +7,7 @@
 //   msm_plan_pipeline  its bucket-pipeline half on its own
 //   msm_plan_fallback  the re-run of a short commitment whose bucket lists overflowed (msm_finish_batch)
 //   msm_plan_call      one call of plk_msm_g1 / _dev / _partial_dev: piece length, pieces in flight, number of pieces
+//   msm_plan_bases_pass / msm_plan_bases_call   the same two for caller-supplied bases (plk_msm_g1_bases*): no key, no table
 // msm.hip's host side computes a plan, then reserves, launches and records; it decides nothing.
 #pragma once
 #include <stdint.h>
@@ -297,6 +298,28 @@ inline MsmCallPlan msm_plan_call(uint64_t terms, uint64_t srs_n, bool fifo_empty
     MsmCallPlan C;
     C.piece_terms = pipelined ? MSM_PIPELINE_PIECE : MSM_PASS_MAX_TERMS;
     C.depth = pipelined ? MSM_SLOTS : 1;
+    C.pieces = terms ? (terms + C.piece_terms - 1) / C.piece_terms : 1;
+    return C;
+}
+
+// ---------------------------------------------------------------------------------------------- caller-supplied bases
+// plk_msm_g1_bases / _dev / _batch_dev: the points are the caller's, converted once per pass into a scratch of `terms` records — no key, so no
+// table: ONE copy, the window widths of a key without shifted copies (13 / 15 / 17 bits), one bucket set per window, the pre-phase through
+// the digit array.  Never the short path (it needs all 15 copies) and never another commitment in flight (the calls refuse that).
+inline MsmPlan msm_plan_bases_pass(uint64_t terms, uint32_t batch, bool fused_allowed) {
+    MsmPlan P;
+    if (terms == 0) P = msm_plan_nothing(terms, batch, terms);
+    else if (terms < MSM_NAIVE_BELOW) P = msm_plan_naive(terms, batch, terms);
+    else P = msm_plan_pipeline(terms, batch, /*srs_n*/ terms, /*copies*/ 1, pick_window_bits(terms, false), msm_index_bits(terms),
+                               /*others_in_flight*/ false, fused_allowed);
+    P.table_request = 0;
+    return P;
+}
+// one call: passes of 2^24 terms, one at a time, partial sums added on the host
+inline MsmCallPlan msm_plan_bases_call(uint64_t terms) {
+    MsmCallPlan C;
+    C.piece_terms = MSM_PASS_MAX_TERMS;
+    C.depth = 1;
     C.pieces = terms ? (terms + C.piece_terms - 1) / C.piece_terms : 1;
     return C;
 }
