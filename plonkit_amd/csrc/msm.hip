@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(1024) msm_scan_bins(uint32_t *hist, uint32_t *
     const uint32_t per = (total_bins + 1023) / 1024;
     uint32_t lo = tid * per, hi = lo + per < total_bins ? lo + per : total_bins, s = 0, ts = 0;
     if (lo > total_bins) lo = total_bins;
-    for (uint32_t i = lo; i < hi; i++) { s += hist[i]; ts += (hist[i] + TASK_MAX - 1) / TASK_MAX; }
+    for (uint32_t i = lo; i < hi; i++) { s += hist[i]; ts += msm_bin_tasks(hist[i]); }
     sums[tid] = s; tsums[tid] = ts;
     __syncthreads();
     for (uint32_t off = 1; off < 1024; off <<= 1) {
@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(1024) msm_scan_bins(uint32_t *hist, uint32_t *
     for (uint32_t i = lo; i < hi; i++) {
         uint32_t c = hist[i];
         bin_start[i] = run; run += c;
-        task_start[i] = trun; trun += (c + TASK_MAX - 1) / TASK_MAX;
+        task_start[i] = trun; trun += msm_bin_tasks(c);
         hist[i] = 0;
     }
     if (tid == 1023) { bin_start[total_bins] = sums[1023]; task_start[total_bins] = tsums[1023]; }
@@ -529,10 +529,13 @@ static int32_t ensure_base_table(plk_ctx *ctx, uint32_t copies, hipStream_t stre
 // dependent additions) when the launch leaves SIMDs idle anyway (one or two commitments: latency is all that counts), 16 lanes (27 % fewer
 // lane-additions, a chain of 35) when a batch of three or more commitments puts two waves of these chains on every SIMD and the work decides
 // (profiles/r04_msm_reduce_rl_ab.txt: 16 lanes everywhere is +6 % on a single commitment and -1 % on a stream of them).
-constexpr uint32_t HOT_SPAN = 8;
+// (HOT_SPAN and the span of a bucket: msm_plan.h, the bucket schedule.  The three kernels below derive mu from a task's entry count with
+//  msm_lane_entries' expression WRITTEN OUT, (nc + MSM_THREADS - 1) / MSM_THREADS: through the function the compiler allocates other registers
+//  in all five instantiations, and the refactoring that introduced the rules was to leave every instruction stream as it was.  msm_lane_entries
+//  carries the cross-reference; tests/test_msm_bucket_cases_host.py holds the two texts together.)
 __device__ __forceinline__ uint32_t bucket_span(const uint32_t *meta, uint32_t b, uint32_t mu) {
     const uint32_t s0 = meta[b], e0 = meta[b + 1];
-    return e0 > s0 ? (e0 - 1) / mu - s0 / mu : 0;
+    return msm_bucket_span(s0, e0, mu);
 }
 // The reduction kernels below are chains of dependent additions run by one or two waves per SIMD: they need few issue slots, but every slot
 // they wait for lengthens the tail of a commitment, which is on the critical path of a proof.  When they share a SIMD with throughput
@@ -552,14 +555,14 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_fold_hot(XyzzW *partials, con
     if (!__any(nc != 0 && !(nc_raw & TASK_OWNED_BIT))) return;      // (owned tasks have one sum per bucket: nothing is spread)
     const uint32_t mu = (nc_raw & TASK_OWNED_BIT) ? 0x7fffffffu : (nc ? (nc + MSM_THREADS - 1) / MSM_THREADS : 1);
     uint32_t hot_mask = 0;                                    // which of this lane's RB buckets are wide
-    if (nc) for (uint32_t k = 0; k < RB; k++) if (bucket_span(meta, RB * sub + k, mu) > HOT_SPAN) hot_mask |= 1u << k;
+    if (nc) for (uint32_t k = 0; k < RB; k++) if (msm_span_folded(bucket_span(meta, RB * sub + k, mu))) hot_mask |= 1u << k;
     if (!__any(hot_mask != 0)) return;
     XyzzW *P = partials + (size_t)(live ? task : 0) * SLOTS_PER_TASK;
     for (uint32_t owner = 0; owner < RL; owner++) {
         const uint32_t m = __shfl(hot_mask, owner, RL);        // uniform over the RL lanes of the task
         for (uint32_t k = 0; k < RB; k++) {
             if (!((m >> k) & 1)) continue;
-            const uint32_t b = RB * owner + k, tf = meta[b] / mu, tl = (meta[b + 1] - 1) / mu;
+            const uint32_t b = RB * owner + k, tf = msm_bucket_first_lane(meta[b], mu), tl = msm_bucket_last_lane(meta[b + 1], mu);
             XyzzW acc = xyzzw_identity();
             for (uint32_t t = tf + 1 + sub; t <= tl; t += RL) { XyzzW o = load_xyzzw(P + SLOT_HEAD + t); xyzzw_add_nl(acc, o); }
             for (uint32_t x = 1; x < RL; x <<= 1) { XyzzW o = shfl_xor_w(acc, x); xyzzw_add_nl(acc, o); }
@@ -617,12 +620,12 @@ __global__ void __launch_bounds__(MSM_THREADS, 2) msm_task_reduce(const XyzzW *p
                 k--;
                 const uint32_t b = RB * sub + k, s0 = meta[b], e0 = meta[b + 1];
                 if (e0 > s0) {
-                    const uint32_t tf = s0 / mu, tl = (e0 - 1) / mu;
+                    const uint32_t tf = msm_bucket_first_lane(s0, mu), tl = msm_bucket_last_lane(e0, mu);
                     pending_sum = true;
                     if (tf == tl) O = load_xyzzw(P + SLOT_PRIMARY + b);
                     else {
                         O = load_xyzzw(P + SLOT_TAIL + tf);
-                        if (tl - tf > HOT_SPAN) { piece = SLOT_PRIMARY + b; piece_end = piece + 1; }      // folded by B0
+                        if (msm_span_folded(tl - tf)) { piece = SLOT_PRIMARY + b; piece_end = piece + 1; }      // folded by B0
                         else { piece = SLOT_HEAD + tf + 1; piece_end = SLOT_HEAD + tl + 1; }
                     }
                 } else to_y = true;                           // empty bucket: only Y += X
@@ -686,12 +689,12 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_task_reduce_quad(const XyzzW 
                 k--;
                 const uint32_t b = RB * sub + k, s0 = meta[b], e0 = meta[b + 1];
                 if (e0 > s0) {
-                    const uint32_t tf = s0 / mu, tl = (e0 - 1) / mu;
+                    const uint32_t tf = msm_bucket_first_lane(s0, mu), tl = msm_bucket_last_lane(e0, mu);
                     pending_sum = true;
                     if (tf == tl) O = load_coord(P + SLOT_PRIMARY + b, coord);
                     else {
                         O = load_coord(P + SLOT_TAIL + tf, coord);
-                        if (tl - tf > HOT_SPAN) { piece = SLOT_PRIMARY + b; piece_end = piece + 1; }      // folded by B0
+                        if (msm_span_folded(tl - tf)) { piece = SLOT_PRIMARY + b; piece_end = piece + 1; }      // folded by B0
                         else { piece = SLOT_HEAD + tf + 1; piece_end = SLOT_HEAD + tl + 1; }
                     }
                 } else to_y = true;                           // empty bucket: only Y += X
@@ -728,13 +731,13 @@ __global__ void __launch_bounds__(MSM_THREADS) msm_task_reduce_quad(const XyzzW 
 // (same bucket range), so one wave per such bin folds them first: lane l takes tasks l, l + 64, .. then a shuffle tree;
 // the bin's first task receives (sum S, sum T), the others the identity.  Bins with <= BIN_FOLD_MIN tasks are left alone:
 // for uniform scalars the kernel only reads the task offsets.
-constexpr uint32_t BIN_FOLD_MIN = 4;
+// (BIN_FOLD_MIN: msm_plan.h, the bucket schedule)
 __global__ void __launch_bounds__(MSM_THREADS) msm_bin_fold(XyzzW *task_out, const uint32_t *task_start, uint32_t total_bins) {
     latency_chain_priority();
     const uint32_t bin = blockIdx.x * (MSM_THREADS / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
     if (bin >= total_bins) return;
     const uint32_t t0 = task_start[bin], t1 = task_start[bin + 1];
-    if (t1 - t0 <= BIN_FOLD_MIN) return;                       // wave-uniform
+    if (!msm_bin_folded(t1 - t0)) return;                       // wave-uniform
     for (uint32_t which = 0; which < 2; which++) {            // 0: S, 1: T
         XyzzW acc = xyzzw_identity();
         for (uint32_t t = t0 + lane; t < t1; t += 64) { XyzzW o = load_xyzzw(task_out + 2 * (size_t)t + which); xyzzw_add_nl(acc, o); }

@@ -54,8 +54,8 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
     // a bin that needs k tasks is cut into k EQUAL slices (not CHUNK, CHUNK, ..., remainder): with ~6 tasks per
     // workgroup slot a mix of full and quarter-size tasks left the last full ones running alone (measured at 2^21:
     // 3.7 ms instead of 2.6 ms for the same additions)
-    const uint32_t k_bin = task_start[bin + 1] - task_start[bin], per = (be - bs + k_bin - 1) / k_bin;
-    const uint32_t s = bs + slice * per < be ? bs + slice * per : be, e = (s + per < be) ? s + per : be, nc = e - s;
+    const uint32_t k_bin = task_start[bin + 1] - task_start[bin], per = msm_slice_per(be - bs, k_bin);
+    const uint32_t s = msm_slice_begin(bs, be, per, slice), e = msm_slice_end(s, be, per), nc = e - s;       // (msm_plan.h, the bucket schedule)
 
     if (tid < FINE) { cnt[tid] = 0; cursor[tid] = 0; }
     __syncthreads();
@@ -114,8 +114,8 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
     }
     __syncthreads();
     uint32_t *meta = task_meta + (size_t)task * META_PER_TASK;
-    const uint32_t mu = (nc + MSM_THREADS - 1) / MSM_THREADS;
-    const bool owned = OWNED && FINE * 4 == MSM_THREADS && max_cnt <= 8 * mu + 24;     // (workgroup-uniform)
+    const uint32_t mu = msm_lane_entries(nc);
+    const bool owned = OWNED && FINE * 4 == MSM_THREADS && msm_task_owned(max_cnt, mu);     // (workgroup-uniform)
     if (tid <= FINE) meta[tid] = start[tid];
     if (tid == 0) meta[FINE + 1] = nc | (owned ? TASK_OWNED_BIT : 0u);
     if (wave_hot) {
@@ -150,7 +150,7 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
         //     addition reads while the packed words of the next gather arrive, cost eight instructions an iteration;
         //   - the bucket of the current run and where the run began are not kept in registers: a flush reads the bucket back from the
         //     entry before it (i == bend > lo, so there is one), and "the run began at lo" is the flag `first_run`.
-        const uint32_t lo = tid * mu < nc ? tid * mu : nc, hi = lo + mu < nc ? lo + mu : nc;
+        const uint32_t lo = msm_lane_lo(tid, mu, nc), hi = msm_lane_hi(lo, mu, nc);
         if (lo >= hi) return;
         uint32_t en = sorted[lo];
         G1Affine pt = load_affine(point_of(en));
@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(MSM_THREADS, MINW) msm_accumulate(const G1Affi
     uint32_t lo, hi;
     if (own) { lo = start[tid >> 2] + (tid & 3u); hi = start[(tid >> 2) + 1]; }
     else {
-        lo = tid * mu < nc ? tid * mu : nc; hi = lo + mu < nc ? lo + mu : nc;
+        lo = msm_lane_lo(tid, mu, nc); hi = msm_lane_hi(lo, mu, nc);
         if (lo >= hi) return;
     }
     uint32_t en = 0, b = tid >> 2, bend = 0xffffffffu, run_start = lo;

@@ -8,6 +8,8 @@
 //   msm_plan_fallback  the re-run of a short commitment whose bucket lists overflowed (msm_finish_batch)
 //   msm_plan_call      one call of plk_msm_g1 / _dev / _partial_dev: piece length, pieces in flight, number of pieces
 //   msm_plan_bases_pass / msm_plan_bases_call   the same two for caller-supplied bases (plk_msm_g1_bases*): no key, no table
+//   "the bucket schedule"   the integer rules INSIDE the kernels (slices of a bin, entries per lane, owned tasks, the span of a bucket, folding
+//                      a bin's tasks): constexpr, called by the kernels and by tests/host/msm_bucket_cases_check.cpp alike
 // msm.hip's host side computes a plan, then reserves, launches and records; it decides nothing.
 #pragma once
 #include <stdint.h>
@@ -69,6 +71,51 @@ constexpr uint64_t MSM_PIPELINE_MIN_TERMS = 1ull << 23, MSM_PIPELINE_PIECE = 1ul
 constexpr uint32_t THREADS_LOG = 8;
 static_assert((1u << THREADS_LOG) == MSM_THREADS, "THREADS_LOG");
 constexpr uint32_t WS_BIT_ROLES = THREADS_LOG, WS_FIRST_F_ROLE = 1 + WS_BIT_ROLES;
+
+// ---------------------------------------------------------------------------------------------- the bucket schedule
+// The integer rules that decide which code a bucket takes between the scan of the bins and the bucket reduction.  constexpr, so the kernels
+// (msm_scan_bins, msm_accumulate, msm_fold_hot, msm_task_reduce, msm_task_reduce_quad, msm_bin_fold) and a stand-alone host program
+// (tests/host/msm_bucket_cases_check.cpp) evaluate the SAME text: a threshold has one copy, and a case table that sits on it is checked
+// on the CPU (tests/test_msm_bucket_cases_host.py) before the GPU runs it (tests/test_gpu_msm_bucket_edges.py).
+//
+// (MSM_RULE: inlined before anything else is optimised, so a kernel that calls a rule compiles to the instructions of the expression written out.)
+#define MSM_RULE constexpr __attribute__((always_inline))
+// A bin of `count` entries becomes k = ceil(count / TASK_MAX) tasks (msm_scan_bins), cut into k EQUAL slices of ceil(count / k) entries, the
+// last one shorter (head of msm_accumulate).  [bs, be) is the bin's range in the entry array.
+MSM_RULE uint32_t msm_bin_tasks(uint32_t count) { return (count + TASK_MAX - 1) / TASK_MAX; }
+MSM_RULE uint32_t msm_slice_per(uint32_t count, uint32_t k) { return (count + k - 1) / k; }
+MSM_RULE uint32_t msm_slice_begin(uint32_t bs, uint32_t be, uint32_t per, uint32_t slice) { return bs + slice * per < be ? bs + slice * per : be; }
+MSM_RULE uint32_t msm_slice_end(uint32_t s, uint32_t be, uint32_t per) { return (s + per < be) ? s + per : be; }
+MSM_RULE uint32_t msm_slice_len(uint32_t count, uint32_t k, uint32_t slice) {
+    return msm_slice_end(msm_slice_begin(0, count, msm_slice_per(count, k), slice), count, msm_slice_per(count, k)) - msm_slice_begin(0, count, msm_slice_per(count, k), slice);
+}
+// The sorted slice of nc entries is cut into MSM_THREADS equal pieces of mu entries: lane `tid` takes [lo, hi); lanes with lo >= hi leave
+// early and the last live lane has a short piece.  (msm_fold_hot, msm_task_reduce and msm_task_reduce_quad recompute mu from the task's
+// meta with msm_lane_entries' expression written out — see the note above bucket_span in msm.hip; a change here is a change there.)
+MSM_RULE uint32_t msm_lane_entries(uint32_t nc) { return (nc + MSM_THREADS - 1) / MSM_THREADS; }
+MSM_RULE uint32_t msm_lane_lo(uint32_t tid, uint32_t mu, uint32_t nc) { return tid * mu < nc ? tid * mu : nc; }
+MSM_RULE uint32_t msm_lane_hi(uint32_t lo, uint32_t mu, uint32_t nc) { return lo + mu < nc ? lo + mu : nc; }
+// A task of the owned build (commitments of <= MSM_OWNED_MAX terms) is OWNED — four lanes per bucket, one PRIMARY sum per bucket,
+// TASK_OWNED_BIT in its meta — iff its fullest bucket holds at most MSM_OWNED_SPAN * mu + MSM_OWNED_SLACK entries.
+constexpr uint32_t MSM_OWNED_SPAN = 8, MSM_OWNED_SLACK = 24;
+MSM_RULE bool msm_task_owned(uint32_t max_cnt, uint32_t mu) { return max_cnt <= MSM_OWNED_SPAN * mu + MSM_OWNED_SLACK; }
+// A bucket [s0, e0) of the sorted slice, s0 < e0, lies in the pieces of lanes tf .. tl.  tf == tl: one PRIMARY sum.  Otherwise the TAIL of
+// lane tf and the HEADs of lanes tf + 1 .. tl, which the reduction walks when tl - tf <= HOT_SPAN and msm_fold_hot folds into the bucket's
+// PRIMARY slot beforehand when the span is larger.
+constexpr uint32_t HOT_SPAN = 8;
+MSM_RULE uint32_t msm_bucket_first_lane(uint32_t s0, uint32_t mu) { return s0 / mu; }
+MSM_RULE uint32_t msm_bucket_last_lane(uint32_t e0, uint32_t mu) { return (e0 - 1) / mu; }
+MSM_RULE uint32_t msm_bucket_span(uint32_t s0, uint32_t e0, uint32_t mu) { return e0 > s0 ? msm_bucket_last_lane(e0, mu) - msm_bucket_first_lane(s0, mu) : 0; }
+MSM_RULE bool msm_span_folded(uint32_t span) { return span > HOT_SPAN; }
+enum : uint32_t { MSM_BUCKET_EMPTY = 0, MSM_BUCKET_PRIMARY = 1, MSM_BUCKET_WALKED = 2, MSM_BUCKET_FOLDED = 3 };
+MSM_RULE uint32_t msm_bucket_class(uint32_t s0, uint32_t e0, uint32_t mu) {
+    return e0 <= s0 ? MSM_BUCKET_EMPTY
+                    : msm_bucket_first_lane(s0, mu) == msm_bucket_last_lane(e0, mu) ? MSM_BUCKET_PRIMARY
+                    : msm_span_folded(msm_bucket_span(s0, e0, mu)) ? MSM_BUCKET_FOLDED : MSM_BUCKET_WALKED;
+}
+// msm_bin_fold adds up the task sums of a bin of MORE than BIN_FOLD_MIN tasks; smaller bins are left to msm_window_sums_quad.
+constexpr uint32_t BIN_FOLD_MIN = 4;
+MSM_RULE bool msm_bin_folded(uint32_t tasks) { return tasks > BIN_FOLD_MIN; }
 
 // record sizes of the device types the buffers hold (msm_shape.h asserts them against the types)
 constexpr size_t MSM_BYTES_FR = 32, MSM_BYTES_AFFINE = 64, MSM_BYTES_XYZZ = 128, MSM_BYTES_XYZZW = 144;

@@ -13,6 +13,10 @@ naive / pipeline switch (4095 / 4096), both ends of each window width (2^17 - 1 
 srs_check_points_dev has plk_srs_check itself as its referee: the same points uploaded as the key of another context must give the same
 (valid, bad_index) under the same seed.  The refused keys are built as in tests/test_gpu_key_check.py.
 
+A call of more than 2^24 terms runs several passes, each with its own offset into the scalars and the bases: 2^24 + 4097 terms, built on the
+device so that a pass which ignored either offset reads other points or other scalars; the checked call names a refused base as
+offset + index, before and behind the seam, and the batch entry point refuses the length.
+
 Checked bases "at 256 and 257 together": a vector of 257 terms has no index 257, so there the pair is 255 and 256 (it straddles the block
 edge of the front kernel all the same); at 4096 terms it is 256 and 257."""
 import ctypes
@@ -367,6 +371,76 @@ def test_checked_bases(ctx, powers, n, kind):
                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(bad), None)
     assert rc == 0 and bad.value == NONE and not np.all(out == PATTERN)
     _assert_shape(ctx, n, 1, (n, kind, "unchecked"))
+
+
+# ------------------------------------------------------------------------------------------------ two passes
+def test_two_passes_with_their_own_offsets(powers):
+    """2^24 + 4097 terms: a pass of 2^24 and one of 4097 (the pipeline, not the naive kernel), each with its own offset into the scalars and
+    the bases.  Everything is built on the device: the first pass's bases are P_0 .. P_65535 tiled 256 times under u in the even and w in
+    the odd blocks, the tail is P_1000 .. P_5096 under v — a pass that ignored its base offset would read P_0 .. instead of P_1000 .., one
+    that ignored its scalar offset u instead of v.  Expected: (128 (u(42) + w(42)) + 42^1000 v(42)) G.  About 2.6 GiB of device memory."""
+    import torch
+    import plonkit_amd as pa
+    L = pa.lib()
+    BLOCK, TILES, FIRST, TAIL, SHIFT = 1 << 16, 256, 1 << 24, 4097, 1000
+    n = FIRST + TAIL
+    u, w, v = scalars("uniform", BLOCK, 71), scalars("uniform", BLOCK, 73), scalars("uniform", TAIL, 79)
+    total = (128 * (ol.poly_eval(u, 42) + ol.poly_eval(w, 42)) + pow(42, SHIFT, R_MOD) * ol.poly_eval(v, 42)) % R_MOD
+    want = ol.g1_mul(ol.g1_generator(), total)
+    d_bases = torch.empty((n, 8), dtype=torch.int64, device="cuda:0")
+    d_bases[:FIRST].view(TILES, BLOCK, 8).copy_(_dev(powers[:BLOCK]))
+    d_bases[FIRST:].copy_(_dev(powers[SHIFT:SHIFT + TAIL]))
+    d_s = torch.empty((n, 4), dtype=torch.int64, device="cuda:0")
+    pairs = d_s[:FIRST].view(TILES // 2, 2, BLOCK, 4)
+    pairs[:, 0].copy_(_dev(u))
+    pairs[:, 1].copy_(_dev(w))
+    d_s[FIRST:].copy_(_dev(v))
+    torch.cuda.synchronize()
+    c = pa.Context(0)
+    try:
+        def good(check):
+            got = c.msm_bases_dev(d_bases, d_s, n, check=check)
+            shape, last = c.msm_last_shape(), expected_shape(TAIL, 1)               # the record of the last pass, and of the call
+            last.update(pieces=2, piece_terms=FIRST)
+            assert shape == last, {k: (shape[k], last[k]) for k in FIELDS if shape[k] != last[k]}
+            assert np.array_equal(got, want), "check=%s" % check
+
+        def spoil(index, source):
+            row = np.array(powers[source], copy=True)
+            assert row.any()
+            row[4:] = _raw_add(row[4:], 1)                                          # y + 1: off the curve
+            d_bases[index].copy_(_dev(row))
+
+        def mend(index, source):
+            d_bases[index].copy_(_dev(powers[source]))
+
+        good(False)
+        good(True)
+        before, after = FIRST - 1, FIRST + 5                                        # the last base of the first pass, the sixth of the second
+        src = {before: BLOCK - 1, after: SHIFT + 5}
+        for k, (bad, named) in enumerate((((after,), after), ((before,), before), ((before, after), before))):
+            for i in bad:
+                spoil(i, src[i])
+            with pytest.raises(pa.PlkError) as err:
+                c.msm_bases_dev(d_bases, d_s, n, check=True)
+            assert err.value.code == ERR_FORMAT and err.value.bad_index == named, (bad, err.value.bad_index)
+            for i in bad:
+                mend(i, src[i])
+            good(k != 1)
+        # the batch entry point does not split: refused before anything is launched
+        shape = c.msm_last_shape()
+        out, bad = np.full((2, 8), PATTERN, dtype=np.uint64), ctypes.c_uint64(5)
+        ptrs = (ctypes.c_void_p * 2)(d_s.data_ptr(), d_s.data_ptr())
+        rc = L.plk_msm_g1_bases_batch_dev(c._h, ctypes.c_void_p(d_bases.data_ptr()), ptrs, ctypes.c_uint32(2), ctypes.c_uint64(n), ctypes.c_uint32(0),
+                                          out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(bad), None)
+        assert rc == ERR_SIZE and np.all(out == PATTERN) and bad.value == NONE and c.msm_last_shape() == shape
+        with pytest.raises(pa.PlkError) as err:
+            c.msm_bases_batch_dev(d_bases, [d_s, d_s], n, check=True)
+        assert err.value.code == ERR_SIZE and c.msm_last_shape() == shape
+    finally:
+        c.close()
+        del d_bases, d_s, pairs
+        torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------------------------------------ the key check of points that are no key
