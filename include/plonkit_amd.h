@@ -466,6 +466,64 @@ void plk_transcript_absorb_g1(plk_transcript *t, const plk_g1_affine *p);
 void plk_transcript_challenge(plk_transcript *t, plk_fr *out);
 void plk_keccak256(const uint8_t *in, uint64_t len, uint8_t out[32]);
 
+/* ---- a transcript of the CALLER's: the `T: Transcript<Fr>` of prove_by_steps::<_, _, T> and verifier::verify::<_, _, T> as a table of
+ *      callbacks (src/plonk.rs:160-169 and 198-204: the "rescue" arms, whose RescueTranscriptForRNS lives in franklin-crypto).  THIS LIBRARY
+ *      HOLDS NO HASH BUT KECCAK and gains none here: nothing in the rounds depends on which hash the transcript uses, so a host that owns a
+ *      correct transcript hands it over and the prover and the host verifier draw their challenges from it.  With no table set everything
+ *      runs the built-in RollingKeccakTranscript exactly as before.
+ *   The table.    begin = Transcript::new (or new_from_params: `user` carries the parameters) and leaves the new transcript in *state;
+ *                 absorb_fr = commit_field_element; absorb_g1 = commit_fe(x), commit_fe(y) — both coordinates in one call, the point at
+ *                 infinity arrives as (0, 0); challenge = get_challenge; end releases the state.  Elements cross as everywhere in this ABI:
+ *                 ff_ce's in-memory Montgomery Fr, x ‖ y Montgomery Fq — a Rust callback reinterprets them, no conversion.  The table is
+ *                 COPIED when it is handed over (`user` and the functions must stay valid, the struct need not).  All five functions are
+ *                 required (a null one: PLK_ERR_ARG); unknown flag bits: PLK_ERR_ARG.
+ *   Order.        The calls follow prove_by_steps: begin; the public inputs (absorb_fr each); the 4 wire commitments; challenge beta,
+ *                 challenge gamma; the grand-product commitment; challenge alpha; the 4 quotient commitments; challenge z; the 11 values
+ *                 a b c d at z, d at z omega, sigma_1..3 at z, t(z), r(z), z(z omega); challenge v; — the prover stops here: end.  The
+ *                 verifier goes on: W_z, W_z_omega, challenge u, end.  With one public input that is 27 calls for the prover, begin included and
+ *                 end not, and 30 for the verifier.
+ *   Failure.      A callback returns 0 for success.  Anything else ends the library call with PLK_ERR_IO and words that name the callback
+ *                 and its position ("... the transcript's absorb_g1 callback (call 3 after begin) returned -7").  A challenge whose limbs
+ *                 are not below r is refused with PLK_ERR_ARG before any arithmetic, on the host or the device, consumes it.  After the
+ *                 first failure no callback but end is called.  EVERY SUCCESSFUL begin IS FOLLOWED BY EXACTLY ONE end, on every way out:
+ *                 an unsatisfied witness, a HIP error, a refused challenge, a failed callback.  (A begin that fails gets no end.)
+ *                 The prover's own refusals of a challenge keep their code and words whatever the transcript: "challenge z = 0",
+ *                 "challenge z = 1", "grand product denominator vanished ..." — PLK_ERR_UNSAT, the context stays usable; the verifier's
+ *                 z^N = 1 stays a verdict (*valid = 0).
+ *   Threads.      The prover and plk_verify_with / plk_verify_terms_with call back on the calling thread, at the points where the host
+ *                 already waits for a commitment; launches, streams and the background stream are what they are under Keccak.
+ *                 plk_verify_many_with runs begin .. end of DIFFERENT proofs from its up to 16 host threads at once when the table's
+ *                 flags hold PLK_TRANSCRIPT_CONCURRENT, and from the calling thread only, one proof after the other, without it.
+ *   plk_ctx_set_transcript.  Per context, like the key: every proving entry point of the context (plk_prove, plk_prove_witness, _witness_dev,
+ *                 _wtns, plk_prove_assembled, _assembled_dev) then takes its challenges from the table; plk_prove_trace follows the last proof
+ *                 as before.  NULL restores Keccak.  Several contexts of one device may hold different tables; in replicate mode each rank's
+ *                 context calls its own.  Both key forms (monomial only, and with a Lagrange-form key) give the same bytes under any
+ *                 transcript.
+ *   plk_verify_with, plk_verify_terms_with.  plk_verify_ex and plk_verify_terms under the caller's transcript (ops == NULL: exactly those
+ *                 calls): same parser, same refusals, same words, and a refused key or proof never reaches begin.
+ *   plk_verify_many_with.  plk_verify_many with its host front end running the caller's transcript per proof; the kernels are the same.
+ *                 verdict[i] is what plk_verify_with says about proof i (PLK_VERDICT_MALFORMED for a proof it refuses as malformed); a
+ *                 failed callback or a refused challenge ends the whole call with that proof's error, "proof <i>: ..." for the lowest
+ *                 such i, and launches nothing more.
+ *   NOT COVERED.  plk_verify_many_packed, plk_verify_many_dev, plk_verify_front_dev and the plk_verify_mixed* family run Keccak inside their
+ *                 front kernel and take no table; a foreign transcript on the device is out of scope.  The `plonkit` binary keeps refusing
+ *                 `-t rescue` (exit 101): it has no transcript to hand over.                                                              */
+#define PLK_TRANSCRIPT_CONCURRENT 1u   /* begin .. end of different proofs may run on several threads at once (plk_verify_many_with) */
+typedef struct plk_transcript_ops {
+    void    *user;
+    int32_t (*begin)(void *user, void **state);
+    int32_t (*absorb_fr)(void *state, const plk_fr *v);
+    int32_t (*absorb_g1)(void *state, const plk_g1_affine *p);
+    int32_t (*challenge)(void *state, plk_fr *out);
+    void    (*end)(void *user, void *state);
+    uint32_t flags;
+} plk_transcript_ops;
+int32_t plk_ctx_set_transcript(plk_ctx *ctx, const plk_transcript_ops *ops /* NULL: the built-in Keccak transcript */);
+int32_t plk_verify_with(const uint8_t *vk, uint64_t vk_len, const uint8_t *proof, uint64_t proof_len, uint32_t flags,
+                        const plk_transcript_ops *ops, int32_t *valid);
+int32_t plk_verify_terms_with(const uint8_t *vk, uint64_t vk_len, const uint8_t *proof, uint64_t proof_len, uint32_t flags,
+                              const plk_transcript_ops *ops, plk_g1_affine points[25], plk_fr scalars[25], int32_t *early);
+
 /* ---- verifier (pure CPU, as in the reference): verifier::verify::<E,P,RollingKeccakTranscript>(&proof,&vk,None)
  *      behind plonk::verify (src/plonk.rs:189-210; CLI src/bin/main.rs:425-437).  Takes the bytes of vk.bin and
  *      proof.bin; *valid = 1/0.  Malformed files (short, point off the curve, scalar >= r)
@@ -555,6 +613,10 @@ typedef struct plk_vk plk_vk;
 int32_t plk_vk_load(plk_ctx *ctx, const uint8_t *vk, uint64_t vk_len, uint32_t flags, plk_vk **out);
 void plk_vk_free(plk_vk *vk);
 int32_t plk_verify_many(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict, uint64_t *first_bad);
+/* plk_verify_many under the caller's transcript (see "a transcript of the CALLER's" above; ops == NULL: exactly plk_verify_many).  The packed,
+ * _dev, front and mixed calls below run Keccak in their front kernel and take no table.                                                 */
+int32_t plk_verify_many_with(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count,
+                             const plk_transcript_ops *ops, uint8_t *verdict, uint64_t *first_bad);
 int32_t plk_verify_many_last_ms(plk_ctx *ctx, float out_ms[6]);
 int32_t plk_pairing_check_many_dev(plk_ctx *ctx, const void *a_dev, const void *b_dev, uint64_t n, const uint8_t g2[256], void *verdict_dev, void *stream);
 int32_t plk_verify_terms(const uint8_t *vk, uint64_t vk_len, const uint8_t *proof, uint64_t proof_len, uint32_t flags,

@@ -134,6 +134,99 @@ class _CopyReportStruct(ctypes.Structure):
                           (int(self.col2), int(self.row2)) if self.kind == COPY_BROKEN else None)
 
 
+TRANSCRIPT_CONCURRENT = 1                                             # PLK_TRANSCRIPT_CONCURRENT (never set by the Python tables)
+
+
+class TranscriptOps:
+    """A Fiat-Shamir transcript of the caller's (plk_transcript_ops): subclass it and override begin().  begin() returns a fresh
+    transcript object with absorb_fr(bytes32), absorb_g1(bytes64) and challenge() -> bytes32; the bytes are the ABI's in-memory
+    elements (4 / 8 little-endian u64 limbs, Montgomery form; the point at infinity is 64 zero bytes).  If that object has an
+    end() method it is called once when the library is done with it, on every way out.  The call order is prove_by_steps's
+    (include/plonkit_amd.h).  An exception raised in any of them ends the library call and is re-raised from the
+    Python call that made it."""
+
+    def begin(self):
+        raise NotImplementedError("TranscriptOps.begin")
+
+
+class _TranscriptOpsStruct(ctypes.Structure):
+    """plk_transcript_ops (include/plonkit_amd.h)"""
+    _BEGIN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p))
+    _ABSORB = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p)
+    _END = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
+    _fields_ = [("user", ctypes.c_void_p), ("begin", _BEGIN), ("absorb_fr", _ABSORB), ("absorb_g1", _ABSORB), ("challenge", _ABSORB),
+                ("end", _END), ("flags", ctypes.c_uint32)]
+
+
+class _TranscriptTable:
+    """The ctypes trampolines around a TranscriptOps object.  Whoever hands `.struct` to the library keeps this object alive for as
+    long as the library may call back.  An exception inside a callback is caught here (it cannot cross the C frames), makes the
+    callback return nonzero, and is raised again by reraise() once the C call is back."""
+
+    def __init__(self, obj):
+        if not callable(getattr(obj, "begin", None)):
+            raise TypeError("a transcript must have a begin() method (see TranscriptOps), got %r" % (obj,))
+        self.obj = obj
+        self.error = None
+        self._live = {}                                               # state handle -> the object begin() returned
+        self._next = 1
+        S = _TranscriptOpsStruct
+        self._keep = (S._BEGIN(self._begin), S._ABSORB(self._absorb_fr), S._ABSORB(self._absorb_g1), S._ABSORB(self._challenge), S._END(self._end))
+        self.struct = S(None, *self._keep, 0)
+
+    def _guard(self, fn):
+        try:
+            fn()
+            return 0
+        except BaseException as e:                                    # noqa: B902 — nothing may unwind into the C frames
+            if self.error is None:
+                self.error = e
+            return -1
+
+    def _begin(self, user, state_out):
+        def run():
+            t = self.obj.begin()
+            handle, self._next = self._next, self._next + 1
+            self._live[handle] = t
+            state_out[0] = handle
+        return self._guard(run)
+
+    def _absorb_fr(self, state, ptr):
+        return self._guard(lambda: self._live[state].absorb_fr(ctypes.string_at(ptr, 32)))
+
+    def _absorb_g1(self, state, ptr):
+        return self._guard(lambda: self._live[state].absorb_g1(ctypes.string_at(ptr, 64)))
+
+    def _challenge(self, state, out):
+        def run():
+            c = bytes(self._live[state].challenge())
+            if len(c) != 32:
+                raise ValueError("a transcript's challenge() must return 32 bytes, got %d" % len(c))
+            ctypes.memmove(out, c, 32)
+        return self._guard(run)
+
+    def _end(self, user, state):
+        t = self._live.pop(state, None)
+        if callable(getattr(t, "end", None)):
+            self._guard(t.end)
+
+    def reraise(self):
+        e, self.error = self.error, None
+        if e is not None:
+            raise e
+
+
+def _table_of(transcript):
+    return None if transcript is None else _TranscriptTable(transcript)
+
+
+def _finish(rc, table):
+    """the end of a C call that took a transcript table: the callback's own exception first, then the library's error"""
+    if table is not None:
+        table.reraise()
+    _check(rc)
+
+
 class Context:
     """plk_ctx: one GPU.  Mirrors where the reference builds `Worker::new()` (src/plonk.rs:41,47,183)."""
 
@@ -155,6 +248,16 @@ class Context:
 
     def synchronize(self):
         _check(lib().plk_synchronize(self._h))
+
+    def set_transcript(self, transcript):
+        """plk_ctx_set_transcript: every proof of this context takes its challenges from `transcript` (a TranscriptOps; None: the
+        built-in Keccak transcript again).  The trampolines live as long as the context holds them."""
+        table = _table_of(transcript)
+        _check(lib().plk_ctx_set_transcript(self._h, ctypes.byref(table.struct) if table is not None else None))
+        self._transcript = table
+
+    def _finish_prove(self, rc):
+        _finish(rc, getattr(self, "_transcript", None))
 
     # ---- SRS
     def srs_upload(self, bases):
@@ -746,7 +849,7 @@ class SetupForProver:
         return out.raw[:n.value]
 
     def prove(self, circuit, ctx=None):
-        """proof.bin bytes (keccak transcript, monomial key — src/plonk.rs:152-159).  `ctx`: another context on the same device
+        """proof.bin bytes (the context's transcript: Keccak unless Context.set_transcript gave another — src/plonk.rs:152-159).  `ctx`: another context on the same device
         (one per host thread: several proofs of this setup may be in flight at once; ctypes releases the GIL for the call)"""
         h = (ctx or self.ctx)._h
         cap = 1 << 16
@@ -757,7 +860,7 @@ class SetupForProver:
             cap = n.value
             out = ctypes.create_string_buffer(cap)
             rc = lib().plk_prove(h, self._h, circuit._h, out, ctypes.c_uint64(cap), ctypes.byref(n))
-        _check(rc)
+        (ctx or self.ctx)._finish_prove(rc)
         return out.raw[:n.value]
 
     # ---- assembled input (plk_setup_from_polynomials / plk_prove_assembled*): bellman's SetupPolynomials and the prover assembly's
@@ -781,7 +884,7 @@ class SetupForProver:
                                                 ctypes.byref(self._h)))
         return self
 
-    def _prove_into(self, call):
+    def _prove_into(self, call, ctx=None):
         cap = 1 << 16
         out = ctypes.create_string_buffer(cap)
         n = ctypes.c_uint64(0)
@@ -790,7 +893,7 @@ class SetupForProver:
             cap = n.value
             out = ctypes.create_string_buffer(cap)
             rc = call(out, cap, n)
-        _check(rc)
+        (ctx or self.ctx)._finish_prove(rc)
         return out.raw[:n.value]
 
     def prove_assembled(self, columns, ctx=None):
@@ -803,7 +906,7 @@ class SetupForProver:
         arr = (ctypes.c_void_p * 4)(*[_np(c) for c in cols])
         h = (ctx or self.ctx)._h
         return self._prove_into(lambda out, cap, n: lib().plk_prove_assembled(h, self._h, arr, ctypes.c_uint64(rows), out,
-                                                                              ctypes.c_uint64(cap), ctypes.byref(n)))
+                                                                              ctypes.c_uint64(cap), ctypes.byref(n)), ctx)
 
     def prove_assembled_dev(self, ptrs, rows, stream=None, ctx=None):
         """the same from columns already on the device (4 torch tensors / ints, rows x 32 bytes each), ordered after `stream`"""
@@ -813,7 +916,7 @@ class SetupForProver:
         h = (ctx or self.ctx)._h
         st = _stream(stream)
         return self._prove_into(lambda out, cap, n: lib().plk_prove_assembled_dev(h, self._h, arr, ctypes.c_uint64(rows), out,
-                                                                                  ctypes.c_uint64(cap), ctypes.byref(n), st))
+                                                                                  ctypes.c_uint64(cap), ctypes.byref(n), st), ctx)
 
     # ---- which copy constraint is broken (plk_setup_check_permutation / plk_check_copies*): what to call when prove_assembled says
     #      "copy constraints".  Exact checks, no key needed; every verdict is a CopyReport (kind 0 = all is well)
@@ -860,13 +963,13 @@ class SetupForProver:
         w = _fr_vectors([w], "prove_witness", allow_empty=True)[0]
         h = (ctx or self.ctx)._h
         return self._prove_into(lambda out, cap, n: lib().plk_prove_witness(h, self._h, _np(w), ctypes.c_uint64(w.shape[0]), out,
-                                                                            ctypes.c_uint64(cap), ctypes.byref(n)))
+                                                                            ctypes.c_uint64(cap), ctypes.byref(n)), ctx)
 
     def prove_witness_dev(self, ptr, n, stream=None, ctx=None):
         """the same for n elements already on the device (torch tensor / int), ordered after `stream`"""
         h, st = (ctx or self.ctx)._h, _stream(stream)
         return self._prove_into(lambda out, cap, ln: lib().plk_prove_witness_dev(h, self._h, _devptr(ptr), ctypes.c_uint64(n), out,
-                                                                                 ctypes.c_uint64(cap), ctypes.byref(ln), st))
+                                                                                 ctypes.c_uint64(cap), ctypes.byref(ln), st), ctx)
 
     def prove_wtns(self, data, ctx=None):
         """the same from the bytes of a .wtns file, decoded and range-checked on the device; an element >= r raises PlkError with
@@ -875,7 +978,7 @@ class SetupForProver:
         h, bad = (ctx or self.ctx)._h, ctypes.c_uint64(0)
         try:
             return self._prove_into(lambda out, cap, n: lib().plk_prove_wtns(h, self._h, _np(buf), ctypes.c_uint64(buf.size), out,
-                                                                             ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(bad)))
+                                                                             ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(bad)), ctx)
         except PlkError as e:
             e.bad_index = bad.value if bad.value != 2**64 - 1 else None
             raise
@@ -1006,12 +1109,20 @@ def fr_from_bytes(b):
     return out
 
 
-def verify(vk_bytes, proof_bytes, strict_inputs=None):
+def verify(vk_bytes, proof_bytes, strict_inputs=None, transcript=None):
     """plonk::verify(&vk, &proof, "keccak") (src/plonk.rs:189-210) on the bytes of vk.bin / proof.bin; pure CPU.
     strict_inputs: None = plk_verify (accepts num_inputs = 0 unless PLK_VERIFY_STRICT_INPUTS is set); True / False = plk_verify_ex with /
-    without PLK_VERIFY_STRICT_INPUTS (the Solidity verifier's `num_inputs >= 1`, contrib/template.sol:697)."""
+    without PLK_VERIFY_STRICT_INPUTS (the Solidity verifier's `num_inputs >= 1`, contrib/template.sol:697).
+    transcript: a TranscriptOps — plk_verify_with under the caller's transcript instead of Keccak."""
     valid = ctypes.c_int32(0)
-    if strict_inputs is None:
+    if transcript is not None:
+        if strict_inputs is None:
+            e = os.environ.get("PLK_VERIFY_STRICT_INPUTS", "")
+            strict_inputs = bool(e) and e[0] != "0"
+        table = _TranscriptTable(transcript)
+        _finish(lib().plk_verify_with(bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), bytes(proof_bytes), ctypes.c_uint64(len(proof_bytes)),
+                                      ctypes.c_uint32(1 if strict_inputs else 0), ctypes.byref(table.struct), ctypes.byref(valid)), table)
+    elif strict_inputs is None:
         _check(lib().plk_verify(bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), bytes(proof_bytes), ctypes.c_uint64(len(proof_bytes)), ctypes.byref(valid)))
     else:
         _check(lib().plk_verify_ex(bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), bytes(proof_bytes), ctypes.c_uint64(len(proof_bytes)),
@@ -1032,15 +1143,21 @@ class VerificationKey:
         _check(lib().plk_vk_load(ctx._h, bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), ctypes.c_uint32(1 if strict_inputs else 0), ctypes.byref(self._h)))
         self.first_bad = None
 
-    def verify_many(self, proofs, ctx=None):
-        """numpy uint8 per proof: 1 valid, 0 invalid, 2 malformed; .first_bad = lowest index that is not 1, or None"""
+    def verify_many(self, proofs, ctx=None, transcript=None):
+        """numpy uint8 per proof: 1 valid, 0 invalid, 2 malformed; .first_bad = lowest index that is not 1, or None.
+        transcript: a TranscriptOps — plk_verify_many_with: the host front end runs it per proof, on the calling thread"""
         proofs = [bytes(p) for p in proofs]
         n = len(proofs)
         ptrs = (ctypes.c_char_p * max(n, 1))(*proofs)
         lens = (ctypes.c_uint64 * max(n, 1))(*[len(p) for p in proofs])
         verdict = np.zeros(max(n, 1), dtype=np.uint8)
         first_bad = ctypes.c_uint64(0)
-        _check(lib().plk_verify_many((ctx or self.ctx)._h, self._h, ptrs, lens, ctypes.c_uint64(n), _np(verdict), ctypes.byref(first_bad)))
+        if transcript is not None:
+            table = _TranscriptTable(transcript)
+            _finish(lib().plk_verify_many_with((ctx or self.ctx)._h, self._h, ptrs, lens, ctypes.c_uint64(n), ctypes.byref(table.struct), _np(verdict),
+                                               ctypes.byref(first_bad)), table)
+        else:
+            _check(lib().plk_verify_many((ctx or self.ctx)._h, self._h, ptrs, lens, ctypes.c_uint64(n), _np(verdict), ctypes.byref(first_bad)))
         self.first_bad = None if first_bad.value == 2 ** 64 - 1 else int(first_bad.value)
         return verdict[:n]
 
@@ -1198,14 +1315,21 @@ class VerificationKeySet:
             pass
 
 
-def verify_terms(vk_bytes, proof_bytes, strict_inputs=False):
+def verify_terms(vk_bytes, proof_bytes, strict_inputs=False, transcript=None):
     """plk_verify_terms: (points [25, 8] uint64 Montgomery affine, scalars [25, 4] uint64 Montgomery, early).  pg = sum of terms 0..22,
-    px = terms 23 + 24; early False: already invalid without group arithmetic.  Pure CPU."""
+    px = terms 23 + 24; early False: already invalid without group arithmetic.  Pure CPU.
+    transcript: a TranscriptOps — plk_verify_terms_with under the caller's transcript."""
     pts = np.zeros((25, 8), dtype=np.uint64)
     sc = np.zeros((25, 4), dtype=np.uint64)
     early = ctypes.c_int32(0)
-    _check(lib().plk_verify_terms(bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), bytes(proof_bytes), ctypes.c_uint64(len(proof_bytes)),
-                                  ctypes.c_uint32(1 if strict_inputs else 0), _np(pts), _np(sc), ctypes.byref(early)))
+    if transcript is not None:
+        table = _TranscriptTable(transcript)
+        _finish(lib().plk_verify_terms_with(bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), bytes(proof_bytes), ctypes.c_uint64(len(proof_bytes)),
+                                            ctypes.c_uint32(1 if strict_inputs else 0), ctypes.byref(table.struct), _np(pts), _np(sc),
+                                            ctypes.byref(early)), table)
+    else:
+        _check(lib().plk_verify_terms(bytes(vk_bytes), ctypes.c_uint64(len(vk_bytes)), bytes(proof_bytes), ctypes.c_uint64(len(proof_bytes)),
+                                      ctypes.c_uint32(1 if strict_inputs else 0), _np(pts), _np(sc), ctypes.byref(early)))
     return pts, sc, bool(early.value)
 
 

@@ -433,7 +433,7 @@ static int run(int argc, char **argv) {
     } else if (cmd == "prove") {                                     // src/bin/main.rs:384-424
         Args a = parse(argc, argv, {{"m", "srs_monomial_form"}, {"l", "srs_lagrange_form"}, {"c", "circuit"}, {"w", "witness"},
                                     {"p", "proof"}, {"j", "proofjson"}, {"i", "publicjson"}, {"t", "transcript"}});
-        if (a.get("transcript", "keccak") != "keccak") { fprintf(stderr, "not implemented: transcript '%s' (only keccak; rescue needs franklin-crypto)\n", a.get("transcript").c_str()); return 101; }
+        if (a.get("transcript", "keccak") != "keccak") { fprintf(stderr, "not implemented: transcript '%s' (only keccak; rescue needs franklin-crypto: a host that links it hands its transcript to the library, INTEGRATION.md 3e)\n", a.get("transcript").c_str()); return 101; }
         phase("start");
         const Ranks rk = ranks_from_env();
         std::string wf = a.get("witness", "witness.wtns");
@@ -791,7 +791,7 @@ static int run(int argc, char **argv) {
         // VerifyOpts (src/bin/main.rs:125-137): the key is `-v` / `--verification_key` here, while export-verification-key
         // names its output `--vk` (src/bin/main.rs:186-187); `--vk` is kept as an alias on verify
         Args a = parse(argc, argv, {{"p", "proof"}, {"v", "verification_key|vk"}, {"t", "transcript"}});
-        if (a.get("transcript", "keccak") != "keccak") { fprintf(stderr, "not implemented: transcript '%s' (only keccak; rescue needs franklin-crypto)\n", a.get("transcript").c_str()); return 101; }
+        if (a.get("transcript", "keccak") != "keccak") { fprintf(stderr, "not implemented: transcript '%s' (only keccak; rescue needs franklin-crypto: a host that links it hands its transcript to the library, INTEGRATION.md 3e)\n", a.get("transcript").c_str()); return 101; }
         std::vector<uint8_t> vk = slurp(a.get("verification_key", "vk.bin"), "read vk file err"), pr = slurp(a.get("proof", "proof.bin"), "read proof file err");
         int32_t valid = 0;
         CK("fail to verify proof", plk_verify(vk.data(), vk.size(), pr.data(), pr.size(), &valid));

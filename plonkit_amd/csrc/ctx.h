@@ -123,6 +123,8 @@ struct plk_ctx {
     size_t pinned_cap = 0;
     void *pinned2 = nullptr;                 // pinned staging of the prover's temporaries
     size_t pinned2_cap = 0;
+    plk_transcript_ops tr_ops = {};          // plk_ctx_set_transcript: the caller's Fiat-Shamir transcript for this context's proofs (a copy of the table)
+    bool tr_set = false;                     // false: the built-in RollingKeccak
     std::vector<double> timings;
     // intermediate vectors of the last plk_prove, still resident in prove_ws (plk_prove_trace: test / debugging hook)
     struct Trace { const plk::Fr *ptr[12] = {nullptr}; uint64_t len[12] = {0}; bool valid = false; } trace;

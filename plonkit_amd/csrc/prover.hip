@@ -19,6 +19,7 @@
 #include "poly.h"
 #include "circuit.h"
 #include "keccak.h"
+#include "transcript_ops.h"
 #include "comm.h"
 #include <chrono>
 #include <memory>
@@ -638,10 +639,13 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     PLK_HIP(hipEventSynchronize(ctx->flag_ready));
     PLK_TRY(front_verdict(ctx, S, F));
     PLK_TRY(commit_end(ctx, 4, wire_c));
-    RollingKeccak tr;
+    // the built-in Keccak transcript, or the table of plk_ctx_set_transcript: begin here, end wherever the function is left.  A
+    // callback that failed or a challenge with limbs >= r ends the proof right behind the challenge, before anything consumes it
+    ProofTranscript tr(ctx->tr_set ? &ctx->tr_ops : nullptr, F.who);
     for (const HFr &x : inputs) tr.absorb_fr(x);
     for (int j = 0; j < 4; j++) tr.absorb_g1(wire_c[j]);
     const HFr beta = tr.challenge(), gamma = tr.challenge();
+    PLK_TRY(tr.report());
     lap();                                                                    // [1] round 1
 
     // ---- round 2: grand product z  (z_i = prod_{k<i} num_k / den_k, no per-element inversion:
@@ -710,6 +714,7 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     PLK_TRY(commit_end(ctx, 1, &z_c));
     tr.absorb_g1(z_c);
     const HFr alpha = tr.challenge();
+    PLK_TRY(tr.report());
     lap();                                                                    // [2] round 2
 
     // ---- round 3: quotient on the coset 7*<omega_4N>: 18 x LDE, fused point-wise kernel, coset iNTT(4N)
@@ -793,6 +798,7 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     bg_guard.armed = false;                                   // the quotient consumed everything the background stream produced
     for (int k = 0; k < 4; k++) tr.absorb_g1(t_c[k]);
     const HFr z = tr.challenge();
+    PLK_TRY(tr.report());
     lap();                                                                    // [3] round 3
 
     // ---- round 4: evaluations at z and z*omega, linearisation
@@ -802,6 +808,9 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     // GPU waits for between the rounds
     const HFr l0_den = HFr::from_u64(N) * (z - HFr::one());
     if (l0_den.is_zero()) { set_error("challenge z = 1"); return PLK_ERR_UNSAT; }
+    // any other point of the domain: every verifier refuses z^N = 1 (verify.cpp), so no proof is written for it.  Keccak gets here with
+    // probability N / r; a caller's transcript (plk_ctx_set_transcript) may be made to
+    if (zN == HFr::one()) { set_error("challenge z^N = 1"); return PLK_ERR_UNSAT; }
     const HFr inv_all = (z * zw * l0_den).inv();
     const HFr z_inv = inv_all * zw * l0_den, zw_inv = inv_all * z * l0_den, l0_den_inv = inv_all * z * zw;
     PowTable pts4[4];
@@ -846,6 +855,7 @@ static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, 
     for (int j = 0; j < 3; j++) tr.absorb_fr(sz[j]);
     tr.absorb_fr(tz); tr.absorb_fr(rz); tr.absorb_fr(zzw);
     const HFr v = tr.challenge();
+    PLK_TRY(tr.report());
     lap();                                                                    // [4] round 4
 
     // ---- round 5: opening proofs W_z, W_zw by synthetic division (suffix sums of p_j z^j, times z^-(k+1))
@@ -1227,6 +1237,7 @@ static int32_t prove_assembled_impl(plk_ctx *ctx, const plk_setup *S, const void
     ctx->timings.clear();
     ctx->trace.valid = false;
     ProveFront F;
+    F.who = on_device ? "plk_prove_assembled_dev" : "plk_prove_assembled";
     F.assembled = true;
     F.close_perm = true;
     F.t_prev = now_ms();
@@ -1431,6 +1442,16 @@ static int32_t not_a_worker(plk_ctx *ctx, const char *who) {
 int32_t plk_setup_write_vk(plk_ctx *ctx, const plk_setup *s, const uint8_t g2_bytes[256], uint8_t *out, uint64_t cap, uint64_t *len) {
     PLK_TRY(not_a_worker(ctx, "plk_setup_write_vk"));
     return guarded("plk_setup_write_vk", PLK_ERR_HIP, [&] { return setup_write_vk_impl(ctx, s, g2_bytes, out, cap, len); });
+}
+// the `T: Transcript` of prove_by_steps::<_, _, T> (src/plonk.rs:160-169) for every proof of this context; host state only
+int32_t plk_ctx_set_transcript(plk_ctx *ctx, const plk_transcript_ops *ops) {
+    if (!ctx) { set_error("plk_ctx_set_transcript: null context"); return PLK_ERR_ARG; }
+    if (!ops) { ctx->tr_set = false; ctx->tr_ops = plk_transcript_ops{}; return PLK_OK; }
+    if (!transcript_ops_complete(ops)) { set_error("plk_ctx_set_transcript: the transcript table has a null callback"); return PLK_ERR_ARG; }
+    if (ops->flags & ~(uint32_t)PLK_TRANSCRIPT_CONCURRENT) { set_error("plk_ctx_set_transcript: unknown flag in the transcript table"); return PLK_ERR_ARG; }
+    ctx->tr_ops = *ops;
+    ctx->tr_set = true;
+    return PLK_OK;
 }
 int32_t plk_prove(plk_ctx *ctx, const plk_setup *S, const plk_circuit *c, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
     PLK_TRY(not_a_worker(ctx, "plk_prove"));

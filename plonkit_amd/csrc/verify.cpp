@@ -2,12 +2,13 @@
 // (reference call site src/plonk.rs:189-210, CLI src/bin/main.rs:425-437); the algorithm is the one the
 // reference's Solidity template spells out (contrib/template.sol:445-494 verify_initial, 496-586
 // verify_at_z, 588-689 reconstruct_d, 691-758 verify_commitments) over the file formats of SURVEY.md A.1.
-// Keccak transcript only (`-t keccak`); CPU code in the reference too.
+// The transcript is the built-in Keccak one (`-t keccak`) or the caller's table (transcript_ops.h); CPU code in the reference too.
 #include <cstdlib>
 #include "../../include/plonkit_amd.h"
 #include "keccak.h"
 #include "pairing.h"
 #include "verify_many.h"
+#include "transcript_ops.h"
 #include <string>
 #include <vector>
 
@@ -103,7 +104,10 @@ HFr omega_of(uint32_t log_n) {                                // omega_{2^28} = 
 HJac smul(const HAffine &p, const HFr &k) { uint64_t c[4]; k.to_canonical(c); return jac_mul(jac_from_affine(p), c); }
 HJac smulj(const HJac &p, const HFr &k) { uint64_t c[4]; k.to_canonical(c); return jac_mul(p, c); }
 
-bool verify_keccak(const Vk &vk, const ProofData &P, bool strict_inputs) {
+// Tr: KeccakTranscript (ops unused: the code of the Keccak-only verifier) or ProofTranscript over the caller's table.  *tr_rc / *tr_msg: a
+// failure of the caller's transcript (the result is false then and means nothing)
+template <class Tr> bool verify_keccak(const Vk &vk, const ProofData &P, bool strict_inputs, const plk_transcript_ops *ops = nullptr, int32_t *tr_rc = nullptr,
+                   std::string *tr_msg = nullptr) {
     const uint64_t N = vk.n + 1;
     if (N < 2 || (N & (N - 1)) || N > (1ull << 28)) return false;
     uint32_t log_n = 0; while ((1ull << log_n) < N) log_n++;
@@ -116,14 +120,19 @@ bool verify_keccak(const Vk &vk, const ProofData &P, bool strict_inputs) {
     // legal (num_inputs = 1 = wire ONE only, src/reader.rs:197, src/circom_circuit.rs:78): zero inputs are accepted here.
     if (P.n != vk.n || P.inputs.size() != vk.num_inputs) return false;
     const HFr om = omega_of(log_n), one = HFr::one();
-    RollingKeccak tr;
+    Tr tr(ops, "plk_verify");
+    TranscriptOutcome<Tr> tr_out{tr, tr_rc, tr_msg};
+    (void)tr_out;
     for (const HFr &x : P.inputs) tr.absorb_fr(x);
     for (const HAffine &c : P.wires) tr.absorb_g1(c);
     const HFr beta = tr.challenge(), gamma = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
     tr.absorb_g1(P.grand_product);
     const HFr alpha = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
     for (const HAffine &c : P.quotient) tr.absorb_g1(c);
     const HFr z = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
     HFr zN = z; for (uint32_t i = 0; i < log_n; i++) zN = zN.sqr();
     if (zN == one) return false;
     // L_i(z) = w^i (z^N - 1) / (N (z - w^i)) for the public-input rows
@@ -147,8 +156,10 @@ bool verify_keccak(const Vk &vk, const ProofData &P, bool strict_inputs) {
     for (const HFr &x : sz) tr.absorb_fr(x);
     tr.absorb_fr(P.t_z); tr.absorb_fr(P.r_z); tr.absorb_fr(P.z_zw);
     const HFr v = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
     tr.absorb_g1(P.open_z); tr.absorb_g1(P.open_zw);
     const HFr u = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
 
     // reconstruct_d: the commitment of the linearisation polynomial
     HJac d = jac_from_affine(vk.selectors[5]);
@@ -196,21 +207,27 @@ bool verify_keccak(const Vk &vk, const ProofData &P, bool strict_inputs) {
 // distinct point, so that pg = sum_{k<23} s_k P_k and px = s_23 P_23 + s_24 P_24 can be formed by independent scalar multiplications
 // (verify_many.hip).  Returns false where verify_keccak returns false before any group arithmetic.  verify_keccak keeps its own arithmetic;
 // tests/test_verify_terms_host.py pins the two against each other.
-bool flatten_keccak(const Vk &vk, const ProofData &P, bool strict_inputs, HAffine pts[VERIFY_TERMS], HFr sc[VERIFY_TERMS]) {
+template <class Tr> bool flatten_keccak(const Vk &vk, const ProofData &P, bool strict_inputs, HAffine pts[VERIFY_TERMS], HFr sc[VERIFY_TERMS],
+                    const plk_transcript_ops *ops = nullptr, int32_t *tr_rc = nullptr, std::string *tr_msg = nullptr) {
     const uint64_t N = vk.n + 1;
     if (N < 2 || (N & (N - 1)) || N > (1ull << 28)) return false;
     uint32_t log_n = 0; while ((1ull << log_n) < N) log_n++;
     if (strict_inputs && vk.num_inputs < 1) return false;
     if (P.n != vk.n || P.inputs.size() != vk.num_inputs) return false;
     const HFr om = omega_of(log_n), one = HFr::one();
-    RollingKeccak tr;
+    Tr tr(ops, "plk_verify");
+    TranscriptOutcome<Tr> tr_out{tr, tr_rc, tr_msg};
+    (void)tr_out;
     for (const HFr &x : P.inputs) tr.absorb_fr(x);
     for (const HAffine &c : P.wires) tr.absorb_g1(c);
     const HFr beta = tr.challenge(), gamma = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
     tr.absorb_g1(P.grand_product);
     const HFr alpha = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
     for (const HAffine &c : P.quotient) tr.absorb_g1(c);
     const HFr z = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
     HFr zN = z; for (uint32_t i = 0; i < log_n; i++) zN = zN.sqr();
     if (zN == one) return false;
     std::vector<HFr> lag(vk.num_inputs ? vk.num_inputs : 1);
@@ -232,8 +249,10 @@ bool flatten_keccak(const Vk &vk, const ProofData &P, bool strict_inputs, HAffin
     for (const HFr &x : sz) tr.absorb_fr(x);
     tr.absorb_fr(P.t_z); tr.absorb_fr(P.r_z); tr.absorb_fr(P.z_zw);
     const HFr v = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
     tr.absorb_g1(P.open_z); tr.absorb_g1(P.open_zw);
     const HFr u = tr.challenge();
+    if (tr.status() != PLK_OK) return false;
 
     // points: selectors 0..5, next_step 6, sigma 7..10 | wires 11..14, grand product 15, quotient 16..19, W_z 20, W_zw 21 | G 22 | W_z 23, W_zw 24
     for (int j = 0; j < 6; j++) pts[j] = vk.selectors[j];
@@ -312,36 +331,68 @@ void parsed_vk_front(const ParsedVk *v, uint64_t *n, uint64_t *num_inputs, plk_f
     memcpy(omega, &om, 32);
 }
 int32_t verify_terms_parsed(const ParsedVk *v, const uint8_t *proof, uint64_t len, uint32_t flags, plk_g1_affine points[VERIFY_TERMS],
-                            plk_fr scalars[VERIFY_TERMS], int32_t *early) {
+                            plk_fr scalars[VERIFY_TERMS], int32_t *early, const plk_transcript_ops *ops, std::string *tr_msg) {
     ProofData pr;
     if (!parse_proof(proof, len, &pr)) { set_error("plk_verify: malformed proof"); return PLK_ERR_ARG; }
     HAffine pts[VERIFY_TERMS]; HFr sc[VERIFY_TERMS];
     memset(points, 0, VERIFY_TERMS * sizeof(plk_g1_affine)); memset(scalars, 0, VERIFY_TERMS * sizeof(plk_fr));
-    *early = flatten_keccak(vk_of(v), pr, (flags & PLK_VERIFY_STRICT_INPUTS) != 0, pts, sc) ? 1 : 0;
+    int32_t tr_rc = PLK_OK;
+    const bool strict = (flags & PLK_VERIFY_STRICT_INPUTS) != 0;
+    *early = (ops ? flatten_keccak<ProofTranscript>(vk_of(v), pr, strict, pts, sc, ops, &tr_rc, tr_msg)
+                  : flatten_keccak<KeccakTranscript>(vk_of(v), pr, strict, pts, sc)) ? 1 : 0;
+    if (tr_rc != PLK_OK) { *early = 0; return tr_rc; }
     if (*early) for (int k = 0; k < VERIFY_TERMS; k++) { memcpy(&points[k], &pts[k], 64); memcpy(&scalars[k], &sc[k], 32); }
     return PLK_OK;
 }
 }  // namespace plk
 
-PLK_API int32_t plk_verify_terms(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, uint32_t flags,
-                                 plk_g1_affine points[25], plk_fr scalars[25], int32_t *early) {
+// what plk_verify_with, plk_verify_terms_with and plk_verify_many_with ask of a table before they use it
+static int32_t check_ops(const plk_transcript_ops *ops, const char *who) {
+    if (!ops) return PLK_OK;
+    if (!transcript_ops_complete(ops)) { set_error(std::string(who) + ": the transcript table has a null callback"); return PLK_ERR_ARG; }
+    if (ops->flags & ~(uint32_t)PLK_TRANSCRIPT_CONCURRENT) { set_error(std::string(who) + ": unknown flag in the transcript table"); return PLK_ERR_ARG; }
+    return PLK_OK;
+}
+
+PLK_API int32_t plk_verify_terms_with(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, uint32_t flags,
+                                      const plk_transcript_ops *ops, plk_g1_affine points[25], plk_fr scalars[25], int32_t *early) {
     if (!vk_bytes || !proof_bytes || !points || !scalars || !early) { set_error("plk_verify_terms: null argument"); return PLK_ERR_ARG; }
     if (flags & ~(uint32_t)PLK_VERIFY_STRICT_INPUTS) { set_error("plk_verify_ex: unknown flag"); return PLK_ERR_ARG; }
+    if (const int32_t rc = check_ops(ops, "plk_verify_terms_with")) return rc;
+    const plk_transcript_ops table = ops ? *ops : plk_transcript_ops{};       // the caller's struct is copied, as plk_ctx_set_transcript copies it
     ParsedVk *v = parsed_vk_new(vk_bytes, vk_len);
     if (!v) { set_error("plk_verify: malformed verification key"); return PLK_ERR_ARG; }
-    const int32_t rc = verify_terms_parsed(v, proof_bytes, proof_len, flags, points, scalars, early);
+    std::string tr_msg;
+    const int32_t rc = verify_terms_parsed(v, proof_bytes, proof_len, flags, points, scalars, early, ops ? &table : nullptr, &tr_msg);
+    if (!tr_msg.empty()) set_error(tr_msg);
     parsed_vk_free(v);
     return rc;
 }
 
-PLK_API int32_t plk_verify_ex(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, uint32_t flags, int32_t *valid) {
+PLK_API int32_t plk_verify_terms(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, uint32_t flags,
+                                 plk_g1_affine points[25], plk_fr scalars[25], int32_t *early) {
+    return plk_verify_terms_with(vk_bytes, vk_len, proof_bytes, proof_len, flags, nullptr, points, scalars, early);
+}
+
+PLK_API int32_t plk_verify_with(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, uint32_t flags,
+                                const plk_transcript_ops *ops, int32_t *valid) {
     if (!vk_bytes || !proof_bytes || !valid) { set_error("plk_verify: null argument"); return PLK_ERR_ARG; }
     if (flags & ~(uint32_t)PLK_VERIFY_STRICT_INPUTS) { set_error("plk_verify_ex: unknown flag"); return PLK_ERR_ARG; }
+    if (const int32_t rc = check_ops(ops, "plk_verify_with")) return rc;
+    const plk_transcript_ops table = ops ? *ops : plk_transcript_ops{};
     Vk vk; ProofData pr;
     if (!parse_vk(vk_bytes, vk_len, &vk)) { set_error("plk_verify: malformed verification key"); return PLK_ERR_ARG; }
     if (!parse_proof(proof_bytes, proof_len, &pr)) { set_error("plk_verify: malformed proof"); return PLK_ERR_ARG; }
-    *valid = verify_keccak(vk, pr, (flags & PLK_VERIFY_STRICT_INPUTS) != 0) ? 1 : 0;
+    int32_t tr_rc = PLK_OK; std::string tr_msg;
+    const bool strict = (flags & PLK_VERIFY_STRICT_INPUTS) != 0;
+    const bool ok = ops ? verify_keccak<ProofTranscript>(vk, pr, strict, &table, &tr_rc, &tr_msg) : verify_keccak<KeccakTranscript>(vk, pr, strict);
+    if (tr_rc != PLK_OK) { set_error(tr_msg); return tr_rc; }
+    *valid = ok ? 1 : 0;
     return PLK_OK;
+}
+
+PLK_API int32_t plk_verify_ex(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, uint32_t flags, int32_t *valid) {
+    return plk_verify_with(vk_bytes, vk_len, proof_bytes, proof_len, flags, nullptr, valid);
 }
 
 PLK_API int32_t plk_verify(const uint8_t *vk_bytes, uint64_t vk_len, const uint8_t *proof_bytes, uint64_t proof_len, int32_t *valid) {

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/plonkit_amd.h"
 #include "pairing.h"
+#include <string>
 
 namespace plk {
 
@@ -18,6 +19,8 @@ void parsed_vk_points(const ParsedVk *v, plk_g1_affine fixed[VERIFY_FIXED], host
 void parsed_vk_front(const ParsedVk *v, uint64_t *n, uint64_t *num_inputs, plk_fr non_residues[3], plk_fr *omega);
 // plk_verify_terms on a parsed key; PLK_ERR_ARG "plk_verify: malformed proof" exactly when plk_verify_ex says so
 int32_t verify_terms_parsed(const ParsedVk *v, const uint8_t *proof, uint64_t len, uint32_t flags, plk_g1_affine points[VERIFY_TERMS],
-                            plk_fr scalars[VERIFY_TERMS], int32_t *early);
+                            plk_fr scalars[VERIFY_TERMS], int32_t *early, const plk_transcript_ops *ops = nullptr, std::string *tr_msg = nullptr);
+// ops: the caller's transcript (null: Keccak).  Its failure is the return code, with the words in *tr_msg (not in the calling thread's
+// last-error slot: plk_verify_many_with's workers have none that anybody reads) and *early = 0.
 
 }  // namespace plk

@@ -24,6 +24,7 @@
 #include "fq12_dev.h"
 #include "pairing_table.h"
 #include "verify_many.h"
+#include "transcript_ops.h"
 #include "verify_front.h"
 #include "vkset_dev.h"
 #include "g2_host.h"
@@ -32,6 +33,8 @@
 #include <chrono>
 #include <cstring>
 #include <memory>
+#include <mutex>
+#include <string>
 
 namespace plk {
 
@@ -246,7 +249,10 @@ extern "C" int32_t plk_pairing_check_many_dev(plk_ctx *ctx, const void *a_dev, c
                           ctx->pair_tab.p, st);
 }
 
-static int32_t verify_many_impl(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict) {
+// ops: the caller's transcript for the host front end (plk_verify_many_with), null for Keccak.  Without PLK_TRANSCRIPT_CONCURRENT the front end
+// then stays on the calling thread, one proof after the other.  The kernels do not know the difference.
+static int32_t verify_many_impl(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict,
+                                const plk_transcript_ops *ops) {
     using clk = std::chrono::steady_clock;
     const bool timed = ctx->ev_on;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -271,18 +277,29 @@ static int32_t verify_many_impl(plk_ctx *ctx, const plk_vk *vk, const uint8_t *c
         const auto t0 = clk::now();
         std::vector<plk_g1_affine> all_pts((size_t)cnt * VM_PROOF_PTS);
         std::vector<plk_fr> all_sc((size_t)cnt * VERIFY_TERMS);
+        const unsigned front_threads = ops && !(ops->flags & PLK_TRANSCRIPT_CONCURRENT) ? 1 : 16;
+        std::mutex tr_mu;                                             // a failure of the caller's transcript: the lowest proof that met one ends the call
+        uint64_t tr_bad = UINT64_MAX; int32_t tr_rc = PLK_OK; std::string tr_words;
         parallel_for((size_t)cnt, 1, [&](size_t lo, size_t hi) {
             plk_g1_affine pts[VERIFY_TERMS]; plk_fr sc[VERIFY_TERMS];
+            std::string msg;
             for (size_t i = lo; i < hi; i++) {
                 int32_t early = 0;
-                const int32_t rc = verify_terms_parsed(vk->parsed, proofs[base + i], lens[base + i], vk->flags, pts, sc, &early);
+                if (front_threads == 1 && tr_rc != PLK_OK) break;      // (one thread: nothing else writes tr_rc) no further begin after a failure
+                const int32_t rc = verify_terms_parsed(vk->parsed, proofs[base + i], lens[base + i], vk->flags, pts, sc, &early, ops, &msg);
+                if (rc != PLK_OK && !msg.empty()) {
+                    std::lock_guard<std::mutex> g(tr_mu);
+                    if (base + i < tr_bad) { tr_bad = base + i; tr_rc = rc; tr_words = msg; }
+                    msg.clear(); verdict[base + i] = 0; continue;
+                }
                 if (rc != PLK_OK) { verdict[base + i] = PLK_VERDICT_MALFORMED; continue; }
                 if (!early) { verdict[base + i] = 0; continue; }
                 verdict[base + i] = 0xff;                             // goes to the device
                 memcpy(&all_pts[i * VM_PROOF_PTS], &pts[11], VM_PROOF_PTS * sizeof(plk_g1_affine));
                 memcpy(&all_sc[i * VERIFY_TERMS], sc, sizeof sc);
             }
-        }, 16);
+        }, front_threads);
+        if (tr_rc != PLK_OK) { set_error("plk_verify_many_with: proof " + std::to_string(tr_bad) + ": " + tr_words); return tr_rc; }
         live.clear();
         for (uint64_t i = 0; i < cnt; i++) if (verdict[base + i] == 0xff) live.push_back(i);
         const uint32_t m = (uint32_t)live.size();
@@ -330,7 +347,8 @@ static int32_t verify_many_impl(plk_ctx *ctx, const plk_vk *vk, const uint8_t *c
     return PLK_OK;
 }
 
-extern "C" int32_t plk_verify_many(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict, uint64_t *first_bad) {
+static int32_t verify_many_entry(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, const plk_transcript_ops *ops,
+                                 uint8_t *verdict, uint64_t *first_bad) {
     if (!ctx || !vk || !verdict || !first_bad || (count && (!proofs || !lens))) { set_error("plk_verify_many: null argument"); return PLK_ERR_ARG; }
     for (uint64_t i = 0; i < count; i++) if (!proofs[i]) { set_error("plk_verify_many: null argument"); return PLK_ERR_ARG; }
     if (vk->device != ctx->device) { set_error("plk_verify_many: the verification key was loaded on another device"); return PLK_ERR_ARG; }
@@ -339,11 +357,25 @@ extern "C" int32_t plk_verify_many(plk_ctx *ctx, const plk_vk *vk, const uint8_t
     if (count == 0) return PLK_OK;
     PLK_HIP(hipSetDevice(ctx->device));
     int32_t rc = PLK_ERR_HIP;
-    try { rc = verify_many_impl(ctx, vk, proofs, lens, count, verdict); }
+    try { rc = verify_many_impl(ctx, vk, proofs, lens, count, verdict, ops); }
     catch (const std::exception &e) { set_error(std::string("plk_verify_many: ") + e.what()); return PLK_ERR_ARG; }
     if (rc != PLK_OK) return rc;
     for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
     return PLK_OK;
+}
+
+extern "C" int32_t plk_verify_many(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict, uint64_t *first_bad) {
+    return verify_many_entry(ctx, vk, proofs, lens, count, nullptr, verdict, first_bad);
+}
+
+// plk_verify_many with the host front end under the caller's transcript (verifier::verify::<_, _, T>, src/plonk.rs:198-204, per proof)
+extern "C" int32_t plk_verify_many_with(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count,
+                                        const plk_transcript_ops *ops, uint8_t *verdict, uint64_t *first_bad) {
+    if (!ops) return verify_many_entry(ctx, vk, proofs, lens, count, nullptr, verdict, first_bad);
+    if (!transcript_ops_complete(ops)) { set_error("plk_verify_many_with: the transcript table has a null callback"); return PLK_ERR_ARG; }
+    if (ops->flags & ~(uint32_t)PLK_TRANSCRIPT_CONCURRENT) { set_error("plk_verify_many_with: unknown flag in the transcript table"); return PLK_ERR_ARG; }
+    const plk_transcript_ops table = *ops;
+    return verify_many_entry(ctx, vk, proofs, lens, count, &table, verdict, first_bad);
 }
 
 // ---- the front end on the device: proofs as raw bytes, packed back to back
