@@ -733,7 +733,7 @@ def prove_columns(S: Setup, w_vals, inputs, crs: Crs, return_debug=False) -> Pro
     P.opening_at_z_omega_proof = commit(crs, W_zw)
     if return_debug:
         return P, dict(beta=beta, gamma=gamma, alpha=alpha, z=z, v=v, w_coef=w_coef, z_coef=z_coef, z_vals=z_vals,
-                       t_coef=t_coef, r=r, W_z=W_z, W_zw=W_zw, w_vals=w_vals, setup=S)
+                       t_coef=t_coef, r=r, W_z=W_z, W_zw=W_zw, w_vals=w_vals, setup=S, l0_z=l0_z, fz=fz, fs=fs)
     return P
 
 

@@ -63,7 +63,6 @@ struct EvalArgs {
     Fr *partials;
 };
 
-int32_t gather(Fr *out, const Fr *values, const uint32_t *vars, uint32_t n, hipStream_t s);
 // out[j][i] = copy[j][i] = values[vars[j][i]] for the four wire columns, one launch
 int32_t gather4_dual(Fr *const out[4], Fr *const copy[4], const Fr *values, const uint32_t *const vars[4], uint32_t n, hipStream_t s);
 int32_t sigma_from_index(Fr *out, const uint32_t *packed, uint32_t n, uint32_t log_n, const PowTable &tw, const Fr k[4], hipStream_t s);
@@ -80,14 +79,14 @@ int32_t eval_witness_ops(Fr *values, const void *ops_dev, const void *terms_dev,
 int32_t eval_witness_runs(Fr *values, const void *ops_dev, const void *terms_dev, const void *run_start_dev, uint32_t n_runs, uint32_t n_ops, uint32_t first_tmp, hipStream_t s);
 int32_t perm_terms(const PermArgs &a, hipStream_t s);
 int32_t mul3(Fr *out, const Fr *a, const Fr *b, const Fr &sc, uint32_t n, hipStream_t s);
-// out may alias in.  mult: product scan, else sum; reverse: suffix; exclusive: shifted by one
-// totals: where the block totals live (default: the context's poly_tmp; two scans in flight on two streams need two)
-int32_t scan(plk_ctx *ctx, Fr *out, const Fr *in, uint32_t n, bool mult, bool reverse, bool exclusive, hipStream_t s, DevBuf *totals = nullptr);
+// sum scan; out may alias in.  reverse: suffix; exclusive: shifted by one
+// totals: where the block totals live (nullptr: the context's poly_tmp; two scans in flight on two streams need two)
+int32_t scan(plk_ctx *ctx, Fr *out, const Fr *in, uint32_t n, bool reverse, bool exclusive, hipStream_t s, DevBuf *totals);
 // two product scans of equal length in one launch per phase (the grand product's numerator prefix / denominator suffix)
-// pre0 / pre1 given: the third phase (block prefixes folded in) is left to mul3_blocks; see poly.hip
+// the third phase (block prefixes folded in) is left to mul3_blocks: *pre0 / *pre1 receive the prefixes, or nullptr for one block; see poly.hip
 constexpr uint32_t POLY_SCAN_BLOCK = 2048;   // elements per block of the scans: a scan of n elements has ceil(n / 2048) prefixes, then its grand total
 int32_t scan_pair_mult(plk_ctx *ctx, Fr *out0, const Fr *in0, bool reverse0, bool exclusive0, Fr *out1, const Fr *in1, bool reverse1, bool exclusive1,
-                       uint32_t n, hipStream_t s, const Fr **pre0 = nullptr, const Fr **pre1 = nullptr);
+                       uint32_t n, hipStream_t s, const Fr **pre0, const Fr **pre1);
 int32_t mul3_blocks(Fr *out, const Fr *a, const Fr *b, const Fr *pre_a, const Fr *pre_b, const Fr &sc, uint32_t n, hipStream_t s);
 int32_t quotient(const QuotientArgs &a, hipStream_t s);
 // assembled.hip: the inputs of plk_setup_from_polynomials / plk_prove_assembled*.
@@ -110,8 +109,11 @@ int32_t copy_check(plk_ctx *ctx, const Fr *const sigma[4], uint32_t log_n, const
 // data = the four per-coset coefficient vectors u_k of icoset4cm_dev (u_k at data + k*n) -> the 4n coefficients, natural order, in place;
 // constants in the W domain: i^-1 (i = omega_4) and s_c = 7^(-N c) / 4
 int32_t icoset_combine(Fr *data, uint32_t n, const Fr &iinv_w, const Fr s_w[4], hipStream_t s);
+// the same constants in the external form, c[0] = i^-1 and c[1 + k] = 7^(-N k) / 4 (prover.hip): what a setup caches and what
+// plk_icoset4_coset_major_dev hands to icoset_combine
+void icoset_constants(uint32_t log_n, host::HFr c[5]);
+int32_t icoset_combine_ext(Fr *data, uint32_t n, const host::HFr c[5], hipStream_t s);
 int32_t lincomb(const LinCombArgs &a, hipStream_t s);
-int32_t mul_powers(Fr *out, const Fr *in, const PowTable &t, uint32_t shift, uint32_t n, hipStream_t s);
 int32_t div_finish(Fr *q, const Fr *suffix, const PowTable &zinv, uint32_t n, hipStream_t s);
 int32_t eval_batch(plk_ctx *ctx, EvalArgs a, Fr *results_dev, hipStream_t s);
 // fills a caller-provided 2*POW_TAB table with powers of `base`

@@ -33,11 +33,6 @@ __device__ __forceinline__ FrW9 pow2l_w_(const PowTable &t, uint32_t e) {
 __device__ __forceinline__ void stw(Fr *p, const FrW9 &v) { store_fp(p, pack<FrParams>(v)); }     // v normalised, < 2^256
 
 // ------------------------------------------------------------------ gather / permutation
-__global__ void __launch_bounds__(PT) k_gather(Fr *out, const Fr *values, const uint32_t *vars, uint32_t n) {
-    uint32_t i = blockIdx.x * PT + threadIdx.x;
-    if (i < n) store_fp(out + i, load_fp(values + vars[i]));
-}
-
 // the four wire columns of a proof in ONE launch, each written twice (values for the grand product, a copy that the iNTT turns
 // into coefficients in place): eight launches of ~12 us each were pure launch latency at the head of round 1
 struct Gather4 { Fr *out[4]; Fr *copy[4]; const uint32_t *vars[4]; };
@@ -193,13 +188,10 @@ __device__ __forceinline__ void scan_apply_body(Fr *out, const Fr *tot, uint32_t
 }
 
 template <bool MULT> __global__ void __launch_bounds__(PT) k_scan_apply(Fr *out, const Fr *tot, uint32_t n, int reverse) { scan_apply_body<MULT>(out, tot, n, reverse); }
-template <bool MULT> __global__ void __launch_bounds__(PT) k_scan_apply_pair(ScanPair a, uint32_t n) {
-    scan_apply_body<MULT>(a.out[blockIdx.y], a.tot[blockIdx.y], n, a.reverse[blockIdx.y]);
-}
 
 // two product scans of length n at once: (out0 <- scan of in0, reverse0, exclusive0) and the same for 1
-// pre0 / pre1 (optional): leave the third phase to the consumer (mul3_blocks) — on return *pre points at the scan's nb block prefixes (scan order)
-// followed by its grand total (canonical), valid until the context's next scan; nullptr when the scans fit one block (then they are complete).
+// The third phase is left to the consumer (mul3_blocks): on return *pre points at the scan's nb block prefixes (scan order) followed by its
+// grand total (canonical), valid until the context's next scan; nullptr when the scans fit one block (then they are complete).
 int32_t scan_pair_mult(plk_ctx *ctx, Fr *out0, const Fr *in0, bool reverse0, bool exclusive0, Fr *out1, const Fr *in1, bool reverse1, bool exclusive1,
                        uint32_t n, hipStream_t s, const Fr **pre0, const Fr **pre1) {
     const uint32_t nb = (n + BLOCK_ELEMS - 1) / BLOCK_ELEMS;
@@ -207,35 +199,24 @@ int32_t scan_pair_mult(plk_ctx *ctx, Fr *out0, const Fr *in0, bool reverse0, boo
     ScanPair a;
     a.out[0] = out0; a.in[0] = in0; a.reverse[0] = reverse0 ? 1 : 0; a.exclusive[0] = exclusive0 ? 1 : 0; a.tot[0] = ctx->poly_tmp.as<Fr>();
     a.out[1] = out1; a.in[1] = in1; a.reverse[1] = reverse1 ? 1 : 0; a.exclusive[1] = exclusive1 ? 1 : 0; a.tot[1] = ctx->poly_tmp.as<Fr>() + nb + 1;
-    const bool defer = pre0 && pre1 && nb > 1;
-    if (pre0) *pre0 = defer ? a.tot[0] : nullptr;
-    if (pre1) *pre1 = defer ? a.tot[1] : nullptr;
+    *pre0 = nb > 1 ? a.tot[0] : nullptr;
+    *pre1 = nb > 1 ? a.tot[1] : nullptr;
     hipLaunchKernelGGL(k_scan_local_pair<true>, dim3(nb, 2), dim3(PT), 0, s, a, n);
-    if (nb > 1) {
-        hipLaunchKernelGGL(k_scan_totals_pair<true>, dim3(1, 2), dim3(1024), 0, s, a, nb);
-        if (!defer) hipLaunchKernelGGL(k_scan_apply_pair<true>, dim3(nb, 2), dim3(PT), 0, s, a, n);
-    }
+    if (nb > 1) hipLaunchKernelGGL(k_scan_totals_pair<true>, dim3(1, 2), dim3(1024), 0, s, a, nb);
     PLK_HIP(hipGetLastError());
     return PLK_OK;
 }
 
-int32_t scan(plk_ctx *ctx, Fr *out, const Fr *in, uint32_t n, bool mult, bool reverse, bool exclusive, hipStream_t s, DevBuf *totals) {
+// a sum scan (the one single scan the rounds run: the suffix sums of the division by x - z; the product scans come in pairs, above)
+int32_t scan(plk_ctx *ctx, Fr *out, const Fr *in, uint32_t n, bool reverse, bool exclusive, hipStream_t s, DevBuf *totals) {
     uint32_t nb = (n + BLOCK_ELEMS - 1) / BLOCK_ELEMS;
     DevBuf &tb = totals ? *totals : ctx->poly_tmp;
     PLK_TRY(tb.reserve((size_t)(nb + 1) * sizeof(Fr)));           // nb block totals + the grand total (scan_totals_body)
     Fr *tot = tb.as<Fr>();
-    if (mult) {
-        hipLaunchKernelGGL(k_scan_local<true>, dim3(nb), dim3(PT), 0, s, out, in, tot, n, reverse ? 1 : 0, exclusive ? 1 : 0);
-        if (nb > 1) {
-            hipLaunchKernelGGL(k_scan_totals<true>, dim3(1), dim3(1024), 0, s, tot, nb);
-            hipLaunchKernelGGL(k_scan_apply<true>, dim3(nb), dim3(PT), 0, s, out, (const Fr *)tot, n, reverse ? 1 : 0);
-        }
-    } else {
-        hipLaunchKernelGGL(k_scan_local<false>, dim3(nb), dim3(PT), 0, s, out, in, tot, n, reverse ? 1 : 0, exclusive ? 1 : 0);
-        if (nb > 1) {
-            hipLaunchKernelGGL(k_scan_totals<false>, dim3(1), dim3(1024), 0, s, tot, nb);
-            hipLaunchKernelGGL(k_scan_apply<false>, dim3(nb), dim3(PT), 0, s, out, (const Fr *)tot, n, reverse ? 1 : 0);
-        }
+    hipLaunchKernelGGL(k_scan_local<false>, dim3(nb), dim3(PT), 0, s, out, in, tot, n, reverse ? 1 : 0, exclusive ? 1 : 0);
+    if (nb > 1) {
+        hipLaunchKernelGGL(k_scan_totals<false>, dim3(1), dim3(1024), 0, s, tot, nb);
+        hipLaunchKernelGGL(k_scan_apply<false>, dim3(nb), dim3(PT), 0, s, out, (const Fr *)tot, n, reverse ? 1 : 0);
     }
     PLK_HIP(hipGetLastError());
     return PLK_OK;
@@ -416,14 +397,8 @@ __global__ void __launch_bounds__(PT) k_lincomb(LinCombArgs a) {
         else { acc = addn(acc, mul2addw(pv, ps, v, sk)); pending = false; }
     }
     if (pending) acc = addn(acc, mulw(pv, ps));
-    if (a.times_pow.lo) stw(a.out + i, csub_p(mulw(normw(acc), pow2l_w_(a.times_pow, i))));   // (k_mul_powers folded in)
+    if (a.times_pow.lo) stw(a.out + i, csub_p(mulw(normw(acc), pow2l_w_(a.times_pow, i))));   // times base^i (base by its W-domain power table)
     else stw(a.out + i, reduce_small(acc));                                             // < 16 p here
-}
-
-// out_i = in_i * base^(i + shift)     (base given by its W-domain power table)
-__global__ void __launch_bounds__(PT) k_mul_powers(Fr *out, const Fr *in, PowTable t, uint32_t shift, uint32_t n) {
-    uint32_t i = blockIdx.x * PT + threadIdx.x;
-    if (i < n) stw(out + i, csub_p(mulw(ldw(in + i), pow2l_w_(t, i + shift))));
 }
 
 // q_k = S_{k+1} * zinv^(k+1), q_{n-1} = 0       (synthetic division by (x - z), see prover.hip)
@@ -506,11 +481,6 @@ __global__ void __launch_bounds__(PT) k_check_gates(CheckArgs a, unsigned long l
 // ------------------------------------------------------------------------- launchers
 static inline dim3 grid1(uint32_t n) { return dim3((n + PT - 1) / PT); }
 
-int32_t gather(Fr *out, const Fr *values, const uint32_t *vars, uint32_t n, hipStream_t s) {
-    hipLaunchKernelGGL(k_gather, grid1(n), dim3(PT), 0, s, out, values, vars, n);
-    PLK_HIP(hipGetLastError());
-    return PLK_OK;
-}
 int32_t gather4_dual(Fr *const out[4], Fr *const copy[4], const Fr *values, const uint32_t *const vars[4], uint32_t n, hipStream_t s) {
     Gather4 a;
     for (int j = 0; j < 4; j++) { a.out[j] = out[j]; a.copy[j] = copy[j]; a.vars[j] = vars[j]; }
@@ -572,11 +542,6 @@ int32_t quotient(const QuotientArgs &args, hipStream_t s) {
 }
 int32_t lincomb(const LinCombArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_lincomb, grid1(a.n), dim3(PT), 0, s, a);
-    PLK_HIP(hipGetLastError());
-    return PLK_OK;
-}
-int32_t mul_powers(Fr *out, const Fr *in, const PowTable &t, uint32_t shift, uint32_t n, hipStream_t s) {
-    hipLaunchKernelGGL(k_mul_powers, grid1(n), dim3(PT), 0, s, out, in, t, shift, n);
     PLK_HIP(hipGetLastError());
     return PLK_OK;
 }

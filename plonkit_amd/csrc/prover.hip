@@ -21,8 +21,10 @@
 #include "keccak.h"
 #include "transcript_ops.h"
 #include "comm.h"
+#include "prover_math.h"
 #include <chrono>
 #include <memory>
+#include <optional>
 #include <thread>
 #include <mutex>
 #include <algorithm>
@@ -30,8 +32,6 @@
 
 namespace plk {
 using namespace host;
-
-static const uint64_t NON_RESIDUES[4] = {1, 5, 7, 10};     // k_j (vk.bin stores 5, 7, 10); k_quotient (poly.hip) forms 5x, 7x, 10x by shifts
 
 static inline Fr to_dev(const HFr &h) { Fr f; memcpy(f.l, h.l, 32); return f; }
 int32_t ensure_pinned2(plk_ctx *ctx, size_t bytes);
@@ -42,6 +42,13 @@ static inline double now_ms() { return std::chrono::duration<double, std::milli>
 static HFr host_omega(uint32_t log_n) {
     Fr w = ntt_omega(log_n);
     HFr h; memcpy(h.l, w.l, 32); return h;
+}
+// the combine step of the coset iNTT (poly.h): its constants once, for a setup's cache (round 3) and for plk_icoset4_coset_major_dev
+void icoset_constants(uint32_t log_n, HFr c[5]) { icoset_constants_from(host_omega(2), log_n, c); }
+int32_t icoset_combine_ext(Fr *data, uint32_t n, const HFr c[5], hipStream_t s) {
+    Fr s_w[4];
+    for (int k = 0; k < 4; k++) s_w[k] = to_dev(to_w(c[1 + k]));
+    return icoset_combine(data, n, to_dev(to_w(c[0])), s_w, s);
 }
 
 // KZG commitments of vectors resident on the device: up to 8 over the same SRS prefix share one pass of the MSM
@@ -538,7 +545,18 @@ struct ProveFront {
 // the verdict of the front end's checks, read after round 1 has been enqueued (before any commitment is used)
 static int32_t front_verdict(plk_ctx *ctx, const plk_setup *S, ProveFront &F) {
     const volatile uint32_t *flag = reinterpret_cast<volatile uint32_t *>(ctx->pinned);
-    if (!F.assembled) {
+    if (F.assembled) {
+        if (const uint32_t bad = flag[0]) {
+            std::string which;
+            for (int j = 0; j < 4; j++) if (bad >> j & 1) { which += which.empty() ? "" : ", "; which += "abcd"[j]; }
+            set_error("plk_prove_assembled: column " + which + " holds an element that is not a canonical residue (limbs >= r)");
+            return PLK_ERR_ARG;
+        }
+        if (const uint32_t f = flag[1]) {
+            set_error("must satisfy: the assembled columns fail the gate equation at row " + std::to_string(S->N - f) + " (the lowest failing row)");
+            return PLK_ERR_UNSAT;
+        }
+    } else {
         if (F.wire_check) {
             F.wire_bad = *reinterpret_cast<const volatile uint64_t *>(flag + 2);
             if (F.wire_bad != ~0ull && F.wire_check == 2) { set_error("read witness failed: not in field"); return PLK_ERR_FORMAT; }
@@ -548,18 +566,6 @@ static int32_t front_verdict(plk_ctx *ctx, const plk_setup *S, ProveFront &F) {
             }
         }
         if (flag[0]) { set_error("must satisfy: witness does not satisfy the circuit"); return PLK_ERR_UNSAT; }
-        if (F.inputs_pinned) F.inputs.assign(F.inputs_pinned, F.inputs_pinned + S->num_inputs);
-        return PLK_OK;
-    }
-    if (const uint32_t bad = flag[0]) {
-        std::string which;
-        for (int j = 0; j < 4; j++) if (bad >> j & 1) { which += which.empty() ? "" : ", "; which += "abcd"[j]; }
-        set_error("plk_prove_assembled: column " + which + " holds an element that is not a canonical residue (limbs >= r)");
-        return PLK_ERR_ARG;
-    }
-    if (const uint32_t f = flag[1]) {
-        set_error("must satisfy: the assembled columns fail the gate equation at row " + std::to_string(S->N - f) + " (the lowest failing row)");
-        return PLK_ERR_UNSAT;
     }
     if (F.inputs_pinned) F.inputs.assign(F.inputs_pinned, F.inputs_pinned + S->num_inputs);
     return PLK_OK;
@@ -573,357 +579,383 @@ static void append_copy_report(std::string &msg, const plk_copy_report &r) {
     else if (r.kind == PLK_COPY_NOT_A_LABEL) msg += "; sigma is not a permutation: its value at cell " + cell(r.col, r.row) + " is not a cell label";
 }
 
-// Rounds 1-5 and Proof::write, shared by plk_prove and plk_prove_assembled*: from the wire values a front end left in the workspace.
-static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, ProveFront &F, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
-    auto lap = [&]() { double t = now_ms(); ctx->timings.push_back(t - F.t_prev); F.t_prev = t; };
-    hipStream_t st = ctx->stream;
-    const uint64_t N = S->N, M = 4 * N;
-    const uint32_t log_n = S->log_n, log_m = log_n + 2;
-    const size_t MB = (M * sizeof(Fr) + 255) & ~(size_t)255;
-    const bool direct_pi = W.direct_pi;
-    Fr *const *w_vals = W.w_vals, *const *w_coef = W.w_coef;
-    Fr *const z_coef = W.z_coef, *const t1 = W.t1, *const t2 = W.t2, *const t3 = W.t3, *const r_poly = W.r_poly, *const agg = W.agg;
-    Fr *const pi_coef = W.pi_coef, *const l0_coef = W.l0_coef, *const t_ext = W.t_ext, *const d_results = W.d_results;
-    Fr *const *tab = W.tab;
-    Fr *ext[18];
-    for (int k = 0; k < 18; k++) ext[k] = W.ext[k];
-    std::vector<HFr> &inputs = F.inputs;
-
-    // The extensions that no challenge waits for (wires, z, public inputs: round-3 inputs) run on a low-priority stream of
-    // their own with their own NTT scratch: they fill the SIMDs that the latency-bound ends of a commitment leave idle
-    // without standing between two rounds — on the main stream round 2 queued up behind the four wire extensions, which
-    // in turn were starved by the accumulation they shared the GPU with (round 1: 6.4-7.0 ms).  Up to the 2^24 domain (a
-    // second 4N scratch above that is memory better spent elsewhere); PLK_PROVE_BG=0 restores the single stream.
-    static const bool bg_env = [] { const char *e = getenv("PLK_PROVE_BG"); return !(e && e[0] == '0'); }();
-    const bool use_bg = bg_env && log_n <= 24;
-    if (use_bg && !ctx->bg_stream) {
-        int lo_prio = 0, hi_prio = 0;
-        PLK_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-        PLK_HIP(hipStreamCreateWithPriority(&ctx->bg_stream, hipStreamNonBlocking, lo_prio));
-        PLK_HIP(hipEventCreateWithFlags(&ctx->bg_go, hipEventDisableTiming));
-        PLK_HIP(hipEventCreateWithFlags(&ctx->bg_done, hipEventDisableTiming));
-    }
-    hipStream_t bg = use_bg ? ctx->bg_stream : st;
-    const uint32_t bg_lane = use_bg ? 1 : 0;
-    struct BgGuard {                                          // an early return must not leave background work writing into the arena
-        hipStream_t s; bool armed;
-        ~BgGuard() { if (armed && s) (void)hipStreamSynchronize(s); }
-    } bg_guard{use_bg ? ctx->bg_stream : nullptr, use_bg};
-    // What follows on bg starts after everything enqueued on st so far AND after the accumulation of the commitment enqueued
-    // last: stream priorities do not keep a 8192-workgroup NTT pass from taking the CUs first (measured: the pre-phase of the
-    // wire commitments took 2.1 ms instead of 0.35 behind it), so the start is placed by hand where the GPU has room — the
-    // bucket reduction of that commitment, the point-wise kernels of the next round and the pre-phase of its commitment.
-    // The wire extensions start behind the wires' accumulation, z's extension behind the main stream only (see round 2).
-    auto bg_after_main = [&](bool behind_accumulation) -> int32_t {
-        if (!use_bg) return PLK_OK;
-        PLK_HIP(hipEventRecord(ctx->bg_go, st));
-        PLK_HIP(hipStreamWaitEvent(bg, ctx->bg_go, 0));
-        if (behind_accumulation && ctx->msm_enq != ctx->msm_fin) {
-            plk_ctx::MsmSlot &L = ctx->slot[ctx->fifo[(ctx->msm_enq - 1) % plk_ctx::MSM_SLOTS]];
-            if (L.acc_done) PLK_HIP(hipStreamWaitEvent(bg, L.acc_done, 0));
+// ---- the background lane of a proof
+// The extensions that no challenge waits for (wires, z, public inputs: round-3 inputs) run on a low-priority stream of
+// their own with their own NTT scratch: they fill the SIMDs that the latency-bound ends of a commitment leave idle
+// without standing between two rounds — on the main stream round 2 queued up behind the four wire extensions, which
+// in turn were starved by the accumulation they shared the GPU with (round 1: 6.4-7.0 ms).  Up to the 2^24 domain (a
+// second 4N scratch above that is memory better spent elsewhere); PLK_PROVE_BG=0 restores the single stream: then the
+// lane IS the main stream and every operation below is a no-op.
+struct BgLane {
+    plk_ctx *ctx = nullptr;
+    bool on = false;
+    bool armed = false;                      // work of the lane may still be writing into the arena: an early return waits for it
+    ~BgLane() { if (armed && on && ctx->bg_stream) (void)hipStreamSynchronize(ctx->bg_stream); }
+    hipStream_t stream() const { return on ? ctx->bg_stream : ctx->stream; }
+    uint32_t ntt_lane() const { return on ? 1 : 0; }          // which NTT scratch its transforms use
+    int32_t open(plk_ctx *c, uint32_t log_n) {
+        static const bool bg_env = [] { const char *e = getenv("PLK_PROVE_BG"); return !(e && e[0] == '0'); }();
+        ctx = c;
+        on = armed = bg_env && log_n <= 24;
+        if (on && !ctx->bg_stream) {
+            int lo_prio = 0, hi_prio = 0;
+            PLK_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
+            PLK_HIP(hipStreamCreateWithPriority(&ctx->bg_stream, hipStreamNonBlocking, lo_prio));
+            PLK_HIP(hipEventCreateWithFlags(&ctx->bg_go, hipEventDisableTiming));
+            PLK_HIP(hipEventCreateWithFlags(&ctx->bg_done, hipEventDisableTiming));
         }
         return PLK_OK;
-    };
+    }
+    // What follows on the lane starts after everything enqueued on the main stream so far AND (behind_accumulation) after the accumulation
+    // of the commitment enqueued last: stream priorities do not keep a 8192-workgroup NTT pass from taking the CUs first (measured: the
+    // pre-phase of the wire commitments took 2.1 ms instead of 0.35 behind it), so the start is placed by hand where the GPU has room — the
+    // bucket reduction of that commitment, the point-wise kernels of the next round and the pre-phase of its commitment.
+    int32_t start_behind_main(bool behind_accumulation) {
+        if (!on) return PLK_OK;
+        PLK_HIP(hipEventRecord(ctx->bg_go, ctx->stream));
+        PLK_HIP(hipStreamWaitEvent(ctx->bg_stream, ctx->bg_go, 0));
+        if (behind_accumulation && ctx->msm_enq != ctx->msm_fin) {
+            plk_ctx::MsmSlot &L = ctx->slot[ctx->fifo[(ctx->msm_enq - 1) % plk_ctx::MSM_SLOTS]];
+            if (L.acc_done) PLK_HIP(hipStreamWaitEvent(ctx->bg_stream, L.acc_done, 0));
+        }
+        return PLK_OK;
+    }
+    // the lane's work of this phase is all enqueued (marked where it ends, so that the main stream can be made to wait for it later) ...
+    int32_t mark_done() { if (on) PLK_HIP(hipEventRecord(ctx->bg_done, ctx->bg_stream)); return PLK_OK; }
+    // ... and the main stream waits for the mark
+    int32_t main_waits() { if (on) PLK_HIP(hipStreamWaitEvent(ctx->stream, ctx->bg_done, 0)); return PLK_OK; }
+};
 
+// ---- what the rounds of one proof share: a round reads what the earlier ones left here and adds its own results
+struct ProveState {
+    plk_ctx *ctx;
+    const plk_setup *S;
+    const ProveWs &W;
+    ProveFront &F;
+    const uint64_t N;                        // the domain
+    hipStream_t st;                          // the context's stream: the round-critical kernels
+    BgLane lane;                             // (before the transcript: `end` runs first on the way out, then the lane is waited for)
+    std::optional<ProofTranscript> tr;       // begins in round 1, once the front end's verdict is in; ends wherever the proof is left
+    bool use_lagrange = false;               // the witness and grand-product polynomials are committed from their values (round 1 decides)
+    HFr beta, gamma, alpha, v;
+    ZPoint at;                               // the challenge z with its powers and inverses (round 4)
+    HAffine wire_c[4], z_c, t_c[4], Wz, Wzw;
+    Evals ev;
+    PowTable pt_z, pt_zinv, pt_zw, pt_zwinv;
+    void lap() { double t = now_ms(); ctx->timings.push_back(t - F.t_prev); F.t_prev = t; }
+};
+static void beta_k_dev(const HFr &beta, Fr out[4]) { for (int j = 0; j < 4; j++) out[j] = to_dev(beta * HFr::from_u64(NON_RESIDUES[j])); }
 
-    // ---- round 1: wire polynomials, 4 x iNTT(N) in one launch per pass, 4 x MSM(N)
-    PLK_TRY(ntt_columns_dev(ctx, w_coef, 4, log_n, true, st));
+// ---- round 1: wire polynomials, 4 x iNTT(N) in one launch per pass, 4 x MSM(N)
+static int32_t round1_wires(ProveState &P) {
+    plk_ctx *ctx = P.ctx;
+    const uint64_t N = P.N;
+    PLK_TRY(ntt_columns_dev(ctx, P.W.w_coef, 4, P.S->log_n, true, P.st));
     // with a Lagrange-form key of the domain's size resident (`prove -l`, src/plonk.rs:138-146) the witness and
     // grand-product polynomials are committed from their evaluations, as bellman's prove() does; same proof bytes
-    const bool use_lagrange = ctx->lag.pts != nullptr;
-    if (use_lagrange && (ctx->combine ? ctx->lag.n != ctx->srs_n : ctx->lag.n != N)) { set_error("Lagrange-form key has a different size than the circuit's domain"); return PLK_ERR_SRS; }
-    HAffine wire_c[4];
-    PLK_TRY(commit_begin(ctx, use_lagrange ? w_vals : w_coef, 4, N, use_lagrange));
-    PLK_TRY(bg_after_main(true));
-    PLK_TRY(lde4cm_batch_dev(ctx, w_coef, 4, log_n, ext, bg, bg_lane));                       // round-3 work that needs no challenge
+    P.use_lagrange = ctx->lag.pts != nullptr;
+    if (P.use_lagrange && (ctx->combine ? ctx->lag.n != ctx->srs_n : ctx->lag.n != N)) { set_error("Lagrange-form key has a different size than the circuit's domain"); return PLK_ERR_SRS; }
+    PLK_TRY(commit_begin(ctx, P.use_lagrange ? P.W.w_vals : P.W.w_coef, 4, N, P.use_lagrange));
+    // round-3 work that needs no challenge: the wire extensions start behind the wires' accumulation
+    PLK_TRY(P.lane.start_behind_main(true));
+    PLK_TRY(lde4cm_batch_dev(ctx, P.W.w_coef, 4, P.S->log_n, P.W.ext, P.lane.stream(), P.lane.ntt_lane()));
     PLK_HIP(hipEventSynchronize(ctx->flag_ready));
-    PLK_TRY(front_verdict(ctx, S, F));
-    PLK_TRY(commit_end(ctx, 4, wire_c));
+    PLK_TRY(front_verdict(ctx, P.S, P.F));
+    PLK_TRY(commit_end(ctx, 4, P.wire_c));
     // the built-in Keccak transcript, or the table of plk_ctx_set_transcript: begin here, end wherever the function is left.  A
     // callback that failed or a challenge with limbs >= r ends the proof right behind the challenge, before anything consumes it
-    ProofTranscript tr(ctx->tr_set ? &ctx->tr_ops : nullptr, F.who);
-    for (const HFr &x : inputs) tr.absorb_fr(x);
-    for (int j = 0; j < 4; j++) tr.absorb_g1(wire_c[j]);
-    const HFr beta = tr.challenge(), gamma = tr.challenge();
-    PLK_TRY(tr.report());
-    lap();                                                                    // [1] round 1
+    P.tr.emplace(ctx->tr_set ? &ctx->tr_ops : nullptr, P.F.who);
+    for (const HFr &x : P.F.inputs) P.tr->absorb_fr(x);
+    for (int j = 0; j < 4; j++) P.tr->absorb_g1(P.wire_c[j]);
+    P.beta = P.tr->challenge(); P.gamma = P.tr->challenge();
+    return P.tr->report();
+}
 
-    // ---- round 2: grand product z  (z_i = prod_{k<i} num_k / den_k, no per-element inversion:
-    //      z_i = A_i * C_i / C_0 with A = exclusive prefix product of num, C = inclusive suffix product of den)
-    HFr kk[4];
-    for (int j = 0; j < 4; j++) kk[j] = HFr::from_u64(NON_RESIDUES[j]);
-    {
-        PermArgs pa;
-        pa.num = t1; pa.den = t2;
-        for (int j = 0; j < 4; j++) { pa.w[j] = w_vals[j]; pa.sigma[j] = S->sig_vals[j]; pa.beta_k[j] = to_dev(beta * kk[j]); }
-        pa.beta = to_dev(beta * HFr::from_u64(32)); pa.gamma = to_dev(gamma); pa.fix = to_dev(HFr::from_u64(1u << 25));   // domains: poly.h
-        pa.n = (uint32_t)N; pa.log_n = log_n; pa.tw = ctx->tw_fwd_w;
-        PLK_TRY(perm_terms(pa, st));
-        // (the scans stop after their second phase when they span several blocks: the block prefixes are folded in by the product below,
-        //  and C_0 — the product of all denominators — is the suffix scan's grand total, which its second phase leaves behind the prefixes)
-        const Fr *pre_a = nullptr, *pre_c = nullptr;
-        PLK_TRY(scan_pair_mult(ctx, t1, t1, false, true, t2, t2, true, false, (uint32_t)N, st, &pre_a, &pre_c));
-        const uint32_t scan_blocks = pre_c ? (uint32_t)((N + POLY_SCAN_BLOCK - 1) / POLY_SCAN_BLOCK) : 0;
-        HFr total, num_total;
-        PLK_HIP(hipMemcpyAsync(total.l, pre_c ? pre_c + scan_blocks : t2, sizeof(Fr), hipMemcpyDeviceToHost, st));
-        // copy constraints of a caller's sigma (assembled front): the argument closes iff prod num == prod den.  The numerators' grand total
-        // sits in the scan's block-total slot (poly.hip: behind the nb prefixes; with one block the block total itself, lazily reduced) and
-        // comes back with the same synchronisation as the denominators' one
-        const uint32_t nb_all = (uint32_t)((N + POLY_SCAN_BLOCK - 1) / POLY_SCAN_BLOCK);
-        if (F.close_perm) PLK_HIP(hipMemcpyAsync(num_total.l, ctx->poly_tmp.as<Fr>() + (nb_all > 1 ? nb_all : 0), sizeof(Fr), hipMemcpyDeviceToHost, st));
-        PLK_HIP(hipStreamSynchronize(st));
-        if (total.is_zero()) { set_error("grand product denominator vanished (probability ~2^-230)"); return PLK_ERR_UNSAT; }
-        if (F.close_perm) {
-            if (HFr::geq_p(num_total.l)) HFr::sub_p(num_total.l);
-            if (num_total != total) {
-                std::string msg = "copy constraints: the permutation argument does not close (prod of numerators != prod of denominators at beta, gamma): "
-                                  "the columns break the copy constraints of the setup's sigma";
-                // which one: the exact checks on the columns as they sit in the workspace (only here, on the way out with an error)
-                const Fr *cols[4] = {w_vals[0], w_vals[1], w_vals[2], w_vals[3]};
-                plk_copy_report rep;
-                if (copy_check(ctx, S->sig_vals, log_n, cols, N, &rep, st) == PLK_OK) append_copy_report(msg, rep);
-                set_error(msg);
-                return PLK_ERR_UNSAT;
-            }
-        }
-        // the scans live in the W domain: what was read is 32 * C_0, so E(1 / C_0) = 32 * E(1 / (32 C_0))
-        const Fr inv_c0 = to_dev(total.inv() * HFr::from_u64(32));
-        if (pre_c) PLK_TRY(mul3_blocks(z_coef, t1, t2, pre_a, pre_c, inv_c0, (uint32_t)N, st));
-        else PLK_TRY(mul3(z_coef, t1, t2, inv_c0, (uint32_t)N, st));
-        if (use_lagrange) PLK_HIP(hipMemcpyAsync(t1, z_coef, N * sizeof(Fr), hipMemcpyDeviceToDevice, st));   // keep the values
-        PLK_TRY(ntt_dev(ctx, z_coef, log_n, true, nullptr, st));
+// The grand product z_i = prod_{k<i} num_k / den_k of a permutation argument, as values over the domain, without a per-element inversion:
+// z_i = A_i * C_i / C_0 with A = exclusive prefix product of num, C = inclusive suffix product of den (pa.num, pa.den: scratch of n each).
+// This is what round 2 runs between its challenges and the iNTT, and all of what plk_permutation_grand_product_dev runs.
+// The scans stop after their second phase when they span several blocks: the block prefixes are folded in by the product (mul3_blocks),
+// and C_0 — the product of all denominators — is the suffix scan's grand total, which its second phase leaves behind the prefixes.
+// den_total <- C_0; num_total (optional) <- the product of all numerators, which sits in the scan's block-total slot (poly.hip: behind the
+// nb prefixes; with one block the block total itself, lazily reduced) and comes back with the same synchronisation.
+static int32_t grand_product(plk_ctx *ctx, const PermArgs &pa, Fr *out, hipStream_t st, const char *vanished, HFr *den_total, HFr *num_total) {
+    PLK_TRY(perm_terms(pa, st));
+    const Fr *pre_a = nullptr, *pre_c = nullptr;
+    PLK_TRY(scan_pair_mult(ctx, pa.num, pa.num, false, true, pa.den, pa.den, true, false, pa.n, st, &pre_a, &pre_c));
+    const uint32_t nb = (pa.n + POLY_SCAN_BLOCK - 1) / POLY_SCAN_BLOCK;
+    PLK_HIP(hipMemcpyAsync(den_total->l, pre_c ? pre_c + nb : pa.den, sizeof(Fr), hipMemcpyDeviceToHost, st));
+    if (num_total) PLK_HIP(hipMemcpyAsync(num_total->l, ctx->poly_tmp.as<Fr>() + (nb > 1 ? nb : 0), sizeof(Fr), hipMemcpyDeviceToHost, st));
+    PLK_HIP(hipStreamSynchronize(st));
+    if (den_total->is_zero()) { set_error(vanished); return PLK_ERR_UNSAT; }
+    if (num_total && HFr::geq_p(num_total->l)) HFr::sub_p(num_total->l);
+    // the scans live in the W domain: what was read is 32 * C_0, so E(1 / C_0) = 32 * E(1 / (32 C_0))
+    const Fr inv_c0 = to_dev(to_w(den_total->inv()));
+    if (pre_c) return mul3_blocks(out, pa.num, pa.den, pre_a, pre_c, inv_c0, pa.n, st);
+    return mul3(out, pa.num, pa.den, inv_c0, pa.n, st);
+}
+static PermArgs perm_args(plk_ctx *ctx, const Fr *const w[4], const Fr *const sigma[4], const HFr &beta, const HFr &gamma, uint32_t log_n, Fr *num, Fr *den) {
+    PermArgs pa;
+    pa.num = num; pa.den = den;
+    for (int j = 0; j < 4; j++) { pa.w[j] = w[j]; pa.sigma[j] = sigma[j]; }
+    beta_k_dev(beta, pa.beta_k);
+    pa.beta = to_dev(to_w(beta)); pa.gamma = to_dev(gamma); pa.fix = to_dev(HFr::from_u64(W_FOUR_E_FACTORS));
+    pa.n = 1u << log_n; pa.log_n = log_n; pa.tw = ctx->tw_fwd_w;
+    return pa;
+}
+
+// ---- round 2: grand product z
+static int32_t round2_grand_product(ProveState &P) {
+    plk_ctx *ctx = P.ctx;
+    const plk_setup *S = P.S;
+    hipStream_t st = P.st;
+    const uint64_t N = P.N;
+    HFr total, num_total;
+    PLK_TRY(grand_product(ctx, perm_args(ctx, P.W.w_vals, S->sig_vals, P.beta, P.gamma, S->log_n, P.W.t1, P.W.t2), P.W.z_coef, st,
+                          "grand product denominator vanished (probability ~2^-230)", &total, P.F.close_perm ? &num_total : nullptr));
+    // copy constraints of a caller's sigma (assembled front): the argument closes iff prod num == prod den
+    if (P.F.close_perm && num_total != total) {
+        std::string msg = "copy constraints: the permutation argument does not close (prod of numerators != prod of denominators at beta, gamma): "
+                          "the columns break the copy constraints of the setup's sigma";
+        // which one: the exact checks on the columns as they sit in the workspace (only here, on the way out with an error)
+        plk_copy_report rep;
+        if (copy_check(ctx, S->sig_vals, S->log_n, P.W.w_vals, N, &rep, st) == PLK_OK) append_copy_report(msg, rep);
+        set_error(msg);
+        return PLK_ERR_UNSAT;
     }
-    HAffine z_c;
-    { const Fr *zp = use_lagrange ? t1 : z_coef; PLK_TRY(commit_begin(ctx, &zp, 1, N, use_lagrange)); }
-    // while z is being committed: its extension, the public-input polynomial, and (first proof only) the constant vectors
-    // (z's extension is the last thing the quotient waits for: it starts as soon as z's coefficients exist and shares the GPU
-    //  with the accumulation of z's commitment — behind that accumulation it ended 0.4 ms after the commitment itself)
-    PLK_TRY(bg_after_main(false));
-    {
-        const Fr *zc = z_coef;
-        PLK_TRY(lde4cm_batch_dev(ctx, &zc, 1, log_n, &ext[4], bg, bg_lane));
-    }
-    if (!direct_pi) {
+    if (P.use_lagrange) PLK_HIP(hipMemcpyAsync(P.W.t1, P.W.z_coef, N * sizeof(Fr), hipMemcpyDeviceToDevice, st));   // keep the values
+    PLK_TRY(ntt_dev(ctx, P.W.z_coef, S->log_n, true, nullptr, st));
+    { const Fr *zp = P.use_lagrange ? P.W.t1 : P.W.z_coef; PLK_TRY(commit_begin(ctx, &zp, 1, N, P.use_lagrange)); }
+    // while z is being committed: its extension and the public-input polynomial.  z's extension is the last thing the quotient waits for:
+    // it starts behind the main stream only, as soon as z's coefficients exist, and shares the GPU with the accumulation of z's
+    // commitment — behind that accumulation it ended 0.4 ms after the commitment itself
+    PLK_TRY(P.lane.start_behind_main(false));
+    hipStream_t bg = P.lane.stream();
+    { const Fr *zc = P.W.z_coef; PLK_TRY(lde4cm_batch_dev(ctx, &zc, 1, S->log_n, &P.W.ext[4], bg, P.lane.ntt_lane())); }
+    if (!P.W.direct_pi) {
+        Fr *pi_coef = P.W.pi_coef;
         PLK_HIP(hipMemsetAsync(pi_coef, 0, N * sizeof(Fr), bg));
-        PLK_HIP(hipMemcpyAsync(pi_coef, inputs.data(), inputs.size() * sizeof(Fr), hipMemcpyHostToDevice, bg));
-        PLK_TRY(ntt_batch_dev(ctx, &pi_coef, 1, log_n, true, nullptr, bg, bg_lane));
+        PLK_HIP(hipMemcpyAsync(pi_coef, P.F.inputs.data(), P.F.inputs.size() * sizeof(Fr), hipMemcpyHostToDevice, bg));
+        PLK_TRY(ntt_batch_dev(ctx, &pi_coef, 1, S->log_n, true, nullptr, bg, P.lane.ntt_lane()));
         const Fr *pc = pi_coef;
-        PLK_TRY(lde4cm_batch_dev(ctx, &pc, 1, log_n, &ext[16], bg, bg_lane));
+        PLK_TRY(lde4cm_batch_dev(ctx, &pc, 1, S->log_n, &P.W.ext[16], bg, P.lane.ntt_lane()));
     }
-    if (use_bg) PLK_HIP(hipEventRecord(ctx->bg_done, bg));
-    PLK_TRY(commit_end(ctx, 1, &z_c));
-    tr.absorb_g1(z_c);
-    const HFr alpha = tr.challenge();
-    PLK_TRY(tr.report());
-    lap();                                                                    // [2] round 2
+    PLK_TRY(P.lane.mark_done());
+    PLK_TRY(commit_end(ctx, 1, &P.z_c));
+    P.tr->absorb_g1(P.z_c);
+    P.alpha = P.tr->challenge();
+    return P.tr->report();
+}
 
-    // ---- round 3: quotient on the coset 7*<omega_4N>: 18 x LDE, fused point-wise kernel, coset iNTT(4N)
-    const HFr coset = HFr::from_u64(7);
-    {
-        std::unique_lock<std::mutex> lazy_lock(S->lazy_mu);
-        if (!S->lde_ready) {
-            // the coset-point vector is a convenience (one load instead of two loads and two products per point):
-            // above 2^24 gates its 4N * 32 bytes are better spent elsewhere (2^26 would not fit in 288 GB)
-            static const bool no_cache_env = getenv("PLK_NO_COSET_CACHE") != nullptr;       // tests: the large-domain branch at a small size
-            const bool cache_x = log_n <= 24 && !no_cache_env;
-            PLK_TRY(S->lde_store.reserve((cache_x ? 13 : 12) * MB));
-            Arena LA{&S->lde_store};
-            for (int k = 0; k < (cache_x ? 13 : 12); k++) S->lde[k] = LA.take<Fr>(M);
-            if (!cache_x) S->lde[12] = nullptr;
-            HFr one = HFr::one();
-            PLK_HIP(hipMemsetAsync(l0_coef, 0, N * sizeof(Fr), st));
-            PLK_HIP(hipMemcpyAsync(l0_coef, one.l, sizeof(Fr), hipMemcpyHostToDevice, st));
-            PLK_TRY(ntt_dev(ctx, l0_coef, log_n, true, nullptr, st));
-            {   // 7 selectors, 4 sigmas, L0: twelve extensions in the coset-major layout of the quotient kernel, four polynomials per launch
-                const Fr *src[12]; Fr *dst[12];
-                for (int k = 0; k < 7; k++) { src[k] = S->sel_coef[k]; dst[k] = S->lde[k]; }
-                for (int j = 0; j < 4; j++) { src[7 + j] = S->sig_coef[j]; dst[7 + j] = S->lde[7 + j]; }
-                src[11] = l0_coef; dst[11] = S->lde[11];
-                PLK_TRY(lde4cm_batch_dev(ctx, src, 12, log_n, dst, st, 0));
-            }
-            // pre-scaled for the 29-bit layer of the quotient kernel (poly.h, QuotientArgs): 2^5 everywhere,
-            // 2^10 on q_m, none on q_const (it is only added); plus the coset points x_i = 7 * omega_4N^i
-            const HFr s5 = HFr::from_u64(1u << 10), s10 = HFr::from_u64(1u << 15);      // as factors of a product that removes 2^5
-            for (int k = 0; k < 12; k++) {
-                if (k == 5) continue;
-                PLK_TRY(scale_const(S->lde[k], S->lde[k], to_dev(k == 4 ? s10 : s5), (uint32_t)M, st));
-            }
-            if (S->lde[12]) PLK_TRY(coset_points_w(S->lde[12], ctx->tw_fwd_w, log_m, to_dev(HFr::from_u64(7u << 5)), (uint32_t)M, st));
-            PLK_HIP(hipStreamSynchronize(st));
-            S->lde_ready = true;
+// The constants a setup's FIRST proof computes and every later one reads: the coset-major extensions of the 7 selectors, 4 sigmas and L_0
+// (pre-scaled for the quotient kernel), the coset points, 1 / Z_H on the four cosets and the constants of the coset iNTT's combine step.
+// One setup may be proved from several contexts / host threads at once: all of it under S->lazy_mu, complete on the device before
+// lde_ready is set.
+static int32_t setup_extensions_ready(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, hipStream_t st) {
+    const uint64_t N = S->N, M = 4 * N;
+    const uint32_t log_n = S->log_n, log_m = log_n + 2;
+    std::lock_guard<std::mutex> lazy_lock(S->lazy_mu);
+    if (!S->lde_ready) {
+        // the coset-point vector is a convenience (one load instead of two loads and two products per point):
+        // above 2^24 gates its 4N * 32 bytes are better spent elsewhere (2^26 would not fit in 288 GB)
+        static const bool no_cache_env = getenv("PLK_NO_COSET_CACHE") != nullptr;       // tests: the large-domain branch at a small size
+        const int vectors = log_n <= 24 && !no_cache_env ? 13 : 12;
+        PLK_TRY(S->lde_store.reserve(vectors * ((M * sizeof(Fr) + 255) & ~(size_t)255)));
+        Arena LA{&S->lde_store};
+        for (int k = 0; k < vectors; k++) S->lde[k] = LA.take<Fr>(M);
+        if (vectors == 12) S->lde[12] = nullptr;
+        HFr one = HFr::one();
+        PLK_HIP(hipMemsetAsync(W.l0_coef, 0, N * sizeof(Fr), st));
+        PLK_HIP(hipMemcpyAsync(W.l0_coef, one.l, sizeof(Fr), hipMemcpyHostToDevice, st));
+        PLK_TRY(ntt_dev(ctx, W.l0_coef, log_n, true, nullptr, st));
+        {   // 7 selectors, 4 sigmas, L0: twelve extensions in the coset-major layout of the quotient kernel, four polynomials per launch
+            const Fr *src[12];
+            for (int k = 0; k < 7; k++) src[k] = S->sel_coef[k];
+            for (int j = 0; j < 4; j++) src[7 + j] = S->sig_coef[j];
+            src[11] = W.l0_coef;
+            PLK_TRY(lde4cm_batch_dev(ctx, src, 12, log_n, S->lde, st, 0));
         }
-        for (int k = 0; k < 11; k++) ext[5 + k] = S->lde[k];
-        ext[17] = S->lde[11];
-        QuotientArgs qa;
-        qa.out = t_ext;
-        for (int j = 0; j < 4; j++) { qa.w[j] = ext[j]; qa.sigma[j] = ext[12 + j]; qa.beta_k[j] = to_dev(beta * kk[j]); }
-        qa.z = ext[4];
-        for (int k = 0; k < 7; k++) qa.q[k] = ext[5 + k];
-        qa.pi = direct_pi ? nullptr : ext[16]; qa.l0 = ext[17]; qa.x = S->lde[12];
-        qa.tw_w = ctx->tw_fwd_w; qa.coset_w = to_dev(HFr::from_u64(7u << 5));
-        qa.num_pi = direct_pi ? (uint32_t)inputs.size() : 0;
-        for (uint32_t k = 0; k < qa.num_pi; k++) qa.pi_in[k] = to_dev(inputs[k]);
-        const HFr two5 = HFr::from_u64(1u << 5), two25 = HFr::from_u64(1u << 25);
-        qa.beta = to_dev(beta); qa.gamma = to_dev(gamma);
-        qa.alpha_pp = to_dev(alpha * two25); qa.alpha2_w = to_dev(alpha * alpha * two5);
-        if (!S->zh_inv_ready) {                                   // 1 / Z_H on the four cosets of <omega_N> inside the 4N domain: circuit constants
-            HFr gN = coset.pow_u64(N), iota = host_omega(log_m).pow_u64(N), ip = HFr::one();
-            for (int k = 0; k < 4; k++) { S->zh_inv[k] = (gN * ip - HFr::one()).inv(); ip = ip * iota; }
-            const HFr gN_inv = gN.inv(), quarter = HFr::from_u64(4).inv();
-            S->icoset_c[0] = iota.inv();                           // iota = omega_4N^N = omega_4
-            S->icoset_c[1] = quarter;
-            for (int c = 1; c < 4; c++) S->icoset_c[1 + c] = S->icoset_c[c] * gN_inv;
-            S->zh_inv_ready = true;
+        // pre-scaled for the 29-bit layer of the quotient kernel (poly.h, QuotientArgs): 2^5 everywhere,
+        // 2^10 on q_m, none on q_const (it is only added); plus the coset points x_i = 7 * omega_4N^i
+        for (int k = 0; k < 12; k++) {
+            if (k == 5) continue;
+            PLK_TRY(scale_const(S->lde[k], S->lde[k], to_dev(HFr::from_u64(k == 4 ? W_LDE_SCALE_QM : W_LDE_SCALE)), (uint32_t)M, st));
         }
-        lazy_lock.unlock();
-        for (int k = 0; k < 4; k++) qa.zh_inv_w[k] = to_dev(S->zh_inv[k] * two5);
-        qa.m = (uint32_t)M; qa.log_m = log_m;
-        if (use_bg) PLK_HIP(hipStreamWaitEvent(st, ctx->bg_done, 0));      // the five extensions (+ PI) of the background stream
-        PLK_TRY(quotient(qa, st));
-        // coset iNTT at 4N from the coset-major layout the kernel wrote: four inverse N-point coset transforms (one launch per
-        // pass) and a 4-point combine, instead of three passes over 4N (0.57 -> 0.48 ms at the 2^20 domain)
-        PLK_TRY(icoset4cm_dev(ctx, t_ext, log_n, st, 0));
-        {
-            const HFr two5 = HFr::from_u64(32);
-            Fr s_w[4];
-            for (int c = 0; c < 4; c++) s_w[c] = to_dev(S->icoset_c[1 + c] * two5);
-            PLK_TRY(icoset_combine(t_ext, (uint32_t)N, to_dev(S->icoset_c[0] * two5), s_w, st));
-        }
+        if (S->lde[12]) PLK_TRY(coset_points_w(S->lde[12], ctx->tw_fwd_w, log_m, to_dev(HFr::from_u64(W_COSET_GEN)), (uint32_t)M, st));
+        PLK_HIP(hipStreamSynchronize(st));
+        S->lde_ready = true;
     }
-    HAffine t_c[4];
-    {
-        const Fr *parts[4] = {t_ext, t_ext + N, t_ext + 2 * N, t_ext + 3 * N};
-        PLK_TRY(commit_many(ctx, parts, 4, N, t_c));
+    if (!S->zh_inv_ready) {                                   // 1 / Z_H on the four cosets of <omega_N> inside the 4N domain: circuit constants
+        HFr gN = HFr::from_u64(7).pow_u64(N), iota = host_omega(2), ip = HFr::one();       // iota = omega_4N^N = omega_4
+        for (int k = 0; k < 4; k++) { S->zh_inv[k] = (gN * ip - HFr::one()).inv(); ip = ip * iota; }
+        icoset_constants(log_n, S->icoset_c);
+        S->zh_inv_ready = true;
     }
-    bg_guard.armed = false;                                   // the quotient consumed everything the background stream produced
-    for (int k = 0; k < 4; k++) tr.absorb_g1(t_c[k]);
-    const HFr z = tr.challenge();
-    PLK_TRY(tr.report());
-    lap();                                                                    // [3] round 3
+    return PLK_OK;
+}
 
-    // ---- round 4: evaluations at z and z*omega, linearisation
-    const HFr omega = host_omega(log_n), zw = z * omega, zN = z.pow_u64(N);
-    if (z.is_zero()) { set_error("challenge z = 0"); return PLK_ERR_UNSAT; }
-    // the three inversions of this round (1/z, 1/(z omega), 1/(N (z - 1)) for L_0(z)) share one: the host inversion is what the
-    // GPU waits for between the rounds
-    const HFr l0_den = HFr::from_u64(N) * (z - HFr::one());
-    if (l0_den.is_zero()) { set_error("challenge z = 1"); return PLK_ERR_UNSAT; }
-    // any other point of the domain: every verifier refuses z^N = 1 (verify.cpp), so no proof is written for it.  Keccak gets here with
-    // probability N / r; a caller's transcript (plk_ctx_set_transcript) may be made to
-    if (zN == HFr::one()) { set_error("challenge z^N = 1"); return PLK_ERR_UNSAT; }
-    const HFr inv_all = (z * zw * l0_den).inv();
-    const HFr z_inv = inv_all * zw * l0_den, zw_inv = inv_all * z * l0_den, l0_den_inv = inv_all * z * zw;
-    PowTable pts4[4];
+// ---- round 3: quotient on the coset 7*<omega_4N>: 18 x LDE, fused point-wise kernel, coset iNTT(4N)
+static int32_t round3_quotient(ProveState &P) {
+    plk_ctx *ctx = P.ctx;
+    const plk_setup *S = P.S;
+    hipStream_t st = ctx->stream;
+    const uint64_t N = S->N;
+    PLK_TRY(setup_extensions_ready(ctx, S, P.W, st));
+    QuotientArgs qa;
+    qa.out = P.W.t_ext;
+    for (int j = 0; j < 4; j++) { qa.w[j] = P.W.ext[j]; qa.sigma[j] = S->lde[7 + j]; }
+    beta_k_dev(P.beta, qa.beta_k);
+    qa.z = P.W.ext[4];
+    for (int k = 0; k < 7; k++) qa.q[k] = S->lde[k];
+    qa.pi = P.W.direct_pi ? nullptr : P.W.ext[16]; qa.l0 = S->lde[11]; qa.x = S->lde[12];
+    qa.tw_w = ctx->tw_fwd_w; qa.coset_w = to_dev(HFr::from_u64(W_COSET_GEN));
+    qa.num_pi = P.W.direct_pi ? (uint32_t)P.F.inputs.size() : 0;
+    for (uint32_t k = 0; k < qa.num_pi; k++) qa.pi_in[k] = to_dev(P.F.inputs[k]);
+    qa.beta = to_dev(P.beta); qa.gamma = to_dev(P.gamma);
+    qa.alpha_pp = to_dev(P.alpha * HFr::from_u64(W_FOUR_E_FACTORS)); qa.alpha2_w = to_dev(to_w(P.alpha * P.alpha));
+    for (int k = 0; k < 4; k++) qa.zh_inv_w[k] = to_dev(to_w(S->zh_inv[k]));
+    qa.m = (uint32_t)(4 * N); qa.log_m = S->log_n + 2;
+    PLK_TRY(P.lane.main_waits());                             // the five extensions (+ PI) of the background lane
+    PLK_TRY(quotient(qa, st));
+    // coset iNTT at 4N from the coset-major layout the kernel wrote: four inverse N-point coset transforms (one launch per
+    // pass) and a 4-point combine, instead of three passes over 4N (0.57 -> 0.48 ms at the 2^20 domain)
+    PLK_TRY(icoset4cm_dev(ctx, P.W.t_ext, S->log_n, st, 0));
+    PLK_TRY(icoset_combine_ext(P.W.t_ext, (uint32_t)N, S->icoset_c, st));
+    const Fr *parts[4] = {P.W.t_ext, P.W.t_ext + N, P.W.t_ext + 2 * N, P.W.t_ext + 3 * N};
+    PLK_TRY(commit_many(ctx, parts, 4, N, P.t_c));
+    P.lane.armed = false;                                     // the quotient consumed everything the background lane produced
+    for (int k = 0; k < 4; k++) P.tr->absorb_g1(P.t_c[k]);
+    P.at.z = P.tr->challenge();
+    return P.tr->report();
+}
+
+// ---- round 4: evaluations at z and z*omega, linearisation
+static int32_t round4_evaluations(ProveState &P) {
+    plk_ctx *ctx = P.ctx;
+    const plk_setup *S = P.S;
+    hipStream_t st = ctx->stream;
+    const uint32_t N = (uint32_t)S->N;
+    if (const char *refused = challenge_point(HFr(P.at.z), host_omega(S->log_n), S->N, &P.at)) { set_error(refused); return PLK_ERR_UNSAT; }
     {
-        const Fr bases4[4] = {to_dev(z), to_dev(z_inv), to_dev(zw), to_dev(zw_inv)};
-        PLK_TRY(fill_pow_tables4_into(ctx, bases4, tab, pts4, st));
+        const Fr bases4[4] = {to_dev(P.at.z), to_dev(P.at.z_inv), to_dev(P.at.zw), to_dev(P.at.zw_inv)};
+        PowTable pts4[4];
+        PLK_TRY(fill_pow_tables4_into(ctx, bases4, P.W.tab, pts4, st));
+        P.pt_z = pts4[0]; P.pt_zinv = pts4[1]; P.pt_zw = pts4[2]; P.pt_zwinv = pts4[3];
     }
-    const PowTable pt_z = pts4[0], pt_zinv = pts4[1], pt_zw = pts4[2], pt_zwinv = pts4[3];
-    HFr ev[11];
     {
         EvalArgs ea{};
-        const Fr *polys[10] = {w_coef[0], w_coef[1], w_coef[2], w_coef[3], w_coef[3], S->sig_coef[0], S->sig_coef[1], S->sig_coef[2], t_ext, z_coef};
-        for (int e = 0; e < 10; e++) { ea.poly[e] = polys[e]; ea.len[e] = (uint32_t)(e == 8 ? M : N); ea.pt[e] = (e == 4 || e == 9) ? pt_zw : pt_z; }
+        const Fr *polys[10] = {P.W.w_coef[0], P.W.w_coef[1], P.W.w_coef[2], P.W.w_coef[3], P.W.w_coef[3],
+                               S->sig_coef[0], S->sig_coef[1], S->sig_coef[2], P.W.t_ext, P.W.z_coef};
+        for (int e = 0; e < 10; e++) { ea.poly[e] = polys[e]; ea.len[e] = e == 8 ? 4 * N : N; ea.pt[e] = (e == 4 || e == 9) ? P.pt_zw : P.pt_z; }
         ea.count = 10;
-        PLK_TRY(eval_batch(ctx, ea, d_results, st));
-        PLK_HIP(hipMemcpyAsync(ev, d_results, 10 * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        PLK_TRY(eval_batch(ctx, ea, P.W.d_results, st));
+        PLK_HIP(hipMemcpyAsync(P.ev.v, P.W.d_results, 10 * sizeof(Fr), hipMemcpyDeviceToHost, st));
         PLK_HIP(hipStreamSynchronize(st));
     }
-    const HFr *wz = ev, w3zw = ev[4], *sz = ev + 5, tz = ev[8], zzw = ev[9];
-    HFr l0z = (zN - HFr::one()) * l0_den_inv;
-    HFr fz = alpha;
-    for (int j = 0; j < 4; j++) fz = fz * (wz[j] + beta * kk[j] * z + gamma);
-    fz = fz + alpha * alpha * l0z;
-    HFr fs = alpha * beta * zzw;
-    for (int j = 0; j < 3; j++) fs = fs * (wz[j] + beta * sz[j] + gamma);
     {
+        HFr fz, fs, sc[9];
+        permutation_factors(P.alpha, P.beta, P.gamma, P.at, P.ev, &fz, &fs);
+        linearisation_coefficients(P.ev, fz, fs, sc);
         LinCombArgs la{};
-        la.out = r_poly; la.n = (uint32_t)N; la.count = 9;
-        const Fr *ps[9] = {S->sel_coef[5], S->sel_coef[0], S->sel_coef[1], S->sel_coef[2], S->sel_coef[3], S->sel_coef[4], S->sel_coef[6], z_coef, S->sig_coef[3]};
-        HFr sc[9] = {HFr::one(), wz[0], wz[1], wz[2], wz[3], wz[0] * wz[1], w3zw, fz, -fs};
-        for (int k = 0; k < 9; k++) { la.p[k] = ps[k]; la.s[k] = to_dev(sc[k] * HFr::from_u64(32)); la.unit[k] = (k == 0); }
+        la.out = P.W.r_poly; la.n = N; la.count = 9;
+        const Fr *ps[9] = {S->sel_coef[5], S->sel_coef[0], S->sel_coef[1], S->sel_coef[2], S->sel_coef[3], S->sel_coef[4], S->sel_coef[6], P.W.z_coef, S->sig_coef[3]};
+        for (int k = 0; k < 9; k++) { la.p[k] = ps[k]; la.s[k] = to_dev(to_w(sc[k])); la.unit[k] = (k == 0); }
         PLK_TRY(lincomb(la, st));
         EvalArgs ea{};
-        ea.poly[0] = r_poly; ea.len[0] = (uint32_t)N; ea.pt[0] = pt_z; ea.count = 1;
-        PLK_TRY(eval_batch(ctx, ea, d_results, st));
-        PLK_HIP(hipMemcpyAsync(&ev[10], d_results, sizeof(Fr), hipMemcpyDeviceToHost, st));
+        ea.poly[0] = P.W.r_poly; ea.len[0] = N; ea.pt[0] = P.pt_z; ea.count = 1;
+        PLK_TRY(eval_batch(ctx, ea, P.W.d_results, st));
+        PLK_HIP(hipMemcpyAsync(&P.ev.v[10], P.W.d_results, sizeof(Fr), hipMemcpyDeviceToHost, st));
         PLK_HIP(hipStreamSynchronize(st));
     }
-    const HFr rz = ev[10];
-    for (int j = 0; j < 4; j++) tr.absorb_fr(wz[j]);
-    tr.absorb_fr(w3zw);
-    for (int j = 0; j < 3; j++) tr.absorb_fr(sz[j]);
-    tr.absorb_fr(tz); tr.absorb_fr(rz); tr.absorb_fr(zzw);
-    const HFr v = tr.challenge();
-    PLK_TRY(tr.report());
-    lap();                                                                    // [4] round 4
+    for (int j = 0; j < 4; j++) P.tr->absorb_fr(P.ev.wz()[j]);
+    P.tr->absorb_fr(P.ev.w3zw());
+    for (int j = 0; j < 3; j++) P.tr->absorb_fr(P.ev.sz()[j]);
+    P.tr->absorb_fr(P.ev.tz()); P.tr->absorb_fr(P.ev.rz()); P.tr->absorb_fr(P.ev.zzw());
+    P.v = P.tr->challenge();
+    return P.tr->report();
+}
 
-    // ---- round 5: opening proofs W_z, W_zw by synthetic division (suffix sums of p_j z^j, times z^-(k+1))
-    HAffine Wz, Wzw;
-    {
-        LinCombArgs la{};
-        la.out = agg; la.n = (uint32_t)N; la.count = 12;
-        HFr vp[11]; vp[0] = HFr::one();
-        for (int k = 1; k <= 10; k++) vp[k] = vp[k - 1] * v;
-        const Fr *ps[12] = {t_ext, t_ext + N, t_ext + 2 * N, t_ext + 3 * N, r_poly, w_coef[0], w_coef[1], w_coef[2], w_coef[3],
-                            S->sig_coef[0], S->sig_coef[1], S->sig_coef[2]};
-        HFr sc[12] = {HFr::one(), zN, zN * zN, zN * zN * zN, vp[1], vp[2], vp[3], vp[4], vp[5], vp[6], vp[7], vp[8]};
-        for (int k = 0; k < 12; k++) { la.p[k] = ps[k]; la.s[k] = to_dev(sc[k] * HFr::from_u64(32)); la.unit[k] = (k == 0); }
-        // The two quotients are independent chains of five small launches each (linear combination times z^i, suffix sums,
-        // times z^-(k+1)): the second one runs on the background stream (idle since round 3) with scratch of its own, so that
-        // the two chains overlap instead of queueing (0.14 ms of pure launch latency at the 2^20 domain).
-        la.times_pow = pt_z; la.out = t1;
-        LinCombArgs lb{};
-        lb.n = (uint32_t)N; lb.count = 2;
-        lb.p[0] = z_coef; lb.s[0] = to_dev(vp[9] * HFr::from_u64(32)); lb.p[1] = w_coef[3]; lb.s[1] = to_dev(vp[10] * HFr::from_u64(32));
-        lb.times_pow = pt_zw;
-        Fr *const b_tmp = use_bg ? pi_coef : t1;                      // (pi_coef: free since the quotient)
-        hipStream_t sb = use_bg ? bg : st;
-        lb.out = b_tmp;
-        bg_guard.armed = use_bg;                                      // (an error below must not leave chain B writing into the arena)
-        if (use_bg) { PLK_HIP(hipEventRecord(ctx->bg_go, st)); PLK_HIP(hipStreamWaitEvent(sb, ctx->bg_go, 0)); }   // the power tables and r(x) come from st
-        PLK_TRY(lincomb(la, st));
-        PLK_TRY(scan(ctx, t1, t1, (uint32_t)N, false, true, false, st));
-        PLK_TRY(div_finish(t2, t1, pt_zinv, (uint32_t)N, st));
-        PLK_TRY(lincomb(lb, sb));
-        PLK_TRY(scan(ctx, b_tmp, b_tmp, (uint32_t)N, false, true, false, sb, use_bg ? &ctx->poly_tmp2 : nullptr));
-        PLK_TRY(div_finish(t3, b_tmp, pt_zwinv, (uint32_t)N, sb));
-        if (use_bg) { PLK_HIP(hipEventRecord(ctx->bg_done, sb)); PLK_HIP(hipStreamWaitEvent(st, ctx->bg_done, 0)); }
-        const Fr *opens[2] = {t2, t3};
-        HAffine oc[2];
-        PLK_TRY(commit_many(ctx, opens, 2, N, oc));
-        bg_guard.armed = false;                                       // the commitments consumed t3: chain B has ended
-        Wz = oc[0]; Wzw = oc[1];
-    }
-    lap();                                                                    // [5] round 5
+// (p(x) - p(z)) / (x - z) of a linear combination p = sum_k s_k p_k by synthetic division: q_k = z^-(k+1) * sum_{j > k} p_j z^j — the
+// combination times z^i (la.times_pow = the table of z), suffix sums in place in la.out, times z^-(k+1) into out.  Round 5 runs it twice;
+// plk_poly_divide_by_linear_dev runs it on one polynomial with the coefficient one.  totals: the scan's block totals (scan, poly.h).
+static int32_t divide_by_linear(plk_ctx *ctx, const LinCombArgs &la, const PowTable &zinv, Fr *out, hipStream_t s, DevBuf *totals) {
+    PLK_TRY(lincomb(la, s));
+    PLK_TRY(scan(ctx, la.out, la.out, la.n, true, false, s, totals));
+    return div_finish(out, la.out, zinv, la.n, s);
+}
 
-    // ---- Proof::write
+// ---- round 5: opening proofs W_z, W_zw
+static int32_t round5_openings(ProveState &P) {
+    plk_ctx *ctx = P.ctx;
+    const plk_setup *S = P.S;
+    const uint64_t N = S->N;
+    Fr *const t_ext = P.W.t_ext;
+    HFr at_z[12], at_zw[2];
+    opening_coefficients(P.at.zN, P.v, at_z, at_zw);
+    LinCombArgs la{};
+    la.n = (uint32_t)N; la.count = 12;
+    const Fr *ps[12] = {t_ext, t_ext + N, t_ext + 2 * N, t_ext + 3 * N, P.W.r_poly, P.W.w_coef[0], P.W.w_coef[1], P.W.w_coef[2], P.W.w_coef[3],
+                        S->sig_coef[0], S->sig_coef[1], S->sig_coef[2]};
+    for (int k = 0; k < 12; k++) { la.p[k] = ps[k]; la.s[k] = to_dev(to_w(at_z[k])); la.unit[k] = (k == 0); }
+    la.times_pow = P.pt_z; la.out = P.W.t1;
+    // The two quotients are independent chains of five small launches each (linear combination times z^i, suffix sums,
+    // times z^-(k+1)): the second one runs on the background lane (idle since round 3) with scratch of its own, so that
+    // the two chains overlap instead of queueing (0.14 ms of pure launch latency at the 2^20 domain).
+    LinCombArgs lb{};
+    lb.n = (uint32_t)N; lb.count = 2;
+    lb.p[0] = P.W.z_coef; lb.s[0] = to_dev(to_w(at_zw[0])); lb.p[1] = P.W.w_coef[3]; lb.s[1] = to_dev(to_w(at_zw[1]));
+    lb.times_pow = P.pt_zw;
+    lb.out = P.lane.on ? P.W.pi_coef : P.W.t1;                    // (pi_coef: free since the quotient)
+    P.lane.armed = P.lane.on;                                     // (an error below must not leave chain B writing into the arena)
+    PLK_TRY(P.lane.start_behind_main(false));                     // the power tables and r(x) come from the main stream
+    PLK_TRY(divide_by_linear(ctx, la, P.pt_zinv, P.W.t2, ctx->stream, nullptr));
+    PLK_TRY(divide_by_linear(ctx, lb, P.pt_zwinv, P.W.t3, P.lane.stream(), P.lane.on ? &ctx->poly_tmp2 : nullptr));
+    PLK_TRY(P.lane.mark_done());
+    PLK_TRY(P.lane.main_waits());
+    const Fr *opens[2] = {P.W.t2, P.W.t3};
+    HAffine oc[2];
+    PLK_TRY(commit_many(ctx, opens, 2, N, oc));
+    P.lane.armed = false;                                         // the commitments consumed t3: chain B has ended
+    P.Wz = oc[0]; P.Wzw = oc[1];
+    return PLK_OK;
+}
+
+// ---- Proof::write, and what plk_prove_trace hands out (all of it lives in ctx->prove_ws until the next proof)
+static int32_t write_proof(ProveState &P, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    const uint64_t N = P.S->N;
+    const std::vector<HFr> &inputs = P.F.inputs;
     std::vector<uint8_t> b;
-    put_u64(b, S->n);
+    put_u64(b, P.S->n);
     put_u64(b, inputs.size());
     for (const HFr &x : inputs) put_fr(b, x);
-    put_u64(b, 4); for (int j = 0; j < 4; j++) put_g1(b, wire_c[j]);
-    put_g1(b, z_c);
-    put_u64(b, 4); for (int k = 0; k < 4; k++) put_g1(b, t_c[k]);
-    put_u64(b, 4); for (int j = 0; j < 4; j++) put_fr(b, wz[j]);
-    put_u64(b, 1); put_fr(b, w3zw);
-    put_fr(b, zzw); put_fr(b, tz); put_fr(b, rz);
-    put_u64(b, 3); for (int j = 0; j < 3; j++) put_fr(b, sz[j]);
-    put_g1(b, Wz); put_g1(b, Wzw);
+    put_u64(b, 4); for (int j = 0; j < 4; j++) put_g1(b, P.wire_c[j]);
+    put_g1(b, P.z_c);
+    put_u64(b, 4); for (int k = 0; k < 4; k++) put_g1(b, P.t_c[k]);
+    put_u64(b, 4); for (int j = 0; j < 4; j++) put_fr(b, P.ev.wz()[j]);
+    put_u64(b, 1); put_fr(b, P.ev.w3zw());
+    put_fr(b, P.ev.zzw()); put_fr(b, P.ev.tz()); put_fr(b, P.ev.rz());
+    put_u64(b, 3); for (int j = 0; j < 3; j++) put_fr(b, P.ev.sz()[j]);
+    put_g1(b, P.Wz); put_g1(b, P.Wzw);
     *len = b.size();
-    {   // what plk_prove_trace hands out (all of it lives in ctx->prove_ws until the next proof)
-        plk_ctx::Trace &tr_ = ctx->trace;
-        for (int j = 0; j < 4; j++) { tr_.ptr[j] = w_coef[j]; tr_.len[j] = N; }
-        tr_.ptr[4] = z_coef; tr_.len[4] = N;
-        tr_.ptr[5] = t_ext; tr_.len[5] = M;
-        tr_.ptr[6] = r_poly; tr_.len[6] = N;
-        tr_.ptr[7] = t2; tr_.len[7] = N;
-        tr_.ptr[8] = t3; tr_.len[8] = N;
-        tr_.valid = true;
-    }
+    plk_ctx::Trace &t = P.ctx->trace;
+    const Fr *vec[9] = {P.W.w_coef[0], P.W.w_coef[1], P.W.w_coef[2], P.W.w_coef[3], P.W.z_coef, P.W.t_ext, P.W.r_poly, P.W.t2, P.W.t3};
+    for (int k = 0; k < 9; k++) { t.ptr[k] = vec[k]; t.len[k] = k == 5 ? 4 * N : N; }
+    t.valid = true;
     if (b.size() > cap) { set_error("plk_prove: proof buffer too small"); return PLK_ERR_ARG; }
     memcpy(proof_out, b.data(), b.size());
-    lap();                                                                    // [6] serialise
+    return PLK_OK;
+}
+
+// Rounds 1-5 and Proof::write, shared by plk_prove and plk_prove_assembled*: from the wire values a front end left in the workspace.
+// Every step but the first ends with a plk_prove_timings entry ([0] is the front end's).
+static int32_t prove_rounds(plk_ctx *ctx, const plk_setup *S, const ProveWs &W, ProveFront &F, uint8_t *proof_out, uint64_t cap, uint64_t *len) {
+    ProveState P{ctx, S, W, F, S->N, ctx->stream};
+    PLK_TRY(P.lane.open(ctx, S->log_n));
+    PLK_TRY(round1_wires(P));             P.lap();        // [1] beta, gamma
+    PLK_TRY(round2_grand_product(P));     P.lap();        // [2] alpha
+    PLK_TRY(round3_quotient(P));          P.lap();        // [3] z
+    PLK_TRY(round4_evaluations(P));       P.lap();        // [4] v
+    PLK_TRY(round5_openings(P));          P.lap();        // [5]
+    PLK_TRY(write_proof(P, proof_out, cap, len)); P.lap();    // [6] serialise
     return PLK_OK;
 }
 
@@ -1366,14 +1398,13 @@ int32_t plk_poly_divide_by_linear_dev(plk_ctx *ctx, const void *coeffs_dev, uint
     DevBuf tab;
     int32_t rc = tab.reserve((size_t)4 * POW_TAB * sizeof(Fr) + (size_t)n * sizeof(Fr));
     if (rc != PLK_OK) return rc;
-    PowTable pz, pzi;
-    Fr *tmp = tab.as<Fr>() + 4 * POW_TAB;
-    rc = fill_pow_table_into(ctx, to_dev(hz), tab.as<Fr>(), &pz, st);
+    PowTable pzi;
+    LinCombArgs la{};                                             // round 5's chain on the one polynomial, coefficient one
+    la.out = tab.as<Fr>() + 4 * POW_TAB; la.n = (uint32_t)n; la.count = 1;
+    la.p[0] = (const Fr *)coeffs_dev; la.unit[0] = 1;
+    rc = fill_pow_table_into(ctx, to_dev(hz), tab.as<Fr>(), &la.times_pow, st);
     if (rc == PLK_OK) rc = fill_pow_table_into(ctx, to_dev(hz.inv()), tab.as<Fr>() + 2 * POW_TAB, &pzi, st);
-    // (p(x) - p(z)) / (x - z): q_k = z^-(k+1) * sum_{j > k} p_j z^j  — the schedule of round 5
-    if (rc == PLK_OK) rc = mul_powers(tmp, (const Fr *)coeffs_dev, pz, 0, (uint32_t)n, st);
-    if (rc == PLK_OK) rc = scan(ctx, tmp, tmp, (uint32_t)n, false, true, false, st);
-    if (rc == PLK_OK) rc = div_finish((Fr *)quotient_dev, tmp, pzi, (uint32_t)n, st);
+    if (rc == PLK_OK) rc = divide_by_linear(ctx, la, pzi, (Fr *)quotient_dev, st, nullptr);
     if (hipStreamSynchronize(st) != hipSuccess && rc == PLK_OK) rc = hip_fail(hipGetLastError(), "sync", __FILE__, __LINE__);
     tab.release();
     return rc;
@@ -1388,18 +1419,10 @@ int32_t plk_permutation_grand_product_dev(plk_ctx *ctx, const void *const wires_
     DevBuf tmp;
     PLK_TRY(tmp.reserve(2 * N * sizeof(Fr)));
     HFr hb, hg; memcpy(hb.l, beta->l, 32); memcpy(hg.l, gamma->l, 32);
-    PermArgs pa;
-    pa.num = tmp.as<Fr>(); pa.den = tmp.as<Fr>() + N;
-    for (int j = 0; j < 4; j++) { pa.w[j] = (const Fr *)wires_dev[j]; pa.sigma[j] = (const Fr *)sigmas_dev[j]; pa.beta_k[j] = to_dev(hb * HFr::from_u64(NON_RESIDUES[j])); }
-    pa.beta = to_dev(hb * HFr::from_u64(32)); pa.gamma = to_dev(hg); pa.fix = to_dev(HFr::from_u64(1u << 25));
-    pa.n = (uint32_t)N; pa.log_n = log_n; pa.tw = ctx->tw_fwd_w;
-    int32_t rc = perm_terms(pa, st);
-    if (rc == PLK_OK) rc = scan_pair_mult(ctx, pa.num, pa.num, false, true, pa.den, pa.den, true, false, (uint32_t)N, st);
+    const PermArgs pa = perm_args(ctx, reinterpret_cast<const Fr *const *>(wires_dev), reinterpret_cast<const Fr *const *>(sigmas_dev), hb, hg, log_n,
+                                  tmp.as<Fr>(), tmp.as<Fr>() + N);
     HFr total;
-    if (rc == PLK_OK && hipMemcpyAsync(total.l, pa.den, sizeof(Fr), hipMemcpyDeviceToHost, st) != hipSuccess) rc = hip_fail(hipGetLastError(), "D2H", __FILE__, __LINE__);
-    if (rc == PLK_OK && hipStreamSynchronize(st) != hipSuccess) rc = hip_fail(hipGetLastError(), "sync", __FILE__, __LINE__);
-    if (rc == PLK_OK && total.is_zero()) { set_error("grand product denominator vanished"); rc = PLK_ERR_UNSAT; }
-    if (rc == PLK_OK) rc = mul3((Fr *)z_values_dev, pa.num, pa.den, to_dev(total.inv() * HFr::from_u64(32)), (uint32_t)N, st);
+    int32_t rc = grand_product(ctx, pa, (Fr *)z_values_dev, st, "grand product denominator vanished", &total, nullptr);      // round 2's own sequence
     if (hipStreamSynchronize(st) != hipSuccess && rc == PLK_OK) rc = hip_fail(hipGetLastError(), "sync", __FILE__, __LINE__);
     tmp.release();
     return rc;

@@ -327,16 +327,9 @@ int32_t plk_icoset4_coset_major_dev(plk_ctx *ctx, void *data_4n_dev, uint32_t lo
     PLK_HIP(hipSetDevice(ctx->device));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     PLK_TRY(icoset4cm_dev(ctx, (Fr *)data_4n_dev, log_n, st, 0));
-    // constants of the combine step: i^-1 (i = omega_4 = omega_4n^n) and 7^(-n c) / 4, in the 2^261 domain of the field layer
-    using host::HFr;
-    const uint64_t n = 1ull << log_n;
-    HFr w4; { Fr w = ntt_omega(2); memcpy(w4.l, w.l, 32); }
-    const HFr gN_inv = HFr::from_u64(7).pow_u64(n).inv(), two5 = HFr::from_u64(32);
-    HFr c = HFr::from_u64(4).inv();
-    Fr s_w[4], iinv;
-    { HFr t = w4.inv() * two5; memcpy(iinv.l, t.l, 32); }
-    for (int k = 0; k < 4; k++) { HFr t = c * two5; memcpy(s_w[k].l, t.l, 32); c = c * gN_inv; }
-    return icoset_combine((Fr *)data_4n_dev, (uint32_t)n, iinv, s_w, st);
+    host::HFr c[5];                                               // what round 3 of a proof caches in its setup
+    icoset_constants(log_n, c);
+    return icoset_combine_ext((Fr *)data_4n_dev, 1u << log_n, c, st);
 }
 
 int32_t plk_lde4(plk_ctx *ctx, const plk_fr *coeffs, uint32_t log_n, plk_fr *out_4n) {

@@ -4,7 +4,9 @@ tests/test_gpu_rounds.py draws every input from values below 2^252 and fixes one
 (plk_permutation_grand_product_dev, plk_poly_evaluate_at_dev, plk_poly_divide_by_linear_dev, plk_lde4_coset_major_dev,
 plk_icoset4_coset_major_dev) see the directed vectors and challenges of tests/gen/round_cases.py — stored residues r - 1, zeros that cross the
 2048-element blocks of the scans, points z with z^2048 = 1 — bit-exact against that file's Python-integer model (itself held against the oracle
-in tests/test_round_cases_host.py).  k_quotient, k_lincomb and the batched evaluation have no entry point of their own: they are reached with
+in tests/test_round_cases_host.py).  The grand-product and division entry points run the sequences of rounds 2 and 5 themselves (k_mul3_blocks
+beyond one scan block; k_lincomb with one unit term and times_pow).  k_quotient, k_lincomb's products and the batched evaluation have no entry
+point of their own: they are reached with
 whole proofs of constant-column circuits (every selector and column r - 1, or 0) through plk_setup_from_polynomials and plk_prove_assembled,
 with the oracle prover as the reference and plk_prove_trace localising a difference to a round."""
 import struct
@@ -61,10 +63,11 @@ def _grand_product(ctx, up, w, sig, beta, gamma, log_n):
 # -------------------------------------------------------------------------------- round 2: grand product
 @pytest.mark.parametrize("log_n", rc.PRODUCT_LOG_N)
 def test_grand_product_at_extreme_residues(ctx, log_n):
-    """k_perm_terms ("limbs < 3 * 2^29 feed mulw's left side"), the pair of product scans and k_mul3 on wires and sigmas of stored r - 1, of 0, of
-    residues next to r, of r - 1 alternating with 0 block by block and of all-ones 29-bit limbs, under beta, gamma from {0, 1, r - 1, r - 2, 2^253,
-    stored r - 1, stored all-ones limbs, random}.
-    2^11 is one scan block exactly, 2^12 two and 2^13 four (k_scan_totals_pair, k_scan_apply_pair).  Combinations with a vanishing denominator
+    """k_perm_terms ("limbs < 3 * 2^29 feed mulw's left side"), the pair of product scans and the closing product on wires and sigmas of stored
+    r - 1, of 0, of residues next to r, of r - 1 alternating with 0 block by block and of all-ones 29-bit limbs, under beta, gamma from {0, 1, r - 1,
+    r - 2, 2^253, stored r - 1, stored all-ones limbs, random}.  The entry point runs round 2's own sequence (grand_product, prover.hip):
+    2^11 is one scan block exactly (the scans are complete, k_mul3), 2^12 two and 2^13 four (k_scan_totals_pair leaves the block prefixes and C_0
+    behind, k_mul3_blocks folds the prefixes in).  Combinations with a vanishing denominator
     belong to test_a_vanished_denominator_is_refused; at least three quarters of the list must remain."""
     combos = rc.grand_product_combinations(log_n)
     up = _Uploads()
@@ -95,6 +98,27 @@ def test_a_zero_numerator_crosses_the_scan_blocks(ctx, log_n):
         want, zero_den = rc.grand_product(w, sig, beta, gamma, log_n)
         assert zero_den is None and all(want[:i + 1]) and not any(want[i + 1:]) and want != free
         assert np.array_equal(_grand_product(ctx, up, w, sig, beta, gamma, log_n), rc.to_array(want)), i
+
+
+def test_grand_product_on_a_caller_stream(ctx):
+    """2^12 (two scan blocks: C_0 comes back from the scans' totals in the context's scratch, the block prefixes are folded in by k_mul3_blocks)
+    on a stream that is not the context's: the entry point is the only caller of round 2's sequence that brings its own stream"""
+    import torch
+    log_n = 12
+    n = 1 << log_n
+    w = [rc.uniform(n, 61 + j) for j in range(4)]
+    sig = [rc.uniform(n, 71 + j) for j in range(4)]
+    beta, gamma = rc.uniform(2, 81)
+    want, zero_den = rc.grand_product(w, sig, beta, gamma, log_n)
+    assert zero_den is None
+    up = _Uploads()
+    d_w, d_sig = [up(v) for v in w], [up(v) for v in sig]
+    out = torch.full((n, 4), -1, dtype=torch.int64, device="cuda:0")
+    stream = torch.cuda.Stream(device="cuda:0")
+    stream.wait_stream(torch.cuda.current_stream())           # the uploads and the fill above
+    ctx.permutation_grand_product_dev(d_w, d_sig, rc.to_limbs(beta), rc.to_limbs(gamma), log_n, out, stream=stream)
+    stream.synchronize()
+    assert np.array_equal(_host(out), rc.to_array(want))
 
 
 def test_a_vanished_denominator_is_refused(ctx):
@@ -132,7 +156,8 @@ def _divide(ctx, d, n, z):
 
 @pytest.mark.parametrize("n", [1, 2, 8, 2047, 2048, 2049, 4096, (1 << 17) + 1])
 def test_evaluation_and_division_at_directed_coefficients_and_points(ctx, n):
-    """k_eval_partial (Horner on raw sums, then x^start per thread and block), k_mul_powers, the suffix sum scan and k_div_finish: every directed
+    """k_eval_partial (Horner on raw sums, then x^start per thread and block), and round 5's division chain (divide_by_linear, prover.hip) on one
+    polynomial with the coefficient one — k_lincomb with its times_pow branch, the suffix sum scan and k_div_finish: every directed
     vector at every point of {1, r - 1, 2, 1/2, omega_n, omega_2048, a generator of the 2^28 subgroup, r - 2, random} up to 4096 coefficients, one
     point per vector in turn at 2^17 + 1 (65 blocks); z = 0 gives c_0 for the evaluation and PLK_ERR_ARG for the division"""
     import plonkit_amd as pa

@@ -4,6 +4,9 @@ only covered through whole-proof byte parity).
   a7  permutation grand product (round 2)            plk_permutation_grand_product_dev  vs  the oracle's vector ops
   a8  quotient (round 3: fused numerator / Z_H, coset iNTT(4N))   plk_prove_trace(5)    vs  the oracle prover's t(x)
   a9  evaluations, linearisation, openings (4, 5)    plk_poly_evaluate_at_dev, plk_poly_divide_by_linear_dev, plk_prove_trace(6..8)
+The two direct entry points of rounds 2 and 5 call the functions the rounds call (prover.hip: grand_product — the scans stop after their second
+phase beyond one block of 2048 and k_mul3_blocks folds the block prefixes in, k_mul3 up to one block; divide_by_linear — k_lincomb with one unit
+term and times_pow, the suffix sum scan, k_div_finish).
 The reference counterparts live in bellman_ce's better_cs prover behind prove_by_steps (src/plonk.rs:152-159); the formulas
 are those of SURVEY.md Appendix A.4, restated in oracle/plonk_oracle.py (pinned by the golden proof)."""
 import json
