@@ -28,6 +28,7 @@ struct alignas(16) XyzzW { FqW9 x, y, zz, zzz; };              // 144 bytes
 #define WMA(a, b, c, d) mul2addw<FqW>((a), (b), (c), (d))  // a*b + c*d, one reduction
 // the latency-bound chains (full addition, doubling: bucket reduction, table build) take the operand-scanning forms
 #define WMA_LZ(a, b, c, d) mul2addw_lz<FqW, LZ_ALL, LbNorm, LbT, LbNorm, LbNppp>((a), (b), (c), (d))   // the fused Y3 of the work-priced additions
+#define WMA_LZF(a, b, c, d, FD) mul2addw_lz<FqW, LZ_ALL, LbNorm, LbT, LbNorm, LbNppp, (FD)>((a), (b), (c), (d))   // the same with the digits of FD folded
 #define LM(a, b) mulw_os<FqW>((a), (b))
 #define LS(a) sqrw_os<FqW>((a))
 #define LMA(a, b, c, d) mul2addw_os<FqW>((a), (b), (c), (d))
@@ -151,6 +152,16 @@ PLK_HD void xyzzw_add_mixed(XyzzW &acc, const AffW &q, bool neg_q) {
 // PP are normalised (out of a column chain or normw), A_PP is LbTw2A; worst column 0.43 * 2^64, checked at compile time.  Values: a tw2 result is below
 // z w / 2^261 + A / 2^29 + p (1 + 2^-26), i.e. the bound of the mulw2_lz it replaces + 2^-28 p: PPP < 1.06, Q < 1.05, ZZ3 < 1.01 as in the table above
 // (tests/host/field29_shared_factor_check.hip: chains of 250 additions from accumulators at the coordinate bounds, this form beside <true, false>).
+// FOLDED DIGITS (with SF, i.e. in <true, true> only; field29_dev.h, "THE FOLD"): the low digits of all ten reductions are divided out by FqW::FOLDC = 2^-29 mod p
+// + 2p instead of a Montgomery step - digits 0..6 of the six nine-digit reductions (FOLD9: the pair (P, R), the squaring pair, ZZZ3 beside ZZ3, the fused Y3),
+// 0..2 of the three tw2 chains (FOLD_TW2), 0..1 of A_PP (FOLD_TW2A): 53 of the 74 v_mul_lo_u32 of an addition are not issued, and the column shift of a
+// folded digit is a multiply-add of the accumulator's high word by eight.  Values: a folded reduction's result is below the unfolded form's bound
+// + 2^32 FOLDC / 2^58 (1 + 2^-28) < + 2.15 * 2^-26 p, so every product here is below its figure in the table at the top + 3.2 * 2^-26 p (lazy and folded
+// together): U2, S2 < 1.02, PP < 1.3, PPP < 1.06, Q < 1.05, ZZ3, ZZZ3 < 1.01, NY3 < 1.5, P < 6.1 and R < 9.1 of maybe_zero_mod_p's 16 - no bound above notices.
+// The integers are the unfolded form's unless a result crosses a multiple of p in that margin (then they differ by p; about once in 2^25 products).
+// Columns, exact worst cases at the declared bounds (checked at compile time): 0.426 * 2^64 for the normalised products and squarings (0.501 unfolded),
+// 0.848 for the +-y chain with its addend (0.923), 0.771 for Y3 (0.845), 0.372 for tw2 (0.425), 0.181 for A_PP (0.211): FOLDC's limbs are smaller than p's.
+// tests/host/field29_fold_check.hip: every folded form against mulw, and chains of 250 additions of this form beside the unfolded one.
 PLK_HD XyzzW xyzzw_flip_xy(const XyzzW &a) { XyzzW r = a; r.x = sub6(w_zero<FqW>(), a.x); r.y = sub6(w_zero<FqW>(), a.y); return r; }
 template <bool NXY, bool SF = false>
 PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bool neg_q) {
@@ -159,10 +170,11 @@ PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bo
         else { acc.x = q.x; acc.y = neg_q ? neg2(q.y) : q.y; }
         acc.zz = w_one<FqW>(); acc.zzz = w_one<FqW>(); fresh = false; return;
     }
+    constexpr unsigned F9 = SF ? FOLD9 : 0u, F5 = SF ? FOLD_TW2 : 0u, F4 = SF ? FOLD_TW2A : 0u;   // the fold sets of the nine-, five- and four-digit reductions
     FqW9 p, r, yq;
 #pragma unroll
     for (int i = 0; i < 9; i++) yq.l[i] = neg_q ? FqW::PAD2[i] - q.y.l[i] : q.y.l[i];           // 2p - y (limbs <= 2.63e9 < MULW_A_LIMB_MAX, value < 2p) or y
-    if constexpr (NXY) mulw2_add_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbSignedY, LbNorm, LbNorm>(q.x, acc.zz, acc.x, yq, acc.zzz, acc.y, p, r);   // P = U2 + NX,  R = S2 + NY
+    if constexpr (NXY) mulw2_add_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbSignedY, LbNorm, LbNorm, F9>(q.x, acc.zz, acc.x, yq, acc.zzz, acc.y, p, r);   // P = U2 + NX,  R = S2 + NY
     else {
         FqW9 ax, ay;
 #pragma unroll
@@ -181,11 +193,11 @@ PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bo
         return;
     }
     FqW9 pp, rr, ppp, qq;
-    sqrw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm>(p, r, pp, rr);
+    sqrw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, F9>(p, r, pp, rr);
     FqW9 a_pp;
     if constexpr (SF) {
-        a_pp = make_tw2_a<FqW>(pp);
-        mul_tw2_2<FqW, TW2_LZ_ALL, TW2_LZ_ALL>(p, a_pp, pp, acc.x, a_pp, pp, ppp, qq);
+        a_pp = make_tw2_a<FqW, TW2A_LZ_ALL, LbNorm, F4>(pp);
+        mul_tw2_2<FqW, TW2_LZ_ALL, TW2_LZ_ALL, LbNorm, LbNorm, LbTw2A, LbNorm, F5>(p, a_pp, pp, acc.x, a_pp, pp, ppp, qq);
     } else
     mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(p, pp, acc.x, pp, ppp, qq);            // (NXY: qq = NQ = -Q)
     FqW9 x3;
@@ -196,13 +208,13 @@ PLK_HD void xyzzw_add_mixed_flag_impl(XyzzW &acc, bool &fresh, const AffW &q, bo
     }
     FqW9 zz3, zzz3;
     if constexpr (SF) {
-        mul_tw2_mulw<FqW, TW2_LZ_ALL, LZ_ALL>(acc.zz, a_pp, pp, acc.zzz, ppp, zz3, zzz3);
+        mul_tw2_mulw<FqW, TW2_LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbTw2A, LbNorm, F5, F9>(acc.zz, a_pp, pp, acc.zzz, ppp, zz3, zzz3);
     } else
     mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(acc.zz, pp, acc.zzz, ppp, zz3, zzz3);
     FqW9 t, nppp;
 #pragma unroll
     for (int i = 0; i < 9; i++) { t.l[i] = qq.l[i] + FqW::PAD6N[i] - x3.l[i]; nppp.l[i] = FqW::PAD2N[i] - ppp.l[i]; }
-    acc.y = WMA_LZ(r, t, acc.y, nppp);                        // R*(Q - X3) - Y*PPP, one reduction (NXY: R*(NQ - NX3) - NY*PPP = NY3)
+    acc.y = WMA_LZF(r, t, acc.y, nppp, F9);                   // R*(Q - X3) - Y*PPP, one reduction (NXY: R*(NQ - NX3) - NY*PPP = NY3)
     acc.x = x3;
     acc.zz = zz3;
     acc.zzz = zzz3;
@@ -258,17 +270,22 @@ PLK_HD void xyzzw_add(XyzzW &a, const XyzzW &b) {
 //   - Lazy Montgomery digits in all thirteen reductions (LZ_ALL, 104 v_and_b32 fewer): the normalised operands above are LbNorm, the addends
 //     LbAny, T and 2p - PPP LbT and LbNppp; worst columns as in xyzzw_add_mixed_flag (0.50 * 2^64 normalised, 0.85 * 2^64 for Y3), checked at
 //     compile time.  Values grow by less than 2^-26 p per product: is_zero_mod_p's a < 16p holds with P, R < 3.05p as before.
-// Values: U, S < 6 * 1.3 * 0.0059p + p < 1.05p; PP < 3.05^2 * 0.0059p + p < 1.06p; X3 < 5.06p; Y3 < (3.05 * 7.1 + 1.05 * 2) * 0.0059p + p < 1.2p.
+//   - Folded digits (field29_dev.h, "THE FOLD"): digits 0..6 of all thirteen reductions (FOLD9) are divided out by FqW::FOLDC instead of a Montgomery step, 91
+//     v_mul_lo_u32 fewer; each result is below the lazy form's bound + 2.15 * 2^-26 p, and its integer is the lazy form's unless it crosses a multiple of p in
+//     that margin - tests/host/field29_pairs_check.hip still finds xyzzw_add's integers in all of its 10^5 cases.  Worst columns 0.426 * 2^64 (normalised
+//     products, squarings, the pair with its LbAny addends) and 0.771 (Y3), checked at compile time; tests/host/field29_fold_check.hip holds chains of 250 of
+//     these additions beside the unfolded form.
+// Values: U, S < 6 * 1.3 * 0.0059p + p < 1.05p; PP < 3.05^2 * 0.0059p + p < 1.06p; X3 < 5.06p; Y3 < (3.05 * 7.1 + 1.05 * 2) * 0.0059p + p < 1.2p (each + 3.2 * 2^-26 p).
 PLK_HD void xyzzw_add_pairs(XyzzW &a, const XyzzW &b) {
     if (is_inf(b)) return;
     if (is_inf(a)) { a = b; return; }
     FqW9 u1, s1, p, r;
-    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(a.x, b.zz, a.y, b.zzz, u1, s1);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm, FOLD9>(a.x, b.zz, a.y, b.zzz, u1, s1);
     {
         FqW9 nu, ns;
 #pragma unroll
         for (int i = 0; i < 9; i++) { nu.l[i] = FqW::PAD2[i] - u1.l[i]; ns.l[i] = FqW::PAD2[i] - s1.l[i]; }     // 2p - U1, 2p - S1: not normalised
-        mulw2_add_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbAny, LbNorm, LbNorm, LbAny>(b.x, a.zz, nu, b.y, a.zzz, ns, p, r);
+        mulw2_add_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbAny, LbNorm, LbNorm, LbAny, FOLD9>(b.x, a.zz, nu, b.y, a.zzz, ns, p, r);
     }
     if (is_zero_mod_p(p)) {
         if (is_zero_mod_p(r)) a = xyzzw_double(a);
@@ -276,14 +293,14 @@ PLK_HD void xyzzw_add_pairs(XyzzW &a, const XyzzW &b) {
         return;
     }
     FqW9 zz12, zzz12;
-    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(a.zz, b.zz, a.zzz, b.zzz, zz12, zzz12);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm, FOLD9>(a.zz, b.zz, a.zzz, b.zzz, zz12, zzz12);
     FqW9 pp, rr, ppp, qq;
     // (P and R are hidden from the optimiser here: knowing from the chain's masks that their limbs are below 2^29, it widens the squarings'
     //  doubled limbs "x << 1" to 33-bit values and pays two multiply-adds and two moves for each of ~100 products)
 #pragma unroll
     for (int i = 0; i < 9; i++) { PLK_CHAIN(p.l[i]); PLK_CHAIN(r.l[i]); }
-    sqrw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm>(p, r, pp, rr);
-    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(p, pp, u1, pp, ppp, qq);
+    sqrw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, FOLD9>(p, r, pp, rr);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm, FOLD9>(p, pp, u1, pp, ppp, qq);
     FqW9 x3;
     {
 #pragma unroll
@@ -293,9 +310,9 @@ PLK_HD void xyzzw_add_pairs(XyzzW &a, const XyzzW &b) {
     FqW9 t, nppp;
 #pragma unroll
     for (int i = 0; i < 9; i++) { t.l[i] = qq.l[i] + FqW::PAD6N[i] - x3.l[i]; nppp.l[i] = FqW::PAD2N[i] - ppp.l[i]; }
-    a.y = WMA_LZ(r, t, s1, nppp);                             // R*(Q - X3) - S1*PPP, one reduction
+    a.y = WMA_LZF(r, t, s1, nppp, FOLD9);                     // R*(Q - X3) - S1*PPP, one reduction
     a.x = x3;
-    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm>(zz12, pp, zzz12, ppp, a.zz, a.zzz);
+    mulw2_lz<FqW, LZ_ALL, LZ_ALL, LbNorm, LbNorm, LbNorm, LbNorm, FOLD9>(zz12, pp, zzz12, ppp, a.zz, a.zzz);
 }
 
 // storage <-> registers

@@ -42,6 +42,9 @@ struct FrW {
     static constexpr uint32_t PAD4[9] = {0x80000004u, 0x9c3eb27au, 0x9970913fu, 0x9f4243c9u, 0x96174a08u, 0x8b6d02feu, 0x829b8500u, 0x997098ccu, 0x00c19135u};
     static constexpr uint32_t PAD6[9] = {0x80000006u, 0x9a5e0bb9u, 0x9628d9e1u, 0x8ee365b0u, 0x8122ef0fu, 0x91238480u, 0x83e94782u, 0x9628e534u, 0x012259d2u};
     static constexpr uint32_t PAD8[9] = {0x80000008u, 0x987d64f8u, 0x92e12283u, 0x9e848797u, 0x8c2e9415u, 0x96da0601u, 0x85370a04u, 0x92e1319cu, 0x0183226fu};
+    // 2^-29 mod p for the folded digits (below, "THE FOLD"); (p + 1) / 2 with no multiple of p added: no form of this field folds yet, and of the
+    // representatives below 4p (the value rule) this one has the smallest worst columns (0.65 * 2^64 for normalised products)
+    static constexpr uint32_t FOLDC[9] = {0x18f05361u, 0x012bb1feu, 0x0f5d8135u, 0x1e6275f6u, 0x07e7a880u, 0x10c6bf1fu, 0x11f74a6cu, 0x06fdaecbu, 0x00183227u};
 };
 
 struct FqW {
@@ -60,6 +63,11 @@ struct FqW {
     // it stands (xyzzw_add_mixed_flag; the 2^31 bias of the pads above is what a subtrahend with limbs up to 2^30 needs)
     static constexpr uint32_t PAD2N[9] = {0x30f9fa8eu, 0x2208c16cu, 0x38e5469du, 0x25aa45a0u, 0x2b0bb2efu, 0x25b68180u, 0x214dc281u, 0x3cb84c67u, 0x0060c89bu};
     static constexpr uint32_t PAD6N[9] = {0x32edefaau, 0x261a4447u, 0x2aafd3d9u, 0x30fed0e4u, 0x212318cfu, 0x31238483u, 0x23e94785u, 0x3628e537u, 0x012259d5u};
+    // 2^-29 mod p + 2p = 2.1414 p for the folded digits (below, "THE FOLD").  Of the 170 representatives below 2^261 this one has by far the smallest
+    // limbs (they sum to 1.03e9 against 1.62e9 for p's) and the smallest worst column in every form that folds: 0.426 * 2^64 for normalised products
+    // and squarings (0.501 unfolded), 0.848 for the +-y chain with its addend (0.923), 0.771 for the fused Y3 (0.845), 0.372 for tw2 (0.425), 0.181
+    // for make_tw2_a (0.211); the next best representative (+ 100p) reaches 0.919 and adds fifty times as much to a result.
+    static constexpr uint32_t FOLDC[9] = {0x0872952du, 0x0808854au, 0x065124e0u, 0x029b9885u, 0x03f6b850u, 0x148e9764u, 0x02b3e954u, 0x0843f777u, 0x0067a061u};
 };
 
 template <class WP>
@@ -167,14 +175,32 @@ template <class WP> PLK_HD W9<WP> addn(const W9<WP> &a, const W9<WP> &b) { retur
 //     the actual limbs of p; the addend where there is one; the carry the worst column before it really leaves) and a static_assert
 //     requires every column below 2^64: a form that does not fit does not compile.  The declared bounds are the caller's promise, checked
 //     on the host at exactly those limbs (tests/host/field29_check.hip, field29_addend_check.hip, field29_lazy_digits_check.hip).
+// THE FOLD.  A Montgomery digit costs one v_mul_lo_u32, as much as a multiply-add, only to find the multiple of p that clears the column.  The same
+// division by 2^29 needs no such product: with C = 2^-29 (mod p) (WP::FOLDC, nine limbs below 2^29) and L the low word of column k's accumulator,
+// L 2^(29 k) = L C 2^(29 (k + 1)) (mod p), so the column is emptied by REMOVING L and adding L * C[j] to columns k + 1 + j, j = 0..8: nine multiply-adds,
+// as many as m_k * p takes (the term in column k goes, one in column k + 9 comes).  FOLD is the set of digits treated so (bit k for digit k; 0 is the
+// text above).  For a folded digit: digit(k) is the accumulator's low register as it stands where the digit is also in LZ - no product, no mask,
+// L < 2^32, and the carry into column k + 1 is (acc - L) / 2^29 = (acc >> 32) << 3 - and acc & M29 with the usual acc >> 29 otherwise; mp0(k) is
+// nothing; column k' > k takes m[k] * FOLDC[k' - k - 1] where it took m[k] * P29[k' - k].
+//   - the VALUE.  L * C is not small as m * p / 2^29 < p is: digit k of D adds L C / 2^(29 (D - 1 - k)) to the result.  So only a PREFIX 0..f-1 with
+//     f <= D - 2 folds: every folded digit is then divided by at least 2^58 and the set adds less than 2^32 C / 2^58 (1 + 2^-28) = (C / p) 2^-26 p
+//     (1 + 2^-28); the last two digits stay Montgomery digits (the last one masked) and bound the result as before.  fold_value_ok requires the
+//     prefix and (C / p) 2^-26 (1 + 2^-28) <= 2^-24 by static_assert in every form: a set with digit D - 2 or D - 1, or with a gap, does not compile.
+//     With FqW::FOLDC = 2.1414 p a folded reduction's result is below the lazy form's bound + 2.15 * 2^-26 p.
+//   - the COLUMN.  lazy_col_bound, tw2_col_bound and tw2a_col_bound take the folded digits (2^32 - 1 unmasked, 2^29 - 1 masked) against FOLDC's limbs
+//     one column up, and the carry as acc >> 29, which (acc >> 32) << 3 never exceeds; the same static_assert refuses a form that does not fit.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PLK_CHAIN(acc) asm("" : "+v"(acc))
 // (the addend enters as a multiply-add by a one the compiler cannot see: the plain 64-bit addition it would otherwise form wants the
 //  addend widened to a register pair, one extra move per limb)
 #define PLK_ADDEND(acc, x) { uint32_t one_ = 1; asm("" : "+s"(one_)); (acc) += (uint64_t)(x) * one_; }
+// (the carry out of a folded unmasked digit, (acc >> 32) << 3, as ONE instruction: the high register times an eight the compiler cannot see, a
+//  multiply-add onto zero that costs what the v_lshrrev_b64 of a Montgomery digit costs; written as shifts it becomes that shift and two masks)
+#define PLK_FOLD_CARRY(acc) { uint32_t eight_ = 8; asm("" : "+s"(eight_)); (acc) = (uint64_t)(uint32_t)((acc) >> 32) * eight_; }
 #else
 #define PLK_CHAIN(acc) do { } while (0)
 #define PLK_ADDEND(acc, x) { (acc) += (uint64_t)(x); }
+#define PLK_FOLD_CARRY(acc) { (acc) = (uint64_t)(uint32_t)((acc) >> 32) << 3; }
 #endif
 struct Limbs9 { uint32_t l[9]; };                              // per-limb upper bounds of an operand (inclusive)
 constexpr Limbs9 lb_uniform(uint32_t v) { return Limbs9{{v, v, v, v, v, v, v, v, v}}; }
@@ -192,8 +218,10 @@ constexpr bool lazy_digit(unsigned lz, int k) { return k < 8 && ((lz >> k) & 1u)
 struct ColBound { uint64_t worst; bool fits; };                // the largest column (wrapped if it does not fit); all columns below 2^64
 // columns of a*b + c*d + e*f + m~*p (+ addend in the high columns), m~ with the digits of lz unmasked.  A squaring is a = b = the operand's
 // bounds: the doubled cross products and the square of a column sum to the same worst case.
+// fold: the set of folded digits and fc the limbs of 2^-29 mod p they are multiplied by (digit i: fc[j] in column i + 1 + j, nothing in column i)
+constexpr bool fold_digit(unsigned fold, int k) { return k >= 0 && k < 32 && ((fold >> k) & 1u); }
 constexpr ColBound lazy_col_bound(const Limbs9 &a, const Limbs9 &b, const Limbs9 &c, const Limbs9 &d, const Limbs9 &addend, const uint32_t (&p)[9], unsigned lz,
-                                  const Limbs9 &e = LbNone::B, const Limbs9 &f = LbNone::B) {
+                                  const Limbs9 &e = LbNone::B, const Limbs9 &f = LbNone::B, unsigned fold = 0, const Limbs9 &fc = LbNone::B) {
     uint64_t carry = 0, worst = 0;
     bool fits = true;
     for (int k = 0; k < 17; k++) {
@@ -202,8 +230,10 @@ constexpr ColBound lazy_col_bound(const Limbs9 &a, const Limbs9 &b, const Limbs9
             fits &= !__builtin_add_overflow(s, (uint64_t)a.l[k - i] * b.l[i], &s);
             fits &= !__builtin_add_overflow(s, (uint64_t)c.l[k - i] * d.l[i], &s);
             fits &= !__builtin_add_overflow(s, (uint64_t)e.l[k - i] * f.l[i], &s);
-            fits &= !__builtin_add_overflow(s, (uint64_t)(lazy_digit(lz, i) ? 0xffffffffu : M29) * p[k - i], &s);
+            if (!fold_digit(fold, i)) fits &= !__builtin_add_overflow(s, (uint64_t)(lazy_digit(lz, i) ? 0xffffffffu : M29) * p[k - i], &s);
         }
+        for (int i = 0; i < 9; i++)
+            if (fold_digit(fold, i) && k - i - 1 >= 0 && k - i - 1 <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)(lazy_digit(lz, i) ? 0xffffffffu : M29) * fc.l[k - i - 1], &s);
         if (k >= 9) fits &= !__builtin_add_overflow(s, (uint64_t)addend.l[k - 9], &s);
         if (s > worst) worst = s;
         carry = s >> 29;
@@ -211,37 +241,85 @@ constexpr ColBound lazy_col_bound(const Limbs9 &a, const Limbs9 &b, const Limbs9
     return ColBound{worst, fits};
 }
 #define PLK_LZ_DIGIT(LZ, k, acc) (lazy_digit((LZ), (k)) ? (uint32_t)(acc) * WP::INV29 : ((uint32_t)(acc) * WP::INV29) & M29)
+// a fold set of a reduction of D digits is sound: a prefix 0..f-1, f <= D - 2 (each folded digit divided by 2^58 or more), and what the set can add to
+// the result, below 2^32 (C_8 + 1) 2^232 / 2^58 (1 + 2^-28), at most 2^-24 p, p >= p_8 2^232:  (C_8 + 1) (2^28 + 1) <= p_8 2^30
+constexpr bool fold_value_ok(unsigned fold, int digits, const uint32_t (&c)[9], const uint32_t (&p)[9]) {
+    if (fold == 0) return true;
+    if ((fold & (fold + 1)) != 0) return false;
+    int f = 0;
+    while ((fold >> f) & 1u) f++;
+    return f <= digits - 2 && ((uint64_t)c[8] + 1) * ((1ull << 28) + 1) <= ((uint64_t)p[8] << 30);
+}
+// c is 2^-29 mod p as nine limbs below 2^29: c 2^29 - 1 = q p with q < 2^58, whose two digits follow from the low limbs (q_k = n_k / p mod 2^29, as
+// in an exact division from the low end); what is left after q p is taken away must be zero
+constexpr bool foldc_ok(const uint32_t (&c)[9], const uint32_t (&p)[9], uint32_t pinv0) {
+    int64_t n[12] = {};
+    for (int i = 0; i < 9; i++) { if (c[i] > M29) return false; n[i + 1] = c[i]; }
+    n[0] = -1;
+    for (int i = 0; i < 11; i++) { int64_t cy = n[i] >> 29; n[i] &= (int64_t)M29; n[i + 1] += cy; }   // normalise c 2^29 - 1 (non-negative: c > 0)
+    for (int k = 0; k < 2; k++) {
+        const int64_t q = (int64_t)(((uint64_t)n[k] * pinv0) & M29);
+        int64_t cy = 0;
+        for (int j = k; j < 12; j++) {
+            const int64_t s = n[j] - (j - k < 9 ? q * (int64_t)p[j - k] : 0) + cy;
+            n[j] = s & (int64_t)M29;
+            cy = s >> 29;
+            if (j == 11) n[j] = s;
+        }
+    }
+    for (int i = 0; i < 12; i++) if (n[i] != 0) return false;
+    return true;
+}
+static_assert(foldc_ok(FqW::FOLDC, FqW::P29, FqW::PINV0), "FqW::FOLDC is not 2^-29 mod p below 2^261");
+static_assert(foldc_ok(FrW::FOLDC, FrW::P29, FrW::PINV0), "FrW::FOLDC is not 2^-29 mod p below 2^261");
+#define PLK_FOLD_MSG "a fold set is a prefix of the digits short of the last two, and adds at most 2^-24 p to the result"
 
 // the second chain of a scan that has only one: every step is nothing
 struct NoChain {
     static constexpr bool FITS = true;
+    static constexpr bool FOLD_OK = true;
+    static constexpr unsigned FOLD = 0;
     uint32_t m[9];
     uint64_t acc;
     PLK_HD void mad(uint64_t, uint32_t) {}
+    PLK_HD void mp(int, int) {}
     PLK_HD void digit(int) {}
     PLK_HD void mp0(int) {}
     PLK_HD void addend(int) {}
     PLK_HD void limb(int) {}
-    PLK_HD void shift() {}
+    PLK_HD void shift(int) {}
     PLK_HD void top() {}
 };
 // one accumulator chain of the scan: its operand half, its result, its addend if LAD is not LbNone (limb j joins the accumulator at
 // column 9 + j, after the column's m*p terms and before output limb j is cut off), its digits and its accumulator
-template <class WP, unsigned LZ, class H, class LAD = LbNone>
+// (FLD: the set of folded digits, "THE FOLD" above; mp(k, i) is digit i's term of column k > i, m_i * p_(k-i) or, folded, m_i * C_(k-i-1))
+template <class WP, unsigned LZ, class H, class LAD = LbNone, unsigned FLD = 0>
 struct MontChain {
     using Half = H;
+    static constexpr unsigned FOLD = FLD;
     static constexpr bool ADD = !std::is_same<LAD, LbNone>::value;
-    static constexpr bool FITS = H::bound(LAD::B, LZ).fits;
+    static constexpr bool FITS = H::bound(LAD::B, LZ, FLD).fits;
+    static constexpr bool FOLD_OK = fold_value_ok(FLD, 9, WP::FOLDC, WP::P29);
     H h;
     const W9<WP> *A = nullptr;
     W9<WP> *r = nullptr;
     uint32_t m[9];
     uint64_t acc = 0;
     PLK_HD void mad(uint64_t a, uint32_t b) { acc += a * b; PLK_CHAIN(acc); }
-    PLK_HD void digit(int k) { m[k] = PLK_LZ_DIGIT(LZ, k, acc); }
-    PLK_HD void mp0(int k) { acc += (uint64_t)m[k] * WP::P29[0]; }
+    PLK_HD void mp(int k, int i) {
+        if (fold_digit(FLD, i)) mad(m[i], WP::FOLDC[k - i - 1]);
+        else if (k - i <= 8) mad(m[i], WP::P29[k - i]);
+    }
+    PLK_HD void digit(int k) {
+        if (fold_digit(FLD, k)) m[k] = lazy_digit(LZ, k) ? (uint32_t)acc : (uint32_t)acc & M29;
+        else m[k] = PLK_LZ_DIGIT(LZ, k, acc);
+    }
+    PLK_HD void mp0(int k) { if (!fold_digit(FLD, k)) acc += (uint64_t)m[k] * WP::P29[0]; }
     PLK_HD void limb(int k) { r->l[k - 9] = (uint32_t)acc & M29; }
-    PLK_HD void shift() { acc >>= 29; }
+    PLK_HD void shift(int k) {
+        if (fold_digit(FLD, k) && lazy_digit(LZ, k)) PLK_FOLD_CARRY(acc)
+        else acc >>= 29;
+    }
     PLK_HD void addend(int k) { if constexpr (ADD) PLK_ADDEND(acc, A->l[k - 9]); }
     PLK_HD void top() { r->l[8] = (uint32_t)acc; if constexpr (ADD) r->l[8] += A->l[8]; }
 };
@@ -261,9 +339,9 @@ struct Products {
     template <class C> static PLK_HD void prepare(C &, int) {}
     template <class C> static PLK_HD void last(C &, int) {}
     template <bool LOW> static PLK_HD bool has_last(int) { return false; }
-    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz) {
+    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz, unsigned fold = 0) {
         const Limbs9 b[6] = {L::B...};                         // (the pairs that are not there: zeros)
-        return lazy_col_bound(b[0], b[1], b[2], b[3], addend, WP::P29, lz, b[4], b[5]);
+        return lazy_col_bound(b[0], b[1], b[2], b[3], addend, WP::P29, lz, b[4], b[5], fold, lb_of(WP::FOLDC));
     }
 };
 // x^2: the cross products x_i*x_j (i < j) are taken once against the doubled operand, then the square on an even column: 45 + 81
@@ -280,7 +358,9 @@ struct Squaring {
     template <class C> static PLK_HD void prepare(C &c, int j) { if constexpr (!std::is_same<C, NoChain>::value) c.h.d[j] = c.h.x.l[j] << 1; }
     template <class C> static PLK_HD void last(C &c, int k) { if constexpr (!std::is_same<C, NoChain>::value) c.mad(c.h.x.l[k / 2], c.h.x.l[k / 2]); }
     template <bool LOW> static PLK_HD bool has_last(int k) { return k % 2 == 0; }
-    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz) { return lazy_col_bound(LX::B, LX::B, LbNone::B, LbNone::B, addend, WP::P29, lz); }
+    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz, unsigned fold = 0) {
+        return lazy_col_bound(LX::B, LX::B, LbNone::B, LbNone::B, addend, WP::P29, lz, LbNone::B, LbNone::B, fold, lb_of(WP::FOLDC));
+    }
 };
 // x * 2^5 (canonical_w): x_k << 5 in column k — nine shifts, no multiply-add.  As a product it is x times the limbs (32, 0, ..., 0).
 template <class WP>
@@ -291,7 +371,9 @@ struct Shift5 {
     template <class C> static PLK_HD void prepare(C &, int) {}
     template <class C> static PLK_HD void last(C &c, int k) { if constexpr (!std::is_same<C, NoChain>::value) c.acc += (uint64_t)c.h.x.l[k] << 5; }
     template <bool LOW> static PLK_HD bool has_last(int) { return LOW; }
-    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz) { return lazy_col_bound(LbNorm::B, Limbs9{{32}}, LbNone::B, LbNone::B, addend, WP::P29, lz); }
+    static constexpr ColBound bound(const Limbs9 &addend, unsigned lz, unsigned fold = 0) {
+        return lazy_col_bound(LbNorm::B, Limbs9{{32}}, LbNone::B, LbNone::B, addend, WP::P29, lz, LbNone::B, LbNone::B, fold, lb_of(WP::FOLDC));
+    }
 };
 // THE scan.  Order is the contract (it is what the schedule and the register count of every hot kernel hang on): inside a column every
 // step goes chain 0, chain 1 — the operand half's terms one by one, the m*p terms one by one, then both digits, both m*p_0, both
@@ -302,6 +384,7 @@ template <class WP, class C0, class C1 = NoChain>
 PLK_HD auto mont_scan(const C0 &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr, W9<WP> *r1 = nullptr) {
     static_assert(C0::FITS, "a column of chain 0 can exceed 64 bits");
     static_assert(C1::FITS, "a column of chain 1 can exceed 64 bits");
+    static_assert(C0::FOLD_OK && C1::FOLD_OK, PLK_FOLD_MSG);
     using H = typename C0::Half;
     constexpr bool ONE = std::is_same<C1, NoChain>::value;     // one chain: the result is returned; two: written to r0, r1
     W9<WP> r;
@@ -317,10 +400,10 @@ PLK_HD auto mont_scan(const C0 &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr, W
         for (int i = 0; H::more(k, i, k); i++) { H::template term<0>(c0, k, i); H::template term<0>(c1, k, i); H::template term<1>(c0, k, i); H::template term<1>(c1, k, i); H::template term<2>(c0, k, i); H::template term<2>(c1, k, i); }
         if (H::template has_last<true>(k)) { H::last(c0, k); H::last(c1, k); }
 #pragma unroll
-        for (int i = 0; i < k; i++) { c0.mad(c0.m[i], WP::P29[k - i]); c1.mad(c1.m[i], WP::P29[k - i]); }
+        for (int i = 0; i < k; i++) { c0.mp(k, i); c1.mp(k, i); }
         c0.digit(k); c1.digit(k);
         c0.mp0(k); c1.mp0(k);
-        c0.shift(); c1.shift();
+        c0.shift(k); c1.shift(k);
     }
 #pragma unroll
     for (int k = 9; k < 17; k++) {
@@ -328,25 +411,26 @@ PLK_HD auto mont_scan(const C0 &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr, W
         for (int i = k - 8; H::more(k, i, 8); i++) { H::template term<0>(c0, k, i); H::template term<0>(c1, k, i); H::template term<1>(c0, k, i); H::template term<1>(c1, k, i); H::template term<2>(c0, k, i); H::template term<2>(c1, k, i); }
         if (H::template has_last<false>(k)) { H::last(c0, k); H::last(c1, k); }
 #pragma unroll
-        for (int i = k - 8; i <= 8; i++) { c0.mad(c0.m[i], WP::P29[k - i]); c1.mad(c1.m[i], WP::P29[k - i]); }
+        for (int i = k - 9; i <= 8; i++) { c0.mp(k, i); c1.mp(k, i); }   // (i = k - 9: a folded digit's last term; nothing for a Montgomery digit)
         c0.addend(k); c1.addend(k);
         c0.limb(k); c1.limb(k);
-        c0.shift(); c1.shift();
+        c0.shift(k); c1.shift(k);
     }
     c0.top(); c1.top();
     if constexpr (ONE) return r;
 }
 
-// ---- the forms with lazy digits.  LA, LB, ...: the declared limb bounds of the operands, in the order of the arguments.
+// ---- the forms with lazy digits.  LA, LB, ...: the declared limb bounds of the operands, in the order of the arguments.  FD: the fold set of
+// the form's chains (0: none folded).
 // mulw2: two independent products in lockstep
-template <class WP, unsigned LZ0, unsigned LZ1, class LA0, class LB0, class LA1, class LB1>
+template <class WP, unsigned LZ0, unsigned LZ1, class LA0, class LB0, class LA1, class LB1, unsigned FD = 0>
 PLK_HD void mulw2_lz(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &a1, const W9<WP> &b1, W9<WP> &r0, W9<WP> &r1) {
-    mont_scan<WP>(MontChain<WP, LZ0, Products<WP, LA0, LB0>>{{{&a0, &b0}}}, MontChain<WP, LZ1, Products<WP, LA1, LB1>>{{{&a1, &b1}}}, &r0, &r1);
+    mont_scan<WP>(MontChain<WP, LZ0, Products<WP, LA0, LB0>, LbNone, FD>{{{&a0, &b0}}}, MontChain<WP, LZ1, Products<WP, LA1, LB1>, LbNone, FD>{{{&a1, &b1}}}, &r0, &r1);
 }
 // sqrw2: two independent squarings in lockstep
-template <class WP, unsigned LZ0, unsigned LZ1, class LX0, class LX1>
+template <class WP, unsigned LZ0, unsigned LZ1, class LX0, class LX1, unsigned FD = 0>
 PLK_HD void sqrw2_lz(const W9<WP> &x0, const W9<WP> &x1, W9<WP> &r0, W9<WP> &r1) {
-    mont_scan<WP>(MontChain<WP, LZ0, Squaring<WP, LX0>>{{x0}}, MontChain<WP, LZ1, Squaring<WP, LX1>>{{x1}}, &r0, &r1);
+    mont_scan<WP>(MontChain<WP, LZ0, Squaring<WP, LX0>, LbNone, FD>{{x0}}, MontChain<WP, LZ1, Squaring<WP, LX1>, LbNone, FD>{{x1}}, &r0, &r1);
 }
 // mulw2_add: the lockstep pair with a 9-limb ADDEND folded into each chain (the mixed addition of msm_accumulate):
 //     r_q = a_q * b_q * 2^-261 + A_q,  normalised,   q = 0, 1
@@ -354,14 +438,14 @@ PLK_HD void sqrw2_lz(const W9<WP> &x0, const W9<WP> &x1, W9<WP> &r0, W9<WP> &r1)
 // normalises the product normalises the sum as well: the result is bit for bit normw(addw(mulw(a, b), A)) — same integer, same (unique)
 // normalised form — without the 9 additions and the 25 instructions of normw, for 8 multiply-adds by one (the top limb is a 32-bit add).
 // The value must stay below 2^261 and the top limb below 2^32: callers add less than 16p to a product below 1.1p.
-template <class WP, unsigned LZ0, unsigned LZ1, class LA0, class LB0, class LAD0, class LA1, class LB1, class LAD1>
+template <class WP, unsigned LZ0, unsigned LZ1, class LA0, class LB0, class LAD0, class LA1, class LB1, class LAD1, unsigned FD = 0>
 PLK_HD void mulw2_add_lz(const W9<WP> &a0, const W9<WP> &b0, const W9<WP> &A0, const W9<WP> &a1, const W9<WP> &b1, const W9<WP> &A1, W9<WP> &r0, W9<WP> &r1) {
-    mont_scan<WP>(MontChain<WP, LZ0, Products<WP, LA0, LB0>, LAD0>{{{&a0, &b0}}, &A0}, MontChain<WP, LZ1, Products<WP, LA1, LB1>, LAD1>{{{&a1, &b1}}, &A1}, &r0, &r1);
+    mont_scan<WP>(MontChain<WP, LZ0, Products<WP, LA0, LB0>, LAD0, FD>{{{&a0, &b0}}, &A0}, MontChain<WP, LZ1, Products<WP, LA1, LB1>, LAD1, FD>{{{&a1, &b1}}, &A1}, &r0, &r1);
 }
 // mul2addw: a*b + c*d with ONE Montgomery reduction (243 mads instead of 324).  Used as a*b - c*e by passing d = k*p - e.
-template <class WP, unsigned LZ, class LA, class LB, class LC, class LD>
+template <class WP, unsigned LZ, class LA, class LB, class LC, class LD, unsigned FD = 0>
 PLK_HD W9<WP> mul2addw_lz(const W9<WP> &a, const W9<WP> &b, const W9<WP> &c, const W9<WP> &d) {
-    return mont_scan<WP>(MontChain<WP, LZ, Products<WP, LA, LB, LC, LD>>{{{&a, &b, &c, &d}}});
+    return mont_scan<WP>(MontChain<WP, LZ, Products<WP, LA, LB, LC, LD>, LbNone, FD>{{{&a, &b, &c, &d}}});
 }
 
 // ---- the masked forms: the same with no digit unmasked and the bounds of their contracts.
@@ -423,7 +507,7 @@ struct Tw3Chain {
     PLK_HD void shift() { acc >>= 29; }
     PLK_HD void top() { r->l[8] = (uint32_t)acc; }
 };
-struct NoTw3Chain : NoChain { PLK_HD void xw(int, uint32_t) {} };
+struct NoTw3Chain : NoChain { PLK_HD void xw(int, uint32_t) {} PLK_HD void shift() {} };
 template <class WP, class C1 = NoTw3Chain>
 PLK_HD auto mul_tw3_scan(const Tw3<WP> &t, const Tw3Chain<WP> &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr, W9<WP> *r1 = nullptr) {
     constexpr bool ONE = std::is_same<C1, NoTw3Chain>::value;
@@ -491,26 +575,35 @@ PLK_HD Tw3<WP> make_tw3(const W9<WP> &w_dom_w) {
 struct LbTw2A { static constexpr Limbs9 B = Limbs9{{(1u << 30) - 1, (1u << 30) - 1, (1u << 30) - 1, (1u << 30) - 1, (1u << 30) - 1, M29, M29, M29, M29}}; };
 constexpr unsigned TW2_LZ_ALL = 0xfu;                          // tw2: m_0..m_3 unmasked
 constexpr unsigned TW2A_LZ_ALL = 0x7u;                         // make_tw2_a: m_0..m_2 unmasked
-constexpr ColBound tw2_col_bound(const Limbs9 &z, const Limbs9 &a, const Limbs9 &w, const uint32_t (&p)[9], unsigned lz) {
+constexpr unsigned FOLD9 = 0x7fu, FOLD_TW2 = 0x7u, FOLD_TW2A = 0x3u;   // the largest fold sets: digits 0..6 of nine, 0..2 of tw2's five, 0..1 of make_tw2_a's four
+constexpr ColBound tw2_col_bound(const Limbs9 &z, const Limbs9 &a, const Limbs9 &w, const uint32_t (&p)[9], unsigned lz, unsigned fold = 0, const Limbs9 &fc = LbNone::B) {
     uint64_t carry = 0, worst = 0;
     bool fits = true;
     for (int k = 0; k < 13; k++) {
         uint64_t s = carry;
         for (int i = 0; i < 4; i++) if (k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)z.l[i] * a.l[k - i], &s);
         for (int i = 0; i < 5; i++) if (k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)z.l[4 + i] * w.l[k - i], &s);
-        for (int i = 0; i < 5; i++) if (k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)(i < 4 && ((lz >> i) & 1u) ? 0xffffffffu : M29) * p[k - i], &s);
+        for (int i = 0; i < 5; i++) {
+            const uint64_t dg = i < 4 && ((lz >> i) & 1u) ? 0xffffffffu : M29;
+            if (!fold_digit(fold, i) && k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, dg * p[k - i], &s);
+            if (fold_digit(fold, i) && k - i - 1 >= 0 && k - i - 1 <= 8) fits &= !__builtin_add_overflow(s, dg * fc.l[k - i - 1], &s);
+        }
         if (s > worst) worst = s;
         carry = s >> 29;
     }
     return ColBound{worst, fits};
 }
-constexpr ColBound tw2a_col_bound(const Limbs9 &w, const uint32_t (&p)[9], unsigned lz) {
+constexpr ColBound tw2a_col_bound(const Limbs9 &w, const uint32_t (&p)[9], unsigned lz, unsigned fold = 0, const Limbs9 &fc = LbNone::B) {
     uint64_t carry = 0, worst = 0;
     bool fits = true;
     for (int k = 0; k < 12; k++) {
         uint64_t s = carry;
         if (k < 4) fits &= !__builtin_add_overflow(s, (uint64_t)w.l[k], &s);
-        for (int i = 0; i < 4; i++) if (k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, (uint64_t)(i < 3 && ((lz >> i) & 1u) ? 0xffffffffu : M29) * p[k - i], &s);
+        for (int i = 0; i < 4; i++) {
+            const uint64_t dg = i < 3 && ((lz >> i) & 1u) ? 0xffffffffu : M29;
+            if (!fold_digit(fold, i) && k - i >= 0 && k - i <= 8) fits &= !__builtin_add_overflow(s, dg * p[k - i], &s);
+            if (fold_digit(fold, i) && k - i - 1 >= 0 && k - i - 1 <= 8) fits &= !__builtin_add_overflow(s, dg * fc.l[k - i - 1], &s);
+        }
         if (s > worst) worst = s;
         carry = s >> 29;
     }
@@ -518,9 +611,10 @@ constexpr ColBound tw2a_col_bound(const Limbs9 &w, const uint32_t (&p)[9], unsig
 }
 // A = w * 2^-116 mod p.  LW: the declared bound of w (its limbs 4..8 below 2^29 for LbTw2A to hold: static_assert).  One chain: every
 // multiply-add reads the one before it.
-template <class WP, unsigned LZ = TW2A_LZ_ALL, class LW = LbNorm>
+template <class WP, unsigned LZ = TW2A_LZ_ALL, class LW = LbNorm, unsigned FD = 0>
 PLK_HD W9<WP> make_tw2_a(const W9<WP> &w) {
-    static_assert(tw2a_col_bound(LW::B, WP::P29, LZ).fits, "a column of make_tw2_a can exceed 64 bits");
+    static_assert(tw2a_col_bound(LW::B, WP::P29, LZ, FD, lb_of(WP::FOLDC)).fits, "a column of make_tw2_a can exceed 64 bits");
+    static_assert(fold_value_ok(FD, 4, WP::FOLDC, WP::P29), PLK_FOLD_MSG);
     static_assert(lb_below(LW::B, 1u << 29), "make_tw2_a: the high limbs of w are added to normalised limbs and must stay below 2^30");
     W9<WP> r;
     uint32_t m[4];
@@ -530,14 +624,17 @@ PLK_HD W9<WP> make_tw2_a(const W9<WP> &w) {
         if (k > 0 && k < 4) PLK_ADDEND(acc, w.l[k]);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            if (i >= k || k - i > 8) continue;
-            acc += (uint64_t)m[i] * WP::P29[k - i]; PLK_CHAIN(acc);
+            if (i >= k || k - i > (fold_digit(FD, i) ? 9 : 8)) continue;
+            acc += (uint64_t)m[i] * (fold_digit(FD, i) ? WP::FOLDC[k - i - 1] : WP::P29[k - i]); PLK_CHAIN(acc);
         }
-        if (k < 4) {
-            m[k] = (k < 3 && ((LZ >> k) & 1u)) ? (uint32_t)acc * WP::INV29 : ((uint32_t)acc * WP::INV29) & M29;
+        const bool lzk = k < 3 && ((LZ >> k) & 1u);
+        if (fold_digit(FD, k)) m[k] = lzk ? (uint32_t)acc : (uint32_t)acc & M29;                  // (fold_value_ok: k < 2)
+        else if (k < 4) {
+            m[k] = lzk ? (uint32_t)acc * WP::INV29 : ((uint32_t)acc * WP::INV29) & M29;
             acc += (uint64_t)m[k] * WP::P29[0];
         } else r.l[k - 4] = (uint32_t)acc & M29;
-        acc >>= 29;
+        if (fold_digit(FD, k) && lzk) PLK_FOLD_CARRY(acc)
+        else acc >>= 29;
     }
     r.l[8] = (uint32_t)acc;
 #pragma unroll
@@ -545,9 +642,11 @@ PLK_HD W9<WP> make_tw2_a(const W9<WP> &w) {
     return r;
 }
 // one accumulator chain of the tw2 scan: z, the two forms of its factor, the result
-template <class WP, unsigned LZ, class LZV, class LA, class LW>
+template <class WP, unsigned LZ, class LZV, class LA, class LW, unsigned FLD = 0>
 struct Tw2Chain {
-    static constexpr bool FITS = tw2_col_bound(LZV::B, LA::B, LW::B, WP::P29, LZ).fits;
+    static constexpr unsigned FOLD = FLD;
+    static constexpr bool FITS = tw2_col_bound(LZV::B, LA::B, LW::B, WP::P29, LZ, FLD, lb_of(WP::FOLDC)).fits;
+    static constexpr bool FOLD_OK = fold_value_ok(FLD, 5, WP::FOLDC, WP::P29);
     const W9<WP> &z, &a, &w;
     W9<WP> *r = nullptr;
     uint32_t m[5];
@@ -555,10 +654,21 @@ struct Tw2Chain {
     PLK_HD void mad(uint64_t x, uint32_t y) { acc += x * y; PLK_CHAIN(acc); }
     PLK_HD void za(int i, int j) { mad(z.l[i], a.l[j]); }
     PLK_HD void zw(int i, int j) { mad(z.l[4 + i], w.l[j]); }
-    PLK_HD void digit(int k) { m[k] = (k < 4 && ((LZ >> k) & 1u)) ? (uint32_t)acc * WP::INV29 : ((uint32_t)acc * WP::INV29) & M29; }
-    PLK_HD void mp0(int k) { acc += (uint64_t)m[k] * WP::P29[0]; }
+    PLK_HD void mp(int k, int i) {
+        if (fold_digit(FLD, i)) mad(m[i], WP::FOLDC[k - i - 1]);
+        else if (k - i <= 8) mad(m[i], WP::P29[k - i]);
+    }
+    static constexpr bool lzd(int k) { return k < 4 && ((LZ >> k) & 1u); }
+    PLK_HD void digit(int k) {
+        if (fold_digit(FLD, k)) m[k] = lzd(k) ? (uint32_t)acc : (uint32_t)acc & M29;
+        else m[k] = lzd(k) ? (uint32_t)acc * WP::INV29 : ((uint32_t)acc * WP::INV29) & M29;
+    }
+    PLK_HD void mp0(int k) { if (!fold_digit(FLD, k)) acc += (uint64_t)m[k] * WP::P29[0]; }
     PLK_HD void limb(int j) { r->l[j] = (uint32_t)acc & M29; }
-    PLK_HD void shift() { acc >>= 29; }
+    PLK_HD void shift(int k) {
+        if (fold_digit(FLD, k) && lzd(k)) PLK_FOLD_CARRY(acc)
+        else acc >>= 29;
+    }
     PLK_HD void top() { r->l[8] = (uint32_t)acc; }
 };
 struct NoTw2Chain : NoChain { PLK_HD void za(int, int) {} PLK_HD void zw(int, int) {} };
@@ -566,6 +676,7 @@ template <class WP, class C0, class C1 = NoTw2Chain>
 PLK_HD auto mul_tw2_scan(const C0 &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr, W9<WP> *r1 = nullptr) {
     static_assert(C0::FITS, "a column of chain 0 can exceed 64 bits");
     static_assert(C1::FITS, "a column of chain 1 can exceed 64 bits");
+    static_assert(C0::FOLD_OK && C1::FOLD_OK, PLK_FOLD_MSG);
     constexpr bool ONE = std::is_same<C1, NoTw2Chain>::value;
     W9<WP> r;
     C0 c0 = s0;
@@ -586,40 +697,41 @@ PLK_HD auto mul_tw2_scan(const C0 &s0, const C1 &s1 = C1{}, W9<WP> *r0 = nullptr
         }
 #pragma unroll
         for (int i = 0; i < 5; i++) {
-            if (i >= k || k - i > 8) continue;
-            c0.mad(c0.m[i], WP::P29[k - i]); c1.mad(c1.m[i], WP::P29[k - i]);
+            if (i >= k || k - i > 9) continue;
+            c0.mp(k, i); c1.mp(k, i);
         }
         if (k < 5) { c0.digit(k); c1.digit(k); c0.mp0(k); c1.mp0(k); }
         else { c0.limb(k - 5); c1.limb(k - 5); }
-        c0.shift(); c1.shift();
+        c0.shift(k); c1.shift(k);
     }
     c0.top(); c1.top();
     if constexpr (ONE) return r;
 }
 // z * w * 2^-261 (mod p) with a = make_tw2_a(w); LZV, LA, LW: the declared limb bounds of z, a, w
-template <class WP, unsigned LZ = 0, class LZV = LbNorm, class LA = LbTw2A, class LW = LbNorm>
-PLK_HD W9<WP> mul_tw2(const W9<WP> &z, const W9<WP> &a, const W9<WP> &w) { return mul_tw2_scan<WP>(Tw2Chain<WP, LZ, LZV, LA, LW>{z, a, w}); }
+template <class WP, unsigned LZ = 0, class LZV = LbNorm, class LA = LbTw2A, class LW = LbNorm, unsigned FD = 0>
+PLK_HD W9<WP> mul_tw2(const W9<WP> &z, const W9<WP> &a, const W9<WP> &w) { return mul_tw2_scan<WP>(Tw2Chain<WP, LZ, LZV, LA, LW, FD>{z, a, w}); }
 // two in lockstep, each by a factor of its own (the same one twice where two products share it)
-template <class WP, unsigned LZ0, unsigned LZ1, class LZV0 = LbNorm, class LZV1 = LbNorm, class LA = LbTw2A, class LW = LbNorm>
+template <class WP, unsigned LZ0, unsigned LZ1, class LZV0 = LbNorm, class LZV1 = LbNorm, class LA = LbTw2A, class LW = LbNorm, unsigned FD = 0>
 PLK_HD void mul_tw2_2(const W9<WP> &z0, const W9<WP> &a0, const W9<WP> &w0, const W9<WP> &z1, const W9<WP> &a1, const W9<WP> &w1, W9<WP> &r0, W9<WP> &r1) {
-    mul_tw2_scan<WP>(Tw2Chain<WP, LZ0, LZV0, LA, LW>{z0, a0, w0}, Tw2Chain<WP, LZ1, LZV1, LA, LW>{z1, a1, w1}, &r0, &r1);
+    mul_tw2_scan<WP>(Tw2Chain<WP, LZ0, LZV0, LA, LW, FD>{z0, a0, w0}, Tw2Chain<WP, LZ1, LZV1, LA, LW, FD>{z1, a1, w1}, &r0, &r1);
 }
 // a tw2 product (chain 0, 13 columns) in lockstep with a plain Montgomery product a * b (chain 1, a MontChain over ONE product, 17 columns): for
 // a pair of which only one factor has its second form.  Column k of both is issued together, the multiply-adds alternating one by one while
 // both have some left (term t of column k of each chain, in the order of their own scans); columns 13..16 are chain 1's alone.
 // (term t of a column as a compile-time code, kind * 16 + i, or -1 past the column's last: left to the optimiser the scan stays a rolled loop)
-constexpr int tw2_term_code(int k, int t) {
+// (a folded digit i has its last term in column i + 9, a Montgomery digit in column i + 8)
+constexpr int tw2_term_code(int k, int t, unsigned fold = 0) {
     int n = 0;
     for (int i = 0; i < 4; i++) if (k - i >= 0 && k - i <= 8) { if (n == t) return i; n++; }
     for (int i = 0; i < 5; i++) if (k - i >= 0 && k - i <= 8) { if (n == t) return 16 + i; n++; }
-    for (int i = 0; i < 5; i++) if (i < k && k - i <= 8) { if (n == t) return 32 + i; n++; }
+    for (int i = 0; i < 5; i++) if (i < k && k - i <= (fold_digit(fold, i) ? 9 : 8)) { if (n == t) return 32 + i; n++; }
     return -1;
 }
-constexpr int mont_term_code(int k, int t) {
+constexpr int mont_term_code(int k, int t, unsigned fold = 0) {
     const int lo = k < 9 ? 0 : k - 8, hi = k < 9 ? k : 8;
     int n = 0;
     for (int i = lo; i <= hi; i++) { if (n == t) return i; n++; }
-    for (int i = lo; i <= hi && i < k; i++) { if (n == t) return 16 + i; n++; }
+    for (int i = (k < 9 ? 0 : k - 9); i <= hi && i < k; i++) if (k - i <= (fold_digit(fold, i) ? 9 : 8)) { if (n == t) return 16 + i; n++; }
     return -1;
 }
 // (static_for for code that the host checks compile too)
@@ -630,6 +742,7 @@ PLK_HD void mul_tw2_mulw_scan(const CT &s0, const CM &s1, W9<WP> *r0, W9<WP> *r1
     static_assert(CT::FITS, "a column of chain 0 can exceed 64 bits");
     static_assert(CM::FITS, "a column of chain 1 can exceed 64 bits");
     static_assert(CM::Half::T == 1 && !CM::ADD, "chain 1 is one product without an addend");
+    static_assert(CT::FOLD_OK && CM::FOLD_OK, PLK_FOLD_MSG);
     CT c0 = s0;
     CM c1 = s1;
     c0.r = r0; c1.r = r1;
@@ -637,11 +750,11 @@ PLK_HD void mul_tw2_mulw_scan(const CT &s0, const CM &s1, W9<WP> *r0, W9<WP> *r1
         constexpr int k = decltype(K)::value;
         static_for_hd<18>([&](auto T) {
             constexpr int t = decltype(T)::value;
-            constexpr int e0 = k < 13 ? tw2_term_code(k, t) : -1, e1 = mont_term_code(k, t);
-            if constexpr (e0 >= 32) c0.mad(c0.m[e0 - 32], WP::P29[k - (e0 - 32)]);
+            constexpr int e0 = k < 13 ? tw2_term_code(k, t, CT::FOLD) : -1, e1 = mont_term_code(k, t, CM::FOLD);
+            if constexpr (e0 >= 32) c0.mp(k, e0 - 32);
             else if constexpr (e0 >= 16) c0.zw(e0 - 16, k - (e0 - 16));
             else if constexpr (e0 >= 0) c0.za(e0, k - e0);
-            if constexpr (e1 >= 16) c1.mad(c1.m[e1 - 16], WP::P29[k - (e1 - 16)]);
+            if constexpr (e1 >= 16) c1.mp(k, e1 - 16);
             else if constexpr (e1 >= 0) c1.mad(c1.h.x[0]->l[k - e1], c1.h.x[1]->l[e1]);
         });
         if constexpr (k < 5) c0.digit(k);
@@ -650,16 +763,16 @@ PLK_HD void mul_tw2_mulw_scan(const CT &s0, const CM &s1, W9<WP> *r0, W9<WP> *r1
         if constexpr (k < 9) c1.mp0(k);
         if constexpr (k >= 5 && k < 13) c0.limb(k - 5);
         if constexpr (k >= 9) c1.limb(k);
-        if constexpr (k < 13) c0.shift();
-        c1.shift();
+        if constexpr (k < 13) c0.shift(k);
+        c1.shift(k);
         if constexpr (k == 12) c0.top();
     });
     c1.top();
 }
 // r0 = tw2(z; a, w), r1 = x * y * 2^-261, in lockstep
-template <class WP, unsigned LZ0, unsigned LZ1, class LZV = LbNorm, class LX = LbNorm, class LY = LbNorm, class LA = LbTw2A, class LW = LbNorm>
+template <class WP, unsigned LZ0, unsigned LZ1, class LZV = LbNorm, class LX = LbNorm, class LY = LbNorm, class LA = LbTw2A, class LW = LbNorm, unsigned FD0 = 0, unsigned FD1 = 0>
 PLK_HD void mul_tw2_mulw(const W9<WP> &z, const W9<WP> &a, const W9<WP> &w, const W9<WP> &x, const W9<WP> &y, W9<WP> &r0, W9<WP> &r1) {
-    mul_tw2_mulw_scan<WP>(Tw2Chain<WP, LZ0, LZV, LA, LW>{z, a, w}, MontChain<WP, LZ1, Products<WP, LX, LY>>{{{&x, &y}}}, &r0, &r1);
+    mul_tw2_mulw_scan<WP>(Tw2Chain<WP, LZ0, LZV, LA, LW, FD0>{z, a, w}, MontChain<WP, LZ1, Products<WP, LX, LY>, LbNone, FD1>{{{&x, &y}}}, &r0, &r1);
 }
 
 // ---- OPERAND-SCANNING forms of the same three products (identical results, bit for bit): ten independent 64-bit
