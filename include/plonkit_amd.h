@@ -919,6 +919,65 @@ int32_t plk_setup_check_permutation(plk_ctx *ctx, const plk_setup *s, plk_copy_r
 int32_t plk_check_copies(plk_ctx *ctx, const plk_setup *s, const plk_fr *const columns[4], uint64_t rows, plk_copy_report *out);
 int32_t plk_check_copies_dev(plk_ctx *ctx, const plk_setup *s, const void *const columns_dev[4], uint64_t rows, plk_copy_report *out, void *stream);
 
+/* ---- KZG openings on their own (kzg.hip): bellman's kate_commitment beyond the commitments (the module src/plonk.rs:4 takes `Crs` from) —
+ *      commit_using_monomials / commit_using_values, open_from_monomials / open_from_values and is_valid_opening.  The prover does all of
+ *      this inside round 5; here a caller opens a commitment at a point, from coefficients or from the values on the domain, and checks
+ *      openings.  Scalars are Montgomery plk_fr below r, points plk_g1_affine with (0, 0) as infinity; polynomials live in device memory,
+ *      16-byte aligned, and are never written (the one exception: a quotient written over its own input where that is said to be allowed).
+ *      N = 2^log_n, omega = the library's root of unity of that order (plk_ntt_dev's).
+ *
+ *   plk_poly_evaluate_values_at_dev.  f(z) from the N values f(omega^i), 1 <= log_n <= 28, by the barycentric formula
+ *                f(z) = (z^N - 1) / N * sum_i f_i omega^i / (z - omega^i); z = omega^k returns f_k exactly, read from the array.  No transform,
+ *                no per-element inversion: per-element denominators from the context's omega table, prefix x suffix products (the scans of
+ *                the grand product) and ONE host inversion.  Blocks, like plk_poly_evaluate_at_dev.  No host pass over the N elements.
+ *   plk_poly_divide_values_by_linear_dev.  The N values of q = (f - y) / (x - z): q_i = (f_i - y) / (omega^i - z) for omega^i != z; for
+ *                z = omega^k position k holds q(omega^k) = sum_{i != k} (f_i - y) omega^i / (z (z - omega^i)), the value there of the
+ *                polynomial quotient of degree < N - 1.  y == NULL: f(z), computed as above.  A caller's y is taken on trust outside the
+ *                domain, as open_from_values takes its expected value; inside the domain y != f_k is PLK_ERR_ARG (no polynomial quotient
+ *                exists).  The output may be the input.  Waits before it returns, as plk_poly_divide_by_linear_dev.
+ *   plk_kzg_commit_dev.  commit_using_monomials: exactly plk_msm_g1_batch_dev at offset 0 (count <= 8).  With PLK_KZG_VALUES the vectors are
+ *                values and are summed against the Lagrange-form slot (commit_using_values); no such key, or one whose size is not n:
+ *                PLK_ERR_SRS, "Lagrange-form key has a different size than the circuit's domain" (the prover's words).
+ *   plk_kzg_open_dev.  y_j = f_j(z) into evals[j], F = sum_j v^j f_j, Y = sum_j v^j y_j, *proof = commit((F - Y) / (x - z)): the shape of
+ *                round 5.  v may be NULL when count == 1.  Without flags the inputs are coefficients, 1 <= n <= plk_srs_size: the linear
+ *                combination, division and evaluation kernels of the prover; z = 0 works here (the quotient is the combination moved down
+ *                by one coefficient, y = c_0) while plk_poly_divide_by_linear_dev keeps its refusal.  With PLK_KZG_VALUES n is the
+ *                Lagrange-form key's size (else PLK_ERR_SRS as above), the quotient is formed in values by the kernels of the two calls above
+ *                and committed against the Lagrange-form slot: no transform is launched, and the proof is the same point, bit for bit, as
+ *                the coefficient route gives for the interpolated polynomials.  Blocks.  A commitment in flight on the context: PLK_ERR_ARG,
+ *                as the other blocking calls.  Null pointers, count outside 1..8, n = 0, unknown flags, a scalar >= r: PLK_ERR_ARG.
+ *                Scratch (3 N x 32 B in values, 2 n x 32 B + 2 MiB in coefficients) grows only; a call that grew it past 64 MiB frees it
+ *                before it returns.  Single-GPU: the commitment is plk_msm_g1_dev's, a sharded key commits its own slice only.
+ *   plk_kzg_verify.  is_valid_opening, pure CPU, no context.  C = sum_j v^j C_j, Y = sum_j v^j y_j; *valid = 1 exactly when
+ *                e(C - Y G + z pi, g2[0]) e(-pi, g2[1]) == 1, through plk_pairing_check (its G2 decoding, its refusals, its words).
+ *                Infinity is a legal commitment (the zero polynomial) and a legal proof (a constant).  A point off the curve, a coordinate
+ *                >= q, a scalar >= r, count outside 1..8, v == NULL with count > 1: PLK_ERR_ARG.
+ *   plk_kzg_verify_many_dev.  n independent single-polynomial openings in device memory: commitments, z, evaluations, proofs (16-byte
+ *                aligned) and one verdict byte each (any alignment).  Ordered on `stream`, does not wait.  NO COUNTERPART IN THE REFERENCE.
+ *                One lane per opening range-checks the two scalars, curve-checks the two points and forms A_i = C_i + z_i pi_i + (-y_i) G
+ *                and B_i = -pi_i (two GLV multiplications of g1_mul_dev.h); plk_pairing_check_many_dev's kernel then decides every
+ *                e(A_i, Q_0) e(B_i, Q_1) == 1 on its own.  Verdict i = 1 / 0 / PLK_VERDICT_MALFORMED is what plk_kzg_verify says about
+ *                opening i (malformed: where it returns PLK_ERR_ARG for the opening's own data): no random combination across openings, the
+ *                rule of plk_verify_many; a malformed entry does not touch its neighbours.  g2 as plk_pairing_check_many_dev (a pair the
+ *                context did not see last waits for the stream once).  n == 0 launches nothing.  Memory and order as plk_verify_many_dev:
+ *                274 B per opening (at most 2^16 per pass) in a grows-only buffer of its own outside the staging arena, kernels on the
+ *                context's stream between two events.
+ *                BREAK-EVEN (one MI355X, profiles/kzg_open.txt): a call costs ~88 ms whatever the batch up to a few thousand openings (one
+ *                pairing lane per opening), a plk_kzg_verify 12.5 ms.  Measured at 1 / 256 / 4096 openings: 92 / 89 / 89 ms against 13 / 198 /
+ *                3218 ms for a loop of plk_kzg_verify on 16 host threads — 256 is the first measured size at which this call wins (the
+ *                figures cross near 110).  Below that, prefer plk_kzg_verify on host threads.                                          */
+#define PLK_KZG_VALUES 1u     /* the vectors are values on <omega_N>, committed against the Lagrange-form key */
+int32_t plk_poly_evaluate_values_at_dev(plk_ctx *ctx, const void *values_dev, uint32_t log_n, const plk_fr *z, plk_fr *out, void *stream);
+int32_t plk_poly_divide_values_by_linear_dev(plk_ctx *ctx, const void *values_dev, uint32_t log_n, const plk_fr *z, const plk_fr *y /* NULL: f(z) */,
+                                             void *quotient_values_dev, void *stream);
+int32_t plk_kzg_commit_dev(plk_ctx *ctx, const void *const *polys_dev, uint32_t count, uint64_t n, uint32_t flags, plk_g1_affine *out, void *stream);
+int32_t plk_kzg_open_dev(plk_ctx *ctx, const void *const *polys_dev, uint32_t count, uint64_t n, const plk_fr *z, const plk_fr *v /* may be NULL when count == 1 */,
+                         uint32_t flags, plk_fr *evals, plk_g1_affine *proof, void *stream);
+int32_t plk_kzg_verify(const plk_g1_affine *commitments, uint32_t count, const plk_fr *z, const plk_fr *evals, const plk_fr *v /* may be NULL when count == 1 */,
+                       const plk_g1_affine *proof, const uint8_t g2[256], int32_t *valid);
+int32_t plk_kzg_verify_many_dev(plk_ctx *ctx, const void *commitments_dev, const void *z_dev, const void *evals_dev, const void *proofs_dev, uint64_t n,
+                                const uint8_t g2[256], void *verdict_dev, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

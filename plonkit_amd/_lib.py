@@ -688,6 +688,46 @@ class Context:
         z = np.ascontiguousarray(z, dtype=np.uint64)
         _check(lib().plk_poly_divide_by_linear_dev(self._h, _devptr(ptr), ctypes.c_uint64(n), _np(z), _devptr(out_ptr), _stream(stream)))
 
+    # ---- KZG openings on their own (kzg.hip): values on the domain as well as coefficients
+    def poly_evaluate_values_at_dev(self, ptr, log_n, z, stream=None):
+        """plk_poly_evaluate_values_at_dev: f(z) from the 2^log_n values f(omega^i) in device memory (barycentric; z = omega^k reads f_k)"""
+        z = np.ascontiguousarray(z, dtype=np.uint64)
+        out = np.zeros(4, dtype=np.uint64)
+        _check(lib().plk_poly_evaluate_values_at_dev(self._h, _devptr(ptr), ctypes.c_uint32(log_n), _np(z), _np(out), _stream(stream)))
+        return out
+
+    def poly_divide_values_by_linear_dev(self, ptr, log_n, z, out_ptr, y=None, stream=None):
+        """plk_poly_divide_values_by_linear_dev: the values of (f - y) / (x - z) from the values of f; y=None: f(z).  out_ptr may be ptr."""
+        z = np.ascontiguousarray(z, dtype=np.uint64)
+        y = np.ascontiguousarray(y, dtype=np.uint64) if y is not None else None
+        _check(lib().plk_poly_divide_values_by_linear_dev(self._h, _devptr(ptr), ctypes.c_uint32(log_n), _np(z), _np(y) if y is not None else None,
+                                                          _devptr(out_ptr), _stream(stream)))
+
+    def kzg_commit_dev(self, ptrs, n, values=False, stream=None):
+        """plk_kzg_commit_dev: [count, 8] commitments of count <= 8 device vectors of n elements: coefficients against the resident key, or
+        (values=True) values on the domain against the Lagrange-form key"""
+        arr = (ctypes.c_void_p * len(ptrs))(*[_devptr(p) for p in ptrs])
+        out = np.zeros((len(ptrs), 8), dtype=np.uint64)
+        _check(lib().plk_kzg_commit_dev(self._h, arr, ctypes.c_uint32(len(ptrs)), ctypes.c_uint64(n), ctypes.c_uint32(1 if values else 0), _np(out), _stream(stream)))
+        return out
+
+    def kzg_open_dev(self, ptrs, n, z, v=None, values=False, stream=None):
+        """plk_kzg_open_dev: opens count <= 8 polynomials at z, combined by powers of v (None allowed for one polynomial):
+        ([count, 4] evaluations, the proof point [8])"""
+        arr = (ctypes.c_void_p * len(ptrs))(*[_devptr(p) for p in ptrs])
+        z = np.ascontiguousarray(z, dtype=np.uint64)
+        v = np.ascontiguousarray(v, dtype=np.uint64) if v is not None else None
+        evals, proof = np.zeros((len(ptrs), 4), dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+        _check(lib().plk_kzg_open_dev(self._h, arr, ctypes.c_uint32(len(ptrs)), ctypes.c_uint64(n), _np(z), _np(v) if v is not None else None,
+                                      ctypes.c_uint32(1 if values else 0), _np(evals), _np(proof), _stream(stream)))
+        return evals, proof
+
+    def kzg_verify_many_dev(self, commitments_ptr, z_ptr, evals_ptr, proofs_ptr, n, g2_bytes, verdict_ptr, stream=None):
+        """plk_kzg_verify_many_dev: n single-polynomial openings in device memory, one verdict byte each (1 / 0, 2 = malformed), each what
+        kzg_verify says about that opening; ordered on `stream`, does not wait"""
+        _check(lib().plk_kzg_verify_many_dev(self._h, _devptr(commitments_ptr), _devptr(z_ptr), _devptr(evals_ptr), _devptr(proofs_ptr), ctypes.c_uint64(n),
+                                             bytes(g2_bytes), _devptr(verdict_ptr), _stream(stream)))
+
     def permutation_grand_product_dev(self, wires, sigmas, beta, gamma, log_n, out_ptr, stream=None):
         w = (ctypes.c_void_p * 4)(*[_devptr(p) for p in wires])
         s = (ctypes.c_void_p * 4)(*[_devptr(p) for p in sigmas])
@@ -1338,6 +1378,24 @@ def pairing_check(a, g2_a, b, g2_b):
     out = ctypes.c_int32(0)
     a = np.ascontiguousarray(a, dtype=np.uint64); b = np.ascontiguousarray(b, dtype=np.uint64)
     _check(lib().plk_pairing_check(_np(a), bytes(g2_a), _np(b), bytes(g2_b), ctypes.byref(out)))
+    return bool(out.value)
+
+
+def kzg_verify(commitments, z, evals, proof, g2_bytes, v=None):
+    """plk_kzg_verify (pure CPU): is `proof` an opening of the commitments ([count, 8]) at z to evals ([count, 4]), combined by powers of v
+    (None allowed for one commitment)?  g2_bytes: the 256 bytes of the key file's G2 section.  Malformed input raises PlkError."""
+    c = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+    e = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+    if c.shape[0] != e.shape[0]:
+        raise ValueError("kzg_verify: %d commitments and %d evaluations" % (c.shape[0], e.shape[0]))
+    g2_bytes = bytes(g2_bytes)
+    if len(g2_bytes) != 256:
+        raise ValueError("g2_bytes must be the 256 bytes of a key file's G2 section, got %d" % len(g2_bytes))
+    z = np.ascontiguousarray(z, dtype=np.uint64)
+    v = np.ascontiguousarray(v, dtype=np.uint64) if v is not None else None
+    p = np.ascontiguousarray(proof, dtype=np.uint64)
+    out = ctypes.c_int32(0)
+    _check(lib().plk_kzg_verify(_np(c), ctypes.c_uint32(c.shape[0]), _np(z), _np(e), _np(v) if v is not None else None, _np(p), g2_bytes, ctypes.byref(out)))
     return bool(out.value)
 
 

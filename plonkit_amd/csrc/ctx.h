@@ -141,6 +141,8 @@ struct plk_ctx {
     plk::DevBuf pair_tab;                    // verify_many.hip: line table of the G2 pair plk_pairing_check_many_dev saw last
     uint8_t pair_g2[256] = {};
     bool pair_tab_valid = false;
+    plk::DevBuf kzg_ws;                      // kzg.hip: scratch of the blocking opening calls (grows only; a call that grew it past 64 MiB frees it on return)
+    plk::DevBuf kzg_vm;                      // kzg.hip: plk_kzg_verify_many_dev's working memory, its own for vm_stage's reason (the call does not wait)
     // multi-GPU commitments of the prover (plk_set_commit_shard): global index of the first resident SRS point and
     // the caller's all-ranks combiner for the Jacobian partial sums
     uint64_t shard_first = 0;

@@ -203,6 +203,7 @@ void plk_destroy(plk_ctx *ctx) {
         if (S.ev[0]) { (void)hipEventDestroy(S.ev[0]); (void)hipEventDestroy(S.ev[1]); }
     }
     ctx->bases_w.release(); ctx->stage.release(); ctx->vm_stage.release(); ctx->pair_tab.release(); ctx->key_bad.release(); ctx->poly_tmp.release(); ctx->poly_tmp2.release(); ctx->prove_ws.release();
+    ctx->kzg_ws.release(); ctx->kzg_vm.release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned2) (void)hipHostFree(ctx->pinned2);
     if (ctx->flag_ready) (void)hipEventDestroy(ctx->flag_ready);
