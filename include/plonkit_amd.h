@@ -977,6 +977,34 @@ int32_t plk_kzg_verify(const plk_g1_affine *commitments, uint32_t count, const p
                        const plk_g1_affine *proof, const uint8_t g2[256], int32_t *valid);
 int32_t plk_kzg_verify_many_dev(plk_ctx *ctx, const void *commitments_dev, const void *z_dev, const void *evals_dev, const void *proofs_dev, uint64_t n,
                                 const uint8_t g2[256], void *verdict_dev, void *stream);
+/*   plk_kzg_open_all_dev.  The openings at ALL N = 2^log_n points of the domain in one pass (kzg_all.hip, Feist-Khovratovich): proofs_dev[i]
+ *                is, byte for byte, the proof plk_kzg_open_dev returns for the same polynomial at z = omega^i.  NO COUNTERPART IN THE
+ *                REFERENCE (kate_commitment opens one point per call).  With h_k = sum_j f_{k+1+j} s_j (s_j the key's points) the proofs
+ *                are DFT_N(h), and h is one cyclic correlation of length 2N: a scalar NTT of the coefficients at 2N, a point-wise
+ *                G1 x Fr product with the key's transform (2N multiplications of g1_mul_dev.h), the inverse G1 transform at 2N, the
+ *                forward one at N, one conversion to affine.  poly_dev: N coefficients, or with PLK_KZG_VALUES the N values on the domain
+ *                (one inverse NTT into scratch first; this route reads NO Lagrange-form key); never written.  evals_dev, if not NULL,
+ *                receives f(omega^i) (one more NTT; with PLK_KZG_VALUES a copy of the input); it must not be poly_dev.  0 <= log_n <= 25
+ *                (PLK_ERR_SIZE above; log_n = 0 gives the point at infinity); key points 0 .. N - 2 are read: PLK_ERR_SRS when fewer than
+ *                N - 1 are resident.  A borrowed or lent key (plk_srs_set_dev, plk_ctx_share_srs) will do.  Single-GPU (a context with a
+ *                commit shard: PLK_ERR_ARG), 16-byte aligned pointers, no commitment in flight (the transforms of g1ntt.hip share their
+ *                refusals).  Blocks.  Memory: the key's transform, 2N x 144 B, is built by the first call for a size (or by
+ *                plk_kzg_open_all_prepare) and kept by the calling context until its key changes or another size is asked for; scratch of
+ *                2N x 176 B (+ N x 32 B in values) beside it grows only, and a call that grew it past 64 MiB frees it before it returns.
+ *                MEASURED (one MI355X, profiles/kzg_open_all.txt): 2^12 / 2^16 / 2^20 points 22 / 31 / 447 ms with the key's transform kept,
+ *                33 / 46 / 727 ms when the call has to build it; the loop of 4096 plk_kzg_open_dev calls at 2^12 takes 1290 ms.
+ *   plk_kzg_open_all_prepare.  Builds and keeps the key's transform for 2^log_n; optional.  The same refusals.  Blocks.
+ *   plk_kzg_open_all_last_ms.  Device-event times of the last call while plk_set_kernel_timing is on: the key's transform (about 0 when it
+ *                was cached), the scalar NTTs, the point-wise product, the inverse transform, the forward transform with the conversion.
+ *   plk_g1_ntt_dev.  The transform of plk_g1_intt over 2^log_n affine points in device memory (64 B each, (0, 0) = infinity), in either
+ *                direction: inverse != 0 is plk_g1_intt bit for bit (omega^-1, 1 / N); inverse == 0 is out[i] = sum_j omega^(i j) in[j],
+ *                no scaling.  log_n <= 26, no commitment in flight (the scratch is slot 0's).  Ordered on `stream`, does not wait; out_dev
+ *                may be in_dev.                                                                                                          */
+int32_t plk_kzg_open_all_prepare(plk_ctx *ctx, uint32_t log_n);
+int32_t plk_kzg_open_all_dev(plk_ctx *ctx, const void *poly_dev, uint32_t log_n, uint32_t flags /* 0 | PLK_KZG_VALUES */,
+                             void *proofs_dev /* 2^log_n affine points */, void *evals_dev /* may be NULL: f(omega^i) */, void *stream);
+int32_t plk_kzg_open_all_last_ms(plk_ctx *ctx, float out_ms[5]);
+int32_t plk_g1_ntt_dev(plk_ctx *ctx, const void *in_dev, uint32_t log_n, int32_t inverse, void *out_dev, void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -728,6 +728,29 @@ class Context:
         _check(lib().plk_kzg_verify_many_dev(self._h, _devptr(commitments_ptr), _devptr(z_ptr), _devptr(evals_ptr), _devptr(proofs_ptr), ctypes.c_uint64(n),
                                              bytes(g2_bytes), _devptr(verdict_ptr), _stream(stream)))
 
+    def kzg_open_all_prepare(self, log_n):
+        """plk_kzg_open_all_prepare: build and keep the transform of the resident key for the 2^log_n domain (optional; kzg_open_all_dev builds it
+        on first use)"""
+        _check(lib().plk_kzg_open_all_prepare(self._h, ctypes.c_uint32(log_n)))
+
+    def kzg_open_all_dev(self, poly_ptr, log_n, proofs_ptr, evals_ptr=None, values=False, stream=None):
+        """plk_kzg_open_all_dev: proofs_ptr[i] <- the opening proof at omega^i of the polynomial at poly_ptr (2^log_n coefficients, or with
+        values=True its values on the domain), for every i at once; evals_ptr (optional) <- f(omega^i).  Blocks."""
+        _check(lib().plk_kzg_open_all_dev(self._h, _devptr(poly_ptr), ctypes.c_uint32(log_n), ctypes.c_uint32(1 if values else 0), _devptr(proofs_ptr),
+                                          _devptr(evals_ptr) if evals_ptr is not None else None, _stream(stream)))
+
+    def kzg_open_all_last_ms(self):
+        """plk_kzg_open_all_last_ms: [key transform, scalar NTTs, point-wise product, inverse transform, forward transform + affine] of the last
+        kzg_open_all_dev, in ms (set_kernel_timing must be on)"""
+        out = (ctypes.c_float * 5)()
+        _check(lib().plk_kzg_open_all_last_ms(self._h, out))
+        return [float(v) for v in out]
+
+    def g1_ntt_dev(self, in_ptr, log_n, out_ptr, inverse=False, stream=None):
+        """plk_g1_ntt_dev: the G1 transform of 2^log_n affine points in device memory, forward (out[i] = sum_j omega^(i j) in[j]) or inverse
+        (g1_intt's, bit for bit); ordered on `stream`, does not wait"""
+        _check(lib().plk_g1_ntt_dev(self._h, _devptr(in_ptr), ctypes.c_uint32(log_n), ctypes.c_int32(1 if inverse else 0), _devptr(out_ptr), _stream(stream)))
+
     def permutation_grand_product_dev(self, wires, sigmas, beta, gamma, log_n, out_ptr, stream=None):
         w = (ctypes.c_void_p * 4)(*[_devptr(p) for p in wires])
         s = (ctypes.c_void_p * 4)(*[_devptr(p) for p in sigmas])

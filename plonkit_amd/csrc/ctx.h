@@ -143,6 +143,14 @@ struct plk_ctx {
     bool pair_tab_valid = false;
     plk::DevBuf kzg_ws;                      // kzg.hip: scratch of the blocking opening calls (grows only; a call that grew it past 64 MiB frees it on return)
     plk::DevBuf kzg_vm;                      // kzg.hip: plk_kzg_verify_many_dev's working memory, its own for vm_stage's reason (the call does not wait)
+    // kzg_all.hip (all openings on the domain in one pass).  fk_key: DFT_2N of the arranged key, 2N XYZZ points of the 29-bit layer, this
+    // context's own even where the key is borrowed or lent; void with the key (srs_table_invalidate).  fk_ws: scratch of a call (grows only;
+    // a call that grew it past 64 MiB frees it on return).
+    plk::DevBuf fk_key, fk_ws;
+    bool fk_key_valid = false;
+    uint32_t fk_key_log_n = 0;
+    float fk_ms[5] = {0, 0, 0, 0, 0};        // key transform, Fr NTT, pointwise, inverse, forward + affine of the last plk_kzg_open_all_dev (recorded while ev_on)
+    bool fk_ms_valid = false;
     // multi-GPU commitments of the prover (plk_set_commit_shard): global index of the first resident SRS point and
     // the caller's all-ranks combiner for the Jacobian partial sums
     uint64_t shard_first = 0;
@@ -167,7 +175,10 @@ namespace plk {
 // every entry point that replaces a resident key goes through these two: the MSM table of the old key is void, and a table
 // (or key) that was only borrowed must not be written to when the next one is built
 int32_t srs_replace_guard(plk_ctx *c, const char *who, bool lagrange_only = false);   // runtime.hip: PLK_ERR_ARG while another context borrows this one's key
-inline void srs_table_invalidate(plk_ctx *c) { c->srs_w_valid = false; c->srs_w_no_inf = false; if (c->srs_w.borrowed) c->srs_w.release(); }
+inline void srs_table_invalidate(plk_ctx *c) {
+    c->srs_w_valid = false; c->srs_w_no_inf = false; if (c->srs_w.borrowed) c->srs_w.release();
+    c->fk_key_valid = false;                 // the key's transform (kzg_all.hip) cannot outlive its key; the buffer stays for the next one
+}
 inline void lag_table_invalidate(plk_ctx *c) { c->lag.w_valid = false; c->lag.w_no_inf = false; if (c->lag.w.borrowed) c->lag.w.release(); }
 void srs_return_loan(plk_ctx *c);                                 // runtime.hip
 void srs_make_loan(plk_ctx *dst, plk_ctx *src);                   // runtime.hip

@@ -41,9 +41,21 @@ __global__ void __launch_bounds__(256) g1ntt_load(XyzzW *pts, const G1Affine *in
     store_xyzzw(pts + brev32(i, log_n), p);
 }
 
+// the same permutation of points that are XYZZ already, where they lie: the lane of the lower index of a pair swaps it
+__global__ void __launch_bounds__(256) g1ntt_bitrev(XyzzW *pts, uint32_t log_n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (1u << log_n)) return;
+    const uint32_t r = brev32(i, log_n);
+    if (i >= r) return;
+    const XyzzW a = load_xyzzw(pts + i), b = load_xyzzw(pts + r);
+    store_xyzzw(pts + i, b);
+    store_xyzzw(pts + r, a);
+}
+
 // one DIT stage with half-size h = 2^s; SCALE (the last stage): both outputs times n_inv (Montgomery form) — (A n_inv) +- (w n_inv) B
+// tw: the powers of omega^-1 (inverse transform) or of omega (forward: never with SCALE)
 template <bool SCALE, int ISO>
-__global__ void __launch_bounds__(G1NTT_THREADS, 1) g1ntt_stage(XyzzW *pts, uint32_t log_n, uint32_t s, PowTable tw_inv, Fr n_inv) {
+__global__ void __launch_bounds__(G1NTT_THREADS, 1) g1ntt_stage(XyzzW *pts, uint32_t log_n, uint32_t s, PowTable tw, Fr n_inv) {
     extern __shared__ uint32_t g1tab[];
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= (1u << (log_n - 1))) return;
@@ -60,9 +72,9 @@ __global__ void __launch_bounds__(G1NTT_THREADS, 1) g1ntt_stage(XyzzW *pts, uint
     if (jl || SCALE) {
         Fr w = n_inv;
         if (jl) {
-            // omega_N^-(jl * N / 2h)
+            // omega_N^-+(jl * N / 2h)
             uint32_t e = (jl << (log_n - s - 1)) << (MAX_LOG_N - log_n);
-            w = mul(load_fp(tw_inv.lo + (e & (POW_TAB - 1))), load_fp(tw_inv.hi + (e >> POW_SPLIT)));
+            w = mul(load_fp(tw.lo + (e & (POW_TAB - 1))), load_fp(tw.hi + (e >> POW_SPLIT)));
             if (SCALE) w = mul(w, n_inv);
         }
         auto mul = [&](const XyzzW &pt, const Fr &kk) __attribute__((always_inline)) {
@@ -118,15 +130,8 @@ __global__ void __launch_bounds__(256) g1ntt_to_affine(G1Affine *out, const Xyzz
     }
 }
 
-int32_t g1_intt_dev(plk_ctx *ctx, const G1Affine *in, uint32_t log_n, G1Affine *out, hipStream_t st) {
-    if (log_n > 26) { set_error("g1_intt: size exceeds 2^26"); return PLK_ERR_SIZE; }
-    PLK_TRY(ntt_init_tables(ctx));
-    const uint32_t n = 1u << log_n;
-    // the transform borrows the scratch of the first commitment slot: nothing may be in flight there
-    if (ctx->msm_enq != ctx->msm_fin) { set_error("g1_intt: a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
-    PLK_TRY(ctx->slot[0].c.reserve((size_t)n * sizeof(XyzzW)));
-    XyzzW *pts = ctx->slot[0].c.as<XyzzW>();
-    const Fr n_inv = ctx->n_inv[log_n];                           // Montgomery form; 1 for log_n = 0 (no stage, nothing to scale)
+// dynamic LDS of the six stage instantiations, once per process
+static int32_t g1ntt_stage_attrs() {
     static std::atomic<bool> attr_set{false};
     if (!attr_set) {
         PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g1ntt_stage<false, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS));
@@ -137,20 +142,60 @@ int32_t g1_intt_dev(plk_ctx *ctx, const G1Affine *in, uint32_t log_n, G1Affine *
         PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g1ntt_stage<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO8));
         attr_set = true;
     }
+    return PLK_OK;
+}
+
+// The log_n stages over points already in bit-reversed order.  Inverse: omega^-1 and 1/N on the last stage.  Forward: omega, and the last stage is
+// the non-scaling instantiation like the others (no multiplication by 1 goes through the SCALE path).
+static int32_t g1ntt_stages(plk_ctx *ctx, XyzzW *pts, uint32_t log_n, bool inverse, hipStream_t st) {
+    PLK_TRY(g1ntt_stage_attrs());
+    const uint32_t n = 1u << log_n;
+    const Fr n_inv = ctx->n_inv[log_n];                           // Montgomery form; 1 for log_n = 0 (no stage, nothing to scale)
+    const PowTable tw = inverse ? ctx->tw_inv : ctx->tw_fwd;
     // PLK_G1NTT_ISO (A/B knob): 0 = the window table in XYZZ and full additions, as in rounds 4-5; 1 = four effectively affine entries, 3-bit windows; default 2 = eight, 4-bit windows
     // (the same chain in Jacobian coordinates — 4S + 3M doublings — was built, verified and measured 3 % SLOWER: profiles/r06b_g1ntt_jacobian.patch)
     static const int iso = [] { const char *e = getenv("PLK_G1NTT_ISO"); return e ? atoi(e) : 2; }();
-    hipLaunchKernelGGL(g1ntt_load, dim3((n + 255) / 256), dim3(256), 0, st, pts, in, log_n);
     const dim3 sgrid((n / 2 + G1NTT_THREADS - 1) / G1NTT_THREADS);
     auto stage = [&](auto scale_tag, uint32_t s) {
         constexpr bool SC = decltype(scale_tag)::value;
-        if (iso == 2) hipLaunchKernelGGL((g1ntt_stage<SC, 2>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS_ISO8, st, pts, log_n, s, ctx->tw_inv, n_inv);
-        else if (iso == 1) hipLaunchKernelGGL((g1ntt_stage<SC, 1>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, pts, log_n, s, ctx->tw_inv, n_inv);
-        else hipLaunchKernelGGL((g1ntt_stage<SC, 0>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS, st, pts, log_n, s, ctx->tw_inv, n_inv);
+        if (iso == 2) hipLaunchKernelGGL((g1ntt_stage<SC, 2>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS_ISO8, st, pts, log_n, s, tw, n_inv);
+        else if (iso == 1) hipLaunchKernelGGL((g1ntt_stage<SC, 1>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, pts, log_n, s, tw, n_inv);
+        else hipLaunchKernelGGL((g1ntt_stage<SC, 0>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS, st, pts, log_n, s, tw, n_inv);
     };
     for (uint32_t s = 0; s + 1 < log_n; s++) stage(std::false_type{}, s);
-    if (log_n) stage(std::true_type{}, log_n - 1);
+    if (log_n) { if (inverse) stage(std::true_type{}, log_n - 1); else stage(std::false_type{}, log_n - 1); }
+    PLK_HIP(hipGetLastError());
+    return PLK_OK;
+}
+
+int32_t g1_ntt_dev(plk_ctx *ctx, const G1Affine *in, uint32_t log_n, bool inverse, G1Affine *out, hipStream_t st, const char *who) {
+    if (log_n > 26) { set_error(std::string(who) + ": size exceeds 2^26"); return PLK_ERR_SIZE; }
+    PLK_TRY(ntt_init_tables(ctx));
+    const uint32_t n = 1u << log_n;
+    // the transform borrows the scratch of the first commitment slot: nothing may be in flight there
+    if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
+    PLK_TRY(ctx->slot[0].c.reserve((size_t)n * sizeof(XyzzW)));
+    XyzzW *pts = ctx->slot[0].c.as<XyzzW>();
+    hipLaunchKernelGGL(g1ntt_load, dim3((n + 255) / 256), dim3(256), 0, st, pts, in, log_n);
+    PLK_TRY(g1ntt_stages(ctx, pts, log_n, inverse, st));
     hipLaunchKernelGGL(g1ntt_to_affine, dim3(((n + G1NTT_NORM_K - 1) / G1NTT_NORM_K + 255) / 256), dim3(256), 0, st, out, (const XyzzW *)pts, n);
+    PLK_HIP(hipGetLastError());
+    return PLK_OK;
+}
+
+int32_t g1_intt_dev(plk_ctx *ctx, const G1Affine *in, uint32_t log_n, G1Affine *out, hipStream_t st) { return g1_ntt_dev(ctx, in, log_n, true, out, st, "g1_intt"); }
+
+// The transform of 2^log_n XYZZ points where they lie (natural order in and out, any buffer of the caller's: no scratch, no refusal of its own
+// beyond the size).  A chain of transforms (kzg_all.hip) stays on the 29-bit layer and pays for g1ntt_to_affine once.
+int32_t g1_ntt_xyzzw_dev(plk_ctx *ctx, XyzzW *pts, uint32_t log_n, bool inverse, hipStream_t st) {
+    if (log_n > 26) { set_error("g1_ntt: size exceeds 2^26"); return PLK_ERR_SIZE; }
+    PLK_TRY(ntt_init_tables(ctx));
+    const uint32_t n = 1u << log_n;
+    hipLaunchKernelGGL(g1ntt_bitrev, dim3((n + 255) / 256), dim3(256), 0, st, pts, log_n);
+    return g1ntt_stages(ctx, pts, log_n, inverse, st);
+}
+int32_t g1_xyzzw_to_affine_dev(const XyzzW *pts, uint32_t n, G1Affine *out, hipStream_t st) {
+    hipLaunchKernelGGL(g1ntt_to_affine, dim3(((n + G1NTT_NORM_K - 1) / G1NTT_NORM_K + 255) / 256), dim3(256), 0, st, out, pts, n);
     PLK_HIP(hipGetLastError());
     return PLK_OK;
 }
@@ -180,4 +225,13 @@ extern "C" int32_t plk_g1_intt_srs_dev(plk_ctx *ctx, uint32_t log_n, void *out_d
     PLK_HIP(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     return g1_intt_dev(ctx, reinterpret_cast<const G1Affine *>(ctx->srs), log_n, reinterpret_cast<G1Affine *>(out_dev), s);
+}
+
+// either direction, device to device: inverse != 0 is plk_g1_intt's transform, bit for bit; inverse == 0 is out[i] = sum_j omega^(i j) in[j]
+extern "C" int32_t plk_g1_ntt_dev(plk_ctx *ctx, const void *in_dev, uint32_t log_n, int32_t inverse, void *out_dev, void *stream) {
+    if (!ctx || !in_dev || !out_dev) { set_error("plk_g1_ntt_dev: bad argument"); return PLK_ERR_ARG; }
+    if (((uintptr_t)in_dev | (uintptr_t)out_dev) & 15u) { set_error("plk_g1_ntt_dev: device pointers must be 16-byte aligned"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    return g1_ntt_dev(ctx, static_cast<const G1Affine *>(in_dev), log_n, inverse != 0, static_cast<G1Affine *>(out_dev), s, "plk_g1_ntt_dev");
 }

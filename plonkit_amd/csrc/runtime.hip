@@ -96,7 +96,7 @@ void srs_return_loan(plk_ctx *c) {
         if (c->lag_borrowed) lender->lag_borrowers.fetch_sub(1);
         if (lender->srs_borrowers.fetch_sub(1) == 1 && lender->zombie) orphan = lender;
         c->srs_lender = nullptr;
-        c->srs = nullptr; c->srs_n = 0; c->srs_w.release(); c->srs_w_valid = false; c->srs_w_copies = 0; c->srs_w_no_inf = false;
+        c->srs = nullptr; c->srs_n = 0; c->srs_w.release(); c->srs_w_valid = false; c->srs_w_copies = 0; c->srs_w_no_inf = false; c->fk_key_valid = false;
         if (c->lag_borrowed) { c->lag.pts = nullptr; c->lag.n = 0; c->lag.w.release(); c->lag.w_valid = false; c->lag.w_copies = 0; c->lag.w_no_inf = false; }
         c->lag_borrowed = false;
     }
@@ -105,6 +105,7 @@ void srs_return_loan(plk_ctx *c) {
 void srs_make_loan(plk_ctx *dst, plk_ctx *src) {         // (msm.hip plk_ctx_share_srs: the checks and the fallible steps come first)
     std::lock_guard<std::mutex> g(g_share_mu);
     dst->srs = src->srs; dst->srs_n = src->srs_n;
+    dst->fk_key_valid = false;                          // (kzg_all.hip: the transform of the key dst had)
     dst->srs_w.borrow(src->srs_w); dst->srs_w_valid = src->srs_w_valid; dst->srs_w_copies = src->srs_w_copies; dst->srs_w_no_inf = src->srs_w_valid && src->srs_w_no_inf;
     dst->lag.pts = src->lag.pts; dst->lag.n = src->lag.n;
     dst->lag.w.borrow(src->lag.w); dst->lag.w_valid = src->lag.pts ? src->lag.w_valid : false; dst->lag.w_copies = src->lag.w_copies; dst->lag.w_no_inf = dst->lag.w_valid && src->lag.w_no_inf;
@@ -203,7 +204,7 @@ void plk_destroy(plk_ctx *ctx) {
         if (S.ev[0]) { (void)hipEventDestroy(S.ev[0]); (void)hipEventDestroy(S.ev[1]); }
     }
     ctx->bases_w.release(); ctx->stage.release(); ctx->vm_stage.release(); ctx->pair_tab.release(); ctx->key_bad.release(); ctx->poly_tmp.release(); ctx->poly_tmp2.release(); ctx->prove_ws.release();
-    ctx->kzg_ws.release(); ctx->kzg_vm.release();
+    ctx->kzg_ws.release(); ctx->kzg_vm.release(); ctx->fk_key.release(); ctx->fk_ws.release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned2) (void)hipHostFree(ctx->pinned2);
     if (ctx->flag_ready) (void)hipEventDestroy(ctx->flag_ready);
