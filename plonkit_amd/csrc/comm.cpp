@@ -668,7 +668,7 @@ int32_t plk_comm_scatter_selftest(plk_ctx *ctx, uint32_t log_n, uint32_t iterati
     Comm *C = ctx ? static_cast<Comm *>(ctx->comm) : nullptr;
     if (!C || C->tcp || C->world != 1 || !mismatches || log_n > 24) { set_error("plk_comm_scatter_selftest: needs an RCCL communicator of ONE rank on this context (plk_comm_init) and log_n <= 24"); return PLK_ERR_ARG; }
     const uint64_t n = 1ull << log_n;
-    if (!ctx->srs || ctx->srs_n < n) { set_error("plk_comm_scatter_selftest: the resident key is shorter than 2^log_n"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts || ctx->srs().n < n) { set_error("plk_comm_scatter_selftest: the resident key is shorter than 2^log_n"); return PLK_ERR_SRS; }
     if (ctx->msm_enq != ctx->msm_fin) { set_error("plk_comm_scatter_selftest: a commitment is still in flight"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
     *mismatches = 0;
@@ -688,9 +688,9 @@ int32_t plk_comm_scatter_selftest(plk_ctx *ctx, uint32_t log_n, uint32_t iterati
         if (rc == PLK_OK) rc = comm_recv_work(ctx, &w, consumer);
         if (rc == PLK_OK && (w.op != SHARD_COMMIT || w.count != 1 || w.len != n)) { set_error("plk_comm_scatter_selftest: the batch arrived changed"); rc = PLK_ERR_IO; }
         host::HJac got, want;
-        if (rc == PLK_OK) rc = msm_enqueue(ctx, static_cast<const Fr *>(w.vec[0]), n, 0, consumer);
+        if (rc == PLK_OK) rc = msm_enqueue(ctx, ctx->srs(), static_cast<const Fr *>(w.vec[0]), n, 0, consumer);
         if (rc == PLK_OK) rc = msm_finish(ctx, nullptr, &got);
-        if (rc == PLK_OK) rc = msm_enqueue(ctx, v.as<Fr>(), n, 0, ctx->stream);
+        if (rc == PLK_OK) rc = msm_enqueue(ctx, ctx->srs(), v.as<Fr>(), n, 0, ctx->stream);
         if (rc == PLK_OK) rc = msm_finish(ctx, nullptr, &want);
         if (rc == PLK_OK) {
             const host::HAffine a = host::jac_to_affine(got), b = host::jac_to_affine(want);

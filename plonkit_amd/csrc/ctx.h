@@ -51,6 +51,26 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// A resident key: n G1 points on the device, the MSM's fixed-base table of them, and the key's side of a loan (plk_ctx_share_srs).
+// A context holds two, plk_ctx::key[KeyForm]: the monomial SRS and the optional Lagrange-form key, Crs<E, CrsForLagrangeForm>
+// (L_i(tau)*G), which plk_prove uses for commit_using_values (`prove -l`, src/plonk.rs:138-146).  Whoever commits names the key it
+// commits against (msm.h).  A key changes only through the key_* functions below the context.
+enum KeyForm : uint32_t { KEY_MONOMIAL = 0, KEY_LAGRANGE = 1, KEY_FORMS = 2 };
+struct ResidentKey {
+    const void *pts = nullptr;               // device, Montgomery affine, 64 B per point: own.p, the caller's memory (set_dev) or the lender's
+    uint64_t n = 0;
+    DevBuf own;
+    DevBuf w;                                // the same points in the 2^261 Montgomery domain of field29_dev.h (MSM gathers)
+    bool w_valid = false;
+    uint32_t w_copies = 0;                   // shifted copies 2^(16k) * P held in w (fixed-base table of the MSM)
+    bool w_no_inf = false;                   // w holds no point at infinity: established by every build of the table (msm.hip: ensure_base_table), void
+                                             // with it (w_valid) — a key can only change through key_install, so it cannot go stale
+    bool borrowed = false;                   // borrower: pts and w are the lender's, which a borrower must neither free nor grow
+    std::atomic<int> borrowers{0};           // lender: how many contexts hold this key (it may replace the key while none does)
+    void void_table() { w_valid = false; w_no_inf = false; if (w.borrowed) w.release(); }
+    void release() { own.release(); w.release(); }
+};
+
 }  // namespace plk
 
 struct plk_ctx {
@@ -75,21 +95,7 @@ struct plk_ctx {
     plk::DevBuf ntt_scratch[2];              // ping-pong buffers of the NTT passes: [0] main stream, [1] the prover's background stream
     hipStream_t bg_stream = nullptr;         // low-priority stream of the prover: extensions that no challenge waits for
     hipEvent_t bg_go = nullptr, bg_done = nullptr;
-    // SRS
-    const void *srs = nullptr;               // device, Montgomery affine, 64 B per point
-    uint64_t srs_n = 0;
-    plk::DevBuf srs_own;
-    plk::DevBuf srs_w;                       // the same points in the 2^261 Montgomery domain of field29_dev.h (MSM gathers)
-    bool srs_w_valid = false;
-    uint32_t srs_w_copies = 0;               // shifted copies 2^(16k) * P held in srs_w (fixed-base table of the MSM)
-    bool srs_w_no_inf = false;               // srs_w holds no point at infinity: established by every build of the table (msm.hip: ensure_base_table), void
-                                             // with it (srs_w_valid) — a key can only change through srs_table_invalidate, so it cannot go stale
-    // optional second key: Crs<E, CrsForLagrangeForm> (L_i(tau)*G), used by plk_prove for commit_using_values
-    // (`prove -l`, src/plonk.rs:138-146).  Same fields as above; SrsSlotSwap makes it the active key for one call.
-    struct LagrangeKey {
-        const void *pts = nullptr; uint64_t n = 0;
-        plk::DevBuf own, w; bool w_valid = false; uint32_t w_copies = 0; bool w_no_inf = false;
-    } lag;
+    plk::ResidentKey key[plk::KEY_FORMS];    // the SRS and the optional Lagrange-form key
     // MSM: up to three commitments (or batches) may be in flight, each with its own scratch, result buffer and stream:
     // the latency-bound tail of commitment k-1 (bucket reduction) and the digit / partition kernels of k+1 then share the
     // GPU with the accumulation of k, which starts the moment the previous accumulation ends.  A slot is taken lowest
@@ -144,7 +150,7 @@ struct plk_ctx {
     plk::DevBuf kzg_ws;                      // kzg.hip: scratch of the blocking opening calls (grows only; a call that grew it past 64 MiB frees it on return)
     plk::DevBuf kzg_vm;                      // kzg.hip: plk_kzg_verify_many_dev's working memory, its own for vm_stage's reason (the call does not wait)
     // kzg_all.hip (all openings on the domain in one pass).  fk_key: DFT_2N of the arranged key, 2N XYZZ points of the 29-bit layer, this
-    // context's own even where the key is borrowed or lent; void with the key (srs_table_invalidate).  fk_ws: scratch of a call (grows only;
+    // context's own even where the key is borrowed or lent; void with the monomial key (key_changed).  fk_ws: scratch of a call (grows only;
     // a call that grew it past 64 MiB frees it on return).
     plk::DevBuf fk_key, fk_ws;
     bool fk_key_valid = false;
@@ -161,41 +167,34 @@ struct plk_ctx {
     std::vector<plk::host::HJac> commit_pieces;   // partial sums of a commitment longer than one MSM call (prover.hip)
     std::vector<plk::host::HJac> commit_done;     // finished commitments of a batch that is processed one at a time
     // plk_ctx_share_srs: a context that proves beside another one on the same GPU borrows that one's resident key(s) and MSM
-    // fixed-base table(s) instead of holding a second copy.  The lender counts its borrowers and refuses to replace a key
-    // while one exists; a borrower drops the loan when it is given a key of its own or destroyed.
+    // fixed-base table(s) instead of holding a second copy.  The lender counts the borrowers of each key (ResidentKey) and refuses
+    // to replace a key while one exists; a borrower drops the loan when it is given a key of its own or destroyed.
     plk_ctx *srs_lender = nullptr;
-    std::atomic<int> srs_borrowers{0};
-    bool lag_borrowed = false;               // borrower: the Lagrange-form key in `lag` is the lender's (recorded when the loan was made:
-                                             // the lender swaps its own key slots during a proof, so comparing pointers later is a race)
-    std::atomic<int> lag_borrowers{0};       // lender: how many borrowers hold its Lagrange-form key (it may install one while none does)
     bool zombie = false;                     // lender destroyed while borrowers exist: only the lent key and tables are left, freed with the last loan
+    plk::ResidentKey &srs() { return key[plk::KEY_MONOMIAL]; }
+    plk::ResidentKey &lagrange() { return key[plk::KEY_LAGRANGE]; }
 };
 
 namespace plk {
-// every entry point that replaces a resident key goes through these two: the MSM table of the old key is void, and a table
-// (or key) that was only borrowed must not be written to when the next one is built
-int32_t srs_replace_guard(plk_ctx *c, const char *who, bool lagrange_only = false);   // runtime.hip: PLK_ERR_ARG while another context borrows this one's key
-inline void srs_table_invalidate(plk_ctx *c) {
-    c->srs_w_valid = false; c->srs_w_no_inf = false; if (c->srs_w.borrowed) c->srs_w.release();
-    c->fk_key_valid = false;                 // the key's transform (kzg_all.hip) cannot outlive its key; the buffer stays for the next one
+// Every change of a resident key ends in key_install, and with it in key_changed: the key's MSM table is void (a table that was only
+// borrowed is let go, not written to when the next one is built), and so is what the context derived from the monomial key.
+// Before it, every entry point that replaces a key passes the guard.
+int32_t srs_replace_guard(plk_ctx *c, const char *who, KeyForm which = KEY_MONOMIAL);   // runtime.hip: PLK_ERR_ARG while another context borrows that key
+// (the monomial key's transform, kzg_all.hip, cannot outlive its key; the buffer stays for the next one)
+inline void key_changed(plk_ctx *c, KeyForm which) { if (which == KEY_MONOMIAL) c->fk_key_valid = false; }
+// the key is now the n points at `pts`: the key's own buffer filled in place, or memory the caller keeps alive (nullptr, 0: no key)
+inline void key_install(plk_ctx *c, KeyForm which, const void *pts, uint64_t n) {
+    ResidentKey &k = c->key[which];
+    k.pts = pts; k.n = n; k.void_table();
+    key_changed(c, which);
 }
-inline void lag_table_invalidate(plk_ctx *c) { c->lag.w_valid = false; c->lag.w_no_inf = false; if (c->lag.w.borrowed) c->lag.w.release(); }
+// the same for a key that was completed beside the old one: `fresh` becomes the key's own buffer and leaves with the old allocation
+inline void key_install_owned(plk_ctx *c, KeyForm which, DevBuf &fresh, uint64_t n) {
+    std::swap(c->key[which].own, fresh);
+    key_install(c, which, c->key[which].own.p, n);
+}
+inline void key_clear(plk_ctx *c, KeyForm which) { key_install(c, which, nullptr, 0); }
 void srs_return_loan(plk_ctx *c);                                 // runtime.hip
 void srs_make_loan(plk_ctx *dst, plk_ctx *src);                   // runtime.hip
 bool srs_orphan_lender(plk_ctx *c);                               // runtime.hip
-
-// makes the Lagrange key the context's active SRS for the lifetime of the guard (host-side pointer swap only;
-// kernels already enqueued keep the addresses they were launched with)
-struct SrsSlotSwap {
-    plk_ctx *c; bool on;
-    SrsSlotSwap(plk_ctx *ctx, bool lagrange) : c(ctx), on(lagrange) { flip(); }
-    ~SrsSlotSwap() { flip(); }
-    void flip() {
-        if (!on) return;
-        std::swap(c->srs, c->lag.pts); std::swap(c->srs_n, c->lag.n);
-        std::swap(c->srs_own, c->lag.own); std::swap(c->srs_w, c->lag.w);
-        std::swap(c->srs_w_valid, c->lag.w_valid); std::swap(c->srs_w_copies, c->lag.w_copies);
-        std::swap(c->srs_w_no_inf, c->lag.w_no_inf);
-    }
-};
 }  // namespace plk

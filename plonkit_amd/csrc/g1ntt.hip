@@ -221,10 +221,10 @@ extern "C" int32_t plk_g1_intt(plk_ctx *ctx, const plk_g1_affine *in, uint32_t l
 // the same transform applied to the first 2^log_n points of the resident SRS; result left on the device
 extern "C" int32_t plk_g1_intt_srs_dev(plk_ctx *ctx, uint32_t log_n, void *out_dev, void *stream) {
     if (!ctx || !out_dev) { set_error("plk_g1_intt_srs_dev: bad argument"); return PLK_ERR_ARG; }
-    if (!ctx->srs || ctx->srs_n < ((uint64_t)1 << log_n)) { set_error("g1_intt: SRS too small"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts || ctx->srs().n < ((uint64_t)1 << log_n)) { set_error("g1_intt: SRS too small"); return PLK_ERR_SRS; }
     PLK_HIP(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    return g1_intt_dev(ctx, reinterpret_cast<const G1Affine *>(ctx->srs), log_n, reinterpret_cast<G1Affine *>(out_dev), s);
+    return g1_intt_dev(ctx, reinterpret_cast<const G1Affine *>(ctx->srs().pts), log_n, reinterpret_cast<G1Affine *>(out_dev), s);
 }
 
 // either direction, device to device: inverse != 0 is plk_g1_intt's transform, bit for bit; inverse == 0 is out[i] = sum_j omega^(i j) in[j]

@@ -65,7 +65,7 @@ int32_t derive_rho(const char *tag, const uint8_t *seed, HFr *rho) {
 
 // (the twist arithmetic of the two [r]Q = O checks: g2_host.h)
 
-// Where the n points under check live: the resident monomial key (plk_srs_check: commitments through plk_msm_g1_dev and its fixed-base
+// Where the n points under check live: the resident monomial key (plk_srs_check: commitments through msm_commit and the key's fixed-base
 // table, points by plk_srs_download) or n points in device memory that are no key (plk_srs_check_points_dev: commitments through the
 // caller-supplied-bases path, msm_bases_commit, which builds no table and touches nothing resident).  Everything else is shared.
 struct KeyPoints {
@@ -76,7 +76,7 @@ struct KeyPoints {
     int32_t commit(const Fr *pows, uint64_t lo, uint64_t m, HAffine *T) const {
         if (!dev) {
             plk_g1_affine t;
-            PLK_TRY(plk_msm_g1_dev(ctx, pows, m, lo, &t, nullptr));
+            PLK_TRY(msm_commit(ctx, ctx->srs(), pows, m, lo, &t, nullptr));
             memcpy(T, &t, 64);
             return PLK_OK;
         }
@@ -184,9 +184,9 @@ extern "C" int32_t plk_srs_check(plk_ctx *ctx, const uint8_t g2[256], const uint
     if (!ctx || !g2 || !valid || (flags & ~PLK_KEY_LOCATE)) { set_error("plk_srs_check: bad argument"); return PLK_ERR_ARG; }
     G2Affine q[2];
     if (!g2_from_bytes(g2, &q[0]) || !g2_from_bytes(g2 + 128, &q[1])) { set_error("plk_srs_check: G2 point not on the twist"); return PLK_ERR_ARG; }
-    if (!ctx->srs || ctx->srs_n == 0) { set_error("plk_srs_check: no key resident"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts || ctx->srs().n == 0) { set_error("plk_srs_check: no key resident"); return PLK_ERR_SRS; }
     if (ctx->msm_enq != ctx->msm_fin) { set_error("plk_srs_check: a commitment is still in flight on this context"); return PLK_ERR_ARG; }
-    return check_powers("plk_srs_check", KeyPoints{ctx, nullptr, ctx->srs_n}, q, seed, flags, valid, bad_out);
+    return check_powers("plk_srs_check", KeyPoints{ctx, nullptr, ctx->srs().n}, q, seed, flags, valid, bad_out);
 }
 
 // the same verdict on n points in device memory that are not installed (and need not be): nothing resident is read or changed
@@ -210,9 +210,9 @@ extern "C" int32_t plk_srs_lagrange_check(plk_ctx *ctx, const uint8_t seed[32], 
     if (!ctx || !valid) { set_error("plk_srs_lagrange_check: bad argument"); return PLK_ERR_ARG; }
     if (ctx->shard_first != 0) { set_error("plk_srs_lagrange_check: this context holds a slice of the key (first index " + std::to_string(ctx->shard_first) + "): tying the two forms needs the whole prefix"); return PLK_ERR_ARG; }
     if (ctx->msm_enq != ctx->msm_fin) { set_error("plk_srs_lagrange_check: a commitment is still in flight on this context"); return PLK_ERR_ARG; }
-    if (!ctx->lag.pts || ctx->lag.n == 0) { set_error("plk_srs_lagrange_check: no Lagrange-form key resident"); return PLK_ERR_SRS; }
-    const uint64_t N = ctx->lag.n;
-    if (!ctx->srs || ctx->srs_n < N) { set_error("plk_srs_lagrange_check: the monomial key is missing or shorter than the Lagrange-form key"); return PLK_ERR_SRS; }
+    if (!ctx->lagrange().pts || ctx->lagrange().n == 0) { set_error("plk_srs_lagrange_check: no Lagrange-form key resident"); return PLK_ERR_SRS; }
+    const uint64_t N = ctx->lagrange().n;
+    if (!ctx->srs().pts || ctx->srs().n < N) { set_error("plk_srs_lagrange_check: the monomial key is missing or shorter than the Lagrange-form key"); return PLK_ERR_SRS; }
     uint32_t log_n = 0;
     while ((1ull << log_n) < N) log_n++;
     if ((1ull << log_n) != N || log_n > MAX_LOG_N) { set_error("plk_srs_lagrange_check: the Lagrange-form key's size is not a power of two"); return PLK_ERR_SIZE; }
@@ -223,12 +223,9 @@ extern "C" int32_t plk_srs_lagrange_check(plk_ctx *ctx, const uint8_t seed[32], 
     WorkspaceLoan loan{ctx};
     PLK_TRY(fill_powers(ctx, rho, N, &pows, &loan));
     plk_g1_affine by_values, by_coeffs;
-    {
-        SrsSlotSwap active(ctx, true);                          // the Lagrange-form key is the commitment's key for this one call
-        PLK_TRY(plk_msm_g1_dev(ctx, pows, N, 0, &by_values, nullptr));
-    }
+    PLK_TRY(msm_commit(ctx, ctx->lagrange(), pows, N, 0, &by_values, nullptr));
     if (log_n) PLK_TRY(plk_ntt_dev(ctx, pows, log_n, 1, nullptr, nullptr));
-    PLK_TRY(plk_msm_g1_dev(ctx, pows, N, 0, &by_coeffs, nullptr));
+    PLK_TRY(msm_commit(ctx, ctx->srs(), pows, N, 0, &by_coeffs, nullptr));
     *valid = memcmp(&by_values, &by_coeffs, sizeof by_values) == 0 ? 1 : 0;
     return PLK_OK;
 }

@@ -159,7 +159,8 @@ extern "C" int32_t plk_srs_load_key(plk_ctx *ctx, const uint8_t *data, uint64_t 
     const uint64_t kept = count ? count : n - first;
     if (kept == 0) { set_error("plk_srs_load_key: nothing to keep resident"); return PLK_ERR_ARG; }
     // a lender is refused before any work; a borrower's loan is only dropped once the new key is complete (the guard below)
-    if ((lagrange ? ctx->lag_borrowers.load() : ctx->srs_borrowers.load()) > 0) return srs_replace_guard(ctx, "plk_srs_load_key", lagrange);
+    const KeyForm which = lagrange ? KEY_LAGRANGE : KEY_MONOMIAL;
+    if (ctx->key[which].borrowers.load() > 0) return srs_replace_guard(ctx, "plk_srs_load_key", which);
     PLK_HIP(hipSetDevice(ctx->device));
     DevBuf fresh;                                                             // the old key stays what it is until every chunk has passed
     struct Drop { DevBuf &b; ~Drop() { b.release(); } } drop{fresh};
@@ -188,22 +189,16 @@ extern "C" int32_t plk_srs_load_key(plk_ctx *ctx, const uint8_t *data, uint64_t 
     PLK_HIP(hipStreamSynchronize(ctx->stream));
     if (bad_out) *bad_out = bad;
     if (bad != KEY_NONE) { set_error("read key err: point not on curve"); return PLK_ERR_FORMAT; }
-    PLK_TRY(srs_replace_guard(ctx, "plk_srs_load_key", lagrange));
-    if (lagrange) {
-        std::swap(ctx->lag.own, fresh);
-        ctx->lag.pts = ctx->lag.own.p; ctx->lag.n = kept; lag_table_invalidate(ctx);
-    } else {
-        std::swap(ctx->srs_own, fresh);
-        ctx->srs = ctx->srs_own.p; ctx->srs_n = kept; srs_table_invalidate(ctx);
-    }
+    PLK_TRY(srs_replace_guard(ctx, "plk_srs_load_key", which));
+    key_install_owned(ctx, which, fresh, kept);
     return PLK_OK;                                                            // (`fresh` now holds the previous allocation: freed here)
 }
 
 extern "C" int32_t plk_srs_store_key(plk_ctx *ctx, uint32_t flags, const uint8_t g2[256], uint8_t *out, uint64_t cap, uint64_t *len) {
     if (!ctx || !g2 || !len || (flags & ~PLK_KEY_LAGRANGE)) { set_error("plk_srs_store_key: bad argument"); return PLK_ERR_ARG; }
-    const bool lagrange = (flags & PLK_KEY_LAGRANGE) != 0;
-    const char *pts = (const char *)(lagrange ? ctx->lag.pts : ctx->srs);
-    const uint64_t n = lagrange ? ctx->lag.n : ctx->srs_n;
+    const ResidentKey &key = ctx->key[(flags & PLK_KEY_LAGRANGE) ? KEY_LAGRANGE : KEY_MONOMIAL];
+    const char *pts = (const char *)key.pts;
+    const uint64_t n = key.n;
     if (!pts || n == 0) { set_error("plk_srs_store_key: no resident key of that form"); return PLK_ERR_SRS; }
     *len = 8 + 64 * n + 8 + 256;
     if (!out) return PLK_OK;
@@ -242,16 +237,15 @@ extern "C" int32_t plk_srs_lagrange_from_powers(plk_ctx *ctx, uint32_t log_n) {
     if (!ctx) { set_error("plk_srs_lagrange_from_powers: bad argument"); return PLK_ERR_ARG; }
     if (log_n > 26) { set_error("g1_intt: size exceeds 2^26"); return PLK_ERR_SIZE; }
     const uint64_t n = 1ull << log_n;
-    if (!ctx->srs || ctx->srs_n < n) { set_error("g1_intt: SRS too small"); return PLK_ERR_SRS; }
-    if (ctx->lag_borrowers.load() > 0) return srs_replace_guard(ctx, "plk_srs_lagrange_from_powers", true);
+    if (!ctx->srs().pts || ctx->srs().n < n) { set_error("g1_intt: SRS too small"); return PLK_ERR_SRS; }
+    if (ctx->lagrange().borrowers.load() > 0) return srs_replace_guard(ctx, "plk_srs_lagrange_from_powers", KEY_LAGRANGE);
     PLK_HIP(hipSetDevice(ctx->device));
     DevBuf fresh;
     struct Drop { DevBuf &b; ~Drop() { b.release(); } } drop{fresh};
     PLK_TRY(fresh.reserve(n * sizeof(G1Affine)));
-    PLK_TRY(g1_intt_dev(ctx, reinterpret_cast<const G1Affine *>(ctx->srs), log_n, fresh.as<G1Affine>(), ctx->stream));
+    PLK_TRY(g1_intt_dev(ctx, reinterpret_cast<const G1Affine *>(ctx->srs().pts), log_n, fresh.as<G1Affine>(), ctx->stream));
     PLK_HIP(hipStreamSynchronize(ctx->stream));
-    PLK_TRY(srs_replace_guard(ctx, "plk_srs_lagrange_from_powers", true));
-    std::swap(ctx->lag.own, fresh);
-    ctx->lag.pts = ctx->lag.own.p; ctx->lag.n = n; lag_table_invalidate(ctx);
+    PLK_TRY(srs_replace_guard(ctx, "plk_srs_lagrange_from_powers", KEY_LAGRANGE));
+    key_install_owned(ctx, KEY_LAGRANGE, fresh, n);
     return PLK_OK;
 }

@@ -15,6 +15,7 @@
 // Domains (poly.h): vectors and scalars carry 2^256 (E); the scans and the omega table live in the 2^261 domain (W); a product of the
 // 29-bit layer removes 2^261, so W x W = W and W x E = E.
 #include "ctx.h"
+#include "msm.h"
 #include "poly.h"
 #include "ntt.h"
 #include "ec_dev.h"
@@ -316,13 +317,13 @@ int32_t kzg_common_args(const char *who, plk_ctx *ctx, const void *const *polys,
 int32_t kzg_lagrange_key(plk_ctx *ctx, uint64_t n, uint32_t *log_n) {
     uint32_t l = 0;
     while ((1ull << l) < n) l++;
-    if (!ctx->lag.pts || ctx->lag.n != n || (1ull << l) != n || l == 0 || l > MAX_LOG_N) { set_error(KZ_LAGRANGE_SIZE); return PLK_ERR_SRS; }
+    if (!ctx->lagrange().pts || ctx->lagrange().n != n || (1ull << l) != n || l == 0 || l > MAX_LOG_N) { set_error(KZ_LAGRANGE_SIZE); return PLK_ERR_SRS; }
     *log_n = l;
     return PLK_OK;
 }
 
 int32_t open_coefficients(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint64_t n, const HFr &z, const HFr *vp, plk_fr *evals, plk_g1_affine *proof, hipStream_t st) {
-    if (!ctx->srs || n > ctx->srs_n) { set_error("plk_kzg_open_dev: no key resident, or the key is shorter than the polynomials"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts || n > ctx->srs().n) { set_error("plk_kzg_open_dev: no key resident, or the key is shorter than the polynomials"); return PLK_ERR_SRS; }
     if (n > (1ull << MAX_LOG_N)) { set_error("plk_kzg_open_dev: more than 2^28 coefficients"); return PLK_ERR_SIZE; }
     KzgScratch ws(ctx, st);
     PLK_TRY(ws.reserve(((size_t)4 * POW_TAB + KZ_MAX + 2 * n) * sizeof(Fr)));
@@ -352,7 +353,7 @@ int32_t open_coefficients(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint
         }
         PLK_HIP(hipMemsetAsync(q + (n - 1), 0, sizeof(Fr), st));
     }
-    return plk_msm_g1_dev(ctx, q, n, 0, proof, st);               // waits: the evaluations have arrived as well
+    return msm_commit(ctx, ctx->srs(), q, n, 0, proof, st);       // waits: the evaluations have arrived as well
 }
 
 int32_t open_values(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint64_t n, const HFr &z, const HFr *vp, plk_fr *evals, plk_g1_affine *proof, hipStream_t st) {
@@ -373,8 +374,7 @@ int32_t open_values(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint64_t n
         F = p.extra;
     }
     PLK_TRY(values_divide(ctx, p, F, Y, p.extra, st));
-    SrsSlotSwap active(ctx, true);                                 // commit_using_values: the Lagrange-form key is the commitment's key for this one call
-    return plk_msm_g1_dev(ctx, p.extra, n, 0, proof, st);
+    return msm_commit(ctx, ctx->lagrange(), p.extra, n, 0, proof, st);   // commit_using_values
 }
 
 }  // namespace
@@ -425,10 +425,9 @@ extern "C" int32_t plk_poly_divide_values_by_linear_dev(plk_ctx *ctx, const void
 extern "C" int32_t plk_kzg_commit_dev(plk_ctx *ctx, const void *const *polys_dev, uint32_t count, uint64_t n, uint32_t flags, plk_g1_affine *out, void *stream) {
     if (!out) { set_error("plk_kzg_commit_dev: bad argument"); return PLK_ERR_ARG; }
     PLK_TRY(kzg_common_args("plk_kzg_commit_dev", ctx, polys_dev, count, n, flags));
-    if (!(flags & PLK_KZG_VALUES)) return plk_msm_g1_batch_dev(ctx, polys_dev, count, n, 0, out, stream);
-    if (!ctx->lag.pts || ctx->lag.n != n) { set_error(KZ_LAGRANGE_SIZE); return PLK_ERR_SRS; }
-    SrsSlotSwap active(ctx, true);                                 // commit_using_values
-    return plk_msm_g1_batch_dev(ctx, polys_dev, count, n, 0, out, stream);
+    const bool values = (flags & PLK_KZG_VALUES) != 0;             // commit_using_values: against the Lagrange-form key
+    if (values && (!ctx->lagrange().pts || ctx->lagrange().n != n)) { set_error(KZ_LAGRANGE_SIZE); return PLK_ERR_SRS; }
+    return msm_commit_many(ctx, ctx->key[values ? KEY_LAGRANGE : KEY_MONOMIAL], polys_dev, count, n, 0, out, (hipStream_t)stream);
 }
 
 extern "C" int32_t plk_kzg_open_dev(plk_ctx *ctx, const void *const *polys_dev, uint32_t count, uint64_t n, const plk_fr *z, const plk_fr *v, uint32_t flags,

@@ -81,7 +81,7 @@ int32_t fk_common(const char *who, plk_ctx *ctx, uint32_t log_n) {
     if (!fk_size_ok(log_n)) { set_error(std::string(who) + ": more than 2^25 points"); return PLK_ERR_SIZE; }
     if (ctx->combine) { set_error(std::string(who) + ": single-GPU only (this context holds one shard of a key, plk_set_commit_shard)"); return PLK_ERR_ARG; }
     if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment is still in flight on this context"); return PLK_ERR_ARG; }
-    const uint64_t need = fk_key_points_needed(log_n), have = ctx->srs ? ctx->srs_n : 0;
+    const uint64_t need = fk_key_points_needed(log_n), have = ctx->srs().pts ? ctx->srs().n : 0;
     if (!fk_key_ok(log_n, have)) {
         set_error(std::string(who) + ": the pass reads key points 0 .. N - 2: " + std::to_string(need) + " points needed, " + std::to_string(have) + " resident");
         return PLK_ERR_SRS;
@@ -98,7 +98,7 @@ int32_t fk_key_transform(plk_ctx *ctx, uint32_t log_n, hipStream_t st, bool *bui
     PLK_TRY(ctx->fk_key.reserve(fk_key_transform_bytes(log_n)));
     XyzzW *t = ctx->fk_key.as<XyzzW>();
     const uint32_t n2 = 2u << log_n;
-    hipLaunchKernelGGL(k_fk_arrange_t, dim3((n2 + 255) / 256), dim3(256), 0, st, t, static_cast<const G1Affine *>(ctx->srs), log_n);
+    hipLaunchKernelGGL(k_fk_arrange_t, dim3((n2 + 255) / 256), dim3(256), 0, st, t, static_cast<const G1Affine *>(ctx->srs().pts), log_n);
     PLK_HIP(hipGetLastError());
     PLK_TRY(g1_ntt_xyzzw_dev(ctx, t, log_n + 1, false, st));
     *built = true;

@@ -2,14 +2,19 @@
 #include "ctx.h"
 #include "hostmath.h"
 namespace plk {
+// Every commitment against a resident key names it: `key` is one of ctx->key (ctx.h), and all the commitment reads of a key.
 // enqueue the whole Pippenger pipeline on `stream`; results (window sums) are copied to ctx->pinned
-int32_t msm_enqueue(plk_ctx *ctx, const Fr *scalars_dev, uint64_t n, uint64_t base_offset, hipStream_t stream);
+int32_t msm_enqueue(plk_ctx *ctx, ResidentKey &key, const Fr *scalars_dev, uint64_t n, uint64_t base_offset, hipStream_t stream);
 // synchronise and fold the window sums on the host
 int32_t msm_finish(plk_ctx *ctx, hipStream_t stream, host::HJac *out);
 // up to 8 scalar vectors of the same length against the same bases: one pass of every kernel
-int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t batch, uint64_t n, uint64_t base_offset, hipStream_t stream);
+int32_t msm_enqueue_batch(plk_ctx *ctx, ResidentKey &key, const Fr *const *scalars_dev, uint32_t batch, uint64_t n, uint64_t base_offset, hipStream_t stream);
 int32_t msm_finish_batch(plk_ctx *ctx, hipStream_t stream, host::HJac *out);
 int32_t ensure_pinned(plk_ctx *ctx, size_t bytes);
+// plk_msm_g1_partial_dev, plk_msm_g1_dev and plk_msm_g1_batch_dev (include/plonkit_amd.h) against `key`, ctx and out checked by the caller
+int32_t msm_commit_partial(plk_ctx *ctx, ResidentKey &key, const void *scalars_dev, uint64_t n, uint64_t base_offset, plk_g1_jacobian *out, hipStream_t stream);
+int32_t msm_commit(plk_ctx *ctx, ResidentKey &key, const void *scalars_dev, uint64_t n, uint64_t base_offset, plk_g1_affine *out, hipStream_t stream);
+int32_t msm_commit_many(plk_ctx *ctx, ResidentKey &key, const void *const *scalars_dev, uint32_t count, uint64_t n, uint64_t base_offset, plk_g1_affine *out, hipStream_t stream);
 
 // Commitments against caller-supplied bases (device, the key's in-memory form): out[k] = sum_i scalars_dev[k][i] * bases_dev[i], k < batch.
 // Synchronous, ordered after `caller`; refuses (PLK_ERR_ARG) while a commitment is in flight.  batch == 1 takes any length (passes of 2^24

@@ -475,21 +475,21 @@ __global__ void __launch_bounds__(256) table_find_inf_kernel(const G1Affine *tab
     if (any) atomicOr(found, 1u);
 }
 
-static int32_t ensure_base_table(plk_ctx *ctx, uint32_t copies, hipStream_t stream) {
-    if (ctx->srs_w_valid && ctx->srs_w_copies >= copies) return PLK_OK;
-    ctx->srs_w_valid = false; ctx->srs_w_no_inf = false;
-    const uint64_t n = ctx->srs_n;
+static int32_t ensure_base_table(ResidentKey &key, uint32_t copies, hipStream_t stream) {
+    if (key.w_valid && key.w_copies >= copies) return PLK_OK;
+    key.w_valid = false; key.w_no_inf = false;
+    const uint64_t n = key.n;
     const uint32_t blocks = (uint32_t)((n + 255) / 256);
-    PLK_TRY(ctx->srs_w.reserve((size_t)copies * n * sizeof(G1Affine)));
-    G1Affine *table = ctx->srs_w.as<G1Affine>();
-    hipLaunchKernelGGL(srs_to_w_kernel, dim3(blocks), dim3(256), 0, stream, table, reinterpret_cast<const G1Affine *>(ctx->srs), n);
+    PLK_TRY(key.w.reserve((size_t)copies * n * sizeof(G1Affine)));
+    G1Affine *table = key.w.as<G1Affine>();
+    hipLaunchKernelGGL(srs_to_w_kernel, dim3(blocks), dim3(256), 0, stream, table, reinterpret_cast<const G1Affine *>(key.pts), n);
     if (copies > 1) {
         DevBuf xyzz, prefix, aff[2];
         PLK_TRY(xyzz.reserve(n * sizeof(G1Xyzz)));
         PLK_TRY(prefix.reserve(n * sizeof(Fq)));
         PLK_TRY(aff[0].reserve(n * sizeof(G1Affine)));
         PLK_TRY(aff[1].reserve(n * sizeof(G1Affine)));
-        const G1Affine *prev = reinterpret_cast<const G1Affine *>(ctx->srs);
+        const G1Affine *prev = reinterpret_cast<const G1Affine *>(key.pts);
         const uint32_t nblocks = (uint32_t)(((n + NORM_K - 1) / NORM_K + 255) / 256);
         for (uint32_t k = 1; k < copies; k++) {
             G1Affine *next = aff[k & 1].as<G1Affine>();
@@ -516,9 +516,9 @@ static int32_t ensure_base_table(plk_ctx *ctx, uint32_t copies, hipStream_t stre
         PLK_HIP(e);
     }
     PLK_HIP(hipGetLastError());
-    ctx->srs_w_valid = true;
-    ctx->srs_w_copies = copies;
-    ctx->srs_w_no_inf = found_host == 0;
+    key.w_valid = true;
+    key.w_copies = copies;
+    key.w_no_inf = found_host == 0;
     return PLK_OK;
 }
 
@@ -991,33 +991,33 @@ static int32_t slot_open(plk_ctx *ctx, plk_ctx::MsmSlot &S, hipStream_t caller) 
 
 // `caller` is the stream on which the scalars were produced; the commitment runs on its slot's own stream after an
 // event recorded there.  The caller must leave the scalars alone until the matching msm_finish_batch.
-int32_t msm_enqueue_batch(plk_ctx *ctx, const Fr *const *scalars_dev, uint32_t batch, uint64_t n, uint64_t base_offset, hipStream_t caller) {
+int32_t msm_enqueue_batch(plk_ctx *ctx, ResidentKey &key, const Fr *const *scalars_dev, uint32_t batch, uint64_t n, uint64_t base_offset, hipStream_t caller) {
     if (ctx->msm_enq - ctx->msm_fin >= plk_ctx::MSM_SLOTS) { set_error("msm: " + std::to_string(plk_ctx::MSM_SLOTS) + " commitments are already in flight (call the finish function first)"); return PLK_ERR_ARG; }
     uint32_t slot_index = 0;
     while (ctx->slot[slot_index].busy) slot_index++;          // lowest free slot (there is one: fewer than MSM_SLOTS are in flight)
     plk_ctx::MsmSlot &S = ctx->slot[slot_index];
     PLK_TRY(slot_open(ctx, S, caller));                       // (before the SRS, size and batch checks)
     hipStream_t stream = S.stream;
-    if (!ctx->srs) { set_error("msm: no SRS uploaded (plk_srs_upload)"); return PLK_ERR_SRS; }
-    if (base_offset + n > ctx->srs_n) { set_error("msm: SRS too small for this commitment"); return PLK_ERR_SRS; }
+    if (!key.pts) { set_error("msm: no SRS uploaded (plk_srs_upload)"); return PLK_ERR_SRS; }
+    if (base_offset + n > key.n) { set_error("msm: SRS too small for this commitment"); return PLK_ERR_SRS; }
     if (n > MSM_PASS_MAX_TERMS) { set_error("msm: more than 2^24 terms in one pass (plk_msm_g1 / plk_msm_g1_dev / plk_prove split longer commitments; the enqueue and batch entry points do not)"); return PLK_ERR_SIZE; }
     if (batch < 1 || batch > MSM_MAX_BATCH) { set_error("msm: batch must be 1..8"); return PLK_ERR_ARG; }
     // The plan is made from the table state as it is BEFORE ensure_base_table changes it (whether a commitment of fewer than 4096 terms takes the
     // short path depends on what is resident), and from what is in flight before this commitment joins the FIFO.
-    const MsmPlan plan = msm_plan_pass(n, batch, ctx->srs_n, ctx->srs_w_valid, ctx->srs_w_copies, ctx->msm_enq != ctx->msm_fin, fused_recode_allowed());
-    // resident table of the SRS in the 2^261 domain of the lazy field layer; large commitments use its shifted copies.  Ensured on EVERY enqueue,
+    const MsmPlan plan = msm_plan_pass(n, batch, key.n, key.w_valid, key.w_copies, ctx->msm_enq != ctx->msm_fin, fused_recode_allowed());
+    // resident table of the key in the 2^261 domain of the lazy field layer; large commitments use its shifted copies.  Ensured on EVERY enqueue,
     // zero terms and the naive path included (their bases are read from it too): 1 copy unless the window is 17 bits
-    PLK_TRY(ensure_base_table(ctx, plan.table_request, stream));
+    PLK_TRY(ensure_base_table(key, plan.table_request, stream));
     S.plan = plan;
-    S.bases = ctx->srs_w.as<G1Affine>() + base_offset;
+    S.bases = key.w.as<G1Affine>() + base_offset;
     for (uint32_t m = 0; m < batch; m++) S.scalars[m] = scalars_dev[m];
-    PLK_TRY(msm_launch(ctx, S, stream, ctx->srs_w_no_inf));   // (srs_w_no_inf: read after the table is ensured)
+    PLK_TRY(msm_launch(ctx, S, stream, key.w_no_inf));        // (w_no_inf: read after the table is ensured)
     ctx->fifo[ctx->msm_enq % plk_ctx::MSM_SLOTS] = (uint8_t)slot_index; S.busy = true; ctx->msm_enq++;
     return PLK_OK;
 }
 
-int32_t msm_enqueue(plk_ctx *ctx, const Fr *scalars_dev, uint64_t n, uint64_t base_offset, hipStream_t stream) {
-    return msm_enqueue_batch(ctx, &scalars_dev, 1, n, base_offset, stream);
+int32_t msm_enqueue(plk_ctx *ctx, ResidentKey &key, const Fr *scalars_dev, uint64_t n, uint64_t base_offset, hipStream_t stream) {
+    return msm_enqueue_batch(ctx, key, &scalars_dev, 1, n, base_offset, stream);
 }
 
 static host::HJac xyzz_host_to_jac(const uint64_t *v) {
@@ -1155,6 +1155,68 @@ int32_t msm_bases_commit(plk_ctx *ctx, const void *bases_dev, const Fr *const *s
     return PLK_OK;
 }
 
+// the blocking commitments against a resident key of the caller's choice (msm.h); the entry points below pass the monomial key
+int32_t msm_commit_partial(plk_ctx *ctx, ResidentKey &key, const void *scalars_dev, uint64_t n, uint64_t base_offset, plk_g1_jacobian *out, hipStream_t stream) {
+    // one pass, passes of 2^24 terms one at a time, or short pieces with several in flight — the latter only when the FIFO is empty at the
+    // call (msm_plan_call)
+    const MsmCallPlan call = msm_plan_call(n, key.n, ctx->msm_enq == ctx->msm_fin);
+    if (!stream) stream = ctx->stream;
+    if (call.pieces == 1) {
+        if (!scalars_dev && n) { set_error("plk_msm_g1: bad argument"); return PLK_ERR_ARG; }
+        PLK_HIP(hipSetDevice(ctx->device));
+        PLK_TRY(msm_enqueue(ctx, key, (const Fr *)scalars_dev, n, base_offset, stream));
+        return plk_msm_g1_finish(ctx, out);                   // (one pass: the slot's own record says so)
+    }
+    if (!scalars_dev || !out) { set_error("plk_msm_g1: bad argument"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    host::HJac acc = host::HJac::inf();
+    const uint64_t piece = call.piece_terms;
+    const uint32_t depth = call.depth;
+    uint64_t off = 0;
+    uint32_t inflight = 0;
+    int32_t rc = PLK_OK;
+    while (off < n || inflight) {                             // successive SRS ranges, summed on the host
+        while (rc == PLK_OK && off < n && inflight < depth) {
+            rc = msm_enqueue(ctx, key, (const Fr *)scalars_dev + off, n - off < piece ? n - off : piece, base_offset + off, stream);
+            if (rc == PLK_OK) { off += piece; inflight++; }
+        }
+        if (rc != PLK_OK) off = n;                            // stop enqueuing, drain what is in flight
+        if (!inflight) break;
+        host::HJac j;
+        const int32_t rf = msm_finish(ctx, nullptr, &j);
+        inflight--;
+        if (rf != PLK_OK && rc == PLK_OK) rc = rf;
+        if (rc == PLK_OK) acc = host::jac_add(acc, j);
+    }
+    if (rc != PLK_OK) return rc;
+    ctx->call_pieces = (uint32_t)call.pieces; ctx->call_piece_terms = piece; ctx->call_fin = ctx->msm_fin;   // (recorded on this multi-piece path only)
+    memcpy(out->x, acc.x.l, 32); memcpy(out->y, acc.y.l, 32); memcpy(out->z, acc.z.l, 32);
+    return PLK_OK;
+}
+
+int32_t msm_commit(plk_ctx *ctx, ResidentKey &key, const void *scalars_dev, uint64_t n, uint64_t base_offset, plk_g1_affine *out, hipStream_t stream) {
+    plk_g1_jacobian j;
+    PLK_TRY(msm_commit_partial(ctx, key, scalars_dev, n, base_offset, &j, stream));
+    return plk_g1_sum_jacobian(&j, 1, out);
+}
+
+int32_t msm_commit_many(plk_ctx *ctx, ResidentKey &key, const void *const *scalars_dev, uint32_t count, uint64_t n, uint64_t base_offset, plk_g1_affine *out, hipStream_t stream) {
+    PLK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = stream ? stream : ctx->stream;
+    for (uint32_t done = 0; done < count;) {
+        uint32_t b = count - done > MSM_MAX_BATCH ? MSM_MAX_BATCH : count - done;
+        PLK_TRY(msm_enqueue_batch(ctx, key, reinterpret_cast<const Fr *const *>(scalars_dev + done), b, n, base_offset, st));
+        host::HJac j[MSM_MAX_BATCH];
+        PLK_TRY(msm_finish_batch(ctx, st, j));
+        for (uint32_t k = 0; k < b; k++) {
+            host::HAffine a = host::jac_to_affine(j[k]);
+            memcpy(out[done + k].x, a.x.l, 32); memcpy(out[done + k].y, a.y.l, 32);
+        }
+        done += b;
+    }
+    return PLK_OK;
+}
+
 }  // namespace plk
 
 using namespace plk;
@@ -1164,7 +1226,7 @@ extern "C" {
 int32_t plk_msm_g1_enqueue_dev(plk_ctx *ctx, const void *scalars_dev, uint64_t n, uint64_t base_offset, void *stream) {
     if (!ctx || (!scalars_dev && n)) { set_error("plk_msm_g1: bad argument"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
-    return msm_enqueue(ctx, (const Fr *)scalars_dev, n, base_offset, stream ? (hipStream_t)stream : ctx->stream);
+    return msm_enqueue(ctx, ctx->srs(), (const Fr *)scalars_dev, n, base_offset, stream ? (hipStream_t)stream : ctx->stream);
 }
 
 // the same FIFO for a batch of `count` (<= 8) commitments of equal length against the same bases: one pass of the kernels
@@ -1172,7 +1234,7 @@ int32_t plk_msm_g1_enqueue_batch_dev(plk_ctx *ctx, const void *const *scalars_de
     if (!ctx || !scalars_dev || count == 0 || count > MSM_MAX_BATCH) { set_error("plk_msm_g1_enqueue_batch_dev: bad argument"); return PLK_ERR_ARG; }
     for (uint32_t k = 0; k < count; k++) if (!scalars_dev[k] && n) { set_error("plk_msm_g1_enqueue_batch_dev: null vector"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
-    return msm_enqueue_batch(ctx, reinterpret_cast<const Fr *const *>(scalars_dev), count, n, base_offset, stream ? (hipStream_t)stream : ctx->stream);
+    return msm_enqueue_batch(ctx, ctx->srs(), reinterpret_cast<const Fr *const *>(scalars_dev), count, n, base_offset, stream ? (hipStream_t)stream : ctx->stream);
 }
 static int32_t finish_batch_checked(plk_ctx *ctx, uint32_t count, host::HJac *j) {
     if (ctx->msm_fin == ctx->msm_enq) { set_error("msm: nothing in flight"); return PLK_ERR_ARG; }
@@ -1230,63 +1292,19 @@ int32_t plk_msm_g1_finish_sharded(plk_ctx *ctx, plk_g1_affine *out) {
 }
 
 int32_t plk_msm_g1_partial_dev(plk_ctx *ctx, const void *scalars_dev, uint64_t n, uint64_t base_offset, plk_g1_jacobian *out, void *stream) {
-    // one pass, passes of 2^24 terms one at a time, or short pieces with several in flight — the latter only when the FIFO is empty at the
-    // call (msm_plan_call)
-    const MsmCallPlan call = msm_plan_call(n, ctx ? ctx->srs_n : 0, ctx && ctx->msm_enq == ctx->msm_fin);
-    if (call.pieces == 1) {
-        PLK_TRY(plk_msm_g1_enqueue_dev(ctx, scalars_dev, n, base_offset, stream));
-        return plk_msm_g1_finish(ctx, out);                   // (one pass: the slot's own record says so)
-    }
-    if (!ctx || !scalars_dev || !out) { set_error("plk_msm_g1: bad argument"); return PLK_ERR_ARG; }
-    PLK_HIP(hipSetDevice(ctx->device));
-    host::HJac acc = host::HJac::inf();
-    const uint64_t piece = call.piece_terms;
-    const uint32_t depth = call.depth;
-    uint64_t off = 0;
-    uint32_t inflight = 0;
-    int32_t rc = PLK_OK;
-    while (off < n || inflight) {                             // successive SRS ranges, summed on the host
-        while (rc == PLK_OK && off < n && inflight < depth) {
-            rc = msm_enqueue(ctx, (const Fr *)scalars_dev + off, n - off < piece ? n - off : piece, base_offset + off, stream ? (hipStream_t)stream : ctx->stream);
-            if (rc == PLK_OK) { off += piece; inflight++; }
-        }
-        if (rc != PLK_OK) off = n;                            // stop enqueuing, drain what is in flight
-        if (!inflight) break;
-        host::HJac j;
-        const int32_t rf = msm_finish(ctx, nullptr, &j);
-        inflight--;
-        if (rf != PLK_OK && rc == PLK_OK) rc = rf;
-        if (rc == PLK_OK) acc = host::jac_add(acc, j);
-    }
-    if (rc != PLK_OK) return rc;
-    ctx->call_pieces = (uint32_t)call.pieces; ctx->call_piece_terms = piece; ctx->call_fin = ctx->msm_fin;   // (recorded on this multi-piece path only)
-    memcpy(out->x, acc.x.l, 32); memcpy(out->y, acc.y.l, 32); memcpy(out->z, acc.z.l, 32);
-    return PLK_OK;
+    if (!ctx) { set_error("plk_msm_g1: bad argument"); return PLK_ERR_ARG; }
+    return msm_commit_partial(ctx, ctx->srs(), scalars_dev, n, base_offset, out, (hipStream_t)stream);
 }
 
 int32_t plk_msm_g1_dev(plk_ctx *ctx, const void *scalars_dev, uint64_t n, uint64_t base_offset, plk_g1_affine *out, void *stream) {
     if (!out) { set_error("plk_msm_g1: null out"); return PLK_ERR_ARG; }
-    plk_g1_jacobian j;
-    PLK_TRY(plk_msm_g1_partial_dev(ctx, scalars_dev, n, base_offset, &j, stream));
-    return plk_g1_sum_jacobian(&j, 1, out);
+    if (!ctx) { set_error("plk_msm_g1: bad argument"); return PLK_ERR_ARG; }
+    return msm_commit(ctx, ctx->srs(), scalars_dev, n, base_offset, out, (hipStream_t)stream);
 }
 
 int32_t plk_msm_g1_batch_dev(plk_ctx *ctx, const void *const *scalars_dev, uint32_t count, uint64_t n, uint64_t base_offset, plk_g1_affine *out, void *stream) {
     if (!ctx || !scalars_dev || !out || count == 0) { set_error("plk_msm_g1_batch_dev: bad argument"); return PLK_ERR_ARG; }
-    PLK_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    for (uint32_t done = 0; done < count;) {
-        uint32_t b = count - done > MSM_MAX_BATCH ? MSM_MAX_BATCH : count - done;
-        PLK_TRY(msm_enqueue_batch(ctx, reinterpret_cast<const Fr *const *>(scalars_dev + done), b, n, base_offset, st));
-        host::HJac j[MSM_MAX_BATCH];
-        PLK_TRY(msm_finish_batch(ctx, st, j));
-        for (uint32_t k = 0; k < b; k++) {
-            host::HAffine a = host::jac_to_affine(j[k]);
-            memcpy(out[done + k].x, a.x.l, 32); memcpy(out[done + k].y, a.y.l, 32);
-        }
-        done += b;
-    }
-    return PLK_OK;
+    return msm_commit_many(ctx, ctx->srs(), scalars_dev, count, n, base_offset, out, (hipStream_t)stream);
 }
 
 int32_t plk_msm_g1(plk_ctx *ctx, const plk_fr *scalars, uint64_t n, uint64_t base_offset, plk_g1_affine *out) {
@@ -1349,13 +1367,10 @@ int32_t plk_msm_g1_bases(plk_ctx *ctx, const plk_g1_affine *bases, const plk_fr 
 
 int32_t plk_srs_precompute(plk_ctx *ctx) {
     if (!ctx) { set_error("plk_srs_precompute: null ctx"); return PLK_ERR_ARG; }
-    if (!ctx->srs) { set_error("plk_srs_precompute: no SRS resident"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts) { set_error("plk_srs_precompute: no SRS resident"); return PLK_ERR_SRS; }
     PLK_HIP(hipSetDevice(ctx->device));
-    PLK_TRY(ensure_base_table(ctx, table_copies_for(ctx->srs_n), ctx->stream));
-    if (ctx->lag.pts) {
-        SrsSlotSwap active(ctx, true);
-        PLK_TRY(ensure_base_table(ctx, table_copies_for(ctx->srs_n), ctx->stream));
-    }
+    for (ResidentKey &key : ctx->key)
+        if (key.pts) PLK_TRY(ensure_base_table(key, table_copies_for(key.n), ctx->stream));
     return PLK_OK;
 }
 
@@ -1368,15 +1383,13 @@ int32_t plk_ctx_share_srs(plk_ctx *dst, plk_ctx *src) {
     if (!dst || !src || dst == src) { set_error("plk_ctx_share_srs: bad argument"); return PLK_ERR_ARG; }
     if (dst->device != src->device) { set_error("plk_ctx_share_srs: the two contexts are on different devices"); return PLK_ERR_ARG; }
     if (src->srs_lender) { set_error("plk_ctx_share_srs: the source context itself borrows its key (share from the owner)"); return PLK_ERR_ARG; }
-    if (!src->srs) { set_error("plk_ctx_share_srs: the source context has no key resident"); return PLK_ERR_SRS; }
+    if (!src->srs().pts) { set_error("plk_ctx_share_srs: the source context has no key resident"); return PLK_ERR_SRS; }
     if (dst->msm_enq != dst->msm_fin) { set_error("plk_ctx_share_srs: a commitment is still in flight on the destination context"); return PLK_ERR_ARG; }
-    if (dst->srs_borrowers.load() > 0) { set_error("plk_ctx_share_srs: the destination context lends its own key to other contexts"); return PLK_ERR_ARG; }
+    if (dst->srs().borrowers.load() > 0) { set_error("plk_ctx_share_srs: the destination context lends its own key to other contexts"); return PLK_ERR_ARG; }
     PLK_TRY(plk_srs_precompute(src));                        // the fallible step first (synchronises src->stream: the tables are complete before anyone
                                                              // reads them) — dst keeps what it has if this fails
     PLK_TRY(srs_replace_guard(dst, "plk_ctx_share_srs"));    // drops a loan dst may hold
-    dst->srs_own.release(); dst->lag.own.release();
-    dst->lag.w.release();
-    srs_make_loan(dst, src);
+    srs_make_loan(dst, src);                                 // (and with it what dst held of its own)
     return PLK_OK;
 }
 

@@ -68,14 +68,14 @@ static uint64_t msm_piece_terms() {
 }
 // enqueues the pieces of `cnt` commitments over scalars[lo + ...]; every piece but the last is finished here and summed
 // into ctx->commit_pieces, the last one stays in flight (the caller overlaps it and calls commit_end)
-static int32_t enqueue_pieces(plk_ctx *ctx, const Fr *const *vecs, uint32_t cnt, uint64_t lo, uint64_t hi, uint64_t first_base) {
+static int32_t enqueue_pieces(plk_ctx *ctx, ResidentKey &key, const Fr *const *vecs, uint32_t cnt, uint64_t lo, uint64_t hi, uint64_t first_base) {
     const uint64_t piece = msm_piece_terms();
     ctx->commit_pieces.clear();
     const Fr *shifted[8];
     for (uint64_t off = 0;; off += piece) {
         const uint64_t len = hi - lo - off < piece ? hi - lo - off : piece;
         for (uint32_t k = 0; k < cnt; k++) shifted[k] = vecs[k] + lo + off;
-        PLK_TRY(msm_enqueue_batch(ctx, shifted, cnt, len, first_base + off, ctx->stream));
+        PLK_TRY(msm_enqueue_batch(ctx, key, shifted, cnt, len, first_base + off, ctx->stream));
         if (off + len >= hi - lo) break;
         HJac j[8];
         PLK_TRY(msm_finish_batch(ctx, nullptr, j));
@@ -95,11 +95,11 @@ static int32_t finish_pieces(plk_ctx *ctx, uint32_t cnt, HJac *j) {
     return PLK_OK;
 }
 static int32_t commit_begin(plk_ctx *ctx, const Fr *const *vecs, uint32_t count, uint64_t n, bool lagrange = false) {
-    SrsSlotSwap active(ctx, lagrange);
+    ResidentKey &key = ctx->key[lagrange ? KEY_LAGRANGE : KEY_MONOMIAL];
     uint64_t lo = 0, hi = n;
     if (ctx->combine) {
         lo = ctx->shard_first < n ? ctx->shard_first : n;
-        hi = ctx->shard_first + ctx->srs_n < n ? ctx->shard_first + ctx->srs_n : n;
+        hi = ctx->shard_first + key.n < n ? ctx->shard_first + key.n : n;
         if (hi < lo) hi = lo;
     }
     const uint64_t first_base = ctx->combine ? 0 : lo;
@@ -108,7 +108,7 @@ static int32_t commit_begin(plk_ctx *ctx, const Fr *const *vecs, uint32_t count,
     // while this rank commits its own, and meet it in commit_end's exchange
     if (comm_scatter_owner(ctx)) {
         if (ctx->shard_first != 0) { set_error("scatter mode: the owner (rank 0) must hold the first slice of the key"); return PLK_ERR_ARG; }
-        PLK_TRY(comm_send_work(ctx, reinterpret_cast<const void *const *>(vecs), count, n, ctx->srs_n, lagrange, ctx->stream));
+        PLK_TRY(comm_send_work(ctx, reinterpret_cast<const void *const *>(vecs), count, n, key.n, lagrange, ctx->stream));
         ctx->scatter_open = count;                                // the workers now sit in this batch's all-gather: it MUST be run (commit_end, or the FIFO guard)
     }
     // at the largest sizes a batch of commitments would need gigabytes of per-task partial-sum slots (2^26 gates: 16 GiB for
@@ -116,13 +116,13 @@ static int32_t commit_begin(plk_ctx *ctx, const Fr *const *vecs, uint32_t count,
     if (count > 1 && hi - lo > msm_piece_terms()) {
         for (uint32_t k = 0; k + 1 < count; k++) {
             HJac j;
-            PLK_TRY(enqueue_pieces(ctx, vecs + k, 1, lo, hi, first_base));
+            PLK_TRY(enqueue_pieces(ctx, key, vecs + k, 1, lo, hi, first_base));
             PLK_TRY(finish_pieces(ctx, 1, &j));
             ctx->commit_done.push_back(j);
         }
-        return enqueue_pieces(ctx, vecs + count - 1, 1, lo, hi, first_base);
+        return enqueue_pieces(ctx, key, vecs + count - 1, 1, lo, hi, first_base);
     }
-    return enqueue_pieces(ctx, vecs, count, lo, hi, first_base);
+    return enqueue_pieces(ctx, key, vecs, count, lo, hi, first_base);
 }
 static int32_t commit_end(plk_ctx *ctx, uint32_t count, HAffine *out) {
     HJac j[8];
@@ -166,11 +166,8 @@ static int32_t serve_impl(plk_ctx *ctx, uint64_t *batches) {
         PLK_TRY(comm_recv_work(ctx, &w, ctx->stream));
         if (w.op == SHARD_STOP) return PLK_OK;
         const bool lagrange = w.lagrange != 0;
-        if (lagrange && !ctx->lag.pts) { set_error("plk_comm_serve: the owner commits against a Lagrange-form key this rank does not hold"); return PLK_ERR_SRS; }
-        {
-            SrsSlotSwap active(ctx, lagrange);
-            if (ctx->srs_n != w.slice) { set_error("plk_comm_serve: this rank's key slice has a different size than the owner's (every rank holds points [r L, (r+1) L))"); return PLK_ERR_SRS; }
-        }
+        if (lagrange && !ctx->lagrange().pts) { set_error("plk_comm_serve: the owner commits against a Lagrange-form key this rank does not hold"); return PLK_ERR_SRS; }
+        if (ctx->key[lagrange ? KEY_LAGRANGE : KEY_MONOMIAL].n != w.slice) { set_error("plk_comm_serve: this rank's key slice has a different size than the owner's (every rank holds points [r L, (r+1) L))"); return PLK_ERR_SRS; }
         const Fr *vecs[8];
         static const Fr none{};
         for (uint32_t k = 0; k < w.count; k++) vecs[k] = w.len ? static_cast<const Fr *>(w.vec[k]) : &none;
@@ -653,8 +650,8 @@ static int32_t round1_wires(ProveState &P) {
     PLK_TRY(ntt_columns_dev(ctx, P.W.w_coef, 4, P.S->log_n, true, P.st));
     // with a Lagrange-form key of the domain's size resident (`prove -l`, src/plonk.rs:138-146) the witness and
     // grand-product polynomials are committed from their evaluations, as bellman's prove() does; same proof bytes
-    P.use_lagrange = ctx->lag.pts != nullptr;
-    if (P.use_lagrange && (ctx->combine ? ctx->lag.n != ctx->srs_n : ctx->lag.n != N)) { set_error("Lagrange-form key has a different size than the circuit's domain"); return PLK_ERR_SRS; }
+    P.use_lagrange = ctx->lagrange().pts != nullptr;
+    if (P.use_lagrange && (ctx->combine ? ctx->lagrange().n != ctx->srs().n : ctx->lagrange().n != N)) { set_error("Lagrange-form key has a different size than the circuit's domain"); return PLK_ERR_SRS; }
     PLK_TRY(commit_begin(ctx, P.use_lagrange ? P.W.w_vals : P.W.w_coef, 4, N, P.use_lagrange));
     // round-3 work that needs no challenge: the wire extensions start behind the wires' accumulation
     PLK_TRY(P.lane.start_behind_main(true));
@@ -1104,7 +1101,7 @@ static int32_t prove_impl(plk_ctx *ctx, const plk_setup *S, const WitnessSrc &sr
     }
     if (c && !c->has_witness) { set_error("plk_prove: circuit has no witness"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
-    if (!ctx->srs || (!ctx->combine && ctx->srs_n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts || (!ctx->combine && ctx->srs().n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
     if (!S->store.p) { set_error(std::string(who) + ": the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
     PLK_TRY(fifo_must_be_empty(ctx, who));
     FifoGuard fifo_guard(ctx);
@@ -1262,7 +1259,7 @@ static int32_t prove_assembled_impl(plk_ctx *ctx, const plk_setup *S, const void
     for (int j = 0; j < 4; j++) if (!cols[j]) { set_error(who + ": a column pointer is NULL"); return PLK_ERR_ARG; }
     if (rows < S->num_inputs || rows > S->N) { set_error(who + ": rows must satisfy num_inputs <= rows <= N"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
-    if (!ctx->srs || (!ctx->combine && ctx->srs_n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts || (!ctx->combine && ctx->srs().n < S->N)) { set_error("SRS too small for this circuit"); return PLK_ERR_SRS; }
     if (!S->store.p) { set_error(who + ": the setup is not on the device yet (plk_setup_upload)"); return PLK_ERR_ARG; }
     PLK_TRY(fifo_must_be_empty(ctx, who.c_str()));
     FifoGuard fifo_guard(ctx);
@@ -1553,7 +1550,7 @@ int32_t plk_check_copies_dev(plk_ctx *ctx, const plk_setup *s, const void *const
 int32_t plk_comm_serve(plk_ctx *ctx, uint64_t *batches) {
     if (batches) *batches = 0;
     if (!ctx || !comm_scatter_worker(ctx)) { set_error("plk_comm_serve: not a worker rank (rank > 0) of a communicator in scatter mode"); return PLK_ERR_ARG; }
-    if (!ctx->srs) { set_error("plk_comm_serve: no key slice resident"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts) { set_error("plk_comm_serve: no key slice resident"); return PLK_ERR_SRS; }
     PLK_TRY(fifo_must_be_empty(ctx, "plk_comm_serve"));
     return guarded("plk_comm_serve", PLK_ERR_HIP, [&] { PLK_HIP(hipSetDevice(ctx->device)); FifoGuard drain(ctx); return serve_impl(ctx, batches); });
 }

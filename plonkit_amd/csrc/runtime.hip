@@ -68,23 +68,37 @@ int32_t ensure_pinned2(plk_ctx *ctx, size_t bytes) {
 // key of a lender is only frozen while a borrower actually holds it (a lender that had none when the loans were made may install one;
 // its borrowers do not see it — share again for that).
 static std::mutex g_share_mu;                          // loans are made, returned and orphaned under one lock (rare operations)
-int32_t srs_replace_guard(plk_ctx *c, const char *who, bool lagrange_only) {
-    if (lagrange_only ? c->lag_borrowers.load() > 0 : c->srs_borrowers.load() > 0) {
+// the two halves of a loan, one key at a time and under the lock: what dst held of that form is let go either way
+static void key_lend(plk_ctx *dst, plk_ctx *src, KeyForm which) {
+    ResidentKey &d = dst->key[which], &s = src->key[which];
+    d.release();
+    key_install(dst, which, s.pts, s.n);
+    if (!s.pts) return;
+    d.w.borrow(s.w); d.w_valid = s.w_valid; d.w_copies = s.w_copies; d.w_no_inf = s.w_valid && s.w_no_inf;
+    d.borrowed = true; s.borrowers.fetch_add(1);
+}
+static void key_return(plk_ctx *c, KeyForm which) {
+    ResidentKey &k = c->key[which];
+    if (!k.borrowed) return;
+    c->srs_lender->key[which].borrowers.fetch_sub(1);
+    k.borrowed = false; k.w.release(); k.w_copies = 0;
+    key_clear(c, which);
+}
+int32_t srs_replace_guard(plk_ctx *c, const char *who, KeyForm which) {
+    if (c->key[which].borrowers.load() > 0) {
         set_error(std::string(who) + ": this context's key is shared with another context (plk_ctx_share_srs) — destroy the borrowers first");
         return PLK_ERR_ARG;
     }
-    if (!lagrange_only) srs_return_loan(c);              // a borrower that gets a monomial key of its own stops borrowing altogether;
-    else if (c->lag_borrowed) {                          // one that replaces its Lagrange-form key keeps the borrowed monomial key
+    if (which == KEY_MONOMIAL) srs_return_loan(c);       // a borrower that gets a monomial key of its own stops borrowing altogether;
+    else {                                               // one that replaces its Lagrange-form key keeps the borrowed monomial key
         std::lock_guard<std::mutex> g(g_share_mu);
-        c->srs_lender->lag_borrowers.fetch_sub(1);
-        c->lag_borrowed = false;
-        c->lag.pts = nullptr; c->lag.n = 0; c->lag.w.release(); c->lag.w_valid = false; c->lag.w_copies = 0; c->lag.w_no_inf = false;
+        key_return(c, which);
     }
     return PLK_OK;
 }
 static void free_lent(plk_ctx *c) {                      // what a destroyed lender had to keep for its borrowers
     (void)hipSetDevice(c->device);
-    c->srs_own.release(); c->srs_w.release(); c->lag.own.release(); c->lag.w.release();
+    for (ResidentKey &k : c->key) k.release();
     delete c;
 }
 void srs_return_loan(plk_ctx *c) {
@@ -93,32 +107,22 @@ void srs_return_loan(plk_ctx *c) {
     {
         std::lock_guard<std::mutex> g(g_share_mu);
         plk_ctx *const lender = c->srs_lender;
-        if (c->lag_borrowed) lender->lag_borrowers.fetch_sub(1);
-        if (lender->srs_borrowers.fetch_sub(1) == 1 && lender->zombie) orphan = lender;
+        key_return(c, KEY_LAGRANGE); key_return(c, KEY_MONOMIAL);
         c->srs_lender = nullptr;
-        c->srs = nullptr; c->srs_n = 0; c->srs_w.release(); c->srs_w_valid = false; c->srs_w_copies = 0; c->srs_w_no_inf = false; c->fk_key_valid = false;
-        if (c->lag_borrowed) { c->lag.pts = nullptr; c->lag.n = 0; c->lag.w.release(); c->lag.w_valid = false; c->lag.w_copies = 0; c->lag.w_no_inf = false; }
-        c->lag_borrowed = false;
+        if (lender->zombie && lender->srs().borrowers.load() == 0) orphan = lender;
     }
     if (orphan) free_lent(orphan);                       // the lender was destroyed before this, its last, borrower
 }
 void srs_make_loan(plk_ctx *dst, plk_ctx *src) {         // (msm.hip plk_ctx_share_srs: the checks and the fallible steps come first)
     std::lock_guard<std::mutex> g(g_share_mu);
-    dst->srs = src->srs; dst->srs_n = src->srs_n;
-    dst->fk_key_valid = false;                          // (kzg_all.hip: the transform of the key dst had)
-    dst->srs_w.borrow(src->srs_w); dst->srs_w_valid = src->srs_w_valid; dst->srs_w_copies = src->srs_w_copies; dst->srs_w_no_inf = src->srs_w_valid && src->srs_w_no_inf;
-    dst->lag.pts = src->lag.pts; dst->lag.n = src->lag.n;
-    dst->lag.w.borrow(src->lag.w); dst->lag.w_valid = src->lag.pts ? src->lag.w_valid : false; dst->lag.w_copies = src->lag.w_copies; dst->lag.w_no_inf = dst->lag.w_valid && src->lag.w_no_inf;
-    dst->lag_borrowed = src->lag.pts != nullptr;
+    key_lend(dst, src, KEY_MONOMIAL); key_lend(dst, src, KEY_LAGRANGE);
     dst->srs_lender = src;
-    src->srs_borrowers.fetch_add(1);
-    if (dst->lag_borrowed) src->lag_borrowers.fetch_add(1);
 }
 // true: the context lends its key to contexts that are still alive — plk_destroy keeps the key and the tables (and the shell of the
 // context) until the last of them returns its loan
 bool srs_orphan_lender(plk_ctx *c) {
     std::lock_guard<std::mutex> g(g_share_mu);
-    if (c->srs_borrowers.load() == 0) return false;
+    if (c->srs().borrowers.load() == 0) return false;             // (every borrower holds the monomial key)
     c->zombie = true;
     return true;
 }
@@ -194,7 +198,7 @@ void plk_destroy(plk_ctx *ctx) {
     for (auto &kv : ctx->ntt_direct) (void)hipFree(kv.second.buf);
     ctx->coset_direct[0].buf.release(); ctx->coset_direct[1].buf.release();
     ctx->tables.release(); ctx->ntt_scratch[0].release(); ctx->ntt_scratch[1].release();
-    if (!lent) { ctx->srs_own.release(); ctx->srs_w.release(); ctx->lag.own.release(); ctx->lag.w.release(); }
+    if (!lent) for (ResidentKey &k : ctx->key) k.release();
     for (auto &S : ctx->slot) {
         S.a.release(); S.b.release(); S.c.release(); S.d.release(); S.e.release(); S.f.release();
         if (S.pinned) (void)hipHostFree(S.pinned);
@@ -227,29 +231,29 @@ int32_t plk_synchronize(plk_ctx *ctx) {
 }
 
 // ------------------------------------------------------------------------------------ SRS
+static int32_t key_upload(plk_ctx *ctx, KeyForm which, const plk_g1_affine *bases, uint64_t n) {
+    DevBuf &own = ctx->key[which].own;
+    PLK_TRY(own.reserve(n * sizeof(plk_g1_affine)));
+    PLK_HIP(hipMemcpyAsync(own.p, bases, n * sizeof(plk_g1_affine), hipMemcpyHostToDevice, ctx->stream));
+    PLK_HIP(hipStreamSynchronize(ctx->stream));
+    key_install(ctx, which, own.p, n);
+    return PLK_OK;
+}
 int32_t plk_srs_upload(plk_ctx *ctx, const plk_g1_affine *bases, uint64_t n) {
     if (!ctx || !bases || n == 0) { set_error("plk_srs_upload: bad argument"); return PLK_ERR_ARG; }
     PLK_TRY(srs_replace_guard(ctx, "plk_srs_upload"));
     PLK_HIP(hipSetDevice(ctx->device));
-    PLK_TRY(ctx->srs_own.reserve(n * sizeof(plk_g1_affine)));
-    PLK_HIP(hipMemcpyAsync(ctx->srs_own.p, bases, n * sizeof(plk_g1_affine), hipMemcpyHostToDevice, ctx->stream));
-    PLK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->srs = ctx->srs_own.p;
-    ctx->srs_n = n;
-    srs_table_invalidate(ctx);
-    return PLK_OK;
+    return key_upload(ctx, KEY_MONOMIAL, bases, n);
 }
 
 int32_t plk_srs_set_dev(plk_ctx *ctx, const void *bases_dev, uint64_t n) {
     if (!ctx || !bases_dev || n == 0) { set_error("plk_srs_set_dev: bad argument"); return PLK_ERR_ARG; }
     PLK_TRY(srs_replace_guard(ctx, "plk_srs_set_dev"));
-    ctx->srs = bases_dev;
-    ctx->srs_n = n;
-    srs_table_invalidate(ctx);
+    key_install(ctx, KEY_MONOMIAL, bases_dev, n);
     return PLK_OK;
 }
 
-uint64_t plk_srs_size(const plk_ctx *ctx) { return ctx ? ctx->srs_n : 0; }
+uint64_t plk_srs_size(const plk_ctx *ctx) { return ctx ? ctx->key[KEY_MONOMIAL].n : 0; }
 
 int32_t plk_set_commit_shard(plk_ctx *ctx, uint64_t first_index, plk_combine_fn combine, void *user) {
     if (!ctx) { set_error("plk_set_commit_shard: bad argument"); return PLK_ERR_ARG; }
@@ -262,28 +266,24 @@ int32_t plk_set_commit_shard(plk_ctx *ctx, uint64_t first_index, plk_combine_fn 
 // Lagrange-form key (Crs<E, CrsForLagrangeForm>): second resident SRS, see include/plonkit_amd.h
 int32_t plk_srs_lagrange_upload(plk_ctx *ctx, const plk_g1_affine *bases, uint64_t n) {
     if (!ctx || !bases || n == 0) { set_error("plk_srs_lagrange_upload: bad argument"); return PLK_ERR_ARG; }
-    PLK_TRY(srs_replace_guard(ctx, "plk_srs_lagrange_upload", true));
+    PLK_TRY(srs_replace_guard(ctx, "plk_srs_lagrange_upload", KEY_LAGRANGE));
     PLK_HIP(hipSetDevice(ctx->device));
-    PLK_TRY(ctx->lag.own.reserve(n * sizeof(plk_g1_affine)));
-    PLK_HIP(hipMemcpyAsync(ctx->lag.own.p, bases, n * sizeof(plk_g1_affine), hipMemcpyHostToDevice, ctx->stream));
-    PLK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->lag.pts = ctx->lag.own.p; ctx->lag.n = n; lag_table_invalidate(ctx);
-    return PLK_OK;
+    return key_upload(ctx, KEY_LAGRANGE, bases, n);
 }
 int32_t plk_srs_lagrange_set_dev(plk_ctx *ctx, const void *bases_dev, uint64_t n) {
     if (!ctx || !bases_dev || n == 0) { set_error("plk_srs_lagrange_set_dev: bad argument"); return PLK_ERR_ARG; }
-    PLK_TRY(srs_replace_guard(ctx, "plk_srs_lagrange_set_dev", true));
-    ctx->lag.pts = bases_dev; ctx->lag.n = n; lag_table_invalidate(ctx);
+    PLK_TRY(srs_replace_guard(ctx, "plk_srs_lagrange_set_dev", KEY_LAGRANGE));
+    key_install(ctx, KEY_LAGRANGE, bases_dev, n);
     return PLK_OK;
 }
 int32_t plk_srs_lagrange_clear(plk_ctx *ctx) {
     if (!ctx) { set_error("plk_srs_lagrange_clear: bad argument"); return PLK_ERR_ARG; }
-    if (!ctx->lag.pts) return PLK_OK;                                    // nothing resident: nothing to replace (also on a lender)
-    PLK_TRY(srs_replace_guard(ctx, "plk_srs_lagrange_clear", true));
-    ctx->lag.pts = nullptr; ctx->lag.n = 0; lag_table_invalidate(ctx);
+    if (!ctx->lagrange().pts) return PLK_OK;                                    // nothing resident: nothing to replace (also on a lender)
+    PLK_TRY(srs_replace_guard(ctx, "plk_srs_lagrange_clear", KEY_LAGRANGE));
+    key_clear(ctx, KEY_LAGRANGE);
     return PLK_OK;
 }
-uint64_t plk_srs_lagrange_size(const plk_ctx *ctx) { return ctx ? ctx->lag.n : 0; }
+uint64_t plk_srs_lagrange_size(const plk_ctx *ctx) { return ctx ? ctx->key[KEY_LAGRANGE].n : 0; }
 
 // ------------------------------------------------------------------------------------ NTT
 int32_t plk_ntt_dev(plk_ctx *ctx, void *data_dev, uint32_t log_n, int32_t inverse, const plk_fr *coset, void *stream) {

@@ -131,14 +131,13 @@ extern "C" int32_t plk_srs_generate_fr(plk_ctx *ctx, uint64_t n, uint64_t start,
     if (!ctx || n == 0 || !tau) { set_error("plk_srs_generate_fr: bad argument"); return PLK_ERR_ARG; }
     PLK_TRY(srs_replace_guard(ctx, "plk_srs_generate_fr"));
     PLK_HIP(hipSetDevice(ctx->device));
-    PLK_TRY(ctx->srs_own.reserve(n * sizeof(G1Affine)));
+    DevBuf &own = ctx->srs().own;
+    PLK_TRY(own.reserve(n * sizeof(G1Affine)));
     Fr t; memcpy(t.l, tau->l, 32);
-    hipLaunchKernelGGL(srs_powers_general_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->srs_own.as<G1Affine>(), start, n, t);
+    hipLaunchKernelGGL(srs_powers_general_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, own.as<G1Affine>(), start, n, t);
     PLK_HIP(hipGetLastError());
     PLK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->srs = ctx->srs_own.p;
-    ctx->srs_n = n;
-    srs_table_invalidate(ctx);
+    key_install(ctx, KEY_MONOMIAL, own.p, n);
     return PLK_OK;
 }
 
@@ -147,7 +146,8 @@ extern "C" int32_t plk_srs_generate(plk_ctx *ctx, uint64_t n, uint64_t start, ui
     if (!ctx || n == 0 || tau < 2) { set_error("plk_srs_generate: bad argument"); return PLK_ERR_ARG; }
     PLK_TRY(srs_replace_guard(ctx, "plk_srs_generate"));
     PLK_HIP(hipSetDevice(ctx->device));
-    PLK_TRY(ctx->srs_own.reserve(n * sizeof(G1Affine)));
+    DevBuf &own = ctx->srs().own;
+    PLK_TRY(own.reserve(n * sizeof(G1Affine)));
     // the XYZZ scratch is the first commitment slot's: not while a commitment is in flight (then the one-kernel path)
     if (ctx->msm_enq == ctx->msm_fin) {
         const uint64_t chunk = n < SRS_CHUNK ? n : SRS_CHUNK;
@@ -157,27 +157,25 @@ extern "C" int32_t plk_srs_generate(plk_ctx *ctx, uint64_t n, uint64_t start, ui
             const uint64_t len = n - off < chunk ? n - off : chunk;
             const uint64_t threads = (len + SRS_RUN_XYZZ - 1) / SRS_RUN_XYZZ;
             hipLaunchKernelGGL(srs_powers_xyzz_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, ctx->stream, tmp, start + off, len, from_u64<FrParams>(tau), tau);
-            PLK_TRY(srs_to_affine(ctx->srs_own.as<G1Affine>() + off, tmp, len, ctx->stream));
+            PLK_TRY(srs_to_affine(own.as<G1Affine>() + off, tmp, len, ctx->stream));
         }
     } else {
         uint64_t threads = (n + SRS_RUN - 1) / SRS_RUN;
         hipLaunchKernelGGL(srs_powers_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ctx->srs_own.as<G1Affine>(), start, n, from_u64<FrParams>(tau), tau);
+                           own.as<G1Affine>(), start, n, from_u64<FrParams>(tau), tau);
     }
     PLK_HIP(hipGetLastError());
     PLK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->srs = ctx->srs_own.p;
-    ctx->srs_n = n;
-    srs_table_invalidate(ctx);
+    key_install(ctx, KEY_MONOMIAL, own.p, n);
     return PLK_OK;
 }
 
 // copies n resident SRS points (from index `offset`) back to the host
 extern "C" int32_t plk_srs_download(plk_ctx *ctx, uint64_t offset, uint64_t n, plk_g1_affine *out) {
     if (!ctx || !out) { set_error("plk_srs_download: bad argument"); return PLK_ERR_ARG; }
-    if (!ctx->srs || offset + n > ctx->srs_n) { set_error("plk_srs_download: range outside the resident SRS"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts || offset + n > ctx->srs().n) { set_error("plk_srs_download: range outside the resident SRS"); return PLK_ERR_SRS; }
     PLK_HIP(hipSetDevice(ctx->device));
-    PLK_HIP(hipMemcpyAsync(out, (const char *)ctx->srs + offset * sizeof(G1Affine), n * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream));
+    PLK_HIP(hipMemcpyAsync(out, (const char *)ctx->srs().pts + offset * sizeof(G1Affine), n * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream));
     PLK_HIP(hipStreamSynchronize(ctx->stream));
     return PLK_OK;
 }

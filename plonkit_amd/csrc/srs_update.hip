@@ -179,9 +179,9 @@ extern "C" int32_t plk_srs_update_verify(plk_ctx *ctx, const plk_g1_affine old_p
     if (valid) *valid = 0;
     if (reason) *reason = PLK_UPDATE_OK;
     if (!ctx || !old_p01 || !g2_old || !g2_new || !receipt || !valid) { set_error("plk_srs_update_verify: bad argument"); return PLK_ERR_ARG; }
-    if (!ctx->srs || ctx->srs_n == 0) { set_error("plk_srs_update_verify: no key resident"); return PLK_ERR_SRS; }
+    if (!ctx->srs().pts || ctx->srs().n == 0) { set_error("plk_srs_update_verify: no key resident"); return PLK_ERR_SRS; }
     if (ctx->shard_first != 0) { set_error("plk_srs_update_verify: this context holds a slice of the key (first index " + std::to_string(ctx->shard_first) + "): the check needs the whole prefix"); return PLK_ERR_ARG; }
-    const uint32_t points = ctx->srs_n > 1 ? 2 : 1;
+    const uint32_t points = ctx->srs().n > 1 ? 2 : 1;
     plk_g1_affine new_p01[2] = {};
     PLK_TRY(plk_srs_download(ctx, 0, points, new_p01));
     uint32_t why = PLK_UPDATE_OK;
@@ -198,8 +198,8 @@ extern "C" int32_t plk_srs_update_verify(plk_ctx *ctx, const plk_g1_affine old_p
 
 extern "C" int32_t plk_srs_update(plk_ctx *ctx, const plk_fr *s, uint64_t first, const uint8_t g2_old[256], uint8_t g2_new[256], uint8_t receipt[192]) {
     if (!ctx || !g2_old || !g2_new || !receipt) { set_error("plk_srs_update: bad argument"); return PLK_ERR_ARG; }
-    if (!ctx->srs || ctx->srs_n == 0) { set_error("plk_srs_update: no key resident"); return PLK_ERR_SRS; }
-    const uint64_t n = ctx->srs_n;
+    if (!ctx->srs().pts || ctx->srs().n == 0) { set_error("plk_srs_update: no key resident"); return PLK_ERR_SRS; }
+    const uint64_t n = ctx->srs().n;
     if (n > (1ull << MAX_LOG_N) || first > (1ull << MAX_LOG_N) - n) { set_error("plk_srs_update: the highest index, first + size, exceeds 2^28 (the reach of the table of powers of s)"); return PLK_ERR_SIZE; }
     if (s && (fr_is_zero(s) || !fr_is_residue(s))) { set_error("plk_srs_update: s is zero or not a canonical residue"); return PLK_ERR_ARG; }
     G2Affine q[2];
@@ -208,7 +208,7 @@ extern "C" int32_t plk_srs_update(plk_ctx *ctx, const plk_fr *s, uint64_t first,
     if (!sound) { set_error("plk_srs_update: a G2 point of the key is infinity or outside the subgroup"); return PLK_ERR_ARG; }
     // refused before anything is computed; the guard itself runs when the new key is installed (on a borrower it returns the loan,
     // which a failed call must leave as it was)
-    if (ctx->srs_borrowers.load() > 0) return srs_replace_guard(ctx, "plk_srs_update");
+    if (ctx->srs().borrowers.load() > 0) return srs_replace_guard(ctx, "plk_srs_update");
     if (ctx->msm_enq != ctx->msm_fin) { set_error("plk_srs_update: a commitment is still in flight on this context"); return PLK_ERR_ARG; }
 
     HFr hs;
@@ -246,7 +246,7 @@ extern "C" int32_t plk_srs_update(plk_ctx *ctx, const plk_fr *s, uint64_t first,
         memcpy(base.l, hs.l, 32);
         PLK_TRY(fill_pow_table_into(ctx, base, reinterpret_cast<Fr *>(table.p), &pt, ctx->stream));
     }
-    const G1Affine *old = reinterpret_cast<const G1Affine *>(ctx->srs);
+    const G1Affine *old = reinterpret_cast<const G1Affine *>(ctx->srs().pts);
     G1Xyzz *tmp = reinterpret_cast<G1Xyzz *>(scratch.p);
     for (uint64_t off = 0; off < n; off += chunk) {
         const uint64_t len = n - off < chunk ? n - off : chunk;
@@ -260,11 +260,8 @@ extern "C" int32_t plk_srs_update(plk_ctx *ctx, const plk_fr *s, uint64_t first,
     if (ctx->ev_on) { PLK_HIP(hipEventElapsedTime(&ctx->update_ms, timed.ev[0], timed.ev[1])); ctx->update_ms_valid = true; }
 
     PLK_TRY(srs_replace_guard(ctx, "plk_srs_update"));
-    std::swap(ctx->srs_own, fresh);                             // (`fresh` now holds the old key, if the context owned it: released on the way out)
-    ctx->srs = ctx->srs_own.p;
-    ctx->srs_n = n;
-    srs_table_invalidate(ctx);
-    ctx->lag.pts = nullptr; ctx->lag.n = 0; lag_table_invalidate(ctx);      // the old Lagrange-form key no longer belongs
+    key_install_owned(ctx, KEY_MONOMIAL, fresh, n);             // (`fresh` now holds the old key, if the context owned it: released on the way out)
+    key_clear(ctx, KEY_LAGRANGE);                               // the old Lagrange-form key no longer belongs
     memcpy(g2_new, g2_out, 256);
     memcpy(receipt, receipt_out, 192);
     return PLK_OK;
