@@ -1005,6 +1005,54 @@ int32_t plk_kzg_open_all_dev(plk_ctx *ctx, const void *poly_dev, uint32_t log_n,
                              void *proofs_dev /* 2^log_n affine points */, void *evals_dev /* may be NULL: f(omega^i) */, void *stream);
 int32_t plk_kzg_open_all_last_ms(plk_ctx *ctx, float out_ms[5]);
 int32_t plk_g1_ntt_dev(plk_ctx *ctx, const void *in_dev, uint32_t log_n, int32_t inverse, void *out_dev, void *stream);
+/*   Many polynomials at several points with a proof of two points (kzg_multi.hip; Boneh-Drake-Fisch-Gabizon 2020, the scheme that needs
+ *   only [tau]_2).  NO COUNTERPART IN THE REFERENCE: kate_commitment opens at one point per call.  f_0 .. f_{m-1} have n coefficients each,
+ *   t_0 .. t_{p-1} are distinct points, and bit j of sets[i] says that f_i is opened at t_j (S_i; T = all p points).  No set is empty, no
+ *   bit at or above p is set, every point belongs to some set.  Z_A(x) = prod_{a in A} (x - a), r_i = the polynomial of degree < |S_i| that
+ *   agrees with f_i on S_i, w_ij = 1 / prod_{l in S_i, l != j} (t_j - t_l), gamma^i is indexed by the polynomial's position.
+ *       W  = commit(h),  h = sum_i gamma^i (f_i - r_i) / Z_{S_i} = sum_j D_{t_j}[ sum_{i: j in S_i} gamma^i w_ij f_i ],  D_t[g] = (g - g(t)) / (x - t)
+ *       u  = the caller's challenge, drawn after W
+ *       W' = commit(L / (x - u)),  L = sum_i c_i (f_i - r_i(u)) - Z_T(u) h,  c_i = gamma^i Z_{T \ S_i}(u)
+ *   and an opening is valid exactly when e(F + u W', g2[0]) e(-W', g2[1]) == 1 with F = sum_i c_i (C_i - r_i(u) G) - Z_T(u) W.
+ *
+ *   plk_poly_quotient_multi_dev.  The operator behind both quotients, as a call of its own (what the tests hold against the definition):
+ *                out[k] = sum_j sum_{l > k} G_j[l] t_j^(l-k-1),  G_j[l] = sum_i coef[i * npoints + j] f_i[l],  k < n; out[n-1] = 0.
+ *                That is sum_j D_{t_j}[G_j].  count 1..64, npoints 1..8, 1 <= n <= 2^28; coef and points are host arrays of scalars
+ *                below r; a zero entry of coef costs no product.  Every polynomial is read once per pass for all points (two passes over
+ *                tiles of 2048 coefficients and a carry between them: (2 count + 1) x 32 n bytes), no npoints x n intermediate exists, no
+ *                inverse is taken, and t_j = 0 is an ordinary point (the shifted combination).  The points need not be distinct here.
+ *                The same pointer may appear twice among the inputs; out_dev is none of them (PLK_ERR_ARG).  Blocks.
+ *   plk_kzg_open_multi_dev.  The prover above.  Inputs are COEFFICIENTS, 1 <= n <= plk_srs_size, n <= 2^28, count 1..32, npoints 1..8; there
+ *                is no PLK_KZG_VALUES route: a holder of values runs plk_ntt_dev first.  evals[i * npoints + j] = f_i(t_j) for j in S_i and
+ *                zero elsewhere (the evaluation kernel of the prover, 12 pairs per launch); the two points do not depend on them.
+ *                `challenge` is called ONCE, on the calling thread, after W has reached the host, and not at all when the call fails
+ *                earlier; it writes u.  A non-zero return: PLK_ERR_IO, the message names the callback and its return value; u >= r:
+ *                PLK_ERR_ARG; the context stays usable after either.  Any u below r is legal, 0 and the points included, and so is any
+ *                point below r.  *u_out receives u, proof[0] = W, proof[1] = W'.  Polynomials are never written; the same pointer may
+ *                appear twice.  PLK_ERR_ARG: null pointers, counts out of range, duplicate points, an empty set, a set bit at or above
+ *                npoints, a point no set uses, a scalar >= r, pointers not 16-byte aligned, a commitment in flight, a context with a
+ *                commit shard (single-GPU).  PLK_ERR_SRS: no key resident, or the key is shorter than n.  Blocks.  Scratch (h, one value
+ *                per tile and point, the matrix, the power tables of the points: about n x 32 B + 8.3 MiB) lives in the opening calls'
+ *                buffer: grows only, and a call that grew it past 64 MiB frees it before it returns.
+ *   plk_kzg_verify_multi.  The verifier above, pure CPU, no context: count + 3 scalar multiplications and plk_pairing_check (its G2
+ *                decoding, its refusals, its words).  evals is count x npoints, entries outside a set are not read.  Infinity is a legal
+ *                commitment and a legal W or W'.  The refusals of plk_kzg_verify and those of the sets above: PLK_ERR_ARG.  count 1..32.
+ *   plk_kzg_open_multi_last_ms.  Device-event times of the last plk_kzg_open_multi_dev while plk_set_kernel_timing is on: the evaluations,
+ *                the quotient h, the commitment W, the second quotient with the commitment W'.                                            */
+typedef int32_t (*plk_kzg_challenge_fn)(void *user, const plk_g1_affine *w, plk_fr *u_out);   /* 0 = success */
+int32_t plk_poly_quotient_multi_dev(plk_ctx *ctx, const void *const *polys_dev, uint32_t count /* 1..64 */, uint64_t n,
+                                    const plk_fr *points, uint32_t npoints /* 1..8 */, const plk_fr *coef /* count x npoints, row-major */,
+                                    void *out_dev /* n elements; not one of the inputs */, void *stream);
+int32_t plk_kzg_open_multi_dev(plk_ctx *ctx, const void *const *polys_dev, uint32_t count /* 1..32 */, uint64_t n,
+                               const plk_fr *points, uint32_t npoints /* 1..8 */, const uint32_t *sets /* count masks */,
+                               const plk_fr *gamma, plk_kzg_challenge_fn challenge, void *user,
+                               plk_fr *evals /* count x npoints; entries outside a set are written as zero */,
+                               plk_fr *u_out, plk_g1_affine proof[2] /* W, W' */, void *stream);
+int32_t plk_kzg_verify_multi(const plk_g1_affine *commitments, uint32_t count, const plk_fr *points, uint32_t npoints,
+                             const uint32_t *sets, const plk_fr *evals /* count x npoints; entries outside a set are not read */,
+                             const plk_fr *gamma, const plk_fr *u, const plk_g1_affine proof[2],
+                             const uint8_t g2[256], int32_t *valid);
+int32_t plk_kzg_open_multi_last_ms(plk_ctx *ctx, float out_ms[4]);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

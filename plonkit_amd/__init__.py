@@ -15,11 +15,11 @@ from ._lib import (PlkError, lib, lib_path, Context, last_error, have_gpu,   # n
                    g1_sum_jacobian, g1_to_bytes, g1_from_bytes, fr_to_bytes, fr_from_bytes,
                    Transcript, keccak256, Circuit, SetupForProver, verify, pairing_check, crs42_g2_bytes,
                    comm_unique_id, R1cs, r1cs_long_lc_terms, VerificationKey, VerificationKeySet, verify_terms,
-                   srs_update_receipt, srs_update_check_receipt, UPDATE_REASONS, kzg_verify,
+                   srs_update_receipt, srs_update_check_receipt, UPDATE_REASONS, kzg_verify, kzg_verify_multi,
                    CopyReport, COPY_OK, COPY_NOT_A_LABEL, COPY_NOT_BIJECTIVE, COPY_BROKEN, TranscriptOps)
 
 __all__ = ["PlkError", "lib", "lib_path", "Context", "last_error", "have_gpu", "g1_sum_jacobian",
            "g1_to_bytes", "g1_from_bytes", "fr_to_bytes", "fr_from_bytes", "Transcript", "keccak256", "Circuit", "SetupForProver",
            "verify", "pairing_check", "crs42_g2_bytes", "comm_unique_id", "R1cs", "r1cs_long_lc_terms", "VerificationKey", "VerificationKeySet", "verify_terms",
-           "srs_update_receipt", "srs_update_check_receipt", "UPDATE_REASONS", "kzg_verify",
+           "srs_update_receipt", "srs_update_check_receipt", "UPDATE_REASONS", "kzg_verify", "kzg_verify_multi",
            "CopyReport", "COPY_OK", "COPY_NOT_A_LABEL", "COPY_NOT_BIJECTIVE", "COPY_BROKEN", "TranscriptOps"]

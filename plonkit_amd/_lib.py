@@ -746,6 +746,64 @@ class Context:
         _check(lib().plk_kzg_open_all_last_ms(self._h, out))
         return [float(v) for v in out]
 
+    # ---- many polynomials at several points, a proof of two points (kzg_multi.hip)
+    _KZG_CHALLENGE = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64))
+
+    def poly_quotient_multi_dev(self, ptrs, n, points, coef, out_ptr, stream=None):
+        """plk_poly_quotient_multi_dev: out[k] = sum_j sum_{l > k} G_j[l] t_j^(l-k-1) with G_j = sum_i coef[i][j] f_i, for count <= 64 device
+        polynomials of n coefficients, points [npoints <= 8, 4] and coef [count, npoints, 4]; out_ptr is none of the inputs.  Blocks."""
+        arr = (ctypes.c_void_p * len(ptrs))(*[_devptr(p) for p in ptrs])
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        cf = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
+        if cf.shape[0] != len(ptrs) * pts.shape[0]:
+            raise ValueError("poly_quotient_multi_dev: %d polynomials and %d points need %d coefficients, got %d"
+                             % (len(ptrs), pts.shape[0], len(ptrs) * pts.shape[0], cf.shape[0]))
+        _check(lib().plk_poly_quotient_multi_dev(self._h, arr, ctypes.c_uint32(len(ptrs)), ctypes.c_uint64(n), _np(pts), ctypes.c_uint32(pts.shape[0]), _np(cf),
+                                                 _devptr(out_ptr), _stream(stream)))
+
+    def kzg_open_multi_dev(self, ptrs, n, points, sets, gamma, challenge, stream=None):
+        """plk_kzg_open_multi_dev: opens count <= 32 device polynomials of n coefficients, polynomial i at the points named by the bits of
+        sets[i] (points: [npoints <= 8, 4]), with a proof of two points.  challenge: a callable W ([8] uint64) -> u ([4] uint64), called once
+        after the first commitment, or a fixed scalar u.  Returns ([count, npoints, 4] evaluations, zero outside the sets; u; [2, 8] W, W').
+        An exception raised by the callable is raised again here, after the call has failed with PLK_ERR_IO."""
+        arr = (ctypes.c_void_p * len(ptrs))(*[_devptr(p) for p in ptrs])
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        masks = np.ascontiguousarray(sets, dtype=np.uint32).reshape(-1)
+        if masks.shape[0] != len(ptrs):
+            raise ValueError("kzg_open_multi_dev: %d polynomials and %d sets" % (len(ptrs), masks.shape[0]))
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64)
+        raised = []
+
+        def _call(_user, w, u_out):
+            try:
+                u = challenge(np.array([w[k] for k in range(8)], dtype=np.uint64)) if callable(challenge) else challenge
+                if isinstance(u, int):                                # a plain int from the callable is the C callback's return code (non-zero: failure)
+                    return u
+                u = np.ascontiguousarray(u, dtype=np.uint64).reshape(4)
+                for k in range(4):
+                    u_out[k] = int(u[k])
+                return 0
+            except Exception as e:                                    # noqa: BLE001 — an exception must not cross the C frames
+                raised.append(e)
+                return -1
+
+        cb = self._KZG_CHALLENGE(_call)                               # kept alive by this frame until the call has returned
+        evals = np.zeros((len(ptrs), pts.shape[0], 4), dtype=np.uint64)
+        u, proof = np.zeros(4, dtype=np.uint64), np.zeros((2, 8), dtype=np.uint64)
+        rc = lib().plk_kzg_open_multi_dev(self._h, arr, ctypes.c_uint32(len(ptrs)), ctypes.c_uint64(n), _np(pts), ctypes.c_uint32(pts.shape[0]), _np(masks),
+                                          _np(gamma), cb, None, _np(evals), _np(u), _np(proof), _stream(stream))
+        if raised:
+            raise raised[0]
+        _check(rc)
+        return evals, u, proof
+
+    def kzg_open_multi_last_ms(self):
+        """plk_kzg_open_multi_last_ms: [evaluations, first quotient, its commitment, second quotient with its commitment] of the last
+        kzg_open_multi_dev, in ms (set_kernel_timing must be on)"""
+        out = (ctypes.c_float * 4)()
+        _check(lib().plk_kzg_open_multi_last_ms(self._h, out))
+        return [float(v) for v in out]
+
     def g1_ntt_dev(self, in_ptr, log_n, out_ptr, inverse=False, stream=None):
         """plk_g1_ntt_dev: the G1 transform of 2^log_n affine points in device memory, forward (out[i] = sum_j omega^(i j) in[j]) or inverse
         (g1_intt's, bit for bit); ordered on `stream`, does not wait"""
@@ -1419,6 +1477,28 @@ def kzg_verify(commitments, z, evals, proof, g2_bytes, v=None):
     p = np.ascontiguousarray(proof, dtype=np.uint64)
     out = ctypes.c_int32(0)
     _check(lib().plk_kzg_verify(_np(c), ctypes.c_uint32(c.shape[0]), _np(z), _np(e), _np(v) if v is not None else None, _np(p), g2_bytes, ctypes.byref(out)))
+    return bool(out.value)
+
+
+def kzg_verify_multi(commitments, points, sets, evals, gamma, u, proof, g2_bytes):
+    """plk_kzg_verify_multi (pure CPU): is proof ([2, 8]: W, W') an opening of the commitments ([count, 8]), commitment i at the points
+    ([npoints, 4]) named by the bits of sets[i], to evals ([count, npoints, 4]; entries outside a set are not read), under the batching
+    challenge gamma and the evaluation challenge u?  g2_bytes: the 256 bytes of the key file's G2 section.  Malformed input raises PlkError."""
+    c = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+    masks = np.ascontiguousarray(sets, dtype=np.uint32).reshape(-1)
+    e = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+    if masks.shape[0] != c.shape[0] or e.shape[0] != c.shape[0] * pts.shape[0]:
+        raise ValueError("kzg_verify_multi: %d commitments and %d points need %d sets and %d evaluations, got %d and %d"
+                         % (c.shape[0], pts.shape[0], c.shape[0], c.shape[0] * pts.shape[0], masks.shape[0], e.shape[0]))
+    g2_bytes = bytes(g2_bytes)
+    if len(g2_bytes) != 256:
+        raise ValueError("g2_bytes must be the 256 bytes of a key file's G2 section, got %d" % len(g2_bytes))
+    gamma, u = np.ascontiguousarray(gamma, dtype=np.uint64), np.ascontiguousarray(u, dtype=np.uint64)
+    p = np.ascontiguousarray(proof, dtype=np.uint64).reshape(2, 8)
+    out = ctypes.c_int32(0)
+    _check(lib().plk_kzg_verify_multi(_np(c), ctypes.c_uint32(c.shape[0]), _np(pts), ctypes.c_uint32(pts.shape[0]), _np(masks), _np(e), _np(gamma), _np(u), _np(p),
+                                      g2_bytes, ctypes.byref(out)))
     return bool(out.value)
 
 

@@ -148,6 +148,8 @@ struct plk_ctx {
     uint8_t pair_g2[256] = {};
     bool pair_tab_valid = false;
     plk::DevBuf kzg_ws;                      // kzg.hip: scratch of the blocking opening calls (grows only; a call that grew it past 64 MiB frees it on return)
+    float km_ms[4] = {0, 0, 0, 0};           // kzg_multi.hip: evaluations, h, W, second quotient with W' of the last plk_kzg_open_multi_dev (recorded while ev_on)
+    bool km_ms_valid = false;
     plk::DevBuf kzg_vm;                      // kzg.hip: plk_kzg_verify_many_dev's working memory, its own for vm_stage's reason (the call does not wait)
     // kzg_all.hip (all openings on the domain in one pass).  fk_key: DFT_2N of the arranged key, 2N XYZZ points of the 29-bit layer, this
     // context's own even where the key is borrowed or lent; void with the monomial key (key_changed).  fk_ws: scratch of a call (grows only;

@@ -27,6 +27,7 @@
 #include "prover_math.h"
 #include "pairing.h"
 #include "g2_host.h"
+#include "kzg_scratch.h"
 #include <cstring>
 #include <string>
 
@@ -38,7 +39,6 @@ constexpr uint32_t KZ_BLOCK = KZ_T * KZ_E;
 static_assert(KZ_BLOCK == POLY_SCAN_BLOCK, "the consumers fold in the scan's block prefixes: same block size");
 constexpr uint32_t KZ_MAX = 8;                                  // polynomials per call
 constexpr uint32_t KZ_NONE = 0xffffffffu;
-constexpr size_t KZ_KEEP = (size_t)64 << 20;                    // scratch beyond this is released on return
 constexpr uint64_t KZ_VM_CHUNK = 1u << 16;                      // openings per pass of plk_kzg_verify_many_dev
 
 __device__ __forceinline__ FrW9 kz_ldw(const Fr *p) { return unpack<FrW>(load_fp(p)); }
@@ -198,17 +198,6 @@ inline Fr kz_dev(const HFr &h) { Fr f; memcpy(f.l, h.l, 32); return f; }
 inline HFr kz_host(const plk_fr *p) { HFr h; memcpy(h.l, p->l, 32); return h; }
 inline bool kz_fr_ok(const plk_fr *p) { return !HFr::geq_p(p->l); }
 const char *const KZ_LAGRANGE_SIZE = "Lagrange-form key has a different size than the circuit's domain";     // the prover's words (prover.hip)
-
-// the blocking calls' scratch: grows only, given back on the way out when the call grew it past KZ_KEEP
-struct KzgScratch {
-    plk_ctx *ctx; hipStream_t st; bool grew = false;
-    KzgScratch(plk_ctx *c, hipStream_t s) : ctx(c), st(s) {}
-    int32_t reserve(size_t bytes) {
-        if (bytes > ctx->kzg_ws.cap) { grew = true; PLK_HIP(hipStreamSynchronize(st)); }
-        return ctx->kzg_ws.reserve(bytes);
-    }
-    ~KzgScratch() { if (grew && ctx->kzg_ws.cap > KZ_KEEP) { (void)hipStreamSynchronize(st); ctx->kzg_ws.release(); } }
-};
 
 // Layout of the scratch of a values call: [k word | results | partials | A | B | extra]
 struct ValuesPlan {
