@@ -141,9 +141,8 @@ struct plk_ctx {
     bool update_ms_valid = false;
     float vm_ms[6] = {0, 0, 0, 0, 0, 0};     // verify_many.hip: host flattening (or the front kernel), upload, the three kernels, download of the last plk_verify_many / _packed (recorded while ev_on)
     bool vm_ms_valid = false;
-    plk::DevBuf vm_stage;                    // plk_verify_many_dev's working memory.  NOT `stage`: that call returns without waiting, and every user of
-                                             // `stage` relies on the earlier ones having waited (some write it on a stream the caller chooses)
-    hipEvent_t vm_in = nullptr, vm_done = nullptr;   // plk_verify_many_dev on a caller's stream: its kernels run on `stream`, which alone touches vm_stage, between these two
+    plk::DevBuf vm_stage;                    // working memory of plk_verify_many_dev / plk_verify_mixed_dev, which do not wait: NOT `stage` (on_ctx_stream, below)
+    hipEvent_t vm_in = nullptr, vm_done = nullptr;   // the two events of on_ctx_stream
     plk::DevBuf pair_tab;                    // verify_many.hip: line table of the G2 pair plk_pairing_check_many_dev saw last
     uint8_t pair_g2[256] = {};
     bool pair_tab_valid = false;
@@ -196,6 +195,45 @@ inline void key_install_owned(plk_ctx *c, KeyForm which, DevBuf &fresh, uint64_t
     key_install(c, which, c->key[which].own.p, n);
 }
 inline void key_clear(plk_ctx *c, KeyForm which) { key_install(c, which, nullptr, 0); }
+// plk_set_kernel_timing: N events around the stages of a call, created only while ctx->ev_on and destroyed on the way out.  Without
+// timing, mark and elapsed do nothing.
+template <int N> struct StageTimer {
+    hipEvent_t e[N] = {};
+    bool on = false;
+    StageTimer() = default;
+    StageTimer(const StageTimer &) = delete;
+    ~StageTimer() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    int32_t start(const plk_ctx *c) {
+        if (!c->ev_on) return PLK_OK;
+        on = true;
+        for (int k = 0; k < N; k++) PLK_HIP(hipEventCreate(&e[k]));
+        return PLK_OK;
+    }
+    int32_t mark(int k, hipStream_t st) { if (on) PLK_HIP(hipEventRecord(e[k], st)); return PLK_OK; }
+    int32_t elapsed(int a, int b, float *ms) { if (on) PLK_HIP(hipEventElapsedTime(ms, e[a], e[b])); return PLK_OK; }
+};
+
+// The hand-over of a call that returns without waiting (plk_verify_many_dev, plk_verify_mixed_dev, plk_kzg_verify_many_dev): body(st) enqueues
+// on the context's stream, after what the caller's stream holds now, and the caller's stream goes on after it; a second such call queues
+// behind the first.  Such a call keeps out of the staging arena `stage`, whose users (the blocking calls) each rely on the earlier ones
+// having waited, and some of which write it on a stream of the caller's choice.  Its working memory is a buffer of its own, vm_stage or
+// kzg_vm, which only kernels on the context's stream touch.  Reserve that buffer BEFORE the hand-over: growing it frees the old block, which
+// waits for the device.
+template <class Fn> inline int32_t on_ctx_stream(plk_ctx *c, hipStream_t caller, Fn body) {
+    const hipStream_t st = c->stream;
+    if (caller != st) {
+        if (!c->vm_in) PLK_HIP(hipEventCreateWithFlags(&c->vm_in, hipEventDisableTiming));
+        if (!c->vm_done) PLK_HIP(hipEventCreateWithFlags(&c->vm_done, hipEventDisableTiming));
+        PLK_HIP(hipEventRecord(c->vm_in, caller));
+        PLK_HIP(hipStreamWaitEvent(st, c->vm_in, 0));
+    }
+    PLK_TRY(body(st));
+    if (caller != st) {
+        PLK_HIP(hipEventRecord(c->vm_done, st));
+        PLK_HIP(hipStreamWaitEvent(caller, c->vm_done, 0));
+    }
+    return PLK_OK;
+}
 void srs_return_loan(plk_ctx *c);                                 // runtime.hip
 void srs_make_loan(plk_ctx *dst, plk_ctx *src);                   // runtime.hip
 bool srs_orphan_lender(plk_ctx *c);                               // runtime.hip

@@ -482,9 +482,7 @@ extern "C" int32_t plk_kzg_verify_many_dev(plk_ctx *ctx, const void *commitments
     if (ctx->msm_enq != ctx->msm_fin) { set_error("plk_kzg_verify_many_dev: a commitment is still in flight on this context"); return PLK_ERR_ARG; }
     if (n == 0) return PLK_OK;
     PLK_HIP(hipSetDevice(ctx->device));
-    // As plk_verify_many_dev: the call does not wait, so its working memory is a buffer of its own that only kernels on the context's stream
-    // touch; they run after what the caller's stream holds now, and the caller's stream goes on after them.
-    hipStream_t st = ctx->stream, caller = stream ? (hipStream_t)stream : ctx->stream;
+    // the call does not wait: a buffer of its own and the context's stream (on_ctx_stream, ctx.h)
     const size_t m = (size_t)(n < KZ_VM_CHUNK ? n : KZ_VM_CHUNK), pad = (m + 15) & ~(size_t)15;
     PLK_TRY(ctx->kzg_vm.reserve(m * (2 * sizeof(G1Affine) + sizeof(XyzzW)) + 2 * pad));
     char *d = ctx->kzg_vm.as<char>();
@@ -492,30 +490,22 @@ extern "C" int32_t plk_kzg_verify_many_dev(plk_ctx *ctx, const void *commitments
     XyzzW *tmp = reinterpret_cast<XyzzW *>(b + m);
     uint8_t *vv = reinterpret_cast<uint8_t *>(tmp + m), *bad = vv + pad;
     static_assert(sizeof(XyzzW) % 16 == 0 && sizeof(G1Affine) % 16 == 0, "the arrays behind one another stay 16-byte aligned");
-    if (caller != st) {
-        if (!ctx->vm_in) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_in, hipEventDisableTiming));
-        if (!ctx->vm_done) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_done, hipEventDisableTiming));
-        PLK_HIP(hipEventRecord(ctx->vm_in, caller));
-        PLK_HIP(hipStreamWaitEvent(st, ctx->vm_in, 0));
-    }
-    PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kzg_vm_front), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
-    for (uint64_t base = 0; base < n; base += KZ_VM_CHUNK) {
-        const uint32_t cnt = (uint32_t)(n - base < KZ_VM_CHUNK ? n - base : KZ_VM_CHUNK);
-        hipLaunchKernelGGL(k_kzg_vm_check, dim3((cnt + 255) / 256), dim3(256), 0, st, bad, static_cast<const G1Affine *>(commitments_dev) + base,
-                           static_cast<const Fr *>(z_dev) + base, static_cast<const Fr *>(evals_dev) + base, static_cast<const G1Affine *>(proofs_dev) + base, cnt);
-        hipLaunchKernelGGL(k_kzg_vm_front, dim3((cnt + G1NTT_THREADS - 1) / G1NTT_THREADS), dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, tmp, (const uint8_t *)bad,
-                           static_cast<const G1Affine *>(commitments_dev) + base, static_cast<const Fr *>(z_dev) + base, static_cast<const Fr *>(evals_dev) + base,
-                           static_cast<const G1Affine *>(proofs_dev) + base, cnt);
-        hipLaunchKernelGGL(k_kzg_vm_finish, dim3((cnt + 255) / 256), dim3(256), 0, st, a, b, (const XyzzW *)tmp, (const uint8_t *)bad,
-                           static_cast<const G1Affine *>(proofs_dev) + base, cnt);
-        PLK_HIP(hipGetLastError());
-        PLK_TRY(plk_pairing_check_many_dev(ctx, a, b, cnt, g2, vv, st));
-        hipLaunchKernelGGL(k_kzg_vm_settle, dim3((cnt + 255) / 256), dim3(256), 0, st, static_cast<uint8_t *>(verdict_dev) + base, (const uint8_t *)vv, (const uint8_t *)bad, cnt);
-        PLK_HIP(hipGetLastError());
-    }
-    if (caller != st) {
-        PLK_HIP(hipEventRecord(ctx->vm_done, st));
-        PLK_HIP(hipStreamWaitEvent(caller, ctx->vm_done, 0));
-    }
-    return PLK_OK;
+    return on_ctx_stream(ctx, stream ? (hipStream_t)stream : ctx->stream, [&](hipStream_t st) -> int32_t {
+        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kzg_vm_front), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
+        for (uint64_t base = 0; base < n; base += KZ_VM_CHUNK) {
+            const uint32_t cnt = (uint32_t)(n - base < KZ_VM_CHUNK ? n - base : KZ_VM_CHUNK);
+            hipLaunchKernelGGL(k_kzg_vm_check, dim3((cnt + 255) / 256), dim3(256), 0, st, bad, static_cast<const G1Affine *>(commitments_dev) + base,
+                               static_cast<const Fr *>(z_dev) + base, static_cast<const Fr *>(evals_dev) + base, static_cast<const G1Affine *>(proofs_dev) + base, cnt);
+            hipLaunchKernelGGL(k_kzg_vm_front, dim3((cnt + G1NTT_THREADS - 1) / G1NTT_THREADS), dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, tmp, (const uint8_t *)bad,
+                               static_cast<const G1Affine *>(commitments_dev) + base, static_cast<const Fr *>(z_dev) + base, static_cast<const Fr *>(evals_dev) + base,
+                               static_cast<const G1Affine *>(proofs_dev) + base, cnt);
+            hipLaunchKernelGGL(k_kzg_vm_finish, dim3((cnt + 255) / 256), dim3(256), 0, st, a, b, (const XyzzW *)tmp, (const uint8_t *)bad,
+                               static_cast<const G1Affine *>(proofs_dev) + base, cnt);
+            PLK_HIP(hipGetLastError());
+            PLK_TRY(plk_pairing_check_many_dev(ctx, a, b, cnt, g2, vv, st));
+            hipLaunchKernelGGL(k_kzg_vm_settle, dim3((cnt + 255) / 256), dim3(256), 0, st, static_cast<uint8_t *>(verdict_dev) + base, (const uint8_t *)vv, (const uint8_t *)bad, cnt);
+            PLK_HIP(hipGetLastError());
+        }
+        return PLK_OK;
+    });
 }

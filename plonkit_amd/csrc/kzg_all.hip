@@ -113,11 +113,9 @@ int32_t open_all(plk_ctx *ctx, const Fr *poly, uint32_t log_n, bool values, G1Af
         PLK_HIP(hipStreamSynchronize(st));
         return PLK_OK;
     }
-    const bool timed = ctx->ev_on;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 6; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
-    if (timed) for (int k = 0; k < 6; k++) PLK_HIP(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], st)); return PLK_OK; };
+    StageTimer<6> ev;
+    PLK_TRY(ev.start(ctx));
+    auto mark = [&](int k) { return ev.mark(k, st); };
 
     FkWs ws(ctx, st);
     const FkScratch lay = fk_scratch(log_n, values);
@@ -161,8 +159,8 @@ int32_t open_all(plk_ctx *ctx, const Fr *poly, uint32_t log_n, bool values, G1Af
     PLK_TRY(mark(5));
     PLK_HIP(hipStreamSynchronize(st));
     if (built) { ctx->fk_key_valid = true; ctx->fk_key_log_n = log_n; }
-    if (timed) {
-        for (int k = 0; k < 5; k++) PLK_HIP(hipEventElapsedTime(&ctx->fk_ms[k], ev[k], ev[k + 1]));
+    if (ev.on) {
+        for (int k = 0; k < 5; k++) PLK_TRY(ev.elapsed(k, k + 1, &ctx->fk_ms[k]));
         ctx->fk_ms_valid = true;
     }
     return PLK_OK;

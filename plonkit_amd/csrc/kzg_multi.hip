@@ -232,19 +232,6 @@ int32_t km_common(const char *who, plk_ctx *ctx, const void *const *polys, uint3
     return PLK_OK;
 }
 
-struct KmEvents {
-    hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool on;
-    explicit KmEvents(bool timed) : on(timed) {}
-    int32_t mark(int k, hipStream_t st) {
-        if (!on) return PLK_OK;
-        PLK_HIP(hipEventCreate(&e[k]));
-        PLK_HIP(hipEventRecord(e[k], st));
-        return PLK_OK;
-    }
-    ~KmEvents() { for (int k = 0; k < 6; k++) if (e[k]) (void)hipEventDestroy(e[k]); }
-};
-
 int32_t open_multi(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint64_t n, const HFr *points, uint32_t npoints, const uint32_t *sets, const HFr &gamma,
                    plk_kzg_challenge_fn challenge, void *user, plk_fr *evals, plk_fr *u_out, plk_g1_affine *proof, hipStream_t st) {
     const char *who = "plk_kzg_open_multi_dev";
@@ -257,7 +244,8 @@ int32_t open_multi(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint64_t n,
     KzgScratch ws(ctx, st);
     PLK_TRY(ws.reserve((tab_elems + res_elems + km_scratch_elems(n, npoints) + n) * sizeof(Fr)));
     Fr *tab = ctx->kzg_ws.as<Fr>(), *res = tab + tab_elems, *qs = res + res_elems, *h = qs + km_scratch_elems(n, npoints);
-    KmEvents ev(ctx->ev_on);
+    StageTimer<6> ev;
+    PLK_TRY(ev.start(ctx));
     PLK_TRY(ev.mark(0, st));
     // 1. y_ij = f_i(t_j) for j in S_i, twelve pairs per launch
     PowTable pt[KM_MAX_POINTS];
@@ -307,8 +295,8 @@ int32_t open_multi(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint64_t n,
     PLK_TRY(ev.mark(5, st));
     if (ev.on) {
         PLK_HIP(hipEventSynchronize(ev.e[5]));
-        for (int k = 0; k < 3; k++) PLK_HIP(hipEventElapsedTime(&ctx->km_ms[k], ev.e[k], ev.e[k + 1]));
-        PLK_HIP(hipEventElapsedTime(&ctx->km_ms[3], ev.e[4], ev.e[5]));
+        for (int k = 0; k < 3; k++) PLK_TRY(ev.elapsed(k, k + 1, &ctx->km_ms[k]));
+        PLK_TRY(ev.elapsed(4, 5, &ctx->km_ms[3]));
         ctx->km_ms_valid = true;
     }
     return PLK_OK;

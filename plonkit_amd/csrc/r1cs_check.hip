@@ -152,12 +152,10 @@ static int32_t r1cs_upload_impl(plk_ctx *ctx, const plk_circuit *c, plk_r1cs **o
 // the check proper: `witness` on the device, complete on stream `s` (or written there by work already enqueued)
 static int32_t r1cs_check_impl(plk_ctx *ctx, const plk_r1cs *R, const Fr *witness, Fr *lc_vals, unsigned long long *words, hipStream_t s,
                                const char *who, int32_t *valid, uint64_t *bad_out) {
-    const bool timed = ctx->ev_on;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 5; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+    StageTimer<5> ev;
     ctx->r1cs_ms_valid = false;
-    if (timed) for (int k = 0; k < 5; k++) PLK_HIP(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], s)); return PLK_OK; };
+    PLK_TRY(ev.start(ctx));
+    auto mark = [&](int k) { return ev.mark(k, s); };
     PLK_TRY(mark(0));
     PLK_HIP(hipMemsetAsync(words, 0xff, 16, s));           // words[0]: lowest failing constraint, words[1]: lowest non-canonical wire read
     R1csLcArgs a;
@@ -182,9 +180,9 @@ static int32_t r1cs_check_impl(plk_ctx *ctx, const plk_r1cs *R, const Fr *witnes
     unsigned long long got[2] = {R1CS_NONE, R1CS_NONE};
     PLK_HIP(hipMemcpyAsync(got, words, 16, hipMemcpyDeviceToHost, s));
     PLK_HIP(hipStreamSynchronize(s));                      // the verdict is this call's return value
-    if (timed) {
-        for (int k = 0; k < 3; k++) PLK_HIP(hipEventElapsedTime(&ctx->r1cs_ms[k], ev[k + 1], ev[k + 2]));
-        PLK_HIP(hipEventElapsedTime(&ctx->r1cs_ms[3], ev[0], ev[4]));
+    if (ev.on) {
+        for (int k = 0; k < 3; k++) PLK_TRY(ev.elapsed(k + 1, k + 2, &ctx->r1cs_ms[k]));
+        PLK_TRY(ev.elapsed(0, 4, &ctx->r1cs_ms[3]));
         ctx->r1cs_ms_valid = true;
     }
     if (got[1] != R1CS_NONE) {

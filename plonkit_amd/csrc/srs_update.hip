@@ -226,11 +226,9 @@ extern "C" int32_t plk_srs_update(plk_ctx *ctx, const plk_fr *s, uint64_t first,
         attr_set = true;
     }
     ctx->update_ms_valid = false;
-    struct Events {                                             // plk_set_kernel_timing: a bracket around the device work
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    } timed;
-    if (ctx->ev_on) { PLK_HIP(hipEventCreate(&timed.ev[0])); PLK_HIP(hipEventCreate(&timed.ev[1])); PLK_HIP(hipEventRecord(timed.ev[0], ctx->stream)); }
+    StageTimer<2> timed;                                        // plk_set_kernel_timing: a bracket around the device work
+    PLK_TRY(timed.start(ctx));
+    PLK_TRY(timed.mark(0, ctx->stream));
     DevBuf fresh;                                               // the new key: the context's own once the last chunk is done
     struct Drop { DevBuf &b; ~Drop() { b.release(); } } drop{fresh};
     PLK_TRY(fresh.reserve(n * sizeof(G1Affine)));
@@ -255,9 +253,9 @@ extern "C" int32_t plk_srs_update(plk_ctx *ctx, const plk_fr *s, uint64_t first,
         PLK_HIP(hipGetLastError());
         PLK_TRY(srs_to_affine(fresh.as<G1Affine>() + off, tmp, len, ctx->stream));
     }
-    if (ctx->ev_on) PLK_HIP(hipEventRecord(timed.ev[1], ctx->stream));
+    PLK_TRY(timed.mark(1, ctx->stream));
     PLK_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->ev_on) { PLK_HIP(hipEventElapsedTime(&ctx->update_ms, timed.ev[0], timed.ev[1])); ctx->update_ms_valid = true; }
+    if (timed.on) { PLK_TRY(timed.elapsed(0, 1, &ctx->update_ms)); ctx->update_ms_valid = true; }
 
     PLK_TRY(srs_replace_guard(ctx, "plk_srs_update"));
     key_install_owned(ctx, KEY_MONOMIAL, fresh, n);             // (`fresh` now holds the old key, if the context owned it: released on the way out)

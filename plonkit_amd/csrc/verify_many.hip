@@ -13,9 +13,12 @@
 //   vm_affine_kernel   XYZZ -> affine, one inversion per 8 points (as srs_to_affine_kernel); infinity comes out as x = y = 0
 //   vm_pairing_kernel  one proof per lane: f <- f^2 l_0 l_1 over the uploaded line table, then the shortened final exponentiation of
 //                      fq12_dev.h (which decides the same predicate as pairing.cpp's; the argument is written there)
-// A key set (plk_vkset_create, plk_verify_mixed, _packed, _dev; at the end of this file) verifies proofs of several keys in one pass, the key
-// taken per proof: vm_mul_mixed_kernel and vm_pairing_mixed_kernel are the two kernels above with the key's points and line table looked up per
-// lane (vkset_dev.h), vm_front_mixed_kernel (verify_front.hip) likewise; the other kernels serve both.
+// A key set (plk_vkset_create, plk_verify_mixed, _packed, _dev) verifies proofs of several keys in one pass, the key taken per proof:
+// vm_mul_mixed_kernel and vm_pairing_mixed_kernel are the two kernels above with the key's points and line table looked up per lane
+// (vkset_dev.h), vm_front_mixed_kernel (verify_front.hip) likewise; the other kernels serve both.
+// Host side, in this order: the kernels; plk_vk and plk_vkset; VmArena (the layout of vm_arena.h); VmKeys, one key or a key set, which holds
+// everything that differs between the two; vm_pass, the one order of launches; and one driver per input form (host-parsed proofs, packed
+// bytes on the host, bytes on the device), each behind its two extern "C" calls.
 #include "ctx.h"
 #include "ec_dev.h"
 #include "ec29_dev.h"
@@ -27,6 +30,7 @@
 #include "transcript_ops.h"
 #include "verify_front.h"
 #include "vkset_dev.h"
+#include "vm_arena.h"
 #include "g2_host.h"
 #include "circuit.h"
 #include <atomic>
@@ -249,315 +253,9 @@ extern "C" int32_t plk_pairing_check_many_dev(plk_ctx *ctx, const void *a_dev, c
                           ctx->pair_tab.p, st);
 }
 
-// ops: the caller's transcript for the host front end (plk_verify_many_with), null for Keccak.  Without PLK_TRANSCRIPT_CONCURRENT the front end
-// then stays on the calling thread, one proof after the other.  The kernels do not know the difference.
-static int32_t verify_many_impl(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict,
-                                const plk_transcript_ops *ops) {
-    using clk = std::chrono::steady_clock;
-    const bool timed = ctx->ev_on;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 6; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
-    ctx->vm_ms_valid = false;
-    float ms[6] = {0, 0, 0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (timed) for (int k = 0; k < 6; k++) PLK_HIP(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], st)); return PLK_OK; };
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set) {
-        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vm_mul_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
-        attr_set = true;
-    }
-    std::vector<plk_g1_affine> h_pts;
-    std::vector<plk_fr> h_sc;
-    std::vector<uint64_t> live;
-    std::vector<uint8_t> h_v;
-    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
-        const uint64_t cnt = count - base < VM_CHUNK ? count - base : VM_CHUNK;
-        // host: every proof of the chunk through plk_verify_terms's code; the survivors are packed in index order
-        const auto t0 = clk::now();
-        std::vector<plk_g1_affine> all_pts((size_t)cnt * VM_PROOF_PTS);
-        std::vector<plk_fr> all_sc((size_t)cnt * VERIFY_TERMS);
-        const unsigned front_threads = ops && !(ops->flags & PLK_TRANSCRIPT_CONCURRENT) ? 1 : 16;
-        std::mutex tr_mu;                                             // a failure of the caller's transcript: the lowest proof that met one ends the call
-        uint64_t tr_bad = UINT64_MAX; int32_t tr_rc = PLK_OK; std::string tr_words;
-        parallel_for((size_t)cnt, 1, [&](size_t lo, size_t hi) {
-            plk_g1_affine pts[VERIFY_TERMS]; plk_fr sc[VERIFY_TERMS];
-            std::string msg;
-            for (size_t i = lo; i < hi; i++) {
-                int32_t early = 0;
-                if (front_threads == 1 && tr_rc != PLK_OK) break;      // (one thread: nothing else writes tr_rc) no further begin after a failure
-                const int32_t rc = verify_terms_parsed(vk->parsed, proofs[base + i], lens[base + i], vk->flags, pts, sc, &early, ops, &msg);
-                if (rc != PLK_OK && !msg.empty()) {
-                    std::lock_guard<std::mutex> g(tr_mu);
-                    if (base + i < tr_bad) { tr_bad = base + i; tr_rc = rc; tr_words = msg; }
-                    msg.clear(); verdict[base + i] = 0; continue;
-                }
-                if (rc != PLK_OK) { verdict[base + i] = PLK_VERDICT_MALFORMED; continue; }
-                if (!early) { verdict[base + i] = 0; continue; }
-                verdict[base + i] = 0xff;                             // goes to the device
-                memcpy(&all_pts[i * VM_PROOF_PTS], &pts[11], VM_PROOF_PTS * sizeof(plk_g1_affine));
-                memcpy(&all_sc[i * VERIFY_TERMS], sc, sizeof sc);
-            }
-        }, front_threads);
-        if (tr_rc != PLK_OK) { set_error("plk_verify_many_with: proof " + std::to_string(tr_bad) + ": " + tr_words); return tr_rc; }
-        live.clear();
-        for (uint64_t i = 0; i < cnt; i++) if (verdict[base + i] == 0xff) live.push_back(i);
-        const uint32_t m = (uint32_t)live.size();
-        h_pts.resize((size_t)m * VM_PROOF_PTS); h_sc.resize((size_t)m * VERIFY_TERMS); h_v.resize(m);
-        for (uint32_t k = 0; k < m; k++) {
-            memcpy(&h_pts[(size_t)k * VM_PROOF_PTS], &all_pts[live[k] * VM_PROOF_PTS], VM_PROOF_PTS * sizeof(plk_g1_affine));
-            memcpy(&h_sc[(size_t)k * VERIFY_TERMS], &all_sc[live[k] * VERIFY_TERMS], VERIFY_TERMS * sizeof(plk_fr));
-        }
-        ms[0] += std::chrono::duration<float, std::milli>(clk::now() - t0).count();
-        if (!m) continue;
-        // device: the staging arena holds points | scalars | products | sums | affine pairs | verdict bytes, every part 16-byte aligned
-        const size_t b_pts = (size_t)m * VM_PROOF_PTS * sizeof(G1Affine), b_sc = (size_t)m * VERIFY_TERMS * sizeof(Fr), b_prod = (size_t)m * VERIFY_TERMS * sizeof(XyzzW),
-                     b_sum = (size_t)m * 2 * sizeof(G1Xyzz), b_aff = (size_t)m * 2 * sizeof(G1Affine), b_v = ((size_t)m + 15) & ~(size_t)15;
-        PLK_TRY(ctx->stage.reserve(b_pts + b_sc + b_prod + b_sum + b_aff + b_v));
-        char *d = ctx->stage.as<char>();
-        G1Affine *d_pts = reinterpret_cast<G1Affine *>(d);
-        Fr *d_sc = reinterpret_cast<Fr *>(d + b_pts);
-        XyzzW *d_prod = reinterpret_cast<XyzzW *>(d + b_pts + b_sc);
-        G1Xyzz *d_sum = reinterpret_cast<G1Xyzz *>(d + b_pts + b_sc + b_prod);
-        G1Affine *d_aff = reinterpret_cast<G1Affine *>(d + b_pts + b_sc + b_prod + b_sum);
-        uint8_t *d_v = reinterpret_cast<uint8_t *>(d + b_pts + b_sc + b_prod + b_sum + b_aff);
-        const G1Affine *d_fixed = reinterpret_cast<const G1Affine *>(reinterpret_cast<const char *>(vk->dev) + vk->fixed_off);
-        PLK_TRY(mark(0));
-        PLK_HIP(hipMemcpyAsync(d_pts, h_pts.data(), b_pts, hipMemcpyHostToDevice, st));
-        PLK_HIP(hipMemcpyAsync(d_sc, h_sc.data(), b_sc, hipMemcpyHostToDevice, st));
-        PLK_TRY(mark(1));
-        const uint32_t lanes = m * (uint32_t)VERIFY_TERMS;
-        hipLaunchKernelGGL(vm_mul_kernel, dim3((lanes + G1NTT_THREADS - 1) / G1NTT_THREADS), dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, d_prod, d_fixed, (const G1Affine *)d_pts,
-                           (const Fr *)d_sc, m);
-        PLK_HIP(hipGetLastError());
-        PLK_TRY(mark(2));
-        hipLaunchKernelGGL(vm_sum_kernel, dim3((2 * m + 255) / 256), dim3(256), 0, st, d_sum, (const XyzzW *)d_prod, m);
-        hipLaunchKernelGGL(vm_affine_kernel, dim3(((2 * m + VM_NORM_K - 1) / VM_NORM_K + 255) / 256), dim3(256), 0, st, d_aff, (const G1Xyzz *)d_sum, 2 * m);
-        PLK_HIP(hipGetLastError());
-        PLK_TRY(mark(3));
-        PLK_TRY(pairing_launch(d_v, d_aff, d_aff + 1, 2, m, vk->dev, st));
-        PLK_TRY(mark(4));
-        PLK_HIP(hipMemcpyAsync(h_v.data(), d_v, m, hipMemcpyDeviceToHost, st));
-        PLK_TRY(mark(5));
-        PLK_HIP(hipStreamSynchronize(st));
-        for (uint32_t k = 0; k < m; k++) verdict[base + live[k]] = h_v[k];
-        if (timed) for (int k = 0; k < 5; k++) { float t = 0; PLK_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1])); ms[k + 1] += t; }
-    }
-    if (timed) { memcpy(ctx->vm_ms, ms, sizeof ms); ctx->vm_ms_valid = true; }
-    return PLK_OK;
-}
-
-static int32_t verify_many_entry(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, const plk_transcript_ops *ops,
-                                 uint8_t *verdict, uint64_t *first_bad) {
-    if (!ctx || !vk || !verdict || !first_bad || (count && (!proofs || !lens))) { set_error("plk_verify_many: null argument"); return PLK_ERR_ARG; }
-    for (uint64_t i = 0; i < count; i++) if (!proofs[i]) { set_error("plk_verify_many: null argument"); return PLK_ERR_ARG; }
-    if (vk->device != ctx->device) { set_error("plk_verify_many: the verification key was loaded on another device"); return PLK_ERR_ARG; }
-    if (ctx->msm_enq != ctx->msm_fin) { set_error("plk_verify_many: a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
-    *first_bad = UINT64_MAX;
-    if (count == 0) return PLK_OK;
-    PLK_HIP(hipSetDevice(ctx->device));
-    int32_t rc = PLK_ERR_HIP;
-    try { rc = verify_many_impl(ctx, vk, proofs, lens, count, verdict, ops); }
-    catch (const std::exception &e) { set_error(std::string("plk_verify_many: ") + e.what()); return PLK_ERR_ARG; }
-    if (rc != PLK_OK) return rc;
-    for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
-    return PLK_OK;
-}
-
-extern "C" int32_t plk_verify_many(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict, uint64_t *first_bad) {
-    return verify_many_entry(ctx, vk, proofs, lens, count, nullptr, verdict, first_bad);
-}
-
-// plk_verify_many with the host front end under the caller's transcript (verifier::verify::<_, _, T>, src/plonk.rs:198-204, per proof)
-extern "C" int32_t plk_verify_many_with(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count,
-                                        const plk_transcript_ops *ops, uint8_t *verdict, uint64_t *first_bad) {
-    if (!ops) return verify_many_entry(ctx, vk, proofs, lens, count, nullptr, verdict, first_bad);
-    if (!transcript_ops_complete(ops)) { set_error("plk_verify_many_with: the transcript table has a null callback"); return PLK_ERR_ARG; }
-    if (ops->flags & ~(uint32_t)PLK_TRANSCRIPT_CONCURRENT) { set_error("plk_verify_many_with: unknown flag in the transcript table"); return PLK_ERR_ARG; }
-    const plk_transcript_ops table = *ops;
-    return verify_many_entry(ctx, vk, proofs, lens, count, &table, verdict, first_bad);
-}
-
-// ---- the front end on the device: proofs as raw bytes, packed back to back
-// One pass of cnt <= VM_CHUNK proofs whose bytes and offsets are on the device: the front kernel, then the kernels of plk_verify_many over ALL
-// cnt proofs (a settled proof is 25 zero terms: its sums are the identity), then the verdicts settled from the state bytes into `out`.
-struct VmArena {
-    G1Affine *pts; Fr *sc; XyzzW *prod; G1Xyzz *sum; G1Affine *aff; uint8_t *v, *state; char *tail;
-    static size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-    static size_t bytes(size_t m) {
-        return m * VM_PROOF_PTS * sizeof(G1Affine) + m * VERIFY_TERMS * sizeof(Fr) + m * VERIFY_TERMS * sizeof(XyzzW) + m * 2 * sizeof(G1Xyzz) + m * 2 * sizeof(G1Affine) + 2 * pad16(m);
-    }
-    VmArena(char *d, size_t m) {
-        pts = reinterpret_cast<G1Affine *>(d); d += m * VM_PROOF_PTS * sizeof(G1Affine);
-        sc = reinterpret_cast<Fr *>(d); d += m * VERIFY_TERMS * sizeof(Fr);
-        prod = reinterpret_cast<XyzzW *>(d); d += m * VERIFY_TERMS * sizeof(XyzzW);
-        sum = reinterpret_cast<G1Xyzz *>(d); d += m * 2 * sizeof(G1Xyzz);
-        aff = reinterpret_cast<G1Affine *>(d); d += m * 2 * sizeof(G1Affine);
-        v = reinterpret_cast<uint8_t *>(d); d += pad16(m);
-        state = reinterpret_cast<uint8_t *>(d); d += pad16(m);
-        tail = d;
-    }
-};
-
-template <class Mark>
-static int32_t vm_pass_from_bytes(const plk_vk *vk, const VmArena &A, const uint8_t *d_blob, uint64_t blob_len, const uint64_t *d_off, uint64_t bias, uint32_t cnt,
-                                  uint8_t *d_out, hipStream_t st, Mark mark) {
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set) {
-        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vm_mul_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
-        attr_set = true;
-    }
-    const G1Affine *d_fixed = reinterpret_cast<const G1Affine *>(reinterpret_cast<const char *>(vk->dev) + vk->fixed_off);
-    const FrontVk *d_front = reinterpret_cast<const FrontVk *>(reinterpret_cast<const char *>(vk->dev) + vk->front_off);
-    PLK_TRY(front_launch(A.pts, A.sc, A.state, d_blob, blob_len, d_off, bias, cnt, d_front, d_fixed, false, st));
-    PLK_TRY(mark(2));
-    const uint32_t lanes = cnt * (uint32_t)VERIFY_TERMS;
-    hipLaunchKernelGGL(vm_mul_kernel, dim3((lanes + G1NTT_THREADS - 1) / G1NTT_THREADS), dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, A.prod, d_fixed, (const G1Affine *)A.pts,
-                       (const Fr *)A.sc, cnt);
-    PLK_HIP(hipGetLastError());
-    PLK_TRY(mark(3));
-    hipLaunchKernelGGL(vm_sum_kernel, dim3((2 * cnt + 255) / 256), dim3(256), 0, st, A.sum, (const XyzzW *)A.prod, cnt);
-    hipLaunchKernelGGL(vm_affine_kernel, dim3(((2 * cnt + VM_NORM_K - 1) / VM_NORM_K + 255) / 256), dim3(256), 0, st, A.aff, (const G1Xyzz *)A.sum, 2 * cnt);
-    PLK_HIP(hipGetLastError());
-    PLK_TRY(mark(4));
-    PLK_TRY(pairing_launch(A.v, A.aff, A.aff + 1, 2, cnt, vk->dev, st));
-    PLK_TRY(settle_launch(d_out, A.v, A.state, cnt, st));
-    return mark(5);
-}
-
-static int32_t verify_packed_impl(plk_ctx *ctx, const plk_vk *vk, const uint8_t *blob, const uint64_t *off, uint64_t count, uint8_t *verdict) {
-    const bool timed = ctx->ev_on;
-    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 7; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
-    ctx->vm_ms_valid = false;
-    float ms[6] = {0, 0, 0, 0, 0, 0};
-    hipStream_t st = ctx->stream;
-    if (timed) for (int k = 0; k < 7; k++) PLK_HIP(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], st)); return PLK_OK; };
-    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
-        const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
-        const uint64_t lo = off[base], bytes = off[base + cnt] - lo;
-        // the arena of plk_verify_many, then the state bytes, the pass's cnt + 1 offsets and its raw bytes
-        const size_t b_off = VmArena::pad16(((size_t)cnt + 1) * sizeof(uint64_t));
-        PLK_TRY(ctx->stage.reserve(VmArena::bytes(cnt) + b_off + VmArena::pad16(bytes)));
-        const VmArena A(ctx->stage.as<char>(), cnt);
-        uint64_t *d_off = reinterpret_cast<uint64_t *>(A.tail);
-        uint8_t *d_blob = reinterpret_cast<uint8_t *>(A.tail + b_off);
-        PLK_TRY(mark(0));
-        PLK_HIP(hipMemcpyAsync(d_off, off + base, ((size_t)cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        if (bytes) PLK_HIP(hipMemcpyAsync(d_blob, blob + lo, bytes, hipMemcpyHostToDevice, st));
-        PLK_TRY(mark(1));
-        PLK_TRY(vm_pass_from_bytes(vk, A, d_blob, bytes, d_off, lo, cnt, A.v, st, mark));
-        PLK_HIP(hipMemcpyAsync(verdict + base, A.v, cnt, hipMemcpyDeviceToHost, st));
-        PLK_TRY(mark(6));
-        PLK_HIP(hipStreamSynchronize(st));
-        if (timed) {
-            static const int slot[6] = {1, 0, 2, 3, 4, 5};            // upload, front kernel, mul, sum + affine, pairing + settle, download
-            for (int k = 0; k < 6; k++) { float t = 0; PLK_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1])); ms[slot[k]] += t; }
-        }
-    }
-    if (timed) { memcpy(ctx->vm_ms, ms, sizeof ms); ctx->vm_ms_valid = true; }
-    return PLK_OK;
-}
-
-// the refusals the three calls share with plk_verify_many
-static int32_t vm_bytes_guard(const char *who, plk_ctx *ctx, const plk_vk *vk) {
-    if (vk->device != ctx->device) { set_error(std::string(who) + ": the verification key was loaded on another device"); return PLK_ERR_ARG; }
-    if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
-    return PLK_OK;
-}
-
-static int32_t verify_many_packed_body(plk_ctx *ctx, const plk_vk *vk, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, uint64_t count, uint8_t *verdict,
-                                          uint64_t *first_bad) {
-    if (!ctx || !vk || !verdict || !first_bad || (count && !off) || (blob_len && !blob)) { set_error("plk_verify_many_packed: null argument"); return PLK_ERR_ARG; }
-    PLK_TRY(vm_bytes_guard("plk_verify_many_packed", ctx, vk));
-    for (uint64_t i = 0; i < count; i++)
-        if (off[i] > off[i + 1] || off[i + 1] > blob_len) { set_error("plk_verify_many_packed: offsets decrease or reach past the blob"); return PLK_ERR_ARG; }
-    *first_bad = UINT64_MAX;
-    if (count == 0) return PLK_OK;
-    PLK_HIP(hipSetDevice(ctx->device));
-    PLK_TRY(verify_packed_impl(ctx, vk, blob, off, count, verdict));
-    for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
-    return PLK_OK;
-}
-
-extern "C" int32_t plk_verify_many_packed(plk_ctx *ctx, const plk_vk *vk, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, uint64_t count, uint8_t *verdict,
-                                          uint64_t *first_bad) {
-    try { return verify_many_packed_body(ctx, vk, blob, blob_len, off, count, verdict, first_bad); }   // no C++ exception crosses the C ABI, as plk_verify_many
-    catch (const std::exception &e) { set_error(std::string("plk_verify_many_packed: ") + e.what()); return PLK_ERR_ARG; }
-}
-
-static int32_t verify_many_dev_body(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *verdict_dev,
-                                       void *stream) {
-    if (!ctx || !vk || (count && (!off_dev || !verdict_dev)) || (blob_len && !blob_dev)) { set_error("plk_verify_many_dev: null argument"); return PLK_ERR_ARG; }
-    if ((uintptr_t)off_dev & 7) { set_error("plk_verify_many_dev: the offset table must be 8-byte aligned"); return PLK_ERR_ARG; }
-    PLK_TRY(vm_bytes_guard("plk_verify_many_dev", ctx, vk));
-    if (count == 0) return PLK_OK;
-    PLK_HIP(hipSetDevice(ctx->device));
-    ctx->vm_ms_valid = false;
-    // This call returns without waiting, so it keeps out of the staging arena, whose users each rely on the earlier ones having waited (and
-    // some write it on a stream of the caller's choice).  Its working memory is vm_stage, which only kernels on the context's stream touch:
-    // they run there after what the caller's stream holds now, the caller's stream goes on after them, and a second call queues behind the
-    // first.  Growing vm_stage frees the old block, which waits for the device.
-    hipStream_t st = ctx->stream, caller = stream ? (hipStream_t)stream : ctx->stream;
-    PLK_TRY(ctx->vm_stage.reserve(VmArena::bytes(count < VM_CHUNK ? (size_t)count : (size_t)VM_CHUNK)));
-    if (caller != st) {
-        if (!ctx->vm_in) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_in, hipEventDisableTiming));
-        if (!ctx->vm_done) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_done, hipEventDisableTiming));
-        PLK_HIP(hipEventRecord(ctx->vm_in, caller));
-        PLK_HIP(hipStreamWaitEvent(st, ctx->vm_in, 0));
-    }
-    auto mark = [](int) -> int32_t { return PLK_OK; };
-    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
-        const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
-        const VmArena A(ctx->vm_stage.as<char>(), cnt);
-        PLK_TRY(vm_pass_from_bytes(vk, A, reinterpret_cast<const uint8_t *>(blob_dev), blob_len, reinterpret_cast<const uint64_t *>(off_dev) + base, 0, cnt,
-                                   reinterpret_cast<uint8_t *>(verdict_dev) + base, st, mark));
-    }
-    if (caller != st) {
-        PLK_HIP(hipEventRecord(ctx->vm_done, st));
-        PLK_HIP(hipStreamWaitEvent(caller, ctx->vm_done, 0));
-    }
-    return PLK_OK;
-}
-
-extern "C" int32_t plk_verify_many_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *verdict_dev,
-                                       void *stream) {
-    try { return verify_many_dev_body(ctx, vk, blob_dev, blob_len, off_dev, count, verdict_dev, stream); }   // no C++ exception crosses the C ABI, as plk_verify_many
-    catch (const std::exception &e) { set_error(std::string("plk_verify_many_dev: ") + e.what()); return PLK_ERR_ARG; }
-}
-
-static int32_t verify_front_dev_body(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *points_dev,
-                                        void *scalars_dev, void *state_dev, void *stream) {
-    if (!ctx || !vk || (count && (!off_dev || !points_dev || !scalars_dev || !state_dev)) || (blob_len && !blob_dev)) { set_error("plk_verify_front_dev: null argument"); return PLK_ERR_ARG; }
-    if (((uintptr_t)off_dev & 7) || (((uintptr_t)points_dev | (uintptr_t)scalars_dev) & 15)) { set_error("plk_verify_front_dev: points and scalars must be 16-byte aligned, offsets 8-byte aligned"); return PLK_ERR_ARG; }
-    if (count > (1ull << 26)) { set_error("plk_verify_front_dev: more than 2^26 proofs"); return PLK_ERR_SIZE; }
-    PLK_TRY(vm_bytes_guard("plk_verify_front_dev", ctx, vk));
-    if (count == 0) return PLK_OK;
-    PLK_HIP(hipSetDevice(ctx->device));
-    const G1Affine *d_fixed = reinterpret_cast<const G1Affine *>(reinterpret_cast<const char *>(vk->dev) + vk->fixed_off);
-    const FrontVk *d_front = reinterpret_cast<const FrontVk *>(reinterpret_cast<const char *>(vk->dev) + vk->front_off);
-    return front_launch(reinterpret_cast<G1Affine *>(points_dev), reinterpret_cast<Fr *>(scalars_dev), reinterpret_cast<uint8_t *>(state_dev),
-                        reinterpret_cast<const uint8_t *>(blob_dev), blob_len, reinterpret_cast<const uint64_t *>(off_dev), 0, (uint32_t)count, d_front, d_fixed, true,
-                        stream ? (hipStream_t)stream : ctx->stream);
-}
-
-extern "C" int32_t plk_verify_front_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *points_dev,
-                                        void *scalars_dev, void *state_dev, void *stream) {
-    try { return verify_front_dev_body(ctx, vk, blob_dev, blob_len, off_dev, count, points_dev, scalars_dev, state_dev, stream); }   // no C++ exception crosses the C ABI, as plk_verify_many
-    catch (const std::exception &e) { set_error(std::string("plk_verify_front_dev: ") + e.what()); return PLK_ERR_ARG; }
-}
-
-extern "C" int32_t plk_verify_many_last_ms(plk_ctx *ctx, float out_ms[6]) {
-    if (!ctx || !out_ms) { set_error("plk_verify_many_last_ms: null argument"); return PLK_ERR_ARG; }
-    if (!ctx->vm_ms_valid) { set_error("plk_verify_many_last_ms: no timed plk_verify_many on this context (plk_set_kernel_timing)"); return PLK_ERR_ARG; }
-    for (int k = 0; k < 6; k++) out_ms[k] = ctx->vm_ms[k];
-    return PLK_OK;
-}
-
-// ---- a mixed batch: proofs of several verification keys in one pass (plk_vkset_create, plk_verify_mixed, _packed, _dev).
-// NO COUNTERPART IN THE REFERENCE.  Verdict i is what plk_verify_ex says about proof i under key key_of[i]: the calls above with the key taken
-// per proof.  The front kernel, the scalar multiplications and (when the set holds more than one G2 pair) the pairing kernel go through
+// ---- a key set for a mixed batch: proofs of several verification keys in one pass (plk_vkset_create, plk_verify_mixed, _packed, _dev).
+// NO COUNTERPART IN THE REFERENCE.  Verdict i is what plk_verify_ex says about proof i under key key_of[i]: the single-key calls with the key
+// taken per proof.  The front kernel, the scalar multiplications and (when the set holds more than one G2 pair) the pairing kernel go through
 // vkset_lookup; the sums, XYZZ -> affine and the settling are the kernels above, unchanged.
 static_assert(VKSET_MAX_KEYS == PLK_VKSET_MAX_KEYS, "vkset_plan.h restates the header's bound");
 
@@ -644,61 +342,137 @@ static int32_t vkset_create_body(plk_ctx *ctx, const plk_vk *const *keys, uint32
 }
 
 extern "C" int32_t plk_vkset_create(plk_ctx *ctx, const plk_vk *const *keys, uint32_t n_keys, plk_vkset **out) {
-    try { return vkset_create_body(ctx, keys, n_keys, out); }        // no C++ exception crosses the C ABI, as plk_verify_many
-    catch (const std::exception &e) { set_error(std::string("plk_vkset_create: ") + e.what()); return PLK_ERR_ARG; }
+    return guarded("plk_vkset_create", PLK_ERR_ARG, [&] { return vkset_create_body(ctx, keys, n_keys, out); });
 }
 
-// the refusals the three calls share, as vm_bytes_guard
-static int32_t vm_mixed_guard(const char *who, plk_ctx *ctx, const plk_vkset *set) {
-    if (set->device != ctx->device) { set_error(std::string(who) + ": the key set was made on another device"); return PLK_ERR_ARG; }
-    if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
-    return PLK_OK;
-}
+// ---- the working memory of a pass: the layout of vm_arena.h over a block of the device
+static_assert(VM_ARENA_PTS == VM_PROOF_PTS && VM_ARENA_TERMS == VERIFY_TERMS, "vm_arena.h restates the counts");
+static_assert(sizeof(G1Affine) == VM_AFFINE_BYTES && sizeof(Fr) == VM_FR_BYTES && sizeof(XyzzW) == VM_XYZZW_BYTES && sizeof(G1Xyzz) == VM_XYZZ_BYTES, "vm_arena.h sizes the parts");
 
-static int32_t vm_mixed_indices(const char *who, const plk_vkset *set, const uint32_t *key_of, uint64_t count) {
-    uint64_t bad = 0;
-    if (vkset_indices_ok(key_of, count, set->layout.n_keys, &bad)) return PLK_OK;
-    set_error(std::string(who) + ": key_of[" + std::to_string(bad) + "] = " + std::to_string(key_of[bad]) + " but the set holds " + std::to_string(set->layout.n_keys) + " keys");
-    return PLK_ERR_ARG;
-}
-
-// m proofs whose points, scalars and key indices are on the device: products, sums, affine pairs and the pairing verdicts into v.
-// mark(k) after the multiplications, mark(k + 1) after the sums and the normalisation.
-template <class Mark>
-static int32_t vm_mixed_group(const plk_vkset *set, XyzzW *prod, const G1Affine *pts, const Fr *sc, G1Xyzz *sum, G1Affine *aff, uint8_t *v, const uint32_t *d_key, uint32_t m,
-                              hipStream_t st, Mark mark, int k) {
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set) {
-        PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vm_mul_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
-        attr_set = true;
+struct VmArena {
+    G1Affine *pts; Fr *sc; XyzzW *prod; G1Xyzz *sum; G1Affine *aff; uint8_t *v, *state; uint32_t *keys; uint64_t *off; uint8_t *blob;
+    VmArena(const DevBuf &buf, const VmLayout &L) {
+        char *d = buf.as<char>();
+        pts = reinterpret_cast<G1Affine *>(d + L.pts); sc = reinterpret_cast<Fr *>(d + L.sc); prod = reinterpret_cast<XyzzW *>(d + L.prod);
+        sum = reinterpret_cast<G1Xyzz *>(d + L.sum); aff = reinterpret_cast<G1Affine *>(d + L.aff);
+        v = reinterpret_cast<uint8_t *>(d + L.v); state = reinterpret_cast<uint8_t *>(d + L.state);
+        keys = reinterpret_cast<uint32_t *>(d + L.keys); off = reinterpret_cast<uint64_t *>(d + L.off); blob = reinterpret_cast<uint8_t *>(d + L.blob);
     }
-    const uint32_t lanes = m * (uint32_t)VERIFY_TERMS;
-    hipLaunchKernelGGL(vm_mul_mixed_kernel, dim3((lanes + G1NTT_THREADS - 1) / G1NTT_THREADS), dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, prod, set->view, d_key, pts, sc, m);
-    PLK_HIP(hipGetLastError());
-    PLK_TRY(mark(k));
-    hipLaunchKernelGGL(vm_sum_kernel, dim3((2 * m + 255) / 256), dim3(256), 0, st, sum, (const XyzzW *)prod, m);
-    hipLaunchKernelGGL(vm_affine_kernel, dim3(((2 * m + VM_NORM_K - 1) / VM_NORM_K + 255) / 256), dim3(256), 0, st, aff, (const G1Xyzz *)sum, 2 * m);
-    PLK_HIP(hipGetLastError());
-    PLK_TRY(mark(k + 1));
+};
+
+// where a pass whose front end runs on the device finds its proofs: proof i is blob[off[i] - bias, off[i + 1] - bias), blob_len bytes in all
+struct VmRaw { const uint8_t *blob; uint64_t blob_len; const uint64_t *off; uint64_t bias; };
+
+// ---- whose proofs these are: one key, or a key set with a key index per proof.  What differs between plk_verify_many* and plk_verify_mixed*
+// is answered here; the pass and the three drivers below serve both.
+struct VmKeys {
+    const plk_vk *vk = nullptr;
+    const plk_vkset *set = nullptr;
+    const uint32_t *key_of = nullptr;                              // a set: the key index per proof, in host memory (blocking calls) or on the device (_dev)
+    explicit VmKeys(const plk_vk *k) : vk(k) {}
+    VmKeys(const plk_vkset *s, const uint32_t *ko) : set(s), key_of(ko) {}
+    bool missing(uint64_t count) const { return set ? count && !key_of : !vk; }
+    int device() const { return set ? set->device : vk->device; }
+    const ParsedVk *parsed(uint64_t i) const { return set ? set->parsed[key_of[i]] : vk->parsed; }   // host front end, key_of on the host
+    uint32_t flags(uint64_t i) const { return set ? set->flags[key_of[i]] : vk->flags; }
+    const G1Affine *fixed() const { return reinterpret_cast<const G1Affine *>(reinterpret_cast<const char *>(vk->dev) + vk->fixed_off); }
+    const FrontVk *front_vk() const { return reinterpret_cast<const FrontVk *>(reinterpret_cast<const char *>(vk->dev) + vk->front_off); }
+
+    // the refusals every call shares
+    int32_t guard(const char *who, const plk_ctx *ctx) const {
+        if (device() != ctx->device) {
+            set_error(std::string(who) + (set ? ": the key set was made on another device" : ": the verification key was loaded on another device"));
+            return PLK_ERR_ARG;
+        }
+        if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
+        return PLK_OK;
+    }
+    // key_of on the host: every index names a key of the set
+    int32_t indices_ok(const char *who, uint64_t count) const {
+        uint64_t bad = 0;
+        if (!set || vkset_indices_ok(key_of, count, set->layout.n_keys, &bad)) return PLK_OK;
+        set_error(std::string(who) + ": key_of[" + std::to_string(bad) + "] = " + std::to_string(key_of[bad]) + " but the set holds " + std::to_string(set->layout.n_keys) + " keys");
+        return PLK_ERR_ARG;
+    }
+
+    // the three keyed steps of a pass over m proofs; d_key: the pass's key indices on the device (a set only)
+    int32_t front(const VmArena &A, const VmRaw &R, const uint32_t *d_key, uint32_t m, hipStream_t st) const {
+        if (set) return front_mixed_launch(A.pts, A.sc, A.state, R.blob, R.blob_len, R.off, R.bias, m, set->view, d_key, st);
+        return front_launch(A.pts, A.sc, A.state, R.blob, R.blob_len, R.off, R.bias, m, front_vk(), fixed(), false, st);
+    }
+    int32_t mul(const VmArena &A, const uint32_t *d_key, uint32_t m, hipStream_t st) const {
+        static std::atomic<bool> attr_set{false};
+        if (!attr_set) {
+            PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vm_mul_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
+            PLK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vm_mul_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G1NTT_LDS_ISO));
+            attr_set = true;
+        }
+        const dim3 grid((m * (uint32_t)VERIFY_TERMS + G1NTT_THREADS - 1) / G1NTT_THREADS), block(G1NTT_THREADS);
+        if (set) hipLaunchKernelGGL(vm_mul_mixed_kernel, grid, block, G1NTT_LDS_ISO, st, A.prod, set->view, d_key, (const G1Affine *)A.pts, (const Fr *)A.sc, m);
+        else hipLaunchKernelGGL(vm_mul_kernel, grid, block, G1NTT_LDS_ISO, st, A.prod, fixed(), (const G1Affine *)A.pts, (const Fr *)A.sc, m);
+        PLK_HIP(hipGetLastError());
+        return PLK_OK;
+    }
     // one G2 pair in the set (the common case: keys of one universal key): the single-key kernel, whose line loads are wave-uniform
-    if (set->layout.n_tables == 1) return pairing_launch(v, aff, aff + 1, 2, m, set->view.tables, st);
-    hipLaunchKernelGGL(vm_pairing_mixed_kernel, dim3((m + VM_PAIR_THREADS - 1) / VM_PAIR_THREADS), dim3(VM_PAIR_THREADS), 0, st, v, (const G1Affine *)aff,
-                       (const G1Affine *)(aff + 1), 2u, m, set->view, d_key);
+    int32_t pairing(const VmArena &A, const uint32_t *d_key, uint32_t m, hipStream_t st) const {
+        if (!set || set->layout.n_tables == 1) return pairing_launch(A.v, A.aff, A.aff + 1, 2, m, set ? (const void *)set->view.tables : vk->dev, st);
+        hipLaunchKernelGGL(vm_pairing_mixed_kernel, dim3((m + VM_PAIR_THREADS - 1) / VM_PAIR_THREADS), dim3(VM_PAIR_THREADS), 0, st, A.v, (const G1Affine *)A.aff,
+                           (const G1Affine *)(A.aff + 1), 2u, m, set->view, d_key);
+        PLK_HIP(hipGetLastError());
+        return PLK_OK;
+    }
+};
+
+// ---- one pass over the m proofs of arena A, enqueued on st: [the front kernel over R,] the scalar multiplications, the sums, XYZZ -> affine,
+// the pairing [, and the verdicts settled from the state bytes into d_out].  With R every proof of the pass goes through the kernels, a proof
+// the front end settled as 25 zero terms (its sums are the identity).  Without R the host front end has filled A.pts and A.sc with the proofs
+// that passed it, and the pairing verdicts stay in A.v.  Marks k .. k + 2, or k .. k + 3 with R, behind front | mul | sums, affine | the rest.
+using VmTimer = StageTimer<7>;
+
+static int32_t vm_pass(const VmKeys &K, const VmArena &A, const uint32_t *d_key, uint32_t m, const VmRaw *R, uint8_t *d_out, hipStream_t st, VmTimer &ev, int k) {
+    if (R) { PLK_TRY(K.front(A, *R, d_key, m, st)); PLK_TRY(ev.mark(k++, st)); }
+    PLK_TRY(K.mul(A, d_key, m, st));
+    PLK_TRY(ev.mark(k, st));
+    hipLaunchKernelGGL(vm_sum_kernel, dim3((2 * m + 255) / 256), dim3(256), 0, st, A.sum, (const XyzzW *)A.prod, m);
+    hipLaunchKernelGGL(vm_affine_kernel, dim3(((2 * m + VM_NORM_K - 1) / VM_NORM_K + 255) / 256), dim3(256), 0, st, A.aff, (const G1Xyzz *)A.sum, 2 * m);
     PLK_HIP(hipGetLastError());
+    PLK_TRY(ev.mark(k + 1, st));
+    PLK_TRY(K.pairing(A, d_key, m, st));
+    if (R) PLK_TRY(settle_launch(d_out, A.v, A.state, m, st));
+    return ev.mark(k + 2, st);
+}
+
+// plk_verify_many_last_ms: [0] host flattening, or the front kernel; [1] upload; [2] scalar multiplications; [3] sums and affine; [4] pairing
+// (with settle); [5] download.  A blocking pass marks 0 | upload | 1 | vm_pass from 2 | download | last: its times are added to ms here.
+static int32_t vm_add_times(VmTimer &ev, bool front_kernel, float ms[6]) {
+    if (!ev.on) return PLK_OK;
+    const int f = front_kernel ? 1 : 0;
+    float t = 0;
+    PLK_TRY(ev.elapsed(0, 1, &t)); ms[1] += t;
+    if (f) { PLK_TRY(ev.elapsed(1, 2, &t)); ms[0] += t; }
+    for (int s = 2; s < 6; s++) { PLK_TRY(ev.elapsed(s - 1 + f, s + f, &t)); ms[s] += t; }
     return PLK_OK;
 }
 
-static int32_t verify_mixed_impl(plk_ctx *ctx, const plk_vkset *set, const uint8_t *const *proofs, const uint64_t *lens, const uint32_t *key_of, uint64_t count,
-                                 uint8_t *verdict) {
+static void vm_times_done(plk_ctx *ctx, const VmTimer &ev, const float ms[6]) {
+    if (ev.on) { memcpy(ctx->vm_ms, ms, 6 * sizeof(float)); ctx->vm_ms_valid = true; }
+}
+
+static void vm_first_bad(const uint8_t *verdict, uint64_t count, uint64_t *first_bad) {
+    for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
+}
+
+// ---- driver 1, the host front end (plk_verify_many, _with, plk_verify_mixed).  Per chunk, on up to 16 threads: every proof through
+// plk_verify_terms's code under its own key; the survivors are packed in index order (with their keys) and go through a pass.
+// ops: the caller's transcript (plk_verify_many_with), null for Keccak.  Without PLK_TRANSCRIPT_CONCURRENT the front end then stays on the
+// calling thread, one proof after the other, and the lowest proof that met a failure of the transcript ends the call.
+static int32_t vm_run_host(plk_ctx *ctx, const VmKeys &K, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict, const plk_transcript_ops *ops) {
     using clk = std::chrono::steady_clock;
-    const bool timed = ctx->ev_on;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 6; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+    VmTimer ev;
     ctx->vm_ms_valid = false;
     float ms[6] = {0, 0, 0, 0, 0, 0};
     hipStream_t st = ctx->stream;
-    if (timed) for (int k = 0; k < 6; k++) PLK_HIP(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], st)); return PLK_OK; };
+    PLK_TRY(ev.start(ctx));
     std::vector<plk_g1_affine> h_pts;
     std::vector<plk_fr> h_sc;
     std::vector<uint64_t> live;
@@ -706,24 +480,34 @@ static int32_t verify_mixed_impl(plk_ctx *ctx, const plk_vkset *set, const uint8
     std::vector<uint8_t> h_v;
     for (uint64_t base = 0; base < count; base += VM_CHUNK) {
         const uint64_t cnt = count - base < VM_CHUNK ? count - base : VM_CHUNK;
-        // host: every proof of the chunk through plk_verify_terms's code under its own key; the survivors are packed in index order with their keys
         const auto t0 = clk::now();
         std::vector<plk_g1_affine> all_pts((size_t)cnt * VM_PROOF_PTS);
         std::vector<plk_fr> all_sc((size_t)cnt * VERIFY_TERMS);
+        const unsigned front_threads = ops && !(ops->flags & PLK_TRANSCRIPT_CONCURRENT) ? 1 : 16;
+        std::mutex tr_mu;
+        uint64_t tr_bad = UINT64_MAX; int32_t tr_rc = PLK_OK; std::string tr_words;
         parallel_for((size_t)cnt, 1, [&](size_t lo, size_t hi) {
             plk_g1_affine pts[VERIFY_TERMS]; plk_fr sc[VERIFY_TERMS];
+            std::string msg;
             for (size_t i = lo; i < hi; i++) {
                 int32_t early = 0;
-                const uint32_t key = key_of[base + i];
-                const int32_t rc = verify_terms_parsed(set->parsed[key], proofs[base + i], lens[base + i], set->flags[key], pts, sc, &early);
+                if (front_threads == 1 && tr_rc != PLK_OK) break;      // (one thread: nothing else writes tr_rc) no further begin after a failure
+                const int32_t rc = verify_terms_parsed(K.parsed(base + i), proofs[base + i], lens[base + i], K.flags(base + i), pts, sc, &early, ops, &msg);
+                if (rc != PLK_OK && !msg.empty()) {
+                    std::lock_guard<std::mutex> g(tr_mu);
+                    if (base + i < tr_bad) { tr_bad = base + i; tr_rc = rc; tr_words = msg; }
+                    msg.clear(); verdict[base + i] = 0; continue;
+                }
                 if (rc != PLK_OK) { verdict[base + i] = PLK_VERDICT_MALFORMED; continue; }
                 if (!early) { verdict[base + i] = 0; continue; }
                 verdict[base + i] = 0xff;                             // goes to the device
                 memcpy(&all_pts[i * VM_PROOF_PTS], &pts[11], VM_PROOF_PTS * sizeof(plk_g1_affine));
                 memcpy(&all_sc[i * VERIFY_TERMS], sc, sizeof sc);
             }
-        }, 16);
-        vkset_compact(verdict + base, key_of + base, cnt, &live, &live_key);
+        }, front_threads);
+        if (tr_rc != PLK_OK) { set_error("plk_verify_many_with: proof " + std::to_string(tr_bad) + ": " + tr_words); return tr_rc; }
+        if (K.set) vkset_compact(verdict + base, K.key_of + base, cnt, &live, &live_key);
+        else { live.clear(); for (uint64_t i = 0; i < cnt; i++) if (verdict[base + i] == 0xff) live.push_back(i); }
         const uint32_t m = (uint32_t)live.size();
         h_pts.resize((size_t)m * VM_PROOF_PTS); h_sc.resize((size_t)m * VERIFY_TERMS); h_v.resize(m);
         for (uint32_t k = 0; k < m; k++) {
@@ -732,154 +516,175 @@ static int32_t verify_mixed_impl(plk_ctx *ctx, const plk_vkset *set, const uint8
         }
         ms[0] += std::chrono::duration<float, std::milli>(clk::now() - t0).count();
         if (!m) continue;
-        // device: plk_verify_many's arena and, behind it, the survivors' key indices
-        const size_t b_pts = (size_t)m * VM_PROOF_PTS * sizeof(G1Affine), b_sc = (size_t)m * VERIFY_TERMS * sizeof(Fr), b_prod = (size_t)m * VERIFY_TERMS * sizeof(XyzzW),
-                     b_sum = (size_t)m * 2 * sizeof(G1Xyzz), b_aff = (size_t)m * 2 * sizeof(G1Affine), b_v = ((size_t)m + 15) & ~(size_t)15, b_key = (size_t)m * sizeof(uint32_t);
-        PLK_TRY(ctx->stage.reserve(b_pts + b_sc + b_prod + b_sum + b_aff + b_v + b_key));
-        char *d = ctx->stage.as<char>();
-        G1Affine *d_pts = reinterpret_cast<G1Affine *>(d);
-        Fr *d_sc = reinterpret_cast<Fr *>(d + b_pts);
-        XyzzW *d_prod = reinterpret_cast<XyzzW *>(d + b_pts + b_sc);
-        G1Xyzz *d_sum = reinterpret_cast<G1Xyzz *>(d + b_pts + b_sc + b_prod);
-        G1Affine *d_aff = reinterpret_cast<G1Affine *>(d + b_pts + b_sc + b_prod + b_sum);
-        uint8_t *d_v = reinterpret_cast<uint8_t *>(d + b_pts + b_sc + b_prod + b_sum + b_aff);
-        uint32_t *d_key = reinterpret_cast<uint32_t *>(d + b_pts + b_sc + b_prod + b_sum + b_aff + b_v);
-        PLK_TRY(mark(0));
-        PLK_HIP(hipMemcpyAsync(d_pts, h_pts.data(), b_pts, hipMemcpyHostToDevice, st));
-        PLK_HIP(hipMemcpyAsync(d_sc, h_sc.data(), b_sc, hipMemcpyHostToDevice, st));
-        PLK_HIP(hipMemcpyAsync(d_key, live_key.data(), b_key, hipMemcpyHostToDevice, st));
-        PLK_TRY(mark(1));
-        PLK_TRY(vm_mixed_group(set, d_prod, d_pts, d_sc, d_sum, d_aff, d_v, d_key, m, st, mark, 2));
-        PLK_TRY(mark(4));
-        PLK_HIP(hipMemcpyAsync(h_v.data(), d_v, m, hipMemcpyDeviceToHost, st));
-        PLK_TRY(mark(5));
+        const VmLayout L = vm_layout(m, K.set != nullptr, false, 0);
+        PLK_TRY(ctx->stage.reserve(L.bytes));
+        const VmArena A(ctx->stage, L);
+        PLK_TRY(ev.mark(0, st));
+        PLK_HIP(hipMemcpyAsync(A.pts, h_pts.data(), h_pts.size() * sizeof(plk_g1_affine), hipMemcpyHostToDevice, st));
+        PLK_HIP(hipMemcpyAsync(A.sc, h_sc.data(), h_sc.size() * sizeof(plk_fr), hipMemcpyHostToDevice, st));
+        if (K.set) PLK_HIP(hipMemcpyAsync(A.keys, live_key.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        PLK_TRY(ev.mark(1, st));
+        PLK_TRY(vm_pass(K, A, K.set ? A.keys : nullptr, m, nullptr, nullptr, st, ev, 2));
+        PLK_HIP(hipMemcpyAsync(h_v.data(), A.v, m, hipMemcpyDeviceToHost, st));
+        PLK_TRY(ev.mark(5, st));
         PLK_HIP(hipStreamSynchronize(st));
         for (uint32_t k = 0; k < m; k++) verdict[base + live[k]] = h_v[k];
-        if (timed) for (int k = 0; k < 5; k++) { float t = 0; PLK_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1])); ms[k + 1] += t; }
+        PLK_TRY(vm_add_times(ev, false, ms));
     }
-    if (timed) { memcpy(ctx->vm_ms, ms, sizeof ms); ctx->vm_ms_valid = true; }
+    vm_times_done(ctx, ev, ms);
     return PLK_OK;
+}
+
+static int32_t vm_call_host(const char *who, plk_ctx *ctx, const VmKeys &K, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, const plk_transcript_ops *ops,
+                            uint8_t *verdict, uint64_t *first_bad) {
+    return guarded(who, PLK_ERR_ARG, [&]() -> int32_t {
+        if (!ctx || K.missing(count) || !verdict || !first_bad || (count && (!proofs || !lens))) { set_error(std::string(who) + ": null argument"); return PLK_ERR_ARG; }
+        for (uint64_t i = 0; i < count; i++) if (!proofs[i]) { set_error(std::string(who) + ": null argument"); return PLK_ERR_ARG; }
+        PLK_TRY(K.guard(who, ctx));
+        PLK_TRY(K.indices_ok(who, count));
+        *first_bad = UINT64_MAX;
+        if (count == 0) return PLK_OK;
+        PLK_HIP(hipSetDevice(ctx->device));
+        PLK_TRY(vm_run_host(ctx, K, proofs, lens, count, verdict, ops));
+        vm_first_bad(verdict, count, first_bad);
+        return PLK_OK;
+    });
+}
+
+extern "C" int32_t plk_verify_many(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count, uint8_t *verdict, uint64_t *first_bad) {
+    return vm_call_host("plk_verify_many", ctx, VmKeys(vk), proofs, lens, count, nullptr, verdict, first_bad);
+}
+
+// plk_verify_many with the host front end under the caller's transcript (verifier::verify::<_, _, T>, src/plonk.rs:198-204, per proof)
+extern "C" int32_t plk_verify_many_with(plk_ctx *ctx, const plk_vk *vk, const uint8_t *const *proofs, const uint64_t *lens, uint64_t count,
+                                        const plk_transcript_ops *ops, uint8_t *verdict, uint64_t *first_bad) {
+    if (!ops) return plk_verify_many(ctx, vk, proofs, lens, count, verdict, first_bad);
+    if (!transcript_ops_complete(ops)) { set_error("plk_verify_many_with: the transcript table has a null callback"); return PLK_ERR_ARG; }
+    if (ops->flags & ~(uint32_t)PLK_TRANSCRIPT_CONCURRENT) { set_error("plk_verify_many_with: unknown flag in the transcript table"); return PLK_ERR_ARG; }
+    const plk_transcript_ops table = *ops;
+    return vm_call_host("plk_verify_many", ctx, VmKeys(vk), proofs, lens, count, &table, verdict, first_bad);
 }
 
 extern "C" int32_t plk_verify_mixed(plk_ctx *ctx, const plk_vkset *set, const uint8_t *const *proofs, const uint64_t *lens, const uint32_t *key_of, uint64_t count,
                                     uint8_t *verdict, uint64_t *first_bad) {
-    if (!ctx || !set || !verdict || !first_bad || (count && (!proofs || !lens || !key_of))) { set_error("plk_verify_mixed: null argument"); return PLK_ERR_ARG; }
-    for (uint64_t i = 0; i < count; i++) if (!proofs[i]) { set_error("plk_verify_mixed: null argument"); return PLK_ERR_ARG; }
-    PLK_TRY(vm_mixed_guard("plk_verify_mixed", ctx, set));
-    PLK_TRY(vm_mixed_indices("plk_verify_mixed", set, key_of, count));
-    *first_bad = UINT64_MAX;
-    if (count == 0) return PLK_OK;
-    PLK_HIP(hipSetDevice(ctx->device));
-    int32_t rc = PLK_ERR_HIP;
-    try { rc = verify_mixed_impl(ctx, set, proofs, lens, key_of, count, verdict); }
-    catch (const std::exception &e) { set_error(std::string("plk_verify_mixed: ") + e.what()); return PLK_ERR_ARG; }
-    if (rc != PLK_OK) return rc;
-    for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
-    return PLK_OK;
+    return vm_call_host("plk_verify_mixed", ctx, VmKeys(set, key_of), proofs, lens, count, nullptr, verdict, first_bad);
 }
 
-// vm_pass_from_bytes for a key set: d_key holds the pass's cnt key indices
-template <class Mark>
-static int32_t vm_mixed_pass_from_bytes(const plk_vkset *set, const VmArena &A, const uint8_t *d_blob, uint64_t blob_len, const uint64_t *d_off, uint64_t bias,
-                                        const uint32_t *d_key, uint32_t cnt, uint8_t *d_out, hipStream_t st, Mark mark) {
-    PLK_TRY(front_mixed_launch(A.pts, A.sc, A.state, d_blob, blob_len, d_off, bias, cnt, set->view, d_key, st));
-    PLK_TRY(mark(2));
-    PLK_TRY(vm_mixed_group(set, A.prod, A.pts, A.sc, A.sum, A.aff, A.v, d_key, cnt, st, mark, 3));
-    PLK_TRY(settle_launch(d_out, A.v, A.state, cnt, st));
-    return mark(5);
-}
-
-static int32_t verify_mixed_packed_impl(plk_ctx *ctx, const plk_vkset *set, const uint8_t *blob, const uint64_t *off, const uint32_t *key_of, uint64_t count, uint8_t *verdict) {
-    const bool timed = ctx->ev_on;
-    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 7; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+// ---- driver 2, packed bytes on the host (plk_verify_many_packed, plk_verify_mixed_packed): per chunk the offsets, the key indices and the raw
+// bytes go up, the pass runs its front end on the device, and the settled verdicts come down.
+static int32_t vm_run_packed(plk_ctx *ctx, const VmKeys &K, const uint8_t *blob, const uint64_t *off, uint64_t count, uint8_t *verdict) {
+    VmTimer ev;
     ctx->vm_ms_valid = false;
     float ms[6] = {0, 0, 0, 0, 0, 0};
     hipStream_t st = ctx->stream;
-    if (timed) for (int k = 0; k < 7; k++) PLK_HIP(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) -> int32_t { if (timed) PLK_HIP(hipEventRecord(ev[k], st)); return PLK_OK; };
+    PLK_TRY(ev.start(ctx));
     for (uint64_t base = 0; base < count; base += VM_CHUNK) {
         const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
         const uint64_t lo = off[base], bytes = off[base + cnt] - lo;
-        // the arena of plk_verify_many_packed with the pass's cnt key indices between the offsets and the raw bytes
-        const size_t b_off = VmArena::pad16(((size_t)cnt + 1) * sizeof(uint64_t)), b_key = VmArena::pad16((size_t)cnt * sizeof(uint32_t));
-        PLK_TRY(ctx->stage.reserve(VmArena::bytes(cnt) + b_off + b_key + VmArena::pad16(bytes)));
-        const VmArena A(ctx->stage.as<char>(), cnt);
-        uint64_t *d_off = reinterpret_cast<uint64_t *>(A.tail);
-        uint32_t *d_key = reinterpret_cast<uint32_t *>(A.tail + b_off);
-        uint8_t *d_blob = reinterpret_cast<uint8_t *>(A.tail + b_off + b_key);
-        PLK_TRY(mark(0));
-        PLK_HIP(hipMemcpyAsync(d_off, off + base, ((size_t)cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        PLK_HIP(hipMemcpyAsync(d_key, key_of + base, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if (bytes) PLK_HIP(hipMemcpyAsync(d_blob, blob + lo, bytes, hipMemcpyHostToDevice, st));
-        PLK_TRY(mark(1));
-        PLK_TRY(vm_mixed_pass_from_bytes(set, A, d_blob, bytes, d_off, lo, d_key, cnt, A.v, st, mark));
+        const VmLayout L = vm_layout(cnt, K.set != nullptr, true, bytes);
+        PLK_TRY(ctx->stage.reserve(L.bytes));
+        const VmArena A(ctx->stage, L);
+        PLK_TRY(ev.mark(0, st));
+        PLK_HIP(hipMemcpyAsync(A.off, off + base, ((size_t)cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (K.set) PLK_HIP(hipMemcpyAsync(A.keys, K.key_of + base, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (bytes) PLK_HIP(hipMemcpyAsync(A.blob, blob + lo, bytes, hipMemcpyHostToDevice, st));
+        PLK_TRY(ev.mark(1, st));
+        const VmRaw R{A.blob, bytes, A.off, lo};
+        PLK_TRY(vm_pass(K, A, K.set ? A.keys : nullptr, cnt, &R, A.v, st, ev, 2));
         PLK_HIP(hipMemcpyAsync(verdict + base, A.v, cnt, hipMemcpyDeviceToHost, st));
-        PLK_TRY(mark(6));
+        PLK_TRY(ev.mark(6, st));
         PLK_HIP(hipStreamSynchronize(st));
-        if (timed) {
-            static const int slot[6] = {1, 0, 2, 3, 4, 5};            // upload, front kernel, mul, sum + affine, pairing + settle, download
-            for (int k = 0; k < 6; k++) { float t = 0; PLK_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1])); ms[slot[k]] += t; }
-        }
+        PLK_TRY(vm_add_times(ev, true, ms));
     }
-    if (timed) { memcpy(ctx->vm_ms, ms, sizeof ms); ctx->vm_ms_valid = true; }
+    vm_times_done(ctx, ev, ms);
     return PLK_OK;
 }
 
-static int32_t verify_mixed_packed_body(plk_ctx *ctx, const plk_vkset *set, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, const uint32_t *key_of, uint64_t count,
-                                        uint8_t *verdict, uint64_t *first_bad) {
-    if (!ctx || !set || !verdict || !first_bad || (count && (!off || !key_of)) || (blob_len && !blob)) { set_error("plk_verify_mixed_packed: null argument"); return PLK_ERR_ARG; }
-    PLK_TRY(vm_mixed_guard("plk_verify_mixed_packed", ctx, set));
-    for (uint64_t i = 0; i < count; i++)
-        if (off[i] > off[i + 1] || off[i + 1] > blob_len) { set_error("plk_verify_mixed_packed: offsets decrease or reach past the blob"); return PLK_ERR_ARG; }
-    PLK_TRY(vm_mixed_indices("plk_verify_mixed_packed", set, key_of, count));
-    *first_bad = UINT64_MAX;
-    if (count == 0) return PLK_OK;
-    PLK_HIP(hipSetDevice(ctx->device));
-    PLK_TRY(verify_mixed_packed_impl(ctx, set, blob, off, key_of, count, verdict));
-    for (uint64_t i = 0; i < count; i++) if (verdict[i] != 1) { *first_bad = i; break; }
-    return PLK_OK;
+static int32_t vm_call_packed(const char *who, plk_ctx *ctx, const VmKeys &K, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, uint64_t count, uint8_t *verdict,
+                              uint64_t *first_bad) {
+    return guarded(who, PLK_ERR_ARG, [&]() -> int32_t {
+        if (!ctx || K.missing(count) || !verdict || !first_bad || (count && !off) || (blob_len && !blob)) { set_error(std::string(who) + ": null argument"); return PLK_ERR_ARG; }
+        PLK_TRY(K.guard(who, ctx));
+        for (uint64_t i = 0; i < count; i++)
+            if (off[i] > off[i + 1] || off[i + 1] > blob_len) { set_error(std::string(who) + ": offsets decrease or reach past the blob"); return PLK_ERR_ARG; }
+        PLK_TRY(K.indices_ok(who, count));
+        *first_bad = UINT64_MAX;
+        if (count == 0) return PLK_OK;
+        PLK_HIP(hipSetDevice(ctx->device));
+        PLK_TRY(vm_run_packed(ctx, K, blob, off, count, verdict));
+        vm_first_bad(verdict, count, first_bad);
+        return PLK_OK;
+    });
+}
+
+extern "C" int32_t plk_verify_many_packed(plk_ctx *ctx, const plk_vk *vk, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, uint64_t count, uint8_t *verdict,
+                                          uint64_t *first_bad) {
+    return vm_call_packed("plk_verify_many_packed", ctx, VmKeys(vk), blob, blob_len, off, count, verdict, first_bad);
 }
 
 extern "C" int32_t plk_verify_mixed_packed(plk_ctx *ctx, const plk_vkset *set, const uint8_t *blob, uint64_t blob_len, const uint64_t *off, const uint32_t *key_of,
                                            uint64_t count, uint8_t *verdict, uint64_t *first_bad) {
-    try { return verify_mixed_packed_body(ctx, set, blob, blob_len, off, key_of, count, verdict, first_bad); }   // no C++ exception crosses the C ABI, as plk_verify_many
-    catch (const std::exception &e) { set_error(std::string("plk_verify_mixed_packed: ") + e.what()); return PLK_ERR_ARG; }
+    return vm_call_packed("plk_verify_mixed_packed", ctx, VmKeys(set, key_of), blob, blob_len, off, count, verdict, first_bad);
 }
 
-static int32_t verify_mixed_dev_body(plk_ctx *ctx, const plk_vkset *set, const void *blob_dev, uint64_t blob_len, const void *off_dev, const void *key_of_dev, uint64_t count,
-                                     void *verdict_dev, void *stream) {
-    if (!ctx || !set || (count && (!off_dev || !key_of_dev || !verdict_dev)) || (blob_len && !blob_dev)) { set_error("plk_verify_mixed_dev: null argument"); return PLK_ERR_ARG; }
-    if (((uintptr_t)off_dev & 7) || ((uintptr_t)key_of_dev & 3)) { set_error("plk_verify_mixed_dev: the offset table must be 8-byte aligned, the key indices 4-byte aligned"); return PLK_ERR_ARG; }
-    PLK_TRY(vm_mixed_guard("plk_verify_mixed_dev", ctx, set));
-    if (count == 0) return PLK_OK;
-    PLK_HIP(hipSetDevice(ctx->device));
-    ctx->vm_ms_valid = false;
-    // memory and order exactly as plk_verify_many_dev: vm_stage, the context's stream, between the two events
-    hipStream_t st = ctx->stream, caller = stream ? (hipStream_t)stream : ctx->stream;
-    PLK_TRY(ctx->vm_stage.reserve(VmArena::bytes(count < VM_CHUNK ? (size_t)count : (size_t)VM_CHUNK)));
-    if (caller != st) {
-        if (!ctx->vm_in) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_in, hipEventDisableTiming));
-        if (!ctx->vm_done) PLK_HIP(hipEventCreateWithFlags(&ctx->vm_done, hipEventDisableTiming));
-        PLK_HIP(hipEventRecord(ctx->vm_in, caller));
-        PLK_HIP(hipStreamWaitEvent(st, ctx->vm_in, 0));
-    }
-    auto mark = [](int) -> int32_t { return PLK_OK; };
-    for (uint64_t base = 0; base < count; base += VM_CHUNK) {
-        const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
-        const VmArena A(ctx->vm_stage.as<char>(), cnt);
-        PLK_TRY(vm_mixed_pass_from_bytes(set, A, reinterpret_cast<const uint8_t *>(blob_dev), blob_len, reinterpret_cast<const uint64_t *>(off_dev) + base, 0,
-                                         reinterpret_cast<const uint32_t *>(key_of_dev) + base, cnt, reinterpret_cast<uint8_t *>(verdict_dev) + base, st, mark));
-    }
-    if (caller != st) {
-        PLK_HIP(hipEventRecord(ctx->vm_done, st));
-        PLK_HIP(hipStreamWaitEvent(caller, ctx->vm_done, 0));
-    }
-    return PLK_OK;
+// ---- driver 3, bytes on the device (plk_verify_many_dev, plk_verify_mixed_dev; K.key_of is a device pointer).  The call does not wait: its
+// arena is vm_stage and its passes run on the context's stream (on_ctx_stream, ctx.h).  No times are recorded.
+static int32_t vm_call_dev(const char *who, plk_ctx *ctx, const VmKeys &K, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *verdict_dev,
+                           void *stream) {
+    return guarded(who, PLK_ERR_ARG, [&]() -> int32_t {
+        if (!ctx || K.missing(count) || (count && (!off_dev || !verdict_dev)) || (blob_len && !blob_dev)) { set_error(std::string(who) + ": null argument"); return PLK_ERR_ARG; }
+        if (!K.set && ((uintptr_t)off_dev & 7)) { set_error(std::string(who) + ": the offset table must be 8-byte aligned"); return PLK_ERR_ARG; }
+        if (K.set && (((uintptr_t)off_dev & 7) || ((uintptr_t)K.key_of & 3))) { set_error(std::string(who) + ": the offset table must be 8-byte aligned, the key indices 4-byte aligned"); return PLK_ERR_ARG; }
+        PLK_TRY(K.guard(who, ctx));
+        if (count == 0) return PLK_OK;
+        PLK_HIP(hipSetDevice(ctx->device));
+        ctx->vm_ms_valid = false;
+        const VmLayout L = vm_layout(count < VM_CHUNK ? (size_t)count : (size_t)VM_CHUNK, false, false, 0);
+        PLK_TRY(ctx->vm_stage.reserve(L.bytes));
+        return on_ctx_stream(ctx, stream ? (hipStream_t)stream : ctx->stream, [&](hipStream_t st) -> int32_t {
+            VmTimer none;                                             // never started
+            for (uint64_t base = 0; base < count; base += VM_CHUNK) {
+                const uint32_t cnt = (uint32_t)(count - base < VM_CHUNK ? count - base : VM_CHUNK);
+                const VmArena A(ctx->vm_stage, vm_layout(cnt, false, false, 0));
+                const VmRaw R{reinterpret_cast<const uint8_t *>(blob_dev), blob_len, reinterpret_cast<const uint64_t *>(off_dev) + base, 0};
+                PLK_TRY(vm_pass(K, A, K.set ? K.key_of + base : nullptr, cnt, &R, reinterpret_cast<uint8_t *>(verdict_dev) + base, st, none, 2));
+            }
+            return PLK_OK;
+        });
+    });
+}
+
+extern "C" int32_t plk_verify_many_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *verdict_dev,
+                                       void *stream) {
+    return vm_call_dev("plk_verify_many_dev", ctx, VmKeys(vk), blob_dev, blob_len, off_dev, count, verdict_dev, stream);
 }
 
 extern "C" int32_t plk_verify_mixed_dev(plk_ctx *ctx, const plk_vkset *set, const void *blob_dev, uint64_t blob_len, const void *off_dev, const void *key_of_dev,
                                         uint64_t count, void *verdict_dev, void *stream) {
-    try { return verify_mixed_dev_body(ctx, set, blob_dev, blob_len, off_dev, key_of_dev, count, verdict_dev, stream); }   // no C++ exception crosses the C ABI, as plk_verify_many
-    catch (const std::exception &e) { set_error(std::string("plk_verify_mixed_dev: ") + e.what()); return PLK_ERR_ARG; }
+    return vm_call_dev("plk_verify_mixed_dev", ctx, VmKeys(set, reinterpret_cast<const uint32_t *>(key_of_dev)), blob_dev, blob_len, off_dev, count, verdict_dev, stream);
+}
+
+// the front kernel alone, all 25 terms per proof into the caller's arrays, on the caller's stream
+extern "C" int32_t plk_verify_front_dev(plk_ctx *ctx, const plk_vk *vk, const void *blob_dev, uint64_t blob_len, const void *off_dev, uint64_t count, void *points_dev,
+                                        void *scalars_dev, void *state_dev, void *stream) {
+    const char *who = "plk_verify_front_dev";
+    return guarded(who, PLK_ERR_ARG, [&]() -> int32_t {
+        if (!ctx || !vk || (count && (!off_dev || !points_dev || !scalars_dev || !state_dev)) || (blob_len && !blob_dev)) { set_error("plk_verify_front_dev: null argument"); return PLK_ERR_ARG; }
+        if (((uintptr_t)off_dev & 7) || (((uintptr_t)points_dev | (uintptr_t)scalars_dev) & 15)) { set_error("plk_verify_front_dev: points and scalars must be 16-byte aligned, offsets 8-byte aligned"); return PLK_ERR_ARG; }
+        if (count > (1ull << 26)) { set_error("plk_verify_front_dev: more than 2^26 proofs"); return PLK_ERR_SIZE; }
+        const VmKeys K(vk);
+        PLK_TRY(K.guard(who, ctx));
+        if (count == 0) return PLK_OK;
+        PLK_HIP(hipSetDevice(ctx->device));
+        return front_launch(reinterpret_cast<G1Affine *>(points_dev), reinterpret_cast<Fr *>(scalars_dev), reinterpret_cast<uint8_t *>(state_dev),
+                            reinterpret_cast<const uint8_t *>(blob_dev), blob_len, reinterpret_cast<const uint64_t *>(off_dev), 0, (uint32_t)count, K.front_vk(), K.fixed(), true,
+                            stream ? (hipStream_t)stream : ctx->stream);
+    });
+}
+
+extern "C" int32_t plk_verify_many_last_ms(plk_ctx *ctx, float out_ms[6]) {
+    if (!ctx || !out_ms) { set_error("plk_verify_many_last_ms: null argument"); return PLK_ERR_ARG; }
+    if (!ctx->vm_ms_valid) { set_error("plk_verify_many_last_ms: no timed plk_verify_many on this context (plk_set_kernel_timing)"); return PLK_ERR_ARG; }
+    for (int k = 0; k < 6; k++) out_ms[k] = ctx->vm_ms[k];
+    return PLK_OK;
 }

@@ -455,6 +455,22 @@ def test_refusals(ctx, batch, key):
     assert e.value.code == ERR_ARG
 
 
+def test_timing_slots_of_the_single_key_calls(ctx, batch, key):
+    """the slots of plk_verify_many_last_ms after the two blocking calls, as tests/test_gpu_verify_mixed.py asks of the mixed ones: [0] is the
+    host's flattening or, for the packed call, the front kernel; [2] the multiplications, [4] the pairing"""
+    proofs = batch.proofs[:2]
+    ctx.set_kernel_timing(True)
+    try:
+        assert key.verify_many(proofs).tolist() == [1, 1]
+        ms = ctx.verify_many_last_ms()
+        assert len(ms) == 6 and all(t >= 0 for t in ms) and ms[2] > 0 and ms[4] > 0
+        assert key.verify_many_packed(*pack(proofs)).tolist() == [1, 1]
+        ms = ctx.verify_many_last_ms()
+        assert len(ms) == 6 and all(t >= 0 for t in ms) and ms[0] > 0 and ms[2] > 0 and ms[4] > 0
+    finally:
+        ctx.set_kernel_timing(False)
+
+
 def test_one_key_from_two_contexts(ctx, batch, key):
     import plonkit_amd as pa
     other = pa.Context(0)

@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from oracle import plonk_oracle as po
 from tests.gen import forged_proofs as fp
 from tests.gen import mixed_keys as mk
 
@@ -204,7 +205,14 @@ def test_a_set_of_one_key_answers_as_the_single_key_calls(ctx, golden_dir):
     vk = open(os.path.join(golden_dir, "vk.bin"), "rb").read()
     proof = open(os.path.join(golden_dir, "proof.bin"), "rb").read()
     flip = lambda p, at: p[:at] + bytes([p[at] ^ 1]) + p[at + 1:]
-    batch = [proof, flip(proof, len(proof) - 1), proof, flip(proof, len(proof) - 200), flip(proof, 47), proof[:-1], b"", proof + b"\0", proof, flip(proof, 7)] * 7
+    P = po.read_proof(proof)
+    P.inputs = list(P.inputs) + [1]                                   # one input too many: well-formed, and the host front end settles it as invalid
+    extra_input = po.write_proof(P)
+    assert host_verdict(vk, extra_input) == INVALID and host_verdict(vk, proof[:-1]) == MALFORMED
+    # both drivers' ways out beside the pass: a proof cut by one byte (malformed, compacted away) and one settled early (wrong input count)
+    batch = [proof, flip(proof, len(proof) - 1), proof, flip(proof, len(proof) - 200), flip(proof, 47), proof[:-1], b"", proof + b"\0", proof, flip(proof, 7),
+             extra_input, proof] * 5
+    assert len(batch) < 64
     key = pa.VerificationKey(ctx, vk, strict_inputs=False)
     kset = pa.VerificationKeySet(ctx, [key])
     assert kset.keys == 1 and kset.tables == 1
