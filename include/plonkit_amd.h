@@ -1053,6 +1053,45 @@ int32_t plk_kzg_verify_multi(const plk_g1_affine *commitments, uint32_t count, c
                              const plk_fr *gamma, const plk_fr *u, const plk_g1_affine proof[2],
                              const uint8_t g2[256], int32_t *valid);
 int32_t plk_kzg_open_multi_last_ms(plk_ctx *ctx, float out_ms[4]);
+/*   plk_kzg_verify_multi_many_dev.  n openings of the scheme above in device memory, verified each on its own (kzg_multi_verify.hip).  NO
+ *                COUNTERPART IN THE REFERENCE.  ONE SHAPE serves the batch — count, npoints and the sets (a host array) are one protocol's;
+ *                per opening the arrays hold count commitments, npoints points, count x npoints evaluations (row-major, as
+ *                plk_kzg_verify_multi takes them), gamma, u and the two proof points W, W'.  Verdict i = 1 / 0 / PLK_VERDICT_MALFORMED is
+ *                exactly what plk_kzg_verify_multi says about opening i under that shape: no random combination across openings, no
+ *                bisection, the rule of plk_verify_many.  Malformed is where it returns PLK_ERR_ARG for the opening's own data: a point off
+ *                the curve, a coordinate >= q, gamma, u, a point or an evaluation INSIDE its set >= r, two equal points (decided on the
+ *                device: it is a property of one opening).  Evaluations outside a set are not read.  Infinity is a legal commitment, W and
+ *                W'.  A malformed opening contributes nothing to the arithmetic and does not touch its neighbours.
+ *                What the host refuses, once, from the sets alone (PLK_ERR_ARG, plk_kzg_verify_multi's words): count outside 1..32, npoints
+ *                outside 1..8, an empty set, a bit at or above npoints, a point no set uses.  Otherwise as plk_kzg_verify_many_dev: ordered
+ *                on `stream`, does not wait; n == 0 launches nothing; pointers 16-byte aligned, the verdict pointer of any alignment;
+ *                n <= 2^28 (PLK_ERR_SIZE); G2 in plk_pairing_check's words; a commitment in flight: PLK_ERR_ARG.
+ *                Kernels per pass: one lane per opening checks it and writes the count + 3 scalars (the <= 28 differences of the points
+ *                inverted by ONE inversion, no count x npoints array in a lane); one lane per (opening, term), count + 3 times as many,
+ *                multiplies (g1_mul_dev.h, window table in LDS; a zero scalar or the identity costs nothing); one lane per opening sums its
+ *                products with the complete addition (equal terms double, opposite terms cancel) into A, B = -W';
+ *                plk_pairing_check_many_dev's kernel decides e(A, Q_0) e(B, Q_1) == 1.  Memory: (count + 3) x 176 B + npoints
+ *                (npoints - 1) / 2 x 32 B + 130 B per opening, at most 2^16 openings and 64 MiB per pass (9216 openings at 32 x 8), in
+ *                plk_kzg_verify_many_dev's grows-only buffer outside the staging arena.
+ *                BREAK-EVEN (one MI355X, profiles/kzg_verify_multi_many.txt): a call costs 89 - 94 ms whatever the batch up to 4096 openings
+ *                (the pairing kernel is 87.5 ms of it; plk_kzg_verify_many_dev at the same n on the same box: 89 ms), a
+ *                plk_kzg_verify_multi 13 - 15 ms.  Measured at 1 / 256 / 4096 openings: 90 / 89 / 89 ms at count 3, npoints 3 and 92 / 91 / 94 ms
+ *                at count 32, npoints 8, against 13 / 210 / 3268 ms and 15 / 234 / 3701 ms for a loop of plk_kzg_verify_multi on 16 host
+ *                threads — 256 is the first measured size at which this call wins (the figures cross near 110 and near 100 openings).
+ *                The front (checks and scalars) is 0.6 ms and 2.6 ms of the call, all the new kernels 6.4 ms at 4096 x (32, 8).  Below
+ *                about a hundred openings, prefer plk_kzg_verify_multi on host threads.
+ *   plk_kzg_verify_multi_front_dev.  The front on its own, as plk_verify_front_dev is for proofs: per opening count + 3 Montgomery scalars
+ *                c_0 .. c_{count-1}, -sum_i c_i r_i(u), -Z_T(u), u — what multiplies C_0 .. C_{count-1}, G, W, W' — and a state byte
+ *                (any alignment): 1 = the opening goes on to the group arithmetic, 2 = malformed, its scalars are zero.  There is no
+ *                state 0 in this scheme.  The same refusals and the same order on `stream`; no G2.                                       */
+int32_t plk_kzg_verify_multi_many_dev(plk_ctx *ctx, uint32_t count /* 1..32 */, uint32_t npoints /* 1..8 */, const uint32_t *sets /* host, count masks */,
+                                      const void *commitments_dev /* n x count plk_g1_affine */, const void *points_dev /* n x npoints plk_fr */,
+                                      const void *evals_dev /* n x count x npoints plk_fr */, const void *gamma_dev /* n */, const void *u_dev /* n */,
+                                      const void *proofs_dev /* n x 2: W, W' */, uint64_t n, const uint8_t g2[256], void *verdict_dev /* n bytes */, void *stream);
+int32_t plk_kzg_verify_multi_front_dev(plk_ctx *ctx, uint32_t count, uint32_t npoints, const uint32_t *sets,
+                                       const void *commitments_dev, const void *points_dev, const void *evals_dev, const void *gamma_dev, const void *u_dev,
+                                       const void *proofs_dev, uint64_t n, void *scalars_dev /* n x (count + 3) plk_fr, Montgomery */, void *state_dev /* n bytes */,
+                                       void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -728,6 +728,33 @@ class Context:
         _check(lib().plk_kzg_verify_many_dev(self._h, _devptr(commitments_ptr), _devptr(z_ptr), _devptr(evals_ptr), _devptr(proofs_ptr), ctypes.c_uint64(n),
                                              bytes(g2_bytes), _devptr(verdict_ptr), _stream(stream)))
 
+    @staticmethod
+    def _kzg_multi_masks(who, count, sets):
+        masks = np.ascontiguousarray(sets, dtype=np.uint32).reshape(-1)
+        if 1 <= count <= 32 and masks.shape[0] != count:                 # (a count out of range is the library's to refuse; it reads no set then)
+            raise ValueError("%s: %d polynomials need %d sets, got %d" % (who, count, count, masks.shape[0]))
+        return masks if masks.shape[0] else np.zeros(1, dtype=np.uint32)
+
+    def kzg_verify_multi_many_dev(self, count, npoints, sets, commitments_ptr, points_ptr, evals_ptr, gamma_ptr, u_ptr, proofs_ptr, n, g2_bytes, verdict_ptr,
+                                  stream=None):
+        """plk_kzg_verify_multi_many_dev: n multi-point openings of ONE shape (count polynomials, npoints points, sets: count masks on the host)
+        in device memory — per opening count commitments, npoints points, count x npoints evaluations, gamma, u and the proof points W, W' —
+        one verdict byte each (1 / 0, 2 = malformed), each what kzg_verify_multi says about that opening; ordered on `stream`, does not wait"""
+        masks = self._kzg_multi_masks("kzg_verify_multi_many_dev", count, sets)
+        _check(lib().plk_kzg_verify_multi_many_dev(self._h, ctypes.c_uint32(count), ctypes.c_uint32(npoints), _np(masks), _devptr(commitments_ptr), _devptr(points_ptr),
+                                                   _devptr(evals_ptr), _devptr(gamma_ptr), _devptr(u_ptr), _devptr(proofs_ptr), ctypes.c_uint64(n), bytes(g2_bytes),
+                                                   _devptr(verdict_ptr), _stream(stream)))
+
+    def kzg_verify_multi_front_dev(self, count, npoints, sets, commitments_ptr, points_ptr, evals_ptr, gamma_ptr, u_ptr, proofs_ptr, n, scalars_ptr, state_ptr,
+                                   stream=None):
+        """plk_kzg_verify_multi_front_dev: the front of kzg_verify_multi_many_dev on its own.  Per opening count + 3 Montgomery scalars
+        (c_0 .. c_{count-1}, -sum c_i r_i(u), -Z_T(u), u: what multiplies C_0 .. C_{count-1}, G, W, W') and a state byte: 1 = goes on to
+        the group arithmetic, 2 = malformed (its scalars are zero); ordered on `stream`, does not wait"""
+        masks = self._kzg_multi_masks("kzg_verify_multi_front_dev", count, sets)
+        _check(lib().plk_kzg_verify_multi_front_dev(self._h, ctypes.c_uint32(count), ctypes.c_uint32(npoints), _np(masks), _devptr(commitments_ptr), _devptr(points_ptr),
+                                                    _devptr(evals_ptr), _devptr(gamma_ptr), _devptr(u_ptr), _devptr(proofs_ptr), ctypes.c_uint64(n),
+                                                    _devptr(scalars_ptr), _devptr(state_ptr), _stream(stream)))
+
     def kzg_open_all_prepare(self, log_n):
         """plk_kzg_open_all_prepare: build and keep the transform of the resident key for the 2^log_n domain (optional; kzg_open_all_dev builds it
         on first use)"""

@@ -1,6 +1,7 @@
 // What verify_many.hip (plk_vk_load, plk_verify_many_packed, plk_verify_many_dev, plk_verify_front_dev) shares with the front kernel: the
 // key constants it uploads and the two launchers of verify_front.hip.  The code of a lane is verify_front_dev.h, which only verify_front.hip
-// (and the host check program) include: its out-of-line device functions are emitted once.
+// (and the host check program) include for the proofs' front: its out-of-line device functions are emitted once there.
+// kzg_multi_verify_dev.h takes FRM and fr_inv_call from it, so kzg_multi_verify.hip carries a second copy of them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ec_dev.h"
