@@ -1023,7 +1023,7 @@ int32_t plk_g1_ntt_dev(plk_ctx *ctx, const void *in_dev, uint32_t log_n, int32_t
  *                inverse is taken, and t_j = 0 is an ordinary point (the shifted combination).  The points need not be distinct here.
  *                The same pointer may appear twice among the inputs; out_dev is none of them (PLK_ERR_ARG).  Blocks.
  *   plk_kzg_open_multi_dev.  The prover above.  Inputs are COEFFICIENTS, 1 <= n <= plk_srs_size, n <= 2^28, count 1..32, npoints 1..8; there
- *                is no PLK_KZG_VALUES route: a holder of values runs plk_ntt_dev first.  evals[i * npoints + j] = f_i(t_j) for j in S_i and
+ *                is no flags argument: a holder of values calls plk_kzg_open_multi_values_dev.  evals[i * npoints + j] = f_i(t_j) for j in S_i and
  *                zero elsewhere (the evaluation kernel of the prover, 12 pairs per launch); the two points do not depend on them.
  *                `challenge` is called ONCE, on the calling thread, after W has reached the host, and not at all when the call fails
  *                earlier; it writes u.  A non-zero return: PLK_ERR_IO, the message names the callback and its return value; u >= r:
@@ -1053,6 +1053,47 @@ int32_t plk_kzg_verify_multi(const plk_g1_affine *commitments, uint32_t count, c
                              const plk_fr *gamma, const plk_fr *u, const plk_g1_affine proof[2],
                              const uint8_t g2[256], int32_t *valid);
 int32_t plk_kzg_open_multi_last_ms(plk_ctx *ctx, float out_ms[4]);
+/*   The same openings FROM VALUES ON THE DOMAIN (kzg_multi_values.hip): values_dev[i] holds the N = 2^log_n values f_i(omega^k), the layout
+ *   PLK_KZG_VALUES means elsewhere; no transform runs and no coefficient copy exists.  NO COUNTERPART IN THE REFERENCE.  1 <= log_n <= 28.
+ *   A point may lie on the domain (t_j = omega^k, decided by t_j^N = 1): the evaluation is then read from the arrays and position k of a
+ *   quotient takes the value of the polynomial quotient there, as plk_poly_divide_values_by_linear_dev has it.  ONE inversion serves all
+ *   points of a call (a product scan over prod_j (omega^x - t_j)); working memory is two vectors, the output and one partial sum per
+ *   (polynomial, point) pair and tile of 2048, whatever the number of polynomials.
+ *
+ *   plk_kzg_open_multi_values_dev.  plk_kzg_open_multi_dev for a holder of values: evals, *u_out, proof[0] = W and proof[1] = W' are byte
+ *                for byte what that call returns for the coefficients of the same polynomials with n = N under the same key, points, sets,
+ *                gamma and callback, so plk_kzg_verify_multi and plk_kzg_verify_multi_many_dev take them unchanged.  The commitments go
+ *                against the LAGRANGE-FORM key: none resident, or one of another size than N, is PLK_ERR_SRS in the words of
+ *                plk_kzg_open_dev's values route.  log_n out of range: PLK_ERR_ARG.  Every other refusal, the callback rules (called once,
+ *                on the calling thread, after W has reached the host; non-zero return PLK_ERR_IO; u >= r PLK_ERR_ARG) and the blocking
+ *                are plk_kzg_open_multi_dev's, in its words behind this call's name.  u may be any scalar below r: 0, 1, a point of the
+ *                domain (the value of the second quotient's numerator at u, known from the evaluations, is then held against the arrays:
+ *                a mismatch is PLK_ERR_HIP), one of the t_j.  Inputs are never written; the same pointer may appear twice.
+ *   plk_poly_quotient_multi_values_dev.  The operator on its own: out = the N values of sum_j D_{t_j}[sum_i coef[i * npoints + j] f_i]; it
+ *                finds the G_j(t_j) itself (the evaluation pass over the pairs with a non-zero coefficient).  count 1..64, npoints 1..8,
+ *                the points need not be distinct; out overlaps none of the inputs (PLK_ERR_ARG).  Needs no key.  Blocks.
+ *   plk_poly_evaluate_values_multi_dev.  The evaluation pass on its own: evals[i * npoints + j] = f_i(points[j]) for bit j of sets[i], zero
+ *                elsewhere; every polynomial is read once for all its points.  count 1..64; a set may be empty, a bit at or above npoints
+ *                is PLK_ERR_ARG.  Needs no key.  Blocks.
+ *   plk_kzg_open_multi_last_ms reports the last opening of either route.  On the values route: [0] the denominators, the scan pair, the
+ *                inversion, k_kml_sums / k_kml_sum_finish and the evaluations' way to the host; [1] the matrix upload and k_kml_quot for h;
+ *                [2] the commitment W; [3] the same three steps for u (sums only when u lies on the domain), k_kml_quot<1> over the
+ *                count + 1 vectors and the commitment W'.
+ *   MEASURED at 2^20 (profiles/kzg_open_multi_values.txt), against count copies, count inverse plk_ntt_dev and
+ *                plk_kzg_open_multi_dev: (8 polynomials, 1 point) 3.9 against 4.3 ms, (8, 3) 4.2 against 4.5 ms, (32, 8) 7.2 against 11.6 ms;
+ *                the median lies below the other leg's minimum at each.  A caller that already holds coefficients keeps
+ *                plk_kzg_open_multi_dev at the two small shapes (3.4 and 3.6 ms without the transforms).                                  */
+int32_t plk_kzg_open_multi_values_dev(plk_ctx *ctx, const void *const *values_dev, uint32_t count /* 1..32 */, uint32_t log_n,
+                                      const plk_fr *points, uint32_t npoints /* 1..8 */, const uint32_t *sets /* count masks */,
+                                      const plk_fr *gamma, plk_kzg_challenge_fn challenge, void *user,
+                                      plk_fr *evals /* count x npoints; entries outside a set are written as zero */,
+                                      plk_fr *u_out, plk_g1_affine proof[2] /* W, W' */, void *stream);
+int32_t plk_poly_quotient_multi_values_dev(plk_ctx *ctx, const void *const *values_dev, uint32_t count /* 1..64 */, uint32_t log_n,
+                                           const plk_fr *points, uint32_t npoints /* 1..8 */, const plk_fr *coef /* count x npoints, row-major */,
+                                           void *out_values_dev /* 2^log_n elements; not one of the inputs */, void *stream);
+int32_t plk_poly_evaluate_values_multi_dev(plk_ctx *ctx, const void *const *values_dev, uint32_t count /* 1..64 */, uint32_t log_n,
+                                           const plk_fr *points, uint32_t npoints /* 1..8 */, const uint32_t *sets /* count masks */,
+                                           plk_fr *evals /* count x npoints, zero outside the sets */, void *stream);
 /*   plk_kzg_verify_multi_many_dev.  n openings of the scheme above in device memory, verified each on its own (kzg_multi_verify.hip).  NO
  *                COUNTERPART IN THE REFERENCE.  ONE SHAPE serves the batch — count, npoints and the sets (a host array) are one protocol's;
  *                per opening the arrays hold count commitments, npoints points, count x npoints evaluations (row-major, as

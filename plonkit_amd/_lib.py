@@ -793,11 +793,15 @@ class Context:
         sets[i] (points: [npoints <= 8, 4]), with a proof of two points.  challenge: a callable W ([8] uint64) -> u ([4] uint64), called once
         after the first commitment, or a fixed scalar u.  Returns ([count, npoints, 4] evaluations, zero outside the sets; u; [2, 8] W, W').
         An exception raised by the callable is raised again here, after the call has failed with PLK_ERR_IO."""
+        return self._kzg_open_multi("kzg_open_multi_dev", lib().plk_kzg_open_multi_dev, ptrs, ctypes.c_uint64(n), points, sets, gamma, challenge, stream)
+
+    def _kzg_open_multi(self, name, fn, ptrs, size, points, sets, gamma, challenge, stream):
+        """the two routes of the multi-point opening: the arrays, the callback around `challenge`, the call, the outputs"""
         arr = (ctypes.c_void_p * len(ptrs))(*[_devptr(p) for p in ptrs])
         pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
         masks = np.ascontiguousarray(sets, dtype=np.uint32).reshape(-1)
         if masks.shape[0] != len(ptrs):
-            raise ValueError("kzg_open_multi_dev: %d polynomials and %d sets" % (len(ptrs), masks.shape[0]))
+            raise ValueError("%s: %d polynomials and %d sets" % (name, len(ptrs), masks.shape[0]))
         gamma = np.ascontiguousarray(gamma, dtype=np.uint64)
         raised = []
 
@@ -817,8 +821,8 @@ class Context:
         cb = self._KZG_CHALLENGE(_call)                               # kept alive by this frame until the call has returned
         evals = np.zeros((len(ptrs), pts.shape[0], 4), dtype=np.uint64)
         u, proof = np.zeros(4, dtype=np.uint64), np.zeros((2, 8), dtype=np.uint64)
-        rc = lib().plk_kzg_open_multi_dev(self._h, arr, ctypes.c_uint32(len(ptrs)), ctypes.c_uint64(n), _np(pts), ctypes.c_uint32(pts.shape[0]), _np(masks),
-                                          _np(gamma), cb, None, _np(evals), _np(u), _np(proof), _stream(stream))
+        rc = fn(self._h, arr, ctypes.c_uint32(len(ptrs)), size, _np(pts), ctypes.c_uint32(pts.shape[0]), _np(masks),
+                _np(gamma), cb, None, _np(evals), _np(u), _np(proof), _stream(stream))
         if raised:
             raise raised[0]
         _check(rc)
@@ -826,10 +830,43 @@ class Context:
 
     def kzg_open_multi_last_ms(self):
         """plk_kzg_open_multi_last_ms: [evaluations, first quotient, its commitment, second quotient with its commitment] of the last
-        kzg_open_multi_dev, in ms (set_kernel_timing must be on)"""
+        kzg_open_multi_dev or kzg_open_multi_values_dev, in ms (set_kernel_timing must be on)"""
         out = (ctypes.c_float * 4)()
         _check(lib().plk_kzg_open_multi_last_ms(self._h, out))
         return [float(v) for v in out]
+
+    # ---- the same from values on the domain, against the Lagrange-form key (kzg_multi_values.hip)
+    def kzg_open_multi_values_dev(self, ptrs, log_n, points, sets, gamma, challenge, stream=None):
+        """plk_kzg_open_multi_values_dev: kzg_open_multi_dev for count <= 32 device arrays of the 2^log_n values f_i(omega^k): no transform, the
+        commitments against the Lagrange-form key.  The same arguments otherwise and the same return, byte for byte what kzg_open_multi_dev
+        gives for the coefficients of the same polynomials: ([count, npoints, 4] evaluations, zero outside the sets; u; [2, 8] W, W')."""
+        return self._kzg_open_multi("kzg_open_multi_values_dev", lib().plk_kzg_open_multi_values_dev, ptrs, ctypes.c_uint32(log_n), points, sets, gamma,
+                                    challenge, stream)
+
+    def poly_quotient_multi_values_dev(self, ptrs, log_n, points, coef, out_ptr, stream=None):
+        """plk_poly_quotient_multi_values_dev: out = the 2^log_n values of sum_j D_{t_j}[sum_i coef[i][j] f_i] from the values of count <= 64
+        device polynomials, points [npoints <= 8, 4] (on the domain or off it) and coef [count, npoints, 4]; out_ptr is none of the inputs.  Blocks."""
+        arr = (ctypes.c_void_p * len(ptrs))(*[_devptr(p) for p in ptrs])
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        cf = np.ascontiguousarray(coef, dtype=np.uint64).reshape(-1, 4)
+        if cf.shape[0] != len(ptrs) * pts.shape[0]:
+            raise ValueError("poly_quotient_multi_values_dev: %d polynomials and %d points need %d coefficients, got %d"
+                             % (len(ptrs), pts.shape[0], len(ptrs) * pts.shape[0], cf.shape[0]))
+        _check(lib().plk_poly_quotient_multi_values_dev(self._h, arr, ctypes.c_uint32(len(ptrs)), ctypes.c_uint32(log_n), _np(pts), ctypes.c_uint32(pts.shape[0]),
+                                                        _np(cf), _devptr(out_ptr), _stream(stream)))
+
+    def poly_evaluate_values_multi_dev(self, ptrs, log_n, points, sets, stream=None):
+        """plk_poly_evaluate_values_multi_dev: [count, npoints, 4] evaluations f_i(t_j) for bit j of sets[i], zero elsewhere, from the 2^log_n
+        values of count <= 64 device polynomials; every polynomial is read once for all its points.  Blocks."""
+        arr = (ctypes.c_void_p * len(ptrs))(*[_devptr(p) for p in ptrs])
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        masks = np.ascontiguousarray(sets, dtype=np.uint32).reshape(-1)
+        if masks.shape[0] != len(ptrs):
+            raise ValueError("poly_evaluate_values_multi_dev: %d polynomials and %d sets" % (len(ptrs), masks.shape[0]))
+        evals = np.zeros((len(ptrs), pts.shape[0], 4), dtype=np.uint64)
+        _check(lib().plk_poly_evaluate_values_multi_dev(self._h, arr, ctypes.c_uint32(len(ptrs)), ctypes.c_uint32(log_n), _np(pts), ctypes.c_uint32(pts.shape[0]),
+                                                        _np(masks), _np(evals), _stream(stream)))
+        return evals
 
     def g1_ntt_dev(self, in_ptr, log_n, out_ptr, inverse=False, stream=None):
         """plk_g1_ntt_dev: the G1 transform of 2^log_n affine points in device memory, forward (out[i] = sum_j omega^(i j) in[j]) or inverse

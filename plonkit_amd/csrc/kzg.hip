@@ -303,13 +303,15 @@ int32_t kzg_common_args(const char *who, plk_ctx *ctx, const void *const *polys,
     }
     return PLK_OK;
 }
-int32_t kzg_lagrange_key(plk_ctx *ctx, uint64_t n, uint32_t *log_n) {
+}  // namespace
+int32_t kzg_lagrange_key(plk_ctx *ctx, uint64_t n, uint32_t *log_n) {          // (kzg_scratch.h: kzg_multi_values.hip asks as well)
     uint32_t l = 0;
     while ((1ull << l) < n) l++;
     if (!ctx->lagrange().pts || ctx->lagrange().n != n || (1ull << l) != n || l == 0 || l > MAX_LOG_N) { set_error(KZ_LAGRANGE_SIZE); return PLK_ERR_SRS; }
     *log_n = l;
     return PLK_OK;
 }
+namespace {
 
 int32_t open_coefficients(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint64_t n, const HFr &z, const HFr *vp, plk_fr *evals, plk_g1_affine *proof, hipStream_t st) {
     if (!ctx->srs().pts || n > ctx->srs().n) { set_error("plk_kzg_open_dev: no key resident, or the key is shorter than the polynomials"); return PLK_ERR_SRS; }

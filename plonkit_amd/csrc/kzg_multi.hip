@@ -220,7 +220,8 @@ int32_t quotient_multi(const Fr *const *f, uint32_t count, uint64_t n, const HFr
     return PLK_OK;
 }
 
-int32_t km_common(const char *who, plk_ctx *ctx, const void *const *polys, uint32_t count, uint32_t max_count, uint64_t n, uint32_t npoints) {
+}  // namespace
+int32_t km_common(const char *who, plk_ctx *ctx, const void *const *polys, uint32_t count, uint32_t max_count, uint64_t n, uint32_t npoints) {   // (kzg_scratch.h)
     if (!ctx || !polys || count == 0 || count > max_count || npoints == 0 || npoints > KM_MAX_POINTS || n == 0) { set_error(std::string(who) + ": bad argument"); return PLK_ERR_ARG; }
     for (uint32_t i = 0; i < count; i++) {
         if (!polys[i]) { set_error(std::string(who) + ": bad argument"); return PLK_ERR_ARG; }
@@ -231,6 +232,7 @@ int32_t km_common(const char *who, plk_ctx *ctx, const void *const *polys, uint3
     if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment is still in flight on this context"); return PLK_ERR_ARG; }
     return PLK_OK;
 }
+namespace {
 
 int32_t open_multi(plk_ctx *ctx, const Fr *const *f, uint32_t count, uint64_t n, const HFr *points, uint32_t npoints, const uint32_t *sets, const HFr &gamma,
                    plk_kzg_challenge_fn challenge, void *user, plk_fr *evals, plk_fr *u_out, plk_g1_affine *proof, hipStream_t st) {

@@ -16,4 +16,9 @@ struct KzgScratch {
     ~KzgScratch() { if (grew && ctx->kzg_ws.cap > KZ_KEEP) { (void)hipStreamSynchronize(st); ctx->kzg_ws.release(); } }
 };
 
+// what the values routes refuse about the Lagrange-form key (kzg.hip): it is resident and has exactly n = 2^*log_n points, 1 <= *log_n <= 28
+int32_t kzg_lagrange_key(plk_ctx *ctx, uint64_t n, uint32_t *log_n);
+// what every multi-point call refuses about its polynomials and its context (kzg_multi.hip), with `who` in front
+int32_t km_common(const char *who, plk_ctx *ctx, const void *const *polys, uint32_t count, uint32_t max_count, uint64_t n, uint32_t npoints);
+
 }  // namespace plk
