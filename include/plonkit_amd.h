@@ -999,12 +999,34 @@ int32_t plk_kzg_verify_many_dev(plk_ctx *ctx, const void *commitments_dev, const
  *   plk_g1_ntt_dev.  The transform of plk_g1_intt over 2^log_n affine points in device memory (64 B each, (0, 0) = infinity), in either
  *                direction: inverse != 0 is plk_g1_intt bit for bit (omega^-1, 1 / N); inverse == 0 is out[i] = sum_j omega^(i j) in[j],
  *                no scaling.  log_n <= 26, no commitment in flight (the scratch is slot 0's).  Ordered on `stream`, does not wait; out_dev
- *                may be in_dev.                                                                                                          */
+ *                may be in_dev.
+ *   plk_kzg_open_all_batch_dev.  plk_kzg_open_all_dev for `count` polynomials under the one key in one pass: a holder of many columns (a
+ *                data-availability holder, the cached quotients of a lookup argument) pays the stage launches of one.  polys_dev: count
+ *                polynomials back to back, N = 2^log_n plk_fr each (coefficients, or values with PLK_KZG_VALUES); never written.
+ *                proofs_dev[b N + i] is, byte for byte, what plk_kzg_open_all_dev writes at [i] for polynomial b; evals_dev[b N + i], if
+ *                not NULL, is f_b(omega^i); nothing beyond count x N entries is written.  count >= 1 (0: PLK_ERR_ARG), log_n <= 25 and
+ *                count x 2^(log_n + 1) <= 2^26 (PLK_ERR_SIZE above, nothing allocated: g1ntt's limit for a whole launch, every flattened
+ *                index inside 32 bits); every other refusal of plk_kzg_open_all_dev in its order, under this function's name.  log_n = 0:
+ *                count points at infinity, the evals copied from the input.  The key's transform is THE SAME kept one: either entry point
+ *                (or plk_kzg_open_all_prepare) builds it for both, a change of the key voids it for both.  Scratch: count x 2N x 176 B
+ *                (+ count x N x 32 B in values), the same buffer and rule as the single call's.  Blocks; plk_kzg_open_all_last_ms reports
+ *                its five parts.  Every G1 stage launch covers all count transforms (the polynomial is the slow index, the key's
+ *                transform is read at m mod 2N); the scalar NTTs run one polynomial at a time.
+ *                MEASURED (one MI355X, profiles/kzg_open_all_batch.txt, the key's transform kept): at 2^12, 1 / 4 / 16 / 64 polynomials take
+ *                22.4 / 22.9 / 25.0 / 76.7 ms where the loop of single calls takes 22.3 / 89.2 / 357 / 1428 ms (16: 14.3 x, 64: 18.6 x);
+ *                at 2^16, where one polynomial already fills the chip, 1 / 4 / 16 take 31.5 / 93.1 / 364 ms against 31.4 / 125 / 504 (1.4 x).
+ *   plk_g1_ntt_batch_dev.  plk_g1_ntt_dev over `count` arrays of 2^log_n affine points back to back, in either direction: row b of the
+ *                output equals plk_g1_ntt_dev of row b byte for byte.  count >= 1 (0: PLK_ERR_ARG), count << log_n <= 2^26
+ *                (PLK_ERR_SIZE).  Slot 0's scratch: the refusals of plk_g1_ntt_dev.  Ordered on `stream`, does not wait; out_dev may be
+ *                in_dev.                                                                                                                 */
 int32_t plk_kzg_open_all_prepare(plk_ctx *ctx, uint32_t log_n);
 int32_t plk_kzg_open_all_dev(plk_ctx *ctx, const void *poly_dev, uint32_t log_n, uint32_t flags /* 0 | PLK_KZG_VALUES */,
                              void *proofs_dev /* 2^log_n affine points */, void *evals_dev /* may be NULL: f(omega^i) */, void *stream);
 int32_t plk_kzg_open_all_last_ms(plk_ctx *ctx, float out_ms[5]);
 int32_t plk_g1_ntt_dev(plk_ctx *ctx, const void *in_dev, uint32_t log_n, int32_t inverse, void *out_dev, void *stream);
+int32_t plk_kzg_open_all_batch_dev(plk_ctx *ctx, const void *polys_dev, uint32_t count, uint32_t log_n, uint32_t flags /* 0 | PLK_KZG_VALUES */,
+                                   void *proofs_dev /* count x 2^log_n affine points */, void *evals_dev /* may be NULL */, void *stream);
+int32_t plk_g1_ntt_batch_dev(plk_ctx *ctx, const void *in_dev, uint32_t count, uint32_t log_n, int32_t inverse, void *out_dev, void *stream);
 /*   Many polynomials at several points with a proof of two points (kzg_multi.hip; Boneh-Drake-Fisch-Gabizon 2020, the scheme that needs
  *   only [tau]_2).  NO COUNTERPART IN THE REFERENCE: kate_commitment opens at one point per call.  f_0 .. f_{m-1} have n coefficients each,
  *   t_0 .. t_{p-1} are distinct points, and bit j of sets[i] says that f_i is opened at t_j (S_i; T = all p points).  No set is empty, no

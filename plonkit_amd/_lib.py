@@ -766,6 +766,12 @@ class Context:
         _check(lib().plk_kzg_open_all_dev(self._h, _devptr(poly_ptr), ctypes.c_uint32(log_n), ctypes.c_uint32(1 if values else 0), _devptr(proofs_ptr),
                                           _devptr(evals_ptr) if evals_ptr is not None else None, _stream(stream)))
 
+    def kzg_open_all_batch_dev(self, polys_ptr, count, log_n, proofs_ptr, evals_ptr=None, values=False, stream=None):
+        """plk_kzg_open_all_batch_dev: kzg_open_all_dev for `count` polynomials of 2^log_n back to back at polys_ptr, in one pass under the one
+        key: proofs_ptr[b * N + i] <- the proof at omega^i of polynomial b, evals_ptr (optional) likewise.  Blocks."""
+        _check(lib().plk_kzg_open_all_batch_dev(self._h, _devptr(polys_ptr), ctypes.c_uint32(count), ctypes.c_uint32(log_n), ctypes.c_uint32(1 if values else 0),
+                                                _devptr(proofs_ptr), _devptr(evals_ptr) if evals_ptr is not None else None, _stream(stream)))
+
     def kzg_open_all_last_ms(self):
         """plk_kzg_open_all_last_ms: [key transform, scalar NTTs, point-wise product, inverse transform, forward transform + affine] of the last
         kzg_open_all_dev, in ms (set_kernel_timing must be on)"""
@@ -872,6 +878,12 @@ class Context:
         """plk_g1_ntt_dev: the G1 transform of 2^log_n affine points in device memory, forward (out[i] = sum_j omega^(i j) in[j]) or inverse
         (g1_intt's, bit for bit); ordered on `stream`, does not wait"""
         _check(lib().plk_g1_ntt_dev(self._h, _devptr(in_ptr), ctypes.c_uint32(log_n), ctypes.c_int32(1 if inverse else 0), _devptr(out_ptr), _stream(stream)))
+
+    def g1_ntt_batch_dev(self, in_ptr, count, log_n, out_ptr, inverse=False, stream=None):
+        """plk_g1_ntt_batch_dev: g1_ntt_dev over `count` arrays of 2^log_n affine points back to back, every stage of all of them in one launch;
+        ordered on `stream`, does not wait"""
+        _check(lib().plk_g1_ntt_batch_dev(self._h, _devptr(in_ptr), ctypes.c_uint32(count), ctypes.c_uint32(log_n), ctypes.c_int32(1 if inverse else 0),
+                                          _devptr(out_ptr), _stream(stream)))
 
     def permutation_grand_product_dev(self, wires, sigmas, beta, gamma, log_n, out_ptr, stream=None):
         w = (ctypes.c_void_p * 4)(*[_devptr(p) for p in wires])

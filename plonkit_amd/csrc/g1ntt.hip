@@ -19,6 +19,7 @@
 #include "glv_dev.h"
 #include "g1_mul_dev.h"
 #include "ntt.h"
+#include "kzg_all_plan.h"
 #include <type_traits>
 
 namespace plk {
@@ -29,24 +30,28 @@ __device__ __forceinline__ uint32_t brev32(uint32_t x, uint32_t bits) { return b
 // pts[bitrev(i)] = in[i]   (in: affine, external form; pts: XYZZ on the 29-bit layer).  The factor 1/N is applied by the LAST stage
 // (g1ntt_stage, SCALE): there half of the points are multiplied by a twiddle anyway, which takes 1/N along for nothing, so the
 // scaling costs N/2 scalar multiplications instead of the N of a pass of its own (one stage's worth of the transform's 22).
-__global__ void __launch_bounds__(256) g1ntt_load(XyzzW *pts, const G1Affine *in, uint32_t log_n) {
+// `count` arrays of 2^log_n points back to back, each permuted inside itself (count << log_n <= 2^26: the flattened index fits 32 bits)
+__global__ void __launch_bounds__(256) g1ntt_load(XyzzW *pts, const G1Affine *in, uint32_t log_n, uint32_t count) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (1u << log_n)) return;
+    if (i >= (count << log_n)) return;
     const G1Affine a = load_affine(in + i);
     XyzzW p = xyzzw_identity();
     if (!is_inf(a)) {
         p.x = csub_p(w_from_s(unpack<FqW>(a.x))); p.y = csub_p(w_from_s(unpack<FqW>(a.y)));
         p.zz = w_one<FqW>(); p.zzz = w_one<FqW>();
     }
-    store_xyzzw(pts + brev32(i, log_n), p);
+    const uint32_t k = i & ((1u << log_n) - 1);
+    store_xyzzw(pts + (i - k) + brev32(k, log_n), p);
 }
 
-// the same permutation of points that are XYZZ already, where they lie: the lane of the lower index of a pair swaps it
-__global__ void __launch_bounds__(256) g1ntt_bitrev(XyzzW *pts, uint32_t log_n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (1u << log_n)) return;
-    const uint32_t r = brev32(i, log_n);
+// the same permutation of points that are XYZZ already, where they lie: the lane of the lower index of a pair swaps it.  `count` arrays whose
+// first points lie `stride` points apart (fk_batch_point), the first 2^log_n of each
+__global__ void __launch_bounds__(256) g1ntt_bitrev(XyzzW *pts, uint32_t log_n, uint32_t count, uint32_t stride) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (count << log_n)) return;
+    const uint32_t i = g & ((1u << log_n) - 1), r = brev32(i, log_n);
     if (i >= r) return;
+    pts += fk_batch_point(log_n, stride, g) - i;
     const XyzzW a = load_xyzzw(pts + i), b = load_xyzzw(pts + r);
     store_xyzzw(pts + i, b);
     store_xyzzw(pts + r, a);
@@ -54,20 +59,22 @@ __global__ void __launch_bounds__(256) g1ntt_bitrev(XyzzW *pts, uint32_t log_n) 
 
 // one DIT stage with half-size h = 2^s; SCALE (the last stage): both outputs times n_inv (Montgomery form) — (A n_inv) +- (w n_inv) B
 // tw: the powers of omega^-1 (inverse transform) or of omega (forward: never with SCALE)
+// One launch covers `count` transforms whose first points lie `stride` points apart; the transform is the SLOW index of the launch
+// (fk_batch_butterfly, kzg_all_plan.h), so transforms of fewer than 256 butterflies share a workgroup, of fewer than 64 a wave, and a
+// single transform is a batch of one.  count << (log_n - 1) <= 2^25.
 template <bool SCALE, int ISO>
-__global__ void __launch_bounds__(G1NTT_THREADS, 1) g1ntt_stage(XyzzW *pts, uint32_t log_n, uint32_t s, PowTable tw, Fr n_inv) {
+__global__ void __launch_bounds__(G1NTT_THREADS, 1) g1ntt_stage(XyzzW *pts, uint32_t log_n, uint32_t s, PowTable tw, Fr n_inv, uint32_t count, uint32_t stride) {
     extern __shared__ uint32_t g1tab[];
-    uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= (1u << (log_n - 1))) return;
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (count << (log_n - 1))) return;
+    const FkButterfly bf = fk_batch_butterfly(log_n, g);
+    pts += (size_t)bf.poly * stride;
     // butterfly j of the stage: group jh, position jl inside the half (twiddle exponent).  jl = 0 needs no multiplication; in the early
     // stages (h < 64) consecutive lanes would all differ in jl and every wave would pay for the one lane in h that has it.  There the
     // position is the SLOW index of the launch: whole waves (workgroups) share jl, and those with jl = 0 — half of stage 1, a quarter of
-    // stage 2, .. — only add.  (The accesses become strided; memory traffic is nothing in this kernel.)
-    const uint32_t h = 1u << s;
-    uint32_t jl, jh;
-    if (s < 6 && log_n >= 8) { jl = j >> (log_n - 1 - s); jh = j & ((1u << (log_n - 1 - s)) - 1); }
-    else { jl = j & (h - 1); jh = j >> s; }
-    const uint32_t i0 = (jh << (s + 1)) | jl, i1 = i0 + h;
+    // stage 2, .. — only add.  (The accesses become strided; memory traffic is nothing in this kernel.)  fk_stage_pair has the two forms.
+    const FkPair pr = fk_stage_pair(log_n, s, bf.j);
+    const uint32_t jl = pr.jl, i0 = pr.i0, i1 = pr.i1;
     XyzzW a = load_xyzzw(pts + i0), b = load_xyzzw(pts + i1);
     if (jl || SCALE) {
         Fr w = n_inv;
@@ -96,8 +103,10 @@ __global__ void __launch_bounds__(G1NTT_THREADS, 1) g1ntt_stage(XyzzW *pts, uint
 // XYZZ -> affine with ONE field inversion per G1NTT_NORM_K points (Montgomery's trick on ZZZ; 1 / Z = ZZ / ZZZ, as srs_normalise_kernel does for the MSM table):
 // a Fermat inversion per point was 4.3 ms of a 2^20-point transform.  A thread takes K consecutive points; the second walk reads them again (four products each)
 // rather than keep K x 32 words alive.  Same canonical coordinates as before, bit for bit.
+// out is dense; output point i < n = count << log_n is read at fk_batch_point(log_n, stride, i): the first 2^log_n of arrays `stride` points
+// apart.  The groups of K need not line up with the arrays: the affine coordinates do not depend on what shares an inversion.
 constexpr uint32_t G1NTT_NORM_K = 8;
-__global__ void __launch_bounds__(256) g1ntt_to_affine(G1Affine *out, const XyzzW *pts, uint32_t n) {
+__global__ void __launch_bounds__(256) g1ntt_to_affine(G1Affine *out, const XyzzW *pts, uint32_t n, uint32_t log_n, uint32_t stride) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lo = t * G1NTT_NORM_K, hi = lo + G1NTT_NORM_K < n ? lo + G1NTT_NORM_K : n;
     if (lo >= n) return;
@@ -106,7 +115,7 @@ __global__ void __launch_bounds__(256) g1ntt_to_affine(G1Affine *out, const Xyzz
 #pragma unroll
     for (uint32_t j = 0; j < G1NTT_NORM_K; j++) {
         if (lo + j < hi) {
-            const XyzzW w = load_xyzzw(pts + lo + j);
+            const XyzzW w = load_xyzzw(pts + fk_batch_point(log_n, stride, lo + j));
             if (!is_inf(w)) acc = mul(acc, pack<FqParams>(s_from_w(w.zzz)));
         }
         prefix[j] = acc;
@@ -116,7 +125,7 @@ __global__ void __launch_bounds__(256) g1ntt_to_affine(G1Affine *out, const Xyzz
     for (uint32_t jj = 0; jj < G1NTT_NORM_K; jj++) {
         const uint32_t j = G1NTT_NORM_K - 1 - jj;
         if (lo + j >= hi) continue;
-        const G1Xyzz q = xyzzw_export(load_xyzzw(pts + lo + j));  // back to the external form (canonical, R = 2^256); the identity is all zero
+        const G1Xyzz q = xyzzw_export(load_xyzzw(pts + fk_batch_point(log_n, stride, lo + j)));  // back to the external form (canonical, R = 2^256); the identity is all zero
         G1Affine a; a.x = Fq::zero(); a.y = Fq::zero();
         if (!is_inf(q)) {
             const Fq zi = j ? mul(inv_acc, prefix[j - 1]) : inv_acc;  // 1 / ZZZ_j
@@ -147,20 +156,21 @@ static int32_t g1ntt_stage_attrs() {
 
 // The log_n stages over points already in bit-reversed order.  Inverse: omega^-1 and 1/N on the last stage.  Forward: omega, and the last stage is
 // the non-scaling instantiation like the others (no multiplication by 1 goes through the SCALE path).
-static int32_t g1ntt_stages(plk_ctx *ctx, XyzzW *pts, uint32_t log_n, bool inverse, hipStream_t st) {
+// `count` transforms `stride` points apart in every launch.
+static int32_t g1ntt_stages(plk_ctx *ctx, XyzzW *pts, uint32_t count, uint32_t stride, uint32_t log_n, bool inverse, hipStream_t st) {
     PLK_TRY(g1ntt_stage_attrs());
-    const uint32_t n = 1u << log_n;
+    const uint32_t half = log_n ? count << (log_n - 1) : 0;       // butterflies of a launch
     const Fr n_inv = ctx->n_inv[log_n];                           // Montgomery form; 1 for log_n = 0 (no stage, nothing to scale)
     const PowTable tw = inverse ? ctx->tw_inv : ctx->tw_fwd;
     // PLK_G1NTT_ISO (A/B knob): 0 = the window table in XYZZ and full additions, as in rounds 4-5; 1 = four effectively affine entries, 3-bit windows; default 2 = eight, 4-bit windows
     // (the same chain in Jacobian coordinates — 4S + 3M doublings — was built, verified and measured 3 % SLOWER: profiles/r06b_g1ntt_jacobian.patch)
     static const int iso = [] { const char *e = getenv("PLK_G1NTT_ISO"); return e ? atoi(e) : 2; }();
-    const dim3 sgrid((n / 2 + G1NTT_THREADS - 1) / G1NTT_THREADS);
+    const dim3 sgrid((half + G1NTT_THREADS - 1) / G1NTT_THREADS);
     auto stage = [&](auto scale_tag, uint32_t s) {
         constexpr bool SC = decltype(scale_tag)::value;
-        if (iso == 2) hipLaunchKernelGGL((g1ntt_stage<SC, 2>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS_ISO8, st, pts, log_n, s, tw, n_inv);
-        else if (iso == 1) hipLaunchKernelGGL((g1ntt_stage<SC, 1>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, pts, log_n, s, tw, n_inv);
-        else hipLaunchKernelGGL((g1ntt_stage<SC, 0>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS, st, pts, log_n, s, tw, n_inv);
+        if (iso == 2) hipLaunchKernelGGL((g1ntt_stage<SC, 2>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS_ISO8, st, pts, log_n, s, tw, n_inv, count, stride);
+        else if (iso == 1) hipLaunchKernelGGL((g1ntt_stage<SC, 1>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS_ISO, st, pts, log_n, s, tw, n_inv, count, stride);
+        else hipLaunchKernelGGL((g1ntt_stage<SC, 0>), sgrid, dim3(G1NTT_THREADS), G1NTT_LDS, st, pts, log_n, s, tw, n_inv, count, stride);
     };
     for (uint32_t s = 0; s + 1 < log_n; s++) stage(std::false_type{}, s);
     if (log_n) { if (inverse) stage(std::true_type{}, log_n - 1); else stage(std::false_type{}, log_n - 1); }
@@ -168,34 +178,38 @@ static int32_t g1ntt_stages(plk_ctx *ctx, XyzzW *pts, uint32_t log_n, bool inver
     return PLK_OK;
 }
 
-int32_t g1_ntt_dev(plk_ctx *ctx, const G1Affine *in, uint32_t log_n, bool inverse, G1Affine *out, hipStream_t st, const char *who) {
-    if (log_n > 26) { set_error(std::string(who) + ": size exceeds 2^26"); return PLK_ERR_SIZE; }
+// `count` arrays of 2^log_n points back to back, each transformed on its own
+int32_t g1_ntt_dev(plk_ctx *ctx, const G1Affine *in, uint32_t count, uint32_t log_n, bool inverse, G1Affine *out, hipStream_t st, const char *who) {
+    if (!fk_batch_points_ok(count, log_n)) { set_error(std::string(who) + ": size exceeds 2^26"); return PLK_ERR_SIZE; }
     PLK_TRY(ntt_init_tables(ctx));
-    const uint32_t n = 1u << log_n;
+    const uint32_t n = count << log_n;
     // the transform borrows the scratch of the first commitment slot: nothing may be in flight there
     if (ctx->msm_enq != ctx->msm_fin) { set_error(std::string(who) + ": a commitment enqueued with plk_msm_g1_enqueue_dev is still in flight (call plk_msm_g1_finish first)"); return PLK_ERR_ARG; }
     PLK_TRY(ctx->slot[0].c.reserve((size_t)n * sizeof(XyzzW)));
     XyzzW *pts = ctx->slot[0].c.as<XyzzW>();
-    hipLaunchKernelGGL(g1ntt_load, dim3((n + 255) / 256), dim3(256), 0, st, pts, in, log_n);
-    PLK_TRY(g1ntt_stages(ctx, pts, log_n, inverse, st));
-    hipLaunchKernelGGL(g1ntt_to_affine, dim3(((n + G1NTT_NORM_K - 1) / G1NTT_NORM_K + 255) / 256), dim3(256), 0, st, out, (const XyzzW *)pts, n);
+    hipLaunchKernelGGL(g1ntt_load, dim3((n + 255) / 256), dim3(256), 0, st, pts, in, log_n, count);
+    PLK_TRY(g1ntt_stages(ctx, pts, count, 1u << log_n, log_n, inverse, st));
+    hipLaunchKernelGGL(g1ntt_to_affine, dim3(((n + G1NTT_NORM_K - 1) / G1NTT_NORM_K + 255) / 256), dim3(256), 0, st, out, (const XyzzW *)pts, n, log_n, 1u << log_n);
     PLK_HIP(hipGetLastError());
     return PLK_OK;
 }
 
-int32_t g1_intt_dev(plk_ctx *ctx, const G1Affine *in, uint32_t log_n, G1Affine *out, hipStream_t st) { return g1_ntt_dev(ctx, in, log_n, true, out, st, "g1_intt"); }
+int32_t g1_intt_dev(plk_ctx *ctx, const G1Affine *in, uint32_t log_n, G1Affine *out, hipStream_t st) { return g1_ntt_dev(ctx, in, 1, log_n, true, out, st, "g1_intt"); }
 
 // The transform of 2^log_n XYZZ points where they lie (natural order in and out, any buffer of the caller's: no scratch, no refusal of its own
 // beyond the size).  A chain of transforms (kzg_all.hip) stays on the 29-bit layer and pays for g1ntt_to_affine once.
-int32_t g1_ntt_xyzzw_dev(plk_ctx *ctx, XyzzW *pts, uint32_t log_n, bool inverse, hipStream_t st) {
-    if (log_n > 26) { set_error("g1_ntt: size exceeds 2^26"); return PLK_ERR_SIZE; }
+// `count` transforms in every launch, over the first 2^log_n points of arrays `stride` >= 2^log_n points apart; count * stride <= 2^26.
+int32_t g1_ntt_xyzzw_dev(plk_ctx *ctx, XyzzW *pts, uint32_t count, uint32_t stride, uint32_t log_n, bool inverse, hipStream_t st) {
+    if (!fk_batch_points_ok(count, log_n) || stride < (1u << log_n) || (uint64_t)count * stride > ((uint64_t)1 << FK_BATCH_LOG_POINTS)) { set_error("g1_ntt: size exceeds 2^26"); return PLK_ERR_SIZE; }
     PLK_TRY(ntt_init_tables(ctx));
-    const uint32_t n = 1u << log_n;
-    hipLaunchKernelGGL(g1ntt_bitrev, dim3((n + 255) / 256), dim3(256), 0, st, pts, log_n);
-    return g1ntt_stages(ctx, pts, log_n, inverse, st);
+    const uint32_t n = count << log_n;
+    hipLaunchKernelGGL(g1ntt_bitrev, dim3((n + 255) / 256), dim3(256), 0, st, pts, log_n, count, stride);
+    return g1ntt_stages(ctx, pts, count, stride, log_n, inverse, st);
 }
-int32_t g1_xyzzw_to_affine_dev(const XyzzW *pts, uint32_t n, G1Affine *out, hipStream_t st) {
-    hipLaunchKernelGGL(g1ntt_to_affine, dim3(((n + G1NTT_NORM_K - 1) / G1NTT_NORM_K + 255) / 256), dim3(256), 0, st, out, pts, n);
+// out[b << log_n | i] = the affine form of pts[b * stride + i], b < count, i < 2^log_n
+int32_t g1_xyzzw_to_affine_dev(const XyzzW *pts, uint32_t count, uint32_t stride, uint32_t log_n, G1Affine *out, hipStream_t st) {
+    const uint32_t n = count << log_n;
+    hipLaunchKernelGGL(g1ntt_to_affine, dim3(((n + G1NTT_NORM_K - 1) / G1NTT_NORM_K + 255) / 256), dim3(256), 0, st, out, pts, n, log_n, stride);
     PLK_HIP(hipGetLastError());
     return PLK_OK;
 }
@@ -233,5 +247,15 @@ extern "C" int32_t plk_g1_ntt_dev(plk_ctx *ctx, const void *in_dev, uint32_t log
     if (((uintptr_t)in_dev | (uintptr_t)out_dev) & 15u) { set_error("plk_g1_ntt_dev: device pointers must be 16-byte aligned"); return PLK_ERR_ARG; }
     PLK_HIP(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    return g1_ntt_dev(ctx, static_cast<const G1Affine *>(in_dev), log_n, inverse != 0, static_cast<G1Affine *>(out_dev), s, "plk_g1_ntt_dev");
+    return g1_ntt_dev(ctx, static_cast<const G1Affine *>(in_dev), 1, log_n, inverse != 0, static_cast<G1Affine *>(out_dev), s, "plk_g1_ntt_dev");
+}
+
+// the same transform over `count` arrays of 2^log_n points back to back, every stage of all of them in one launch
+extern "C" int32_t plk_g1_ntt_batch_dev(plk_ctx *ctx, const void *in_dev, uint32_t count, uint32_t log_n, int32_t inverse, void *out_dev, void *stream) {
+    if (!ctx || !in_dev || !out_dev) { set_error("plk_g1_ntt_batch_dev: bad argument"); return PLK_ERR_ARG; }
+    if (count == 0) { set_error("plk_g1_ntt_batch_dev: count must be at least 1"); return PLK_ERR_ARG; }
+    if (((uintptr_t)in_dev | (uintptr_t)out_dev) & 15u) { set_error("plk_g1_ntt_batch_dev: device pointers must be 16-byte aligned"); return PLK_ERR_ARG; }
+    PLK_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    return g1_ntt_dev(ctx, static_cast<const G1Affine *>(in_dev), count, log_n, inverse != 0, static_cast<G1Affine *>(out_dev), s, "plk_g1_ntt_batch_dev");
 }

@@ -61,4 +61,49 @@ PLK_FK_HD FkScratch fk_scratch(uint32_t log_n, bool values) {
     return s;
 }
 
+// ---- a batch: `count` polynomials of N = 2^log_n under one key (plk_kzg_open_all_batch_dev), `count` transforms per stage launch (g1ntt.hip).
+// The polynomial is the SLOW index of every launch; the transforms' first points lie `stride` points apart (2N in the scratch of the openings,
+// N in the public G1 batch).  Every flattened index stays inside 32 bits: a launch covers at most 2^26 points.
+constexpr uint32_t FK_BATCH_LOG_POINTS = 26;                       // g1ntt's limit, applied to the whole launch
+// count transforms of 2^log_points points in one launch
+PLK_FK_HD bool fk_batch_points_ok(uint32_t count, uint32_t log_points) {
+    return count >= 1 && log_points <= FK_BATCH_LOG_POINTS && ((uint64_t)count << log_points) <= ((uint64_t)1 << FK_BATCH_LOG_POINTS);
+}
+// count polynomials of 2^log_n: the 2N-point transforms of all of them are one launch
+PLK_FK_HD bool fk_batch_ok(uint32_t count, uint32_t log_n) { return fk_size_ok(log_n) && fk_batch_points_ok(count, log_n + 1); }
+// scratch of a batch call: [ u: count x 2N XYZZ points | c: count x 2N Fr | coefficients: count x N Fr (PLK_KZG_VALUES only) ]; fk_scratch for count = 1
+PLK_FK_HD FkScratch fk_batch_scratch(uint32_t count, uint32_t log_n, bool values) {
+    const size_t n = (size_t)1 << log_n;
+    FkScratch s;
+    s.u_off = 0;
+    s.c_off = count * 2 * n * FK_XYZZW_BYTES;
+    s.coeff_off = s.c_off + count * 2 * n * FK_FR_BYTES;
+    s.bytes = s.coeff_off + (values ? count * n * FK_FR_BYTES : 0);
+    return s;
+}
+// flattened butterfly g < count * 2^(log_n - 1) of a stage launch over transforms of 2^log_n points (log_n >= 1) -> (transform, butterfly in it)
+struct FkButterfly { uint32_t poly, j; };
+PLK_FK_HD FkButterfly fk_batch_butterfly(uint32_t log_n, uint32_t g) {
+    FkButterfly b;
+    b.poly = g >> (log_n - 1);
+    b.j = g & ((1u << (log_n - 1)) - 1);
+    return b;
+}
+// butterfly j < 2^(log_n - 1) of stage s < log_n (half-size 2^s) -> its two points i0 < i1 inside the transform and its twiddle position jl.
+// In the early stages of a transform of 256 points or more the position is the slow index, so whole waves share a twiddle (g1ntt_stage).
+struct FkPair { uint32_t i0, i1, jl; };
+PLK_FK_HD FkPair fk_stage_pair(uint32_t log_n, uint32_t s, uint32_t j) {
+    const uint32_t h = 1u << s;
+    uint32_t jl, jh;
+    if (s < 6 && log_n >= 8) { jl = j >> (log_n - 1 - s); jh = j & ((1u << (log_n - 1 - s)) - 1); }
+    else { jl = j & (h - 1); jh = j >> s; }
+    FkPair p;
+    p.i0 = (jh << (s + 1)) | jl;
+    p.i1 = p.i0 + h;
+    p.jl = jl;
+    return p;
+}
+// flattened point p < count * 2^log_n (the first 2^log_n of every transform, dense) -> where it lies among transforms `stride` points apart
+PLK_FK_HD uint32_t fk_batch_point(uint32_t log_n, uint32_t stride, uint32_t p) { return (p >> log_n) * stride + (p & ((1u << log_n) - 1)); }
+
 }  // namespace plk
